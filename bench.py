@@ -8,7 +8,19 @@ reduced to (power, power2) energies, with mixture, offsets and weights already r
 HBM.  With N GPUs the candidate list is N times longer and sharded (weak scaling); each
 step ends with the stage's one exchange, an all-gather of the energies over RCCL.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else runs.
+`--full` adds everything beyond the headline: the in-library per-kernel timing of the timed
+steps and the roofline figures built on it, the extra legs (other precisions, T=144000), the
+end-to-end pipeline latency, the CPU baseline and the reference-style GPU baseline (and at
+N > 1 the sharded end-to-end pipeline).  `--no-profile`, `--no-extras`, `--no-e2e` and
+`--cpu-sample 0` leave single parts of `--full` out.
+
+`--dump-outputs DIR` writes what the last timed step returned -- the (power, power2)
+energies of every candidate, float64 [candidates x N, 2] -- to DIR/energies.npy.  Weights,
+scene and candidate offsets are seeded, so the same arguments give the same inputs on every
+run and two builds can be compared output for output.
 
 With N > 1 and no torchrun environment the script starts the N ranks itself
 (`python -m torch.distributed.run ...`, one process per GPU) BEFORE anything touches the
@@ -204,11 +216,16 @@ def main():
     ap.add_argument("--candidates", type=int, default=256, help="candidates per GPU per step")
     ap.add_argument("--samples", type=int, default=48000, help="T: 48000 = 3 s @ 16 kHz (BASELINE literal)")
     ap.add_argument("--batch", type=int, default=256, help="internal candidate batch (spot_batch_size)")
-    ap.add_argument("--cpu-sample", type=int, default=96, help="candidates timed on the CPU baseline (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the in-library per-kernel event timing")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end pipeline latency measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel timing + roofline, extra legs, "
+                         "end-to-end latency, CPU and reference-style GPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the energies returned by the last timed step to DIR/energies.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=96, help="--full: candidates timed on the CPU baseline (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the in-library per-kernel event timing")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end pipeline latency measurement")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra legs (reference-style GPU baseline, f32 mode, T=144000)")
+                    help="--full: skip the extra legs (reference-style GPU baseline, f32 mode, T=144000)")
     ap.add_argument("--precision", choices=["f32", "f16x3"], default="f16x3",
                     help="GEMM arithmetic: exact f32 MFMA, or f16x3 split-operand MFMA (105 dB SNR vs the reference)")
     ap.add_argument("--stub", action="store_true",
@@ -218,6 +235,11 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if not args.full:                                    # a plain run: the headline and nothing else
+        args.no_profile = args.no_e2e = args.no_extras = True
+        args.cpu_sample = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if not args.stub and torch.cuda.device_count() < args.gpus and os.environ.get("ASW_BENCH_BACKEND", "nccl") == "nccl":
             raise SystemExit(f"--gpus {args.gpus}: only {torch.cuda.device_count()} HIP devices visible")
@@ -332,6 +354,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.isfinite(last).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"energies": last})
     from acousticswarms_speech_amd.ops import f16x3_overflow_count
     overflow = f16x3_overflow_count(reset=True)         # f16x3 range guard over warm-up + timed steps
     if overflow:
@@ -513,6 +537,16 @@ def close_ranks(dist, rc):
     guard.cancel()
     dist.destroy_process_group()
     return int(flag.item())
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array (float32 / float64) as out_dir/<name>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def build_sep_model(dev, precision):

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/r3prof
 mkdir -p $OUT
-BENCH="python3 $R/bench.py --no-e2e --no-extras --cpu-sample 0 --steps 5 --warmup 2"
+BENCH="python3 $R/bench.py --full --no-e2e --no-extras --cpu-sample 0 --steps 5 --warmup 2"
 BENCHP="python3 $R/bench.py --no-e2e --no-extras --cpu-sample 0 --steps 3 --warmup 1 --no-profile"
 cd $R
 echo "== kernel stats"; rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1

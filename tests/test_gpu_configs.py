@@ -236,9 +236,9 @@ def test_config3_sixty_four_mixture_batch_at_size(full_weights):
            "mixtures_per_s": round(64 / dt, 2), "plain_loop_mixtures_per_s": round(64 / dt_loop, 2),
            "spot_candidates": int(cands), "candidates_per_s_in_search": round(cands / dt, 1),
            "talkers_found_mean": round(float(np.mean([len(g[2]) for g in got])), 2)}
+    _log(f"config3 at size: {rec}")                                  # creates the diagnostics folder
     with open(os.path.join(ROOT, "gpurun_out", "config3_batch64.json"), "w") as f:
         json.dump(rec, f)
-    _log(f"config3 at size: {rec}")
 
 
 def test_config4_sixteen_mic_dense_lattice_at_size():
@@ -286,9 +286,9 @@ def test_config4_sixteen_mic_dense_lattice_at_size():
     np.testing.assert_allclose(sl, en[:24], rtol=1e-6)
     rec = {"workload": "16 mics, 5 talkers, dense width-2 TDoA lattice at 5 cm, T=48000, FULL net (configs[4])",
            "lattice_candidates": int(len(offs)), "evaluated": 1024, "candidates_per_s": round(1024 / dt, 1)}
+    _log(f"config4 at size: {rec}")                                  # creates the diagnostics folder
     with open(os.path.join(ROOT, "gpurun_out", "config4_dense16.json"), "w") as f:
         json.dump(rec, f)
-    _log(f"config4 at size: {rec}")
 
 
 # ------------------------------------------------------------------------------ flip rate
@@ -409,7 +409,7 @@ def test_bench_two_ranks_rehearsal_sharing_one_gpu():
         env.pop(k, None)
     env["ASW_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--no-extras", "--cpu-sample", "0", "--candidates", "32", "--batch", "32"],
+                        "--full", "--no-extras", "--cpu-sample", "0", "--candidates", "32", "--batch", "32"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -420,3 +420,37 @@ def test_bench_two_ranks_rehearsal_sharing_one_gpu():
     assert "error" not in e2e, e2e
     assert e2e["ranks"] == 2 and e2e["spot_calls"] == {"coarse": 30, "fine": 710} and e2e["talkers_found"] == 27
     assert e2e["separated_rows"] == 27 and e2e["total"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run prints the headline alone (the `--full` records stay null) and
+    `--dump-outputs DIR` writes the energies its last timed step returned: the same energies the
+    hot call gives for the benchmark's seeded weights, scene and candidates."""
+    import subprocess
+    import sys
+    from acousticswarms_speech_amd.config import FULL
+    from acousticswarms_speech_amd.scenes import make_scene, random_offsets
+    from acousticswarms_speech_amd.spot import SpotModel
+    from acousticswarms_speech_amd.weights import make_spot_state_dict
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--candidates", "32", "--batch", "32", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "candidates/s" and line["dtype"].startswith("f32 via f16x3")
+    for k in ("roofline", "cpu_baseline", "refstyle_gpu", "extras", "e2e_latency"):
+        assert line[k] is None, k
+    assert os.listdir(tmp_path / "out") == ["energies.npy"]
+    got = np.load(tmp_path / "out" / "energies.npy")
+    assert got.dtype == np.float64 and got.shape == (32, 2) and np.isfinite(got).all() and (got > 0).all()
+    model = SpotModel(FULL, make_spot_state_dict(FULL, seed=5), batch_size=32, precision="f16x3").to("cuda")
+    mix = torch.from_numpy(make_scene(1010, n_speakers=5, n_mics=7, T=48000, reverb=True).mix).cuda()
+    offs = torch.from_numpy(random_offsets(7, 32, 6, 140)).cuda()
+    _, want = model.shift_and_sep_device(mix, offs, strict=1, want_wave=False, want_energy=True, window=12000)
+    np.testing.assert_allclose(got, want.cpu().numpy(), rtol=1e-6)
