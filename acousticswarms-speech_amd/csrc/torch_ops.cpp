@@ -10,7 +10,7 @@
 // (sep/training/JointModel/network.py:27-104), Network.forward
 // (sep/training/SpeakerLocalization/network.py:363-405), the host energy loops
 // (sep/helpers/local_utils_3d.py:13-17,349-354), si_sdr pairs (sep/helpers/eval_utils.py:11-82),
-// SRP_Map_WINDOW_torch (sep/Traditional_SP/SRP_Prunning.py:387-434) and the joint separation
+// SRP_Map_WINDOW_torch (sep/Traditional_SP/SRP_Prunning.py:387-434), MUSIC_Map_WINDOW / TOPS_Map_WINDOW (:436-497) and the joint separation
 // network's infer_sample / forward (sep/training/SpeakerSeparation/network.py:418-548).
 //
 // Model handles (asw_spot*, asw_sep*) are created and loaded through the C ABI
@@ -21,6 +21,7 @@
 #include <torch/library.h>
 
 #include <tuple>
+#include <vector>
 
 #include "../../include/asw_hip.h"
 
@@ -237,6 +238,94 @@ Tensor srp_phat_map(const Tensor& mix, const Tensor& twiddle, const Tensor& pair
   return out;
 }
 
+// ---- MUSIC / TOPS pruning maps --------------------------------------------------------------------
+// Shared by the ops below: covariance per (window, bin) + magnitude sums (asw_pruner_covariance).
+std::tuple<Tensor, Tensor> covariance_impl(const Launch& l, const Tensor& mix, int bin0, int nbins, int64_t window, int64_t step,
+                                           int nw, int64_t nfft, int64_t hop) {
+  const int M = checked_int(mix.size(0), "M"), T = checked_int(mix.size(1), "T");
+  TORCH_CHECK(nw > 0 && (nw - 1) * step + window <= T, "windows run past the end of the mixture");
+  Tensor cov = at::empty({nw, nbins, M, M}, mix.options().dtype(at::kComplexDouble));
+  Tensor mag = at::empty({nw, nbins}, mix.options().dtype(at::kDouble));
+  check_status(asw_pruner_covariance(mix.data_ptr<float>(), M, T, checked_int(window, "window"), checked_int(step, "step"), nw,
+                                     checked_int(nfft, "nfft"), checked_int(hop, "hop"), bin0, nbins,
+                                     reinterpret_cast<double*>(cov.data_ptr()), mag.data_ptr<double>(), l.stream),
+               "asw_pruner_covariance");
+  return {cov, mag};
+}
+
+std::tuple<Tensor, Tensor> eigh_impl(const Launch& l, const Tensor& a) {
+  const int M = checked_int(a.size(-1), "M");
+  const int64_t n = a.numel() / ((int64_t)M * M);
+  std::vector<int64_t> vshape(a.sizes().begin(), a.sizes().end() - 1);
+  Tensor evals = at::empty(vshape, a.options().dtype(at::kDouble));
+  Tensor evecs = at::empty(a.sizes(), a.options());
+  if (n == 0) return {evals, evecs};
+  check_status(asw_hermitian_eigh(reinterpret_cast<const double*>(a.data_ptr()), checked_int(n, "n"), M, evals.data_ptr<double>(),
+                                  reinterpret_cast<double*>(evecs.data_ptr()), l.stream),
+               "asw_hermitian_eigh");
+  return {evals, evecs};
+}
+
+std::tuple<Tensor, Tensor> pruner_covariance(const Tensor& mix, int64_t bin0, int64_t nbins, int64_t window, int64_t step,
+                                             int64_t n_windows, int64_t nfft, int64_t hop) {
+  need(mix, "mix", at::kFloat, 2);
+  Launch l(mix);
+  return covariance_impl(l, mix, checked_int(bin0, "bin0"), checked_int(nbins, "nbins"), window, step,
+                         checked_int(n_windows, "n_windows"), nfft, hop);
+}
+
+std::tuple<Tensor, Tensor> hermitian_eigh(const Tensor& a) {
+  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kComplexDouble && a.is_contiguous(), "a must be a contiguous complex128 HIP tensor");
+  TORCH_CHECK(a.dim() >= 2 && a.size(-1) == a.size(-2) && a.size(-1) >= 1 && a.size(-1) <= 16, "a must be [..., M, M] with M <= 16");
+  Launch l(a);
+  return eigh_impl(l, a);
+}
+
+Tensor music_map(const Tensor& mix, const Tensor& tau, const Tensor& omega, int64_t bin0, int64_t window, int64_t step,
+                 int64_t n_windows, int64_t nfft, int64_t hop) {
+  need(mix, "mix", at::kFloat, 2);
+  need(tau, "tau", at::kDouble, 2);
+  need(omega, "omega", at::kDouble, 1);
+  for (const Tensor* t : {&tau, &omega}) same_device(mix, *t, "all MUSIC operands");
+  const int M = checked_int(mix.size(0), "M"), G = checked_int(tau.size(0), "G"), nbins = checked_int(omega.size(0), "nbins");
+  const int nw = checked_int(n_windows, "n_windows");
+  TORCH_CHECK(tau.size(1) == M && M >= 4 && M <= 16, "tau must be [G, M] with 4 <= M <= 16");
+  Tensor out = at::zeros({G}, mix.options());
+  if (G == 0) return out;
+  Launch l(mix);
+  auto cm = covariance_impl(l, mix, checked_int(bin0, "bin0"), nbins, window, step, nw, nfft, hop);
+  auto ev = eigh_impl(l, std::get<0>(cm));
+  Tensor p = at::empty({nw, nbins, G}, mix.options().dtype(at::kDouble));
+  Tensor mx = at::empty({nw, nbins}, mix.options().dtype(at::kDouble));
+  check_status(asw_music_map(reinterpret_cast<const double*>(std::get<1>(ev).data_ptr()), nw, nbins, M, tau.data_ptr<double>(), G,
+                             omega.data_ptr<double>(), p.data_ptr<double>(), mx.data_ptr<double>(), out.data_ptr<float>(), l.stream),
+               "asw_music_map");
+  return out;
+}
+
+std::tuple<Tensor, Tensor> tops_map(const Tensor& mix, const Tensor& delta, int64_t bin0, int64_t nbins, double coef, int64_t window,
+                                    int64_t step, int64_t n_windows, int64_t nfft, int64_t hop) {
+  need(mix, "mix", at::kFloat, 2);
+  need(delta, "delta", at::kDouble, 2);
+  same_device(mix, delta, "mix and delta");
+  const int M = checked_int(mix.size(0), "M"), G = checked_int(delta.size(0), "G"), nb = checked_int(nbins, "nbins");
+  const int nw = checked_int(n_windows, "n_windows");
+  TORCH_CHECK(delta.size(1) == M && M >= 4 && M <= 16, "delta must be [G, M] with 4 <= M <= 16");
+  TORCH_CHECK(nb >= 2, "TOPS needs more than one frequency band");
+  Tensor out = at::zeros({G}, mix.options());
+  Tensor max_bin = at::zeros({nw > 0 ? nw : 0}, mix.options().dtype(at::kInt));
+  if (G == 0) return {out, max_bin};
+  Launch l(mix);
+  auto cm = covariance_impl(l, mix, checked_int(bin0, "bin0"), nb, window, step, nw, nfft, hop);
+  auto ev = eigh_impl(l, std::get<0>(cm));
+  Tensor q = at::empty({nw, nb - 1, 3, M - 3, M, 2}, mix.options().dtype(at::kDouble));
+  check_status(asw_tops_map(reinterpret_cast<const double*>(std::get<1>(ev).data_ptr()), std::get<1>(cm).data_ptr<double>(), nw, nb,
+                            checked_int(bin0, "bin0"), M, delta.data_ptr<double>(), G, coef, q.data_ptr<double>(),
+                            max_bin.data_ptr<int32_t>(), out.data_ptr<float>(), l.stream),
+               "asw_tops_map");
+  return {out, max_bin};
+}
+
 // ---- joint separation network ---------------------------------------------------------------------
 Tensor sep_infer(int64_t model, const Tensor& mix, const Tensor& offsets) {
   TORCH_CHECK(model != 0, "sep_infer: null model handle");
@@ -318,6 +407,13 @@ TORCH_LIBRARY(asw, m) {
   m.def("center_rows_(Tensor(a!) y) -> Tensor(a!)");
   m.def("srp_phat_map(Tensor mix, Tensor twiddle, Tensor pair_i, Tensor pair_j, Tensor tau, Tensor omega, int window, "
         "int step, int n_windows, int nfft, int hop, float tol) -> Tensor");
+  m.def("pruner_covariance(Tensor mix, int bin0, int nbins, int window, int step, int n_windows, int nfft, int hop) "
+        "-> (Tensor, Tensor)");
+  m.def("hermitian_eigh(Tensor a) -> (Tensor, Tensor)");
+  m.def("music_map(Tensor mix, Tensor tau, Tensor omega, int bin0, int window, int step, int n_windows, int nfft, "
+        "int hop) -> Tensor");
+  m.def("tops_map(Tensor mix, Tensor delta, int bin0, int nbins, float coef, int window, int step, "
+        "int n_windows, int nfft, int hop) -> (Tensor, Tensor)");
   m.def("sep_infer(int model, Tensor mix, Tensor offsets) -> Tensor");
   m.def("sep_forward(int model, Tensor mix, int n_speakers, int n_mics, int max_speakers) -> Tensor");
   m.def("sep_forward_counts(int model, Tensor mix, int[] counts, int n_mics, int max_speakers) -> Tensor");
@@ -333,6 +429,10 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("segment_sisdr", &segment_sisdr);
   m.impl("center_rows_", &center_rows_);
   m.impl("srp_phat_map", &srp_phat_map);
+  m.impl("pruner_covariance", &pruner_covariance);
+  m.impl("hermitian_eigh", &hermitian_eigh);
+  m.impl("music_map", &music_map);
+  m.impl("tops_map", &tops_map);
   m.impl("sep_infer", &sep_infer);
   m.impl("sep_forward", &sep_forward);
   m.impl("sep_forward_counts", &sep_forward_counts);

@@ -47,17 +47,22 @@ class JointModel(object):
         self.Mic_processor = None
         self._mix_dev = self._mix_src = None
 
-    def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None):
+    def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP"):
         """(Re)build the geometry tables unless the configuration is unchanged (:125-137).
-        One-off per geometry and excluded from latency, as the reference's README notes."""
+        One-off per geometry and excluded from latency, as the reference's README notes.
+        ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS") and is part of the
+        configuration."""
         key = '~'.join([f"{x:.05f}" for x in np.asarray(mic_positions).flatten()]) \
             + '|' + '~'.join([f"{x:.05f}" for x in speaker_range])
+        if prone_method != "SRP":
+            key += '|' + str(prone_method)
         if key == self.previous_config:
             print("reuse the previous recycle!")
             return
         import gc
         gc.unfreeze()                       # a previous geometry may go now
-        self.Mic_processor = MicArray(mic_positions, Spk_Range=speaker_range, device=self.device)
+        self.Mic_processor = MicArray(mic_positions, Spk_Range=speaker_range, Prone_method=prone_method,
+                                      device=self.device)
         self.previous_config = key
         # The geometry tables are tens of thousands of small arrays and lists that live as long as
         # this configuration.  Left in the collector's oldest generation they make every full

@@ -19,6 +19,9 @@ FINE_CHUNK_EDGES = (0.0, 0.07, 0.40, 0.73, 0.93, 1.0)      # pipelined fine stag
 BIN0, BIN1, N_FFT = 2, 200, 2048
 FREQ_BINS = np.arange(BIN0, BIN1)
 
+# pruning map of stage 1 per Prone_method (sep/Mic_Array.py:165-170)
+PRONE_METHODS = {"SRP": "SRP_Map_WINDOW_new", "MUSIC": "MUSIC_Map_WINDOW", "TOPS": "TOPS_Map_WINDOW"}
+
 
 def check_sisnr_win(sisnr_list, SISNR_THRESHOLD=-2, SISNR_THRESHOLD2=-7):
     """Same talker if some segment is similar (> thr) and none is very different (< thr2)
@@ -69,8 +72,9 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
 class MicArray(object):
     def __init__(self, mic_positions, demo=False, Spk_Range=None, grid_size=0.05, Prone_method="SRP",
                  MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None):
-        if Prone_method != "SRP":
-            raise RuntimeError("only the SRP-PHAT pruner is provided (MUSIC/TOPS are out of scope)")
+        if Prone_method not in PRONE_METHODS:
+            # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
+            raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
         self.Prone_method = Prone_method
         self.MIN_TRIGGER_POWER = MIN_TRIGGER_POWER
         self.visual_save = False
@@ -94,14 +98,14 @@ class MicArray(object):
         # clustering, and the global clusters as lists of "g_head" names
         self.trace = {"coarse_kept": [], "fine_clusters": {}, "final_clusters": []}
 
-    # ---- stage 1: SRP-PHAT pruning (sep/Mic_Array.py:152-194) ---------------------------
+    # ---- stage 1: SRP-PHAT / MUSIC / TOPS pruning (sep/Mic_Array.py:152-194) --------------
     def Apply_SRP_PHAT(self, mix_data):
         self.SRP_node.reset()
         self.spotforming_times = 0
         self.original_times = 0
         mix_np = mix_data.numpy() if hasattr(mix_data, "numpy") else np.asarray(mix_data)
         win = 36000 if mix_np.shape[1] >= 72000 else 24000
-        self.SRP_node.SRP_Map_WINDOW_new(mix_np, window=win)
+        getattr(self.SRP_node, PRONE_METHODS[self.Prone_method])(mix_np, window=win)
         patch_list = self.SRP_node.local_source_adaptive()
         return patch_list, np.zeros((3, 3))
 

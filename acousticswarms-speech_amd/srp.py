@@ -10,7 +10,10 @@ a-Q) with the same method names used by the search (``reset``,
 * the [G,198,21] complex128 steering table (:368-381,230-246; 1.16 GB) is never built:
   the HIP map kernel regenerates exp(j w dtau) from the [G,M] propagation delays;
 * the map itself (``SRP_Map_WINDOW_torch``, :387-434) runs in libasw_hip.so
-  (csrc/srp_kernels.hip) -- there is no host fallback.
+  (csrc/srp_kernels.hip) -- there is no host fallback;
+* the alternative MUSIC and TOPS maps (``MUSIC_Map_WINDOW`` / ``TOPS_Map_WINDOW``, :436-497)
+  run in csrc/pruner_kernels.hip.  Where the reference would divide 0/0 (no complete
+  window), they raise ``RuntimeError`` instead of leaving a NaN map.
 """
 import numpy as np
 from scipy.sparse import coo_matrix
@@ -19,6 +22,7 @@ from scipy.sparse.csgraph import connected_components
 from .patch import Patch
 
 ERR_TOLERANCE = 0.2        # SRP_Prunning.py:17
+TOPS_WINDOW = 72000        # TOPS_Map_WINDOW ignores its window argument (SRP_Prunning.py:475)
 
 
 class GridCluster(object):
@@ -97,6 +101,13 @@ class SRPPhat(object):
         dy = self.grids[:, None, 1] - self.mic_pos[None, :, 1]
         self.tau = np.sqrt(dx ** 2 + dy ** 2 + self.grids[:, None, 2] ** 2) / self.C      # [G,M] seconds
         self.omega = 2 * np.pi * FS * self.freq_bins / n_fft
+        # TOPS path differences (TOPS_block.py:45-48,105-112): mics and points centred on the mic mean, in
+        # full 3-D; delta[g, m] = |p_g| - |p_g - m_m|.  The steering phase is tops_coef * (k - f0) * delta.
+        pc = self.grids - self.mic_center
+        mc = self.mic_pos - self.mic_center
+        self.tops_delta = np.linalg.norm(pc, axis=1)[:, None] - np.linalg.norm(pc[:, None, :] - mc[None], axis=2)
+        self.tops_coef = 2 * np.pi * FS / (n_fft * C)
+        self.tops_max_bin = None
         ii, jj = np.triu_indices(self.num_mic, k=1)          # row-major upper triangle == mask_triu order
         self.pair_i, self.pair_j = ii.astype(np.int32), jj.astype(np.int32)
         self.SRP_map = np.zeros(self.grids.shape[0], dtype=np.float32)
@@ -198,8 +209,26 @@ class SRPPhat(object):
                          "tw": torch.from_numpy(tw).to(dev),
                          "tau": torch.from_numpy(np.ascontiguousarray(self.tau)).to(dev),
                          "omega": torch.from_numpy(np.ascontiguousarray(self.omega, dtype=np.float64)).to(dev),
-                         "pi": torch.from_numpy(self.pair_i).to(dev), "pj": torch.from_numpy(self.pair_j).to(dev)}
+                         "pi": torch.from_numpy(self.pair_i).to(dev), "pj": torch.from_numpy(self.pair_j).to(dev),
+                         "delta": torch.from_numpy(np.ascontiguousarray(self.tops_delta)).to(dev)}
         return self._dev
+
+    def _device_signal(self, signal):
+        """(device, mixture as a float32 device tensor zero-padded to a multiple of 4 samples)."""
+        import torch
+        nb = len(self.freq_bins)
+        assert np.array_equal(self.freq_bins, np.arange(self.freq_bins[0], self.freq_bins[0] + nb)), \
+            "the pruning kernels take a contiguous bin range"
+        dev = torch.device(self.device if self.device is not None else "cuda")
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("the pruning maps run only on the MI355X (no host fallback)")
+        M, T = signal.shape
+        assert self.mic_pos.shape[0] == M
+        sig = torch.as_tensor(signal, dtype=torch.float32).to(dev)
+        Tp = (T + 3) // 4 * 4
+        if Tp != T:
+            sig = torch.nn.functional.pad(sig, (0, Tp - T))
+        return dev, sig.contiguous()
 
     def SRP_Map_WINDOW_new(self, signal, window=36000, tol=1e-8):
         """Steered-response map, maximum over half-overlapped windows (:383-434)."""
@@ -227,6 +256,52 @@ class SRPPhat(object):
         out = native.torch_ops().srp_phat_map(sig, t["tw"], t["pi"], t["pj"], t["tau"], t["omega"], int(window), int(step),
                                               int(n_win), int(self.n_fft), int(hop), float(tol))
         self.SRP_map = out.cpu().numpy()
+        self._finish_map()
+
+    @staticmethod
+    def _whole_windows(T, window):
+        """Windows of the MUSIC / TOPS loops (:442-450,476-484): step = window, no overlap."""
+        n = 0
+        for j in range(T // window):
+            if j * window + window > T:
+                break
+            n += 1
+        return n
+
+    def MUSIC_Map_WINDOW(self, signal, window=36000, tol=1e-8):
+        """MUSIC pseudo-spectrum map (:436-467, MUSIC_block.py): per window and bin the noise
+        subspace of the frame-averaged covariance, P = 1/|a^H En En^H a|, normalised per bin by its
+        maximum over the grid, averaged over bins and then over the non-overlapping windows."""
+        from . import native
+        T = signal.shape[1]
+        n_win = self._whole_windows(T, window)
+        if n_win == 0:
+            raise RuntimeError(f"MUSIC map: a {T}-sample mixture holds no whole {window}-sample window "
+                               "(the reference would return a NaN map)")
+        dev, sig = self._device_signal(signal)
+        t = self._device_tables(dev)
+        out = native.torch_ops().music_map(sig, t["tau"], t["omega"], int(self.freq_bins[0]), int(window), int(window),
+                                           int(n_win), int(self.n_fft), int(self.n_fft // 4))
+        self.SRP_map = out.cpu().numpy()
+        self._finish_map()
+
+    def TOPS_Map_WINDOW(self, signal, window=36000, tol=1e-8):
+        """TOPS map (:470-497, TOPS_block.py:62-136): per 72 000-sample window (the argument is ignored, as
+        in the reference) 1/s_min of D = [F0^H diag(conj phi_k) W_k]_k, averaged over windows.
+        ``tops_max_bin`` keeps the reference bin index chosen in each window."""
+        from . import native
+        T = signal.shape[1]
+        n_win = self._whole_windows(T, TOPS_WINDOW)
+        if n_win == 0:
+            raise RuntimeError(f"TOPS map needs at least {TOPS_WINDOW} samples, got {T} "
+                               "(the reference would return a NaN map)")
+        dev, sig = self._device_signal(signal)
+        t = self._device_tables(dev)
+        out, max_bin = native.torch_ops().tops_map(sig, t["delta"], int(self.freq_bins[0]),
+                                                   int(len(self.freq_bins)), float(self.tops_coef), TOPS_WINDOW,
+                                                   TOPS_WINDOW, int(n_win), int(self.n_fft), int(self.n_fft // 4))
+        self.SRP_map = out.cpu().numpy()
+        self.tops_max_bin = max_bin.cpu().numpy()
         self._finish_map()
 
     def set_map(self, srp_map):

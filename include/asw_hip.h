@@ -530,6 +530,42 @@ int asw_srp_map(const float* cc, int n_windows, int nbins, int P, const double* 
                 const double* omega, const int32_t* pair_i, const int32_t* pair_j,
                 float* part_scratch, float* out, void* stream);
 
+/* MUSIC / TOPS pruning maps (sep/Traditional_SP/SRP_Prunning.py:436-497, MUSIC_block.py,
+ * TOPS_block.py), four stages.  All take 4 <= M <= 16 microphones (3 signal vectors).
+ *
+ * asw_pruner_covariance: for each of n_windows windows (start w*step, length `window`) and
+ * each bin k < nbins: X = the STFT bin bin0+k (rectangular, hop `hop`) as a direct DFT in
+ * double; cov[w][k] = (1/frames) sum_f X_f X_f^H as a full Hermitian [M][M] complex double
+ * matrix and magsum[w][k] = sum_m sum_f |X[m][k][f]| in double.
+ *   mix [M][T] float; cov [n_windows][nbins][M][M][2]; magsum [n_windows][nbins].
+ *
+ * asw_hermitian_eigh: n Hermitian matrices a [n][M][M][2] (complex double; the Hermitian part
+ * is used), 1 <= M <= 16, by cyclic complex Jacobi in double.  evals [n][M] ascending,
+ * evecs [n][M][M][2] with eigenvector j in column j (numpy.linalg.eigh's layout).
+ *
+ * asw_music_map: out[g] = mean_w mean_k P[w][k][g] / max_g' P[w][k][g'], with
+ * P = 1 / sum_{j < M-3} |e_j^H a|^2 over the noise columns of evecs [n_windows][nbins] (as
+ * asw_hermitian_eigh writes them) and a_m = exp(+j omega[k] tau[g][m]).  tau [G][M] float64
+ * seconds, omega [nbins] rad/s; p_scratch [n_windows][nbins][G] double;
+ * max_scratch [n_windows][nbins] double; out [G] float.
+ *
+ * asw_tops_map: per window, max_bin[w] = first argmax_k magsum[w][k]; f0 = bin0 + max_bin;
+ * out[g] = mean_w 1/s_min(D), D = [F0^H diag(conj phi_k) W_k] for k = 0 .. nbins-2, F0 the
+ * 3 signal columns of bin max_bin, W_k the M-3 noise columns of bin k,
+ * phi_k[m] = exp(j coef (k - f0) delta[g][m]) (k the raw row index, as the reference has it).
+ * delta [G][M] float64 path differences; q_scratch double[n_windows][nbins-1][3][M-3][M][2];
+ * max_bin int32[n_windows]; out [G] float. */
+int asw_pruner_covariance(const float* mix, int M, int T, int window, int step, int n_windows,
+                          int nfft, int hop, int bin0, int nbins, double* cov, double* magsum,
+                          void* stream);
+int asw_hermitian_eigh(const double* a, int n, int M, double* evals, double* evecs, void* stream);
+int asw_music_map(const double* evecs, int n_windows, int nbins, int M, const double* tau, int G,
+                  const double* omega, double* p_scratch, double* max_scratch, float* out,
+                  void* stream);
+int asw_tops_map(const double* evecs, const double* magsum, int n_windows, int nbins, int bin0,
+                 int M, const double* delta, int G, double coef, double* q_scratch,
+                 int32_t* max_bin, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
