@@ -4,6 +4,7 @@
 // forms, the dilated-residual stack and the linear-layer launch helper.
 #pragma once
 #include <cstdlib>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <string>
@@ -249,5 +250,463 @@ inline int linear(const float* A, const WBuf& W, int prec, const float* bias, in
   return asw_convgemm_f32(&a, s);
 }
 
+// ConvTranspose1d weight w [Cin][N][S] / bias b [N] with kernel == stride as a plain GEMM whose output row t_in holds the
+// S output frames t_in*S .. t_in*S+S-1 back to back: Wt[r*N + n][c], bias[r*N + n] (optionally scaled per output channel)
+inline void pack_conv_transpose(const std::vector<float>& w, const std::vector<float>& b, int Cin, int N, int S,
+                                const float* out_gate, std::vector<float>& wt, std::vector<float>& bb) {
+  wt.assign((size_t)S * N * Cin, 0.f);
+  bb.assign((size_t)S * N, 0.f);
+  for (int r = 0; r < S; ++r)
+    for (int n = 0; n < N; ++n) {
+      bb[(size_t)r * N + n] = out_gate ? b[n] * out_gate[n] : b[n];
+      for (int c = 0; c < Cin; ++c) {
+        const float v = w[((size_t)c * N + n) * S + r];
+        wt[((size_t)r * N + n) * Cin + c] = out_gate ? v * out_gate[n] : v;
+      }
+    }
+}
+
+// ---- the U-Net trunk of both networks ---------------------------------------------------------------------------------
+// preproc output -> encoder blocks (residual stack, stride-k conv, GroupNorm + GLU) -> the network's own bottleneck ->
+// decoder blocks (ConvTranspose as a GEMM with the skip added on load, GroupNorm + GLU, residual stack) -> mask path
+// (reference_bypass, mask_encoder, output_decoder, overlap-add).  asw_spot and asw_sep derive from Trunk.
+
+#define UP(buf, vec) if ((rc = (buf).upload(vec))) return rc
+
+// The U-Net hyper-parameters that asw_spot_config and asw_sep_config both carry, under the same names.
+struct TrunkCfg {
+  int n_mics, kernel_size, depth, stride_list[8], channels, growth, encoder_channels, encoder_kernel_size,
+      encoder_stride, residual_layers, residual_dilation_factor, ffw_dim;
+  template <class Cfg>
+  static TrunkCfg of(const Cfg& c) {
+    TrunkCfg t = {c.n_mics, c.kernel_size, c.depth, {}, c.channels, c.growth, c.encoder_channels,
+                  c.encoder_kernel_size, c.encoder_stride, c.residual_layers, c.residual_dilation_factor, c.ffw_dim};
+    for (int i = 0; i < 8; ++i) t.stride_list[i] = c.stride_list[i];
+    return t;
+  }
+};
+
+// The trunk checks of asw_*_create that need no device.  `who` prefixes the message; `odd` is the network's wording of
+// the odd-kernel message (the separation network's also covers its bottleneck kernel).
+inline int check_trunk_config(const TrunkCfg& c, const char* who, const char* odd) {
+  ASW_CHECK_ARG(c.depth >= 1 && c.depth <= 8, "%s: depth %d", who, c.depth);
+  ASW_CHECK_ARG(c.n_mics >= 1 && c.n_mics <= 32, "%s: n_mics %d", who, c.n_mics);
+  ASW_CHECK_ARG(c.channels % 64 == 0, "%s: channels=%d must be a multiple of 64 for the MFMA tiles", who, c.channels);
+  ASW_CHECK_ARG(c.growth >= 1 && c.residual_layers >= 1, "%s: bad config", who);
+  ASW_CHECK_ARG(c.kernel_size % 2 == 1, "%s: %s", who, odd);
+  ASW_CHECK_ARG(c.encoder_channels % 128 == 0, "%s: encoder_channels must be a multiple of 128", who);
+  ASW_CHECK_ARG(c.encoder_stride % 4 == 0 && c.encoder_kernel_size / 2 == c.encoder_stride && c.encoder_kernel_size <= 64,
+                "%s: encoder kernel/stride %d/%d unsupported (the reference's trim [9:-8] assumes 33/16)", who,
+                c.encoder_kernel_size, c.encoder_stride);
+  ASW_CHECK_ARG(c.ffw_dim % 128 == 0, "%s: ffw_dim must be a multiple of 128", who);
+  return ASW_OK;
+}
+
+struct EncBlock { std::vector<ResLayer> res; DevBuf bias, gn_g, gn_b; };
+struct DecBlock { std::vector<ResLayer> res; DevBuf gn_g, gn_b; };
+// The convolutions a window gate folds into (embed1, spot network.py:101,186): each encoder's down conv (gate per input
+// channel) and each decoder's transposed conv (gate per output channel).  The spot network packs one set per window
+// embedding, the separation network one without a gate.
+struct GatedConvs { std::vector<WBuf> down_wt, up_wt; std::vector<DevBuf> up_bias; };
+struct Tap { const float* p; size_t numel; };
+using ParamList = std::vector<std::pair<std::string, size_t>>;
+
+// The trunk's part of a workspace.  X[i] is the input of encoder block i (X[0] = preproc output).
+struct TrunkPlan {
+  int B, T, Tp, F, RL;                     // B: sequences in this batch
+  std::vector<int> Tl;                     // length at level 0..depth
+  float *mean, *stdv, *refn;
+  std::vector<float*> X, Pb, Qb, raw_dn, raw_up, st_dn, st_up, mr_dn, mr_up;
+  float *Y, *D, *ywave;
+};
+
+struct Trunk {
+  TrunkCfg tc;
+  std::map<std::string, std::vector<float>> raw;   // state dict as set_param received it
+  std::map<std::string, Tap> taps;                 // activations of the last batch
+  bool finalized = false;
+  int device = 0;                          // HIP device the weights and the workspace live on
+  int precision = 0;                       // 0 = exact f32 MFMA, 1 = f16x3 split MFMA, 2 = single-pass f16
+  bool fuse_mask = true;                   // f16x3: GroupNorm + GLU on load; bypass + mask encoder + decoder taps in one launch
+
+  std::vector<int> enc_cin, enc_cout;      // per encoder block
+  std::vector<int> dec_cin, dec_cout, dec_stride;   // per decoder block, in execution order
+  int stride_product = 1;
+
+  DevBuf pre_w, pre_b;
+  std::vector<EncBlock> enc;
+  std::vector<DecBlock> dec;
+  WBuf byp_wt, mask_wt, dec_wt;
+  WBuf byp_wt48;                           // bypass kernel padded to 48 taps, fragment order (fused mask path)
+  DevBuf byp_b, mask_b;
+  float out_bias = 0.f;
+  int byp_k = 0;                           // padded K of the bypass GEMM
+
+  const std::vector<float>& P(const std::string& k) const { return raw.at(k); }
+
+  // ---- create: the device, the derived shape and its checks
+  int init_shape(const TrunkCfg& c, const char* who) {
+    tc = c;
+    ASW_HIP(hipGetDevice(&device));
+    int cin = c.channels, ch = c.channels;
+    for (int i = 0; i < c.depth; ++i) {
+      ASW_CHECK_ARG(c.stride_list[i] >= 1, "%s: stride", who);
+      enc_cin.push_back(cin);
+      enc_cout.push_back(ch);
+      stride_product *= c.stride_list[i];
+      cin = ch;
+      ch *= c.growth;
+    }
+    // decoder blocks in execution order (network.py:221-231 inserts at the front): the encoder's, mirrored
+    dec_cin.assign(enc_cout.rbegin(), enc_cout.rend());
+    dec_cout.assign(enc_cin.rbegin(), enc_cin.rend());
+    dec_stride.assign(std::make_reverse_iterator(c.stride_list + c.depth), std::make_reverse_iterator(c.stride_list));
+    return ASW_OK;
+  }
+  // the last check of create, after the network's bottleneck-width check, which a bad growth or channel count fails first
+  int check_level_widths(const char* who) const {
+    for (int w : enc_cin) ASW_CHECK_ARG(w <= 512 && (w & (w - 1)) == 0, "%s: level width %d must be a power of two <= 512", who, w);
+    return ASW_OK;
+  }
+
+  // ---- finalize
+  ParamList trunk_params() const {
+    ParamList v;
+    const size_t K = tc.kernel_size;
+    v.push_back({"preproc.weight", (size_t)tc.channels * tc.n_mics});
+    v.push_back({"preproc.bias", (size_t)tc.channels});
+    auto res = [&](const std::string& p, size_t ch) {
+      for (int j = 0; j < tc.residual_layers; ++j) {
+        const std::string q = p + ".res.seq." + std::to_string(j);
+        v.push_back({q + ".conv.weight", ch * ch * K});
+        v.push_back({q + ".conv.bias", ch});
+        v.push_back({q + ".norm.weight", ch});
+        v.push_back({q + ".norm.bias", ch});
+      }
+    };
+    for (int i = 0; i < tc.depth; ++i) {
+      const std::string p = "encoder.module_list." + std::to_string(i);
+      const size_t ci = enc_cin[i], co = enc_cout[i];
+      res(p, ci);
+      v.push_back({p + ".conv1.weight", 2 * co * ci * K});
+      v.push_back({p + ".conv1.bias", 2 * co});
+      v.push_back({p + ".norm1.weight", 2 * co});
+      v.push_back({p + ".norm1.bias", 2 * co});
+    }
+    for (int i = 0; i < tc.depth; ++i) {
+      const std::string p = "decoder.module_list." + std::to_string(i);
+      const size_t ci = dec_cin[i], co = dec_cout[i], s = dec_stride[i];
+      v.push_back({p + ".upsample.conv.weight", ci * 2 * co * s});
+      v.push_back({p + ".upsample.conv.bias", 2 * co});
+      v.push_back({p + ".norm1.weight", 2 * co});
+      v.push_back({p + ".norm1.bias", 2 * co});
+      res(p, co);
+    }
+    const size_t E = tc.encoder_channels, EK = tc.encoder_kernel_size;
+    v.push_back({"reference_bypass.weight", E * EK});
+    v.push_back({"reference_bypass.bias", E});
+    v.push_back({"mask_encoder.weight", E * tc.channels * EK});
+    v.push_back({"mask_encoder.bias", E});
+    v.push_back({"output_decoder.weight", E * EK});
+    v.push_back({"output_decoder.bias", 1});
+    return v;
+  }
+
+  // The device check, the strict check of the state dict against `want` (the trunk's keys and the network's own), then
+  // the trunk weights that no gate touches.
+  int finalize_trunk(const char* who, const ParamList& want) {
+    {
+      int dev = -1;
+      ASW_HIP(hipGetDevice(&dev));
+      if (dev != device)
+        return asw::set_error(ASW_ERR_STATE, "%s: model was created on HIP device %d, current device is %d", who, device, dev);
+    }
+    for (const auto& kv : want) {
+      auto it = raw.find(kv.first);
+      if (it == raw.end()) return asw::set_error(ASW_ERR_STATE, "state dict is missing key %s", kv.first.c_str());
+      if (it->second.size() != kv.second)
+        return asw::set_error(ASW_ERR_ARG, "%s: %zu elements, expected %zu", kv.first.c_str(), it->second.size(), kv.second);
+    }
+    if (raw.size() != want.size())
+      return asw::set_error(ASW_ERR_ARG, "state dict has %zu unexpected keys", raw.size() - want.size());
+    int rc;
+    const int K = tc.kernel_size, RL = tc.residual_layers, RD = tc.residual_dilation_factor;
+    UP(pre_w, P("preproc.weight"));
+    UP(pre_b, P("preproc.bias"));
+    enc.clear(); enc.resize(tc.depth);
+    dec.clear(); dec.resize(tc.depth);
+    for (int i = 0; i < tc.depth; ++i) {
+      const std::string p = "encoder.module_list." + std::to_string(i);
+      if ((rc = pack_res_layers(raw, p, enc_cin[i], K, RL, RD, enc[i].res))) return rc;
+      UP(enc[i].bias, P(p + ".conv1.bias"));
+      UP(enc[i].gn_g, P(p + ".norm1.weight"));
+      UP(enc[i].gn_b, P(p + ".norm1.bias"));
+    }
+    for (int i = 0; i < tc.depth; ++i) {
+      const std::string p = "decoder.module_list." + std::to_string(i);
+      if ((rc = pack_res_layers(raw, p, dec_cout[i], K, RL, RD, dec[i].res))) return rc;
+      UP(dec[i].gn_g, P(p + ".norm1.weight"));
+      UP(dec[i].gn_b, P(p + ".norm1.bias"));
+    }
+    const int E = tc.encoder_channels, EK = tc.encoder_kernel_size;
+    byp_k = ((EK + 31) / 32) * 32;
+    {
+      const std::vector<float>& w = P("reference_bypass.weight");   // [E][1][EK]
+      std::vector<float> wt((size_t)E * byp_k, 0.f);
+      for (int n = 0; n < E; ++n)
+        for (int k = 0; k < EK; ++k) wt[(size_t)n * byp_k + k] = w[(size_t)n * EK + k];
+      UP(byp_wt, wt);
+      UP(byp_b, P("reference_bypass.bias"));
+      if (E % 32 == 0 && EK <= 48) {
+        std::vector<float> w48((size_t)E * 48, 0.f);
+        for (int n = 0; n < E; ++n)
+          for (int k = 0; k < EK; ++k) w48[(size_t)n * 48 + k] = w[(size_t)n * EK + k];
+        if ((rc = byp_wt48.upload_gemm(w48, E, 48))) return rc;
+      }
+    }
+    if ((rc = mask_wt.upload_gemm(pack_conv(P("mask_encoder.weight"), E, tc.channels, EK, nullptr), E, tc.channels * EK))) return rc;
+    UP(mask_b, P("mask_encoder.bias"));
+    {
+      const std::vector<float>& w = P("output_decoder.weight");     // [E][1][EK]
+      std::vector<float> wt((size_t)64 * E, 0.f);
+      for (int j = 0; j < EK; ++j)
+        for (int e = 0; e < E; ++e) wt[(size_t)j * E + e] = w[(size_t)e * EK + j];
+      if ((rc = dec_wt.upload_gemm(wt, 64, E))) return rc;
+      out_bias = P("output_decoder.bias")[0];
+    }
+    return ASW_OK;
+  }
+
+  // gate(p): the gate of block p ("encoder.module_list.i" / "decoder.module_list.j"), empty for none
+  template <class Gate>
+  int pack_gated(GatedConvs& o, Gate gate) const {
+    const int K = tc.kernel_size;
+    int rc;
+    o.down_wt.clear(); o.down_wt.resize(tc.depth);
+    o.up_wt.clear(); o.up_wt.resize(tc.depth);
+    o.up_bias.clear(); o.up_bias.resize(tc.depth);
+    for (int i = 0; i < tc.depth; ++i) {
+      const std::string p = "encoder.module_list." + std::to_string(i);
+      const std::vector<float> g = gate(p);
+      const int n = 2 * enc_cout[i], ci = enc_cin[i];
+      if ((rc = o.down_wt[i].upload_gemm(pack_conv(P(p + ".conv1.weight"), n, ci, K, g.empty() ? nullptr : g.data()), n, ci * K)))
+        return rc;
+    }
+    for (int j = 0; j < tc.depth; ++j) {
+      const std::string p = "decoder.module_list." + std::to_string(j);
+      const std::vector<float> g = gate(p);
+      const int ci = dec_cin[j], co2 = 2 * dec_cout[j], s = dec_stride[j];
+      std::vector<float> wt, bb;
+      pack_conv_transpose(P(p + ".upsample.conv.weight"), P(p + ".upsample.conv.bias"), ci, co2, s,
+                          g.empty() ? nullptr : g.data(), wt, bb);
+      if ((rc = o.up_wt[j].upload_gemm(wt, s * co2, ci))) return rc;
+      UP(o.up_bias[j], bb);
+    }
+    return ASW_OK;
+  }
+
+  // ---- workspace
+  // The one-launch mask path (asw_mask_path_f16x3) applies in f16x3 mode when the shapes fit its tiles.
+  bool fused_mask_path() const {
+    return fuse_mask && precision >= 1 && tc.encoder_channels % 256 == 0 && tc.channels % 32 == 0 &&
+           tc.encoder_kernel_size <= 48 && tc.encoder_stride % 4 == 0 && byp_wt48.fhi && dec_wt.fhi && mask_wt.fhi;
+  }
+  // the shape of a batch of B sequences of T samples and its level buffers: the head of the workspace
+  void layout_levels(int B, int T, Arena& a, TrunkPlan& pl) const {
+    const int depth = tc.depth, EK = tc.encoder_kernel_size, ES = tc.encoder_stride;
+    pl.B = B; pl.T = T;
+    pl.Tp = ((T - 1) / stride_product + 1) * stride_product;
+    pl.F = (pl.Tp + 2 * (EK / 2) - EK) / ES + 1;
+    pl.RL = ((EK / 2 + pl.Tp + byp_k + 64) + 3) & ~3;
+    pl.Tl.assign(depth + 1, pl.Tp);
+    for (int i = 0; i < depth; ++i) pl.Tl[i + 1] = pl.Tl[i] / tc.stride_list[i];
+    pl.mean = a.take<float>(B);
+    pl.stdv = a.take<float>(B);
+    pl.refn = a.take<float>((size_t)B * pl.RL);
+    pl.X.resize(depth + 1); pl.Pb.resize(depth); pl.Qb.resize(depth);
+    pl.raw_dn.resize(depth); pl.raw_up.resize(depth); pl.st_dn.resize(depth); pl.st_up.resize(depth);
+    pl.mr_up.resize(depth); pl.mr_dn.resize(depth);
+    for (int i = 0; i <= depth; ++i) {
+      const int ch = i == 0 ? tc.channels : enc_cout[i - 1];
+      pl.X[i] = a.take<float>((size_t)B * pl.Tl[i] * ch);
+    }
+    for (int i = 0; i < depth; ++i) {
+      const size_t n = (size_t)B * pl.Tl[i] * enc_cin[i];
+      pl.Pb[i] = a.take<float>(n);
+      pl.Qb[i] = a.take<float>(n);
+      pl.raw_dn[i] = a.take<float>((size_t)B * pl.Tl[i + 1] * 2 * enc_cout[i]);
+      pl.st_dn[i] = a.take<float>((size_t)B * 4 * asw_convgemm_stats_tiles(pl.Tl[i + 1], 2 * enc_cout[i]));
+      pl.mr_dn[i] = a.take<float>((size_t)B * 4);
+    }
+    for (int j = 0; j < depth; ++j) {
+      const int lvl = depth - j;             // input level of decoder block j
+      const int s = dec_stride[j], co2 = 2 * dec_cout[j];
+      pl.raw_up[j] = a.take<float>((size_t)B * pl.Tl[lvl] * s * co2);
+      pl.st_up[j] = a.take<float>((size_t)B * 4 * asw_convgemm_stats_tiles(pl.Tl[lvl], s * co2));
+      pl.mr_up[j] = a.take<float>((size_t)B * 4);
+    }
+  }
+  // the mask path's buffers, after the bottleneck's
+  void layout_mask(Arena& a, TrunkPlan& pl) const {
+    const int E = tc.encoder_channels;
+    const bool fused = fused_mask_path();
+    // fused mask path: no latent, one partial tap tensor per 256-channel column tile
+    pl.Y = fused ? nullptr : a.take<float>((size_t)pl.B * pl.F * E);
+    pl.D = a.take<float>((size_t)(fused ? E / 256 : 1) * pl.B * pl.F * 64);
+    pl.ywave = a.take<float>((size_t)pl.B * pl.T);
+  }
+
+  // ---- run; pl.X[0] / pl.refn are filled
+  // encoder (network.py:98-113,146-156): X[0] -> X[depth]
+  int encode(TrunkPlan& pl, const GatedConvs& g, hipStream_t s) {
+    const int B = pl.B, K = tc.kernel_size;
+    taps.clear();
+    taps["preproc"] = {pl.X[0], (size_t)B * pl.Tl[0] * tc.channels};
+    int rc;
+    GluSrc src = {};
+    bool glu = false;                        // X[i] is still un-normalised in raw_dn[i-1]: block i applies GroupNorm + GLU
+    for (int i = 0; i < tc.depth; ++i) {
+      float* r = nullptr;
+      if ((rc = run_res(enc[i].res, precision, B, pl.Tl[i], enc_cin[i], K, pl.X[i], pl.Pb[i], pl.Qb[i], &r, s,
+                        glu ? &src : nullptr)))
+        return rc;
+      asw_convgemm_args a = {};
+      a.A = r; g.down_wt[i].bind(a, precision); a.bias = enc[i].bias.p; a.out = pl.raw_dn[i]; a.stats = pl.st_dn[i];
+      a.B = B; a.M_out = pl.Tl[i + 1]; a.N = 2 * enc_cout[i]; a.Cin = enc_cin[i]; a.taps = K;
+      a.stride = tc.stride_list[i]; a.dil = 1; a.pad = K / 2;
+      a.a_row_stride = a.Cin; a.a_batch_stride = (int64_t)pl.Tl[i] * a.Cin; a.a_len = a.a_batch_stride;
+      a.chan_mod = a.N;
+      if ((rc = asw_convgemm_f32(&a, s))) return rc;
+      // the next block normalises while its first layer stages rows and writes X[i+1] (the skip connection the
+      // decoder reads) from the same registers: one pass over raw_dn less
+      glu = fuse_mask && i + 1 < tc.depth && glu_on_load_ok(enc[i + 1].res, precision, enc_cout[i]);
+      const int tiles = asw_convgemm_stats_tiles(a.M_out, a.N);
+      if (glu) {
+        if ((rc = asw_gn_finalize(pl.st_dn[i], tiles, B, pl.Tl[i + 1], enc_cout[i], 1e-5f, pl.mr_dn[i], s))) return rc;
+        src = {pl.raw_dn[i], pl.mr_dn[i], enc[i].gn_g.p, enc[i].gn_b.p, pl.X[i + 1]};
+      } else if ((rc = asw_gn_glu(pl.raw_dn[i], pl.st_dn[i], tiles, enc[i].gn_g.p, enc[i].gn_b.p, B, pl.Tl[i + 1],
+                                  enc_cout[i], 1e-5f, pl.X[i + 1], s))) {
+        return rc;
+      }
+      taps["enc" + std::to_string(i)] = {pl.X[i + 1], (size_t)B * pl.Tl[i + 1] * enc_cout[i]};
+    }
+    return ASW_OK;
+  }
+
+  // decoder (network.py:180-200,233-238): x, the bottleneck's output on entry, is the last block's output on return
+  int decode(TrunkPlan& pl, const GatedConvs& g, const float*& x, hipStream_t s) {
+    const int B = pl.B, K = tc.kernel_size;
+    int rc;
+    for (int j = 0; j < tc.depth; ++j) {
+      const int lvl = tc.depth - j, ci = dec_cin[j], co = dec_cout[j], st = dec_stride[j];
+      asw_convgemm_args a = {};
+      a.A = x; a.A2 = pl.X[lvl]; g.up_wt[j].bind(a, precision); a.bias = g.up_bias[j].p; a.out = pl.raw_up[j];
+      a.stats = pl.st_up[j];
+      a.B = B; a.M_out = pl.Tl[lvl]; a.N = st * 2 * co; a.Cin = ci; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
+      a.a_row_stride = ci; a.a_batch_stride = (int64_t)pl.Tl[lvl] * ci; a.a_len = a.a_batch_stride;
+      a.chan_mod = 2 * co;
+      if ((rc = asw_convgemm_f32(&a, s))) return rc;
+      const int To = pl.Tl[lvl] * st;        // == pl.Tl[lvl-1]
+      const int tiles = asw_convgemm_stats_tiles(a.M_out, a.N);
+      float* gb = pl.Qb[lvl - 1];
+      float* r = nullptr;
+      if (fuse_mask && glu_on_load_ok(dec[j].res, precision, co)) {
+        // GroupNorm + GLU happen while the first residual layer stages its rows: at 64 channels the normalised
+        // tensor is neither written nor read back (P -> gb -> P are the stack's own buffers), above that it is
+        // written once for the layer's residual instead of written and read twice
+        if ((rc = asw_gn_finalize(pl.st_up[j], tiles, B, To, co, 1e-5f, pl.mr_up[j], s))) return rc;
+        // (gb: free until the second layer writes it; the wide layers read their residual from there)
+        const GluSrc src = {pl.raw_up[j], pl.mr_up[j], dec[j].gn_g.p, dec[j].gn_b.p, co > 64 ? gb : nullptr};
+        if ((rc = run_res(dec[j].res, precision, B, To, co, K, gb, pl.Pb[lvl - 1], gb, &r, s, &src))) return rc;
+      } else {
+        if ((rc = asw_gn_glu(pl.raw_up[j], pl.st_up[j], tiles, dec[j].gn_g.p, dec[j].gn_b.p, B, To, co, 1e-5f, gb, s)))
+          return rc;
+        // residual ping-pong: gb -> P -> gb -> P ...
+        if ((rc = run_res(dec[j].res, precision, B, To, co, K, gb, pl.Pb[lvl - 1], gb, &r, s))) return rc;
+      }
+      x = r;
+      taps["dec" + std::to_string(j)] = {x, (size_t)B * To * co};
+    }
+    return ASW_OK;
+  }
+
+  // mask path (spot network.py:327-349,397-405): every sequence's mask gates the latent of its reference channel;
+  // x is the last decoder block's output
+  int mask_path(TrunkPlan& pl, const float* x, const float* mean, const float* stdv, float* out_wave, hipStream_t s) {
+    const int B = pl.B, C = tc.channels, E = tc.encoder_channels, EK = tc.encoder_kernel_size, ES = tc.encoder_stride;
+    int rc;
+    asw_convgemm_args me = {};    // mask_encoder
+    me.A = x; mask_wt.bind(me, precision); me.bias = mask_b.p;
+    me.B = B; me.M_out = pl.F; me.N = E; me.Cin = C; me.taps = EK; me.stride = ES; me.dil = 1; me.pad = EK / 2;
+    me.a_row_stride = C; me.a_batch_stride = (int64_t)pl.Tp * C; me.a_len = me.a_batch_stride;
+    if (fused_mask_path()) {
+      asw_maskpath_args f = {};
+      f.enc = me;
+      f.ref = pl.refn; f.ref_batch_stride = pl.RL; f.ref_len = pl.RL; f.ref_hop = ES;
+      f.byp_k = 48; f.byp_taps = EK; f.byp_shift = byp_wt48.shift; f.byp_hi = byp_wt48.fhi; f.byp_lo = byp_wt48.flo;
+      f.byp_bias = byp_b.p;
+      f.dec_hi = dec_wt.fhi; f.dec_lo = dec_wt.flo; f.dec_shift = dec_wt.shift; f.dec_taps = EK;
+      f.taps = pl.D;
+      if ((rc = asw_mask_path_f16x3(&f, s))) return rc;
+      return asw_overlap_add_parts(pl.D, E / 256, B, pl.F, 64, EK, EK / 2, pl.T, 9, 8, out_bias, mean, stdv, out_wave, s);
+    }
+    {
+      asw_convgemm_args a = {};   // reference_bypass: rows of the padded reference channel, hop ES
+      a.A = pl.refn; byp_wt.bind(a, precision); a.bias = byp_b.p; a.out = pl.Y;
+      a.B = B; a.M_out = pl.F; a.N = E; a.Cin = byp_k; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
+      a.a_row_stride = ES; a.a_batch_stride = pl.RL; a.a_len = pl.RL; a.relu = 1;
+      if ((rc = asw_convgemm_f32(&a, s))) return rc;
+    }
+    me.mul = pl.Y; me.out = pl.Y; me.relu = 1;   // mask_encoder, ReLU, times the bypass latent (in place)
+    if ((rc = asw_convgemm_f32(&me, s))) return rc;
+    taps["latent"] = {pl.Y, (size_t)B * pl.F * E};
+    {
+      asw_convgemm_args a = {};   // output_decoder taps: D[f][j] = sum_e latent[f][e] * w[e][j]
+      a.A = pl.Y; dec_wt.bind(a, precision); a.out = pl.D;
+      a.B = B; a.M_out = pl.F; a.N = 64; a.Cin = E; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
+      a.a_row_stride = E; a.a_batch_stride = (int64_t)pl.F * E; a.a_len = a.a_batch_stride;
+      if ((rc = asw_convgemm_f32(&a, s))) return rc;
+    }
+    return asw_overlap_add_unnorm(pl.D, B, pl.F, 64, EK, EK / 2, pl.T, 9, 8, out_bias, mean, stdv, out_wave, s);
+  }
+};
+
+// ---- the handle calls both networks share; `who` / `fin` name the entry point in the messages
+inline int check_ready(const Trunk* m, const char* fin) {
+  if (!m) return asw::set_error(ASW_ERR_ARG, "null model handle");
+  if (!m->finalized) return asw::set_error(ASW_ERR_STATE, "%s() has not been called", fin);
+  int dev = -1;
+  ASW_HIP(hipGetDevice(&dev));
+  if (dev != m->device)
+    return asw::set_error(ASW_ERR_STATE, "model lives on HIP device %d but the current device is %d", m->device, dev);
+  return ASW_OK;
+}
+
+inline int set_precision(Trunk* m, const char* who, int precision) {
+  ASW_CHECK_ARG(m && (precision >= 0 && precision <= 2), "%s: 0 (f32), 1 (f16x3) or 2 (single-pass f16)", who);
+  m->precision = precision;
+  return ASW_OK;
+}
+
+inline int set_param(Trunk* m, const char* who, const char* key, const float* host_data, size_t numel) {
+  ASW_CHECK_ARG(m && key && host_data, "%s: null pointer", who);
+  m->raw[key].assign(host_data, host_data + numel);
+  m->finalized = false;
+  return ASW_OK;
+}
+
+inline int get_tap(const Trunk* m, const char* who, const char* name, float* dst, size_t capacity, size_t* numel,
+                   void* stream) {
+  ASW_CHECK_ARG(m && name && numel, "%s: null pointer", who);
+  auto it = m->taps.find(name);
+  if (it == m->taps.end()) return asw::set_error(ASW_ERR_ARG, "%s: no activation named %s", who, name);
+  *numel = it->second.numel;
+  if (dst) {
+    ASW_CHECK_ARG(capacity >= it->second.numel, "%s: buffer too small", who);
+    ASW_HIP(hipMemcpyAsync(dst, it->second.p, it->second.numel * sizeof(float), hipMemcpyDeviceToDevice,
+                           asw::as_stream(stream)));
+  }
+  return ASW_OK;
+}
 
 }  // namespace asw_model

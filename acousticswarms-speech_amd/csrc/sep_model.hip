@@ -16,6 +16,9 @@
 // once at finalize: speechbrain's per-head (q,k,v) interleave of in_proj_weight is permuted to
 // Q | K | V; the macaron factor 1/2 is folded into the second feed-forward linear; the
 // depthwise kernel is stored tap-major.
+//
+// The U-Net trunk is model_common.h's Trunk, shared with the spot network; this file holds the
+// Conformer / inter-speaker bottleneck, the workspace policy and the C entry points.
 #include <cmath>
 #include <map>
 #include <memory>
@@ -30,8 +33,6 @@ extern "C" int asw_joint_shift_stats_scratch_doubles(void);
 
 namespace {
 
-struct EncBlock { std::vector<ResLayer> res; WBuf down_wt; DevBuf bias, gn_g, gn_b; };
-struct DecBlock { std::vector<ResLayer> res; WBuf up_wt; DevBuf up_bias, gn_g, gn_b; };
 struct Ffn { DevBuf lng, lnb, b1, b2; WBuf w1, w2; };                       // w2 / b2 carry the macaron 1/2
 struct ConfLayer {
   Ffn f1, f2;
@@ -42,70 +43,31 @@ struct ConfLayer {
   WBuf cm_pw, ac_w;
 };
 struct InterLayer { WBuf w_in, w_out, w1, w2; DevBuf b_in, b_out, b1, b2, n1g, n1b, n2g, n2b; };
-struct Tap { const float* p; size_t numel; };
 
 }  // namespace
 
-struct asw_sep {
+struct asw_sep : Trunk {
   asw_sep_config cfg;
-  std::map<std::string, std::vector<float>> raw;
-  bool finalized = false;
-  int device = 0;
-  int precision = 0;
-
-  std::vector<int> enc_cin, enc_cout, dec_cin, dec_cout, dec_stride;
-  int stride_product = 1;
-
-  DevBuf pre_w, pre_b;
-  std::vector<EncBlock> enc;
-  std::vector<DecBlock> dec;
+  GatedConvs convs;                         // down / up convolutions (no window gate in this network)
   std::vector<ConfLayer> conf;
   std::vector<InterLayer> inter;
-  WBuf byp_wt, mask_wt, dec_wt;
-  WBuf byp_wt48;                           // bypass kernel padded to 48 taps, fragment order (fused mask path)
-  DevBuf byp_b, mask_b;
-  float out_bias = 0.f;
-  int byp_k = 0;
   std::vector<float> inv_freq;
   DevBuf pe;                                // sinusoid table [2L-1][d] of the last sequence length
   int pe_L = 0;
 
   char* ws = nullptr;
   size_t ws_bytes = 0;
-  std::map<std::string, Tap> taps;
 
   ~asw_sep() { if (ws) (void)hipFree(ws); }
 };
 
 namespace {
 
-const std::vector<float>& P(const asw_sep* m, const std::string& k) { return m->raw.at(k); }
-
-std::vector<std::pair<std::string, size_t>> expected_params(const asw_sep* m) {
+// the trunk's keys, then the bottleneck's
+ParamList expected_params(const asw_sep* m) {
   const asw_sep_config& c = m->cfg;
-  std::vector<std::pair<std::string, size_t>> v;
-  const size_t K = c.kernel_size;
-  v.push_back({"preproc.weight", (size_t)c.channels * c.n_mics});
-  v.push_back({"preproc.bias", (size_t)c.channels});
-  auto res = [&](const std::string& p, size_t ch) {
-    for (int j = 0; j < c.residual_layers; ++j) {
-      const std::string q = p + ".res.seq." + std::to_string(j);
-      v.push_back({q + ".conv.weight", ch * ch * K});
-      v.push_back({q + ".conv.bias", ch});
-      v.push_back({q + ".norm.weight", ch});
-      v.push_back({q + ".norm.bias", ch});
-    }
-  };
-  for (int i = 0; i < c.depth; ++i) {
-    const std::string p = "encoder.module_list." + std::to_string(i);
-    const size_t ci = m->enc_cin[i], co = m->enc_cout[i];
-    res(p, ci);
-    v.push_back({p + ".conv1.weight", 2 * co * ci * K});
-    v.push_back({p + ".conv1.bias", 2 * co});
-    v.push_back({p + ".norm1.weight", 2 * co});
-    v.push_back({p + ".norm1.bias", 2 * co});
-  }
-  const size_t d = m->enc_cout.back(), f = c.ffw_dim, H = c.num_head, BK = c.bottleneck_ksize;
+  ParamList v = m->trunk_params();
+  const size_t d = m->enc_cout.back(), f = c.ffw_dim, BK = c.bottleneck_ksize;
   v.push_back({"bottleneck.pe_single.inv_freq", d / 2});
   for (int l = 0; l < c.bottleneck_layers; ++l) {
     const std::string cl = "bottleneck.module_list." + std::to_string(l) + ".intra.layers.0";
@@ -154,23 +116,6 @@ std::vector<std::pair<std::string, size_t>> expected_params(const asw_sep* m) {
     v.push_back({t + ".norm2.weight", d});
     v.push_back({t + ".norm2.bias", d});
   }
-  (void)H;
-  for (int i = 0; i < c.depth; ++i) {
-    const std::string p = "decoder.module_list." + std::to_string(i);
-    const size_t ci = m->dec_cin[i], co = m->dec_cout[i], s = m->dec_stride[i];
-    v.push_back({p + ".upsample.conv.weight", ci * 2 * co * s});
-    v.push_back({p + ".upsample.conv.bias", 2 * co});
-    v.push_back({p + ".norm1.weight", 2 * co});
-    v.push_back({p + ".norm1.bias", 2 * co});
-    res(p, co);
-  }
-  const size_t E = c.encoder_channels, EK = c.encoder_kernel_size;
-  v.push_back({"reference_bypass.weight", E * EK});
-  v.push_back({"reference_bypass.bias", E});
-  v.push_back({"mask_encoder.weight", E * c.channels * EK});
-  v.push_back({"mask_encoder.bias", E});
-  v.push_back({"output_decoder.weight", E * EK});
-  v.push_back({"output_decoder.bias", 1});
   return v;
 }
 
@@ -181,62 +126,19 @@ std::vector<float> scaled(const std::vector<float>& w, float a) {
 }
 
 // ---- workspace ---------------------------------------------------------------------------
-struct Plan {
-  int NB, S, BS, T, Tp, F, RL, depth, L, d;
-  std::vector<int> Tl;
-  float *mean, *stdv, *refn;
+struct Plan : TrunkPlan {
+  int NB, S, L, d;                            // B = NB * S sequences
   double* jscr;
-  std::vector<float*> X, Pb, Qb, raw_dn, raw_up, st_dn, st_up, mr_up, mr_dn;
   std::vector<float*> intra_out, inter_out;   // per bottleneck layer (kept apart so every tap stays readable)
   float *h, *g, *x1, *x2, *x3, *qkv, *ctx, *raw2, *u, *v2, *y, *f, *pos;
-  float *Y, *D, *ywave;
   const int32_t* counts = nullptr;            // host [NB]: speakers present per item (NULL: S everywhere), forward() only
 };
 
-// The one-launch mask path (asw_mask_path_f16x3) applies in f16x3 mode when the shapes fit its tiles.
-bool fused_mask_path(const asw_sep* m) {
-  const asw_sep_config& c = m->cfg;
-  return m->precision >= 1 && c.encoder_channels % 256 == 0 && c.channels % 32 == 0 && c.encoder_kernel_size <= 48 &&
-         c.encoder_stride % 4 == 0 && m->byp_wt48.fhi && m->dec_wt.fhi && m->mask_wt.fhi;
-}
-
 void layout(const asw_sep* m, int NB, int S, int T, Arena& a, Plan& pl) {
   const asw_sep_config& c = m->cfg;
-  const int BS = NB * S;
-  pl.NB = NB; pl.S = S; pl.BS = BS; pl.T = T; pl.depth = c.depth;
-  pl.Tp = ((T - 1) / m->stride_product + 1) * m->stride_product;
-  const int EK = c.encoder_kernel_size, ES = c.encoder_stride;
-  pl.F = (pl.Tp + 2 * (EK / 2) - EK) / ES + 1;
-  pl.RL = ((EK / 2 + pl.Tp + m->byp_k + 64) + 3) & ~3;
-  pl.Tl.assign(c.depth + 1, pl.Tp);
-  for (int i = 0; i < c.depth; ++i) pl.Tl[i + 1] = pl.Tl[i] / c.stride_list[i];
-  pl.mean = a.take<float>(BS);
-  pl.stdv = a.take<float>(BS);
-  pl.jscr = a.take<double>(asw_joint_shift_stats_scratch_doubles());
-  pl.refn = a.take<float>((size_t)BS * pl.RL);
-  pl.X.resize(c.depth + 1); pl.Pb.resize(c.depth); pl.Qb.resize(c.depth);
-  pl.raw_dn.resize(c.depth); pl.raw_up.resize(c.depth); pl.st_dn.resize(c.depth); pl.st_up.resize(c.depth);
-  pl.mr_up.resize(c.depth); pl.mr_dn.resize(c.depth);
-  for (int i = 0; i <= c.depth; ++i) {
-    const int ch = i == 0 ? c.channels : m->enc_cout[i - 1];
-    pl.X[i] = a.take<float>((size_t)BS * pl.Tl[i] * ch);
-  }
-  for (int i = 0; i < c.depth; ++i) {
-    const size_t n = (size_t)BS * pl.Tl[i] * m->enc_cin[i];
-    pl.Pb[i] = a.take<float>(n);
-    pl.Qb[i] = a.take<float>(n);
-    pl.raw_dn[i] = a.take<float>((size_t)BS * pl.Tl[i + 1] * 2 * m->enc_cout[i]);
-    pl.st_dn[i] = a.take<float>((size_t)BS * 4 * asw_convgemm_stats_tiles(pl.Tl[i + 1], 2 * m->enc_cout[i]));
-    pl.mr_dn[i] = a.take<float>((size_t)BS * 4);
-  }
-  for (int j = 0; j < c.depth; ++j) {
-    const int lvl = c.depth - j;
-    const int s = m->dec_stride[j], co2 = 2 * m->dec_cout[j];
-    pl.raw_up[j] = a.take<float>((size_t)BS * pl.Tl[lvl] * s * co2);
-    pl.st_up[j] = a.take<float>((size_t)BS * 4 * asw_convgemm_stats_tiles(pl.Tl[lvl], s * co2));
-    pl.mr_up[j] = a.take<float>((size_t)BS * 4);
-  }
-  const size_t L = pl.Tl[c.depth], d = m->enc_cout.back(), rows = (size_t)BS * L;
+  pl.NB = NB; pl.S = S;
+  m->layout_levels(NB * S, T, a, pl);
+  const size_t L = pl.Tl[c.depth], d = m->enc_cout.back(), rows = (size_t)pl.B * L;
   pl.L = (int)L; pl.d = (int)d;
   pl.intra_out.resize(c.bottleneck_layers); pl.inter_out.resize(c.bottleneck_layers);
   for (int l = 0; l < c.bottleneck_layers; ++l) { pl.intra_out[l] = a.take<float>(rows * d); pl.inter_out[l] = a.take<float>(rows * d); }
@@ -246,10 +148,8 @@ void layout(const asw_sep* m, int NB, int S, int T, Arena& a, Plan& pl) {
   pl.raw2 = a.take<float>(rows * 2 * d);
   pl.f = a.take<float>(rows * c.ffw_dim);
   pl.pos = a.take<float>((2 * L - 1) * d);
-  const bool fused = fused_mask_path(m);
-  pl.Y = fused ? nullptr : a.take<float>((size_t)BS * pl.F * c.encoder_channels);
-  pl.D = a.take<float>((size_t)(fused ? c.encoder_channels / 256 : 1) * BS * pl.F * 64);
-  pl.ywave = a.take<float>((size_t)BS * T);
+  m->layout_mask(a, pl);
+  pl.jscr = a.take<double>(asw_joint_shift_stats_scratch_doubles());
 }
 
 int ensure_ws(asw_sep* m, int NB, int S, int T, Plan& pl) {
@@ -304,7 +204,7 @@ int ffn_first(const Ffn& f, int prec, const float* hin, int rows, int d, int ffw
 // one Conformer layer along time for the BS sequences: x -> out (both [BS*L][d])
 int run_conformer(asw_sep* m, Plan& pl, ConfLayer& c, const float* x, float* out, hipStream_t s) {
   const asw_sep_config& cfg = m->cfg;
-  const int rows = pl.BS * pl.L, d = pl.d, ffw = cfg.ffw_dim, prec = m->precision;
+  const int rows = pl.B * pl.L, d = pl.d, ffw = cfg.ffw_dim, prec = m->precision;
   int rc;
   // x1 = x + FFN1(x)/2
   if ((rc = asw_add_layernorm2(x, nullptr, 0.f, c.f1.lng.p, c.f1.lnb.p, rows, d, 1e-5f, 0, nullptr, pl.h, s))) return rc;
@@ -314,14 +214,14 @@ int run_conformer(asw_sep* m, Plan& pl, ConfLayer& c, const float* x, float* out
   // x2 = x1 + MHA(norm1(x1))
   if ((rc = linear(pl.h, c.w_in, prec, nullptr, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
   if ((rc = linear(m->pe.p, c.w_pos, prec, nullptr, 2 * pl.L - 1, d, d, 0, nullptr, nullptr, nullptr, pl.pos, s))) return rc;
-  if ((rc = asw_relpos_attention(pl.qkv, pl.pos, c.bu.p, c.bv.p, pl.BS, pl.L, d, cfg.num_head, 1.0f / sqrtf((float)d), pl.ctx, s)))
+  if ((rc = asw_relpos_attention(pl.qkv, pl.pos, c.bu.p, c.bv.p, pl.B, pl.L, d, cfg.num_head, 1.0f / sqrtf((float)d), pl.ctx, s)))
     return rc;
   if ((rc = linear(pl.ctx, c.w_out, prec, c.b_out.p, rows, d, d, 0, nullptr, nullptr, nullptr, pl.g, s))) return rc;
   if ((rc = asw_add_layernorm2(pl.x1, pl.g, 1.f, c.cm_lng.p, c.cm_lnb.p, rows, d, 1e-5f, 0, pl.x2, pl.h, s))) return rc;
   // x3 = x2 + ConvolutionModule(x2)
   if ((rc = linear(pl.h, c.cm_pw, prec, c.cm_pwb.p, rows, 2 * d, d, 0, nullptr, nullptr, nullptr, pl.raw2, s))) return rc;
   if ((rc = asw_glu_rows(pl.raw2, rows, d, pl.u, s))) return rc;
-  if ((rc = asw_dwconv_ln_swish(pl.u, c.dw_wT.p, c.dw_b.p, c.ac_lng.p, c.ac_lnb.p, pl.BS, pl.L, d, cfg.bottleneck_ksize, 1e-5f,
+  if ((rc = asw_dwconv_ln_swish(pl.u, c.dw_wT.p, c.dw_b.p, c.ac_lng.p, c.ac_lnb.p, pl.B, pl.L, d, cfg.bottleneck_ksize, 1e-5f,
                                 pl.v2, s)))
     return rc;
   if ((rc = linear(pl.v2, c.ac_w, prec, c.ac_b.p, rows, d, d, 0, nullptr, nullptr, nullptr, pl.g, s))) return rc;
@@ -334,7 +234,7 @@ int run_conformer(asw_sep* m, Plan& pl, ConfLayer& c, const float* x, float* out
 
 // post-norm transformer layer across the S speakers of every time step: x -> out
 int run_inter(asw_sep* m, Plan& pl, InterLayer& t, const float* x, float* out, hipStream_t s) {
-  const int rows = pl.BS * pl.L, d = pl.d, ffw = m->cfg.ffw_dim, prec = m->precision;
+  const int rows = pl.B * pl.L, d = pl.d, ffw = m->cfg.ffw_dim, prec = m->precision;
   int rc;
   if ((rc = linear(x, t.w_in, prec, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
   if ((rc = asw_inter_attention(pl.qkv, pl.NB, pl.S, pl.L, d, m->cfg.num_head, pl.ctx, s))) return rc;
@@ -346,36 +246,9 @@ int run_inter(asw_sep* m, Plan& pl, InterLayer& t, const float* x, float* out, h
 // everything after the preproc stage; pl.X[0] / pl.refn are filled
 int run_network(asw_sep* m, Plan& pl, const float* mean, const float* stdv, float* out_wave, hipStream_t s) {
   const asw_sep_config& c = m->cfg;
-  const int B = pl.BS, K = c.kernel_size;
-  m->taps.clear();
+  const int B = pl.B;
   int rc;
-  // ---- encoder (:84-156)
-  GluSrc enc_src = {};
-  bool enc_glu = false;                       // as in spot_model.hip: block i normalises raw_dn[i-1] while it stages
-  for (int i = 0; i < c.depth; ++i) {
-    float* r = nullptr;
-    if ((rc = run_res(m->enc[i].res, m->precision, B, pl.Tl[i], m->enc_cin[i], K, pl.X[i], pl.Pb[i], pl.Qb[i], &r, s,
-                      enc_glu ? &enc_src : nullptr)))
-      return rc;
-    asw_convgemm_args a = {};
-    a.A = r; m->enc[i].down_wt.bind(a, m->precision); a.bias = m->enc[i].bias.p; a.out = pl.raw_dn[i]; a.stats = pl.st_dn[i];
-    a.B = B; a.M_out = pl.Tl[i + 1]; a.N = 2 * m->enc_cout[i]; a.Cin = m->enc_cin[i]; a.taps = K;
-    a.stride = c.stride_list[i]; a.dil = 1; a.pad = K / 2;
-    a.a_row_stride = a.Cin; a.a_batch_stride = (int64_t)pl.Tl[i] * a.Cin; a.a_len = a.a_batch_stride;
-    a.chan_mod = a.N;
-    if ((rc = asw_convgemm_f32(&a, s))) return rc;
-    enc_glu = i + 1 < c.depth && glu_on_load_ok(m->enc[i + 1].res, m->precision, m->enc_cout[i]);
-    if (enc_glu) {
-      if ((rc = asw_gn_finalize(pl.st_dn[i], asw_convgemm_stats_tiles(a.M_out, a.N), B, pl.Tl[i + 1], m->enc_cout[i], 1e-5f,
-                                pl.mr_dn[i], s)))
-        return rc;
-      enc_src = {pl.raw_dn[i], pl.mr_dn[i], m->enc[i].gn_g.p, m->enc[i].gn_b.p, pl.X[i + 1]};
-    } else if ((rc = asw_gn_glu(pl.raw_dn[i], pl.st_dn[i], asw_convgemm_stats_tiles(a.M_out, a.N), m->enc[i].gn_g.p,
-                                m->enc[i].gn_b.p, B, pl.Tl[i + 1], m->enc_cout[i], 1e-5f, pl.X[i + 1], s))) {
-      return rc;
-    }
-    m->taps["enc" + std::to_string(i)] = {pl.X[i + 1], (size_t)B * pl.Tl[i + 1] * m->enc_cout[i]};
-  }
+  if ((rc = m->encode(pl, m->convs, s))) return rc;
   // ---- bottleneck (:296-321): [BS][L][d] is already the (B*S, T, F) layout of the Conformer and,
   // row for row, the (N*T, S, F) layout of the inter-speaker layer
   if ((rc = ensure_pos_table(m, pl.L))) return rc;
@@ -396,83 +269,8 @@ int run_network(asw_sep* m, Plan& pl, const float* mean, const float* stdv, floa
     x = pl.inter_out[l];
   }
   m->taps["bottleneck"] = {x, (size_t)B * pl.L * pl.d};
-  // ---- decoder (:204-238)
-  for (int j = 0; j < c.depth; ++j) {
-    const int lvl = c.depth - j, ci = m->dec_cin[j], co = m->dec_cout[j], st = m->dec_stride[j];
-    asw_convgemm_args a = {};
-    a.A = x; a.A2 = pl.X[lvl]; m->dec[j].up_wt.bind(a, m->precision); a.bias = m->dec[j].up_bias.p; a.out = pl.raw_up[j];
-    a.stats = pl.st_up[j];
-    a.B = B; a.M_out = pl.Tl[lvl]; a.N = st * 2 * co; a.Cin = ci; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
-    a.a_row_stride = ci; a.a_batch_stride = (int64_t)pl.Tl[lvl] * ci; a.a_len = a.a_batch_stride;
-    a.chan_mod = 2 * co;
-    if ((rc = asw_convgemm_f32(&a, s))) return rc;
-    const int To = pl.Tl[lvl] * st;
-    float* g = pl.Qb[lvl - 1];
-    float* r = nullptr;
-    if (true && glu_on_load_ok(m->dec[j].res, m->precision, co)) {
-      // GroupNorm + GLU happen while the first residual layer stages its rows (spot_model.hip, same place)
-      if ((rc = asw_gn_finalize(pl.st_up[j], asw_convgemm_stats_tiles(a.M_out, a.N), B, To, co, 1e-5f, pl.mr_up[j], s))) return rc;
-      const GluSrc src = {pl.raw_up[j], pl.mr_up[j], m->dec[j].gn_g.p, m->dec[j].gn_b.p, co > 64 ? g : nullptr};
-      if ((rc = run_res(m->dec[j].res, m->precision, B, To, co, K, g, pl.Pb[lvl - 1], g, &r, s, &src))) return rc;
-    } else {
-      if ((rc = asw_gn_glu(pl.raw_up[j], pl.st_up[j], asw_convgemm_stats_tiles(a.M_out, a.N), m->dec[j].gn_g.p,
-                           m->dec[j].gn_b.p, B, To, co, 1e-5f, g, s)))
-        return rc;
-      // residual ping-pong: g -> P -> g -> P ...
-      if ((rc = run_res(m->dec[j].res, m->precision, B, To, co, K, g, pl.Pb[lvl - 1], g, &r, s))) return rc;
-    }
-    x = r;
-    m->taps["dec" + std::to_string(j)] = {x, (size_t)B * To * co};
-  }
-  // ---- mask path (:457-484): every speaker's mask gates the latent of the shared reference channel
-  const int E = c.encoder_channels, EK = c.encoder_kernel_size, ES = c.encoder_stride;
-  if (fused_mask_path(m)) {
-    asw_maskpath_args f = {};
-    asw_convgemm_args& a = f.enc;
-    a.A = x; m->mask_wt.bind(a, m->precision); a.bias = m->mask_b.p;
-    a.B = B; a.M_out = pl.F; a.N = E; a.Cin = c.channels; a.taps = EK; a.stride = ES; a.dil = 1; a.pad = EK / 2;
-    a.a_row_stride = c.channels; a.a_batch_stride = (int64_t)pl.Tp * c.channels; a.a_len = a.a_batch_stride;
-    f.ref = pl.refn; f.ref_batch_stride = pl.RL; f.ref_len = pl.RL; f.ref_hop = ES;
-    f.byp_k = 48; f.byp_taps = EK; f.byp_shift = m->byp_wt48.shift; f.byp_hi = m->byp_wt48.fhi; f.byp_lo = m->byp_wt48.flo;
-    f.byp_bias = m->byp_b.p;
-    f.dec_hi = m->dec_wt.fhi; f.dec_lo = m->dec_wt.flo; f.dec_shift = m->dec_wt.shift; f.dec_taps = EK;
-    f.taps = pl.D;
-    if ((rc = asw_mask_path_f16x3(&f, s))) return rc;
-    return asw_overlap_add_parts(pl.D, E / 256, B, pl.F, 64, EK, EK / 2, pl.T, 9, 8, m->out_bias, mean, stdv, out_wave, s);
-  }
-  {
-    asw_convgemm_args a = {};
-    a.A = pl.refn; m->byp_wt.bind(a, m->precision); a.bias = m->byp_b.p; a.out = pl.Y;
-    a.B = B; a.M_out = pl.F; a.N = E; a.Cin = m->byp_k; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
-    a.a_row_stride = ES; a.a_batch_stride = pl.RL; a.a_len = pl.RL; a.relu = 1;
-    if ((rc = asw_convgemm_f32(&a, s))) return rc;
-  }
-  {
-    asw_convgemm_args a = {};
-    a.A = x; m->mask_wt.bind(a, m->precision); a.bias = m->mask_b.p; a.mul = pl.Y; a.out = pl.Y;
-    a.B = B; a.M_out = pl.F; a.N = E; a.Cin = c.channels; a.taps = EK; a.stride = ES; a.dil = 1; a.pad = EK / 2;
-    a.a_row_stride = c.channels; a.a_batch_stride = (int64_t)pl.Tp * c.channels; a.a_len = a.a_batch_stride;
-    a.relu = 1;
-    if ((rc = asw_convgemm_f32(&a, s))) return rc;
-  }
-  {
-    asw_convgemm_args a = {};
-    a.A = pl.Y; m->dec_wt.bind(a, m->precision); a.out = pl.D;
-    a.B = B; a.M_out = pl.F; a.N = 64; a.Cin = E; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
-    a.a_row_stride = E; a.a_batch_stride = (int64_t)pl.F * E; a.a_len = a.a_batch_stride;
-    if ((rc = asw_convgemm_f32(&a, s))) return rc;
-  }
-  return asw_overlap_add_unnorm(pl.D, B, pl.F, 64, EK, EK / 2, pl.T, 9, 8, m->out_bias, mean, stdv, out_wave, s);
-}
-
-int check_ready(const asw_sep* m) {
-  if (!m) return asw::set_error(ASW_ERR_ARG, "null model handle");
-  if (!m->finalized) return asw::set_error(ASW_ERR_STATE, "asw_sep_finalize() has not been called");
-  int dev = -1;
-  ASW_HIP(hipGetDevice(&dev));
-  if (dev != m->device)
-    return asw::set_error(ASW_ERR_STATE, "model lives on HIP device %d but the current device is %d", m->device, dev);
-  return ASW_OK;
+  if ((rc = m->decode(pl, m->convs, x, s))) return rc;
+  return m->mask_path(pl, x, mean, stdv, out_wave, s);
 }
 
 }  // namespace
@@ -480,121 +278,40 @@ int check_ready(const asw_sep* m) {
 extern "C" int asw_sep_create(const asw_sep_config* cfg, asw_sep** out) {
   ASW_CHECK_ARG(cfg && out, "sep_create: null pointer");
   const asw_sep_config& c = *cfg;
-  ASW_CHECK_ARG(c.depth >= 1 && c.depth <= 8, "sep_create: depth %d", c.depth);
-  ASW_CHECK_ARG(c.n_mics >= 1 && c.n_mics <= 32, "sep_create: n_mics %d", c.n_mics);
+  const TrunkCfg tc = TrunkCfg::of(c);
+  int rc = check_trunk_config(tc, "sep_create", "kernel sizes must be odd");
+  if (rc) return rc;
   ASW_CHECK_ARG(c.max_speakers >= 1 && c.max_speakers <= 64, "sep_create: max_speakers %d", c.max_speakers);
-  ASW_CHECK_ARG(c.channels % 64 == 0, "sep_create: channels=%d must be a multiple of 64 for the MFMA tiles", c.channels);
-  ASW_CHECK_ARG(c.growth >= 1 && c.residual_layers >= 1 && c.bottleneck_layers >= 0, "sep_create: bad config");
-  ASW_CHECK_ARG(c.kernel_size % 2 == 1 && c.bottleneck_ksize % 2 == 1, "sep_create: kernel sizes must be odd");
-  ASW_CHECK_ARG(c.encoder_channels % 128 == 0, "sep_create: encoder_channels must be a multiple of 128");
-  ASW_CHECK_ARG(c.encoder_stride % 4 == 0 && c.encoder_kernel_size / 2 == c.encoder_stride && c.encoder_kernel_size <= 64,
-                "sep_create: encoder kernel/stride %d/%d unsupported (the reference's trim [9:-8] assumes 33/16)",
-                c.encoder_kernel_size, c.encoder_stride);
-  ASW_CHECK_ARG(c.ffw_dim % 128 == 0, "sep_create: ffw_dim must be a multiple of 128");
+  ASW_CHECK_ARG(c.bottleneck_layers >= 0, "sep_create: bad config");
+  ASW_CHECK_ARG(c.bottleneck_ksize % 2 == 1, "sep_create: kernel sizes must be odd");
   std::unique_ptr<asw_sep> m(new asw_sep());
   m->cfg = c;
-  ASW_HIP(hipGetDevice(&m->device));
-  int cin = c.channels, ch = c.channels;
-  for (int i = 0; i < c.depth; ++i) {
-    ASW_CHECK_ARG(c.stride_list[i] >= 1, "sep_create: stride");
-    m->enc_cin.push_back(cin);
-    m->enc_cout.push_back(ch);
-    m->stride_product *= c.stride_list[i];
-    cin = ch;
-    ch *= c.growth;
-  }
-  cin = c.channels; ch = c.channels;
-  for (int i = 0; i < c.depth; ++i) {                   // decoder blocks in execution order (:221-231)
-    m->dec_cin.insert(m->dec_cin.begin(), ch);
-    m->dec_cout.insert(m->dec_cout.begin(), cin);
-    m->dec_stride.insert(m->dec_stride.begin(), c.stride_list[i]);
-    cin = ch;
-    ch *= c.growth;
-  }
+  if ((rc = m->init_shape(tc, "sep_create"))) return rc;
   const int d = m->enc_cout.back();
   ASW_CHECK_ARG(d <= 1024 && (d & (d - 1)) == 0 && d >= 128, "sep_create: bottleneck width %d must be a power of two in 128..1024", d);
   const int hd = c.num_head > 0 && d % c.num_head == 0 ? d / c.num_head : 0;
   ASW_CHECK_ARG(hd == 16 || hd == 32 || hd == 64, "sep_create: head_dim %d unsupported (16, 32, 64)", hd);
-  for (int i = 0; i < c.depth; ++i)
-    ASW_CHECK_ARG(m->enc_cin[i] <= 512 && (m->enc_cin[i] & (m->enc_cin[i] - 1)) == 0,
-                  "sep_create: level width %d must be a power of two <= 512", m->enc_cin[i]);
+  if ((rc = m->check_level_widths("sep_create"))) return rc;
   *out = m.release();
   return ASW_OK;
 }
 
 extern "C" void asw_sep_destroy(asw_sep* m) { delete m; }
 
-extern "C" int asw_sep_set_precision(asw_sep* m, int precision) {
-  ASW_CHECK_ARG(m && (precision >= 0 && precision <= 2), "sep_set_precision: 0 (f32), 1 (f16x3) or 2 (single-pass f16)");
-  m->precision = precision;
-  return ASW_OK;
-}
+extern "C" int asw_sep_set_precision(asw_sep* m, int precision) { return set_precision(m, "sep_set_precision", precision); }
 
 extern "C" int asw_sep_set_param(asw_sep* m, const char* key, const float* host_data, size_t numel) {
-  ASW_CHECK_ARG(m && key && host_data, "sep_set_param: null pointer");
-  m->raw[key].assign(host_data, host_data + numel);
-  m->finalized = false;
-  return ASW_OK;
+  return set_param(m, "sep_set_param", key, host_data, numel);
 }
 
 extern "C" int asw_sep_finalize(asw_sep* m) {
   ASW_CHECK_ARG(m, "sep_finalize: null handle");
-  {
-    int dev = -1;
-    ASW_HIP(hipGetDevice(&dev));
-    if (dev != m->device)
-      return asw::set_error(ASW_ERR_STATE, "sep_finalize: model was created on HIP device %d, current device is %d", m->device, dev);
-  }
   const asw_sep_config& c = m->cfg;
-  const auto want = expected_params(m);
-  for (const auto& kv : want) {
-    auto it = m->raw.find(kv.first);
-    if (it == m->raw.end()) return asw::set_error(ASW_ERR_STATE, "state dict is missing key %s", kv.first.c_str());
-    if (it->second.size() != kv.second)
-      return asw::set_error(ASW_ERR_ARG, "%s: %zu elements, expected %zu", kv.first.c_str(), it->second.size(), kv.second);
-  }
-  if (m->raw.size() != want.size())
-    return asw::set_error(ASW_ERR_ARG, "state dict has %zu unexpected keys", m->raw.size() - want.size());
-  int rc;
-#define UP(buf, vec) if ((rc = (buf).upload(vec))) return rc
-  UP(m->pre_w, P(m, "preproc.weight"));
-  UP(m->pre_b, P(m, "preproc.bias"));
-  const int K = c.kernel_size;
-  m->enc.clear(); m->enc.resize(c.depth);
-  m->dec.clear(); m->dec.resize(c.depth);
-  for (int i = 0; i < c.depth; ++i) {
-    const std::string p = "encoder.module_list." + std::to_string(i);
-    EncBlock& e = m->enc[i];
-    if ((rc = pack_res_layers(m->raw, p, m->enc_cin[i], K, c.residual_layers, c.residual_dilation_factor, e.res))) return rc;
-    if ((rc = e.down_wt.upload_gemm(pack_conv(P(m, p + ".conv1.weight"), 2 * m->enc_cout[i], m->enc_cin[i], K, nullptr),
-                                    2 * m->enc_cout[i], m->enc_cin[i] * K)))
-      return rc;
-    UP(e.bias, P(m, p + ".conv1.bias"));
-    UP(e.gn_g, P(m, p + ".norm1.weight"));
-    UP(e.gn_b, P(m, p + ".norm1.bias"));
-  }
-  for (int i = 0; i < c.depth; ++i) {
-    const std::string p = "decoder.module_list." + std::to_string(i);
-    DecBlock& dd = m->dec[i];
-    const int ci = m->dec_cin[i], co2 = 2 * m->dec_cout[i], st = m->dec_stride[i];
-    if ((rc = pack_res_layers(m->raw, p, m->dec_cout[i], K, c.residual_layers, c.residual_dilation_factor, dd.res))) return rc;
-    const std::vector<float>& w = P(m, p + ".upsample.conv.weight");   // [ci][co2][st]
-    const std::vector<float>& b = P(m, p + ".upsample.conv.bias");
-    // ConvTranspose1d with kernel == stride is a plain GEMM whose output row t_in holds the st
-    // output frames t_in*st .. t_in*st+st-1 back to back: column n' = r*co2 + n.
-    std::vector<float> wt((size_t)st * co2 * ci), bb((size_t)st * co2);
-    for (int r = 0; r < st; ++r)
-      for (int n = 0; n < co2; ++n) {
-        bb[(size_t)r * co2 + n] = b[n];
-        for (int cc = 0; cc < ci; ++cc) wt[((size_t)r * co2 + n) * ci + cc] = w[((size_t)cc * co2 + n) * st + r];
-      }
-    if ((rc = dd.up_wt.upload_gemm(wt, st * co2, ci))) return rc;
-    UP(dd.up_bias, bb);
-    UP(dd.gn_g, P(m, p + ".norm1.weight"));
-    UP(dd.gn_b, P(m, p + ".norm1.bias"));
-  }
+  int rc = m->finalize_trunk("sep_finalize", expected_params(m));
+  if (rc) return rc;
+  if ((rc = m->pack_gated(m->convs, [](const std::string&) { return std::vector<float>(); }))) return rc;
   const int d = m->enc_cout.back(), H = c.num_head, hd = d / H, BK = c.bottleneck_ksize;
-  m->inv_freq = P(m, "bottleneck.pe_single.inv_freq");
+  m->inv_freq = m->P("bottleneck.pe_single.inv_freq");
   m->pe_L = 0;
   m->conf.clear(); m->conf.resize(c.bottleneck_layers);
   m->inter.clear(); m->inter.resize(c.bottleneck_layers);
@@ -602,21 +319,21 @@ extern "C" int asw_sep_finalize(asw_sep* m) {
     const std::string cl = "bottleneck.module_list." + std::to_string(l) + ".intra.layers.0";
     ConfLayer& q = m->conf[l];
     auto ffn = [&](Ffn& f, const std::string& p) -> int {
-      UP(f.lng, P(m, p + ".0.weight")); UP(f.lnb, P(m, p + ".0.bias"));
-      UP(f.w1, P(m, p + ".1.ffn.0.weight")); UP(f.b1, P(m, p + ".1.ffn.0.bias"));
-      UP(f.w2, scaled(P(m, p + ".1.ffn.3.weight"), 0.5f)); UP(f.b2, scaled(P(m, p + ".1.ffn.3.bias"), 0.5f));
+      UP(f.lng, m->P(p + ".0.weight")); UP(f.lnb, m->P(p + ".0.bias"));
+      UP(f.w1, m->P(p + ".1.ffn.0.weight")); UP(f.b1, m->P(p + ".1.ffn.0.bias"));
+      UP(f.w2, scaled(m->P(p + ".1.ffn.3.weight"), 0.5f)); UP(f.b2, scaled(m->P(p + ".1.ffn.3.bias"), 0.5f));
       return ASW_OK;
     };
     if ((rc = ffn(q.f1, cl + ".ffn_module1"))) return rc;
     if ((rc = ffn(q.f2, cl + ".ffn_module2"))) return rc;
-    UP(q.n1g, P(m, cl + ".norm1.norm.weight")); UP(q.n1b, P(m, cl + ".norm1.norm.bias"));
-    UP(q.n2g, P(m, cl + ".norm2.norm.weight")); UP(q.n2b, P(m, cl + ".norm2.norm.bias"));
+    UP(q.n1g, m->P(cl + ".norm1.norm.weight")); UP(q.n1b, m->P(cl + ".norm1.norm.bias"));
+    UP(q.n2g, m->P(cl + ".norm2.norm.weight")); UP(q.n2b, m->P(cl + ".norm2.norm.bias"));
     const std::string ce = "bottleneck.module_list." + std::to_string(l) + ".intra.norm.norm";
-    UP(q.fng, P(m, ce + ".weight")); UP(q.fnb, P(m, ce + ".bias"));
+    UP(q.fng, m->P(ce + ".weight")); UP(q.fnb, m->P(ce + ".bias"));
     {
       // RelPosMHAXL cuts the in_proj output per head into (q, k, v): source row h*3*hd + part*hd + c
       // -> row part*d + h*hd + c of the standard Q | K | V layout the attention kernel reads
-      const std::vector<float>& w = P(m, cl + ".mha_layer.in_proj_weight");
+      const std::vector<float>& w = m->P(cl + ".mha_layer.in_proj_weight");
       std::vector<float> o(w.size());
       for (int h = 0; h < H; ++h)
         for (int part = 0; part < 3; ++part)
@@ -624,69 +341,42 @@ extern "C" int asw_sep_finalize(asw_sep* m) {
             memcpy(&o[((size_t)part * d + h * hd + cc) * d], &w[((size_t)h * 3 * hd + part * hd + cc) * d], sizeof(float) * d);
       UP(q.w_in, o);
     }
-    UP(q.w_pos, P(m, cl + ".mha_layer.linear_pos.weight"));
-    UP(q.w_out, P(m, cl + ".mha_layer.out_proj.weight")); UP(q.b_out, P(m, cl + ".mha_layer.out_proj.bias"));
+    UP(q.w_pos, m->P(cl + ".mha_layer.linear_pos.weight"));
+    UP(q.w_out, m->P(cl + ".mha_layer.out_proj.weight")); UP(q.b_out, m->P(cl + ".mha_layer.out_proj.bias"));
     // pos_bias_* are stored [hd][H] and read through .view(1,1,H,hd): the flat buffer, head-major
-    UP(q.bu, P(m, cl + ".mha_layer.pos_bias_u")); UP(q.bv, P(m, cl + ".mha_layer.pos_bias_v"));
-    UP(q.cm_lng, P(m, cl + ".convolution_module.layer_norm.weight"));
-    UP(q.cm_lnb, P(m, cl + ".convolution_module.layer_norm.bias"));
-    UP(q.cm_pw, P(m, cl + ".convolution_module.bottleneck.0.weight"));       // [2d][d][1] == [2d][d]
-    UP(q.cm_pwb, P(m, cl + ".convolution_module.bottleneck.0.bias"));
+    UP(q.bu, m->P(cl + ".mha_layer.pos_bias_u")); UP(q.bv, m->P(cl + ".mha_layer.pos_bias_v"));
+    UP(q.cm_lng, m->P(cl + ".convolution_module.layer_norm.weight"));
+    UP(q.cm_lnb, m->P(cl + ".convolution_module.layer_norm.bias"));
+    UP(q.cm_pw, m->P(cl + ".convolution_module.bottleneck.0.weight"));       // [2d][d][1] == [2d][d]
+    UP(q.cm_pwb, m->P(cl + ".convolution_module.bottleneck.0.bias"));
     {
-      const std::vector<float>& w = P(m, cl + ".convolution_module.conv.weight");   // [d][1][BK] -> [BK][d]
+      const std::vector<float>& w = m->P(cl + ".convolution_module.conv.weight");   // [d][1][BK] -> [BK][d]
       std::vector<float> o((size_t)BK * d);
       for (int cc = 0; cc < d; ++cc)
         for (int k = 0; k < BK; ++k) o[(size_t)k * d + cc] = w[(size_t)cc * BK + k];
       UP(q.dw_wT, o);
     }
-    UP(q.dw_b, P(m, cl + ".convolution_module.conv.bias"));
-    UP(q.ac_lng, P(m, cl + ".convolution_module.after_conv.0.weight"));
-    UP(q.ac_lnb, P(m, cl + ".convolution_module.after_conv.0.bias"));
-    UP(q.ac_w, P(m, cl + ".convolution_module.after_conv.2.weight"));
-    UP(q.ac_b, P(m, cl + ".convolution_module.after_conv.2.bias"));
+    UP(q.dw_b, m->P(cl + ".convolution_module.conv.bias"));
+    UP(q.ac_lng, m->P(cl + ".convolution_module.after_conv.0.weight"));
+    UP(q.ac_lnb, m->P(cl + ".convolution_module.after_conv.0.bias"));
+    UP(q.ac_w, m->P(cl + ".convolution_module.after_conv.2.weight"));
+    UP(q.ac_b, m->P(cl + ".convolution_module.after_conv.2.bias"));
     const std::string t = "bottleneck.module_list." + std::to_string(l) + ".inter.layers.0";
     InterLayer& il = m->inter[l];
-    UP(il.w_in, P(m, t + ".self_attn.in_proj_weight")); UP(il.b_in, P(m, t + ".self_attn.in_proj_bias"));
-    UP(il.w_out, P(m, t + ".self_attn.out_proj.weight")); UP(il.b_out, P(m, t + ".self_attn.out_proj.bias"));
-    UP(il.w1, P(m, t + ".linear1.weight")); UP(il.b1, P(m, t + ".linear1.bias"));
-    UP(il.w2, P(m, t + ".linear2.weight")); UP(il.b2, P(m, t + ".linear2.bias"));
-    UP(il.n1g, P(m, t + ".norm1.weight")); UP(il.n1b, P(m, t + ".norm1.bias"));
-    UP(il.n2g, P(m, t + ".norm2.weight")); UP(il.n2b, P(m, t + ".norm2.bias"));
+    UP(il.w_in, m->P(t + ".self_attn.in_proj_weight")); UP(il.b_in, m->P(t + ".self_attn.in_proj_bias"));
+    UP(il.w_out, m->P(t + ".self_attn.out_proj.weight")); UP(il.b_out, m->P(t + ".self_attn.out_proj.bias"));
+    UP(il.w1, m->P(t + ".linear1.weight")); UP(il.b1, m->P(t + ".linear1.bias"));
+    UP(il.w2, m->P(t + ".linear2.weight")); UP(il.b2, m->P(t + ".linear2.bias"));
+    UP(il.n1g, m->P(t + ".norm1.weight")); UP(il.n1b, m->P(t + ".norm1.bias"));
+    UP(il.n2g, m->P(t + ".norm2.weight")); UP(il.n2b, m->P(t + ".norm2.bias"));
   }
-  const int E = c.encoder_channels, EK = c.encoder_kernel_size;
-  m->byp_k = ((EK + 31) / 32) * 32;
-  {
-    const std::vector<float>& w = P(m, "reference_bypass.weight");   // [E][1][EK]
-    std::vector<float> wt((size_t)E * m->byp_k, 0.f);
-    for (int n = 0; n < E; ++n)
-      for (int k = 0; k < EK; ++k) wt[(size_t)n * m->byp_k + k] = w[(size_t)n * EK + k];
-    UP(m->byp_wt, wt);
-    UP(m->byp_b, P(m, "reference_bypass.bias"));
-    if (E % 32 == 0 && EK <= 48) {
-      std::vector<float> w48((size_t)E * 48, 0.f);
-      for (int n = 0; n < E; ++n)
-        for (int k = 0; k < EK; ++k) w48[(size_t)n * 48 + k] = w[(size_t)n * EK + k];
-      if ((rc = m->byp_wt48.upload_gemm(w48, E, 48))) return rc;
-    }
-  }
-  if ((rc = m->mask_wt.upload_gemm(pack_conv(P(m, "mask_encoder.weight"), E, c.channels, EK, nullptr), E, c.channels * EK))) return rc;
-  UP(m->mask_b, P(m, "mask_encoder.bias"));
-  {
-    const std::vector<float>& w = P(m, "output_decoder.weight");     // [E][1][EK]
-    std::vector<float> wt((size_t)64 * E, 0.f);
-    for (int j = 0; j < EK; ++j)
-      for (int e = 0; e < E; ++e) wt[(size_t)j * E + e] = w[(size_t)e * EK + j];
-    if ((rc = m->dec_wt.upload_gemm(wt, 64, E))) return rc;
-    m->out_bias = P(m, "output_decoder.bias")[0];
-  }
-#undef UP
   m->finalized = true;
   return ASW_OK;
 }
 
 extern "C" int asw_sep_infer(asw_sep* m, const float* mix, int M, int T, const int32_t* offsets, int S, float* out,
                              void* stream) {
-  int rc = check_ready(m);
+  int rc = check_ready(m, "asw_sep_finalize");
   if (rc) return rc;
   ASW_CHECK_ARG(S >= 0 && S <= 64, "sep_infer: S=%d speakers (at most 64 per call)", S);
   if (S == 0) return ASW_OK;
@@ -711,7 +401,7 @@ extern "C" int asw_sep_forward(asw_sep* m, const float* mix_norm, int B, int S, 
 
 extern "C" int asw_sep_forward_counts(asw_sep* m, const float* mix_norm, int B, int S, int M, int t, const int32_t* counts,
                                       float* out, void* stream) {
-  int rc = check_ready(m);
+  int rc = check_ready(m, "asw_sep_finalize");
   if (rc) return rc;
   if (counts) {
     int mx = 0;
@@ -764,14 +454,5 @@ extern "C" int asw_sep_get_config(const asw_sep* m, asw_sep_config* out) {
 }
 
 extern "C" int asw_sep_get_tap(asw_sep* m, const char* name, float* dst, size_t capacity, size_t* numel, void* stream) {
-  ASW_CHECK_ARG(m && name && numel, "sep_get_tap: null pointer");
-  auto it = m->taps.find(name);
-  if (it == m->taps.end()) return asw::set_error(ASW_ERR_ARG, "sep_get_tap: no activation named %s", name);
-  *numel = it->second.numel;
-  if (dst) {
-    ASW_CHECK_ARG(capacity >= it->second.numel, "sep_get_tap: buffer too small");
-    ASW_HIP(hipMemcpyAsync(dst, it->second.p, it->second.numel * sizeof(float), hipMemcpyDeviceToDevice,
-                           asw::as_stream(stream)));
-  }
-  return ASW_OK;
+  return get_tap(m, "sep_get_tap", name, dst, capacity, numel, stream);
 }
