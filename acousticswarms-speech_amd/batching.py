@@ -16,7 +16,9 @@ Only the spot network's workspace is shared between the searches, and only the b
 it (under its lock, on the batcher's own stream); everything else a search launches (SRP map,
 SI-SDR matrices) allocates its own buffers and runs on the search's streams.
 """
+import contextlib
 import copy
+import gc
 import threading
 import time
 
@@ -253,15 +255,60 @@ def mixture_view(mic_array):
     return v
 
 
-def search_batched(joint_model, mixes, concurrent=2):
+def check_geometries(mixes, geometries):
+    """``geometries`` is one ``(mic_positions [M,3], speaker_range [6])`` per mixture and every mixture of the
+    batch has the same M and T (they share one [K,M,T] device stack): ``ValueError`` otherwise.  Looks at shapes
+    only -- nothing is copied and no device is touched."""
+    if geometries is None:
+        return
+    if len(geometries) != len(mixes):
+        raise ValueError(f"geometries holds {len(geometries)} entries for {len(mixes)} mixtures")
+    shapes = [tuple(int(v) for v in np.shape(m)) for m in mixes]
+    if any(len(sh) != 2 for sh in shapes):
+        raise ValueError("every mixture must be [M, T]")
+    if len(set(shapes)) > 1:
+        raise ValueError(f"the mixtures of one batch must share M and T, got the shapes {sorted(set(shapes))}")
+    for k, g in enumerate(geometries):
+        if len(g) != 2:
+            raise ValueError(f"geometries[{k}] must be (mic_positions, speaker_range)")
+        mic_shape = tuple(np.shape(g[0]))
+        if len(mic_shape) != 2 or mic_shape[1] != 3 or (shapes and mic_shape[0] != shapes[0][0]):
+            raise ValueError(f"geometries[{k}]: mic_positions {mic_shape} do not fit mixtures of "
+                             f"{shapes[0][0] if shapes else '?'} channels")
+        if len(g[1]) != 6:
+            raise ValueError(f"geometries[{k}]: speaker_range must hold 6 values")
+
+
+@contextlib.contextmanager
+def no_full_collections():
+    """While a batch with per-mixture arrays runs, the interpreter's oldest generation is not collected: each host-built
+    array is tens of thousands of objects that live for one or two searches, and a full collection walking them is
+    a 50 ms pause inside some search (the reason ``JointModel.setup`` freezes its one array).  The young generations
+    keep running; an evicted array goes by reference counting."""
+    thr = gc.get_threshold()
+    gc.set_threshold(thr[0], thr[1], 1 << 30)
+    try:
+        yield
+    finally:
+        gc.set_threshold(*thr)
+
+
+def search_batched(joint_model, mixes, concurrent=2, geometries=None):
     """The complete localization search (SRP-PHAT -> coarse -> fine -> clustering) of every mixture in
     ``mixes`` on this rank's GPU: ``concurrent`` worker threads pull mixtures from a queue -- a finished
     search is replaced at once, so the GPU never waits for a group to drain -- and score through one
-    CandidateBatcher.  Returns the per-mixture result dicts of shard.localize_batch, in order, and a stats dict."""
+    CandidateBatcher.  Returns the per-mixture result dicts of shard.localize_batch, in order, and a stats dict.
+
+    ``geometries``: one ``(mic_positions, speaker_range)`` per mixture (``check_geometries``).  Search k then runs on
+    a view of the ``MicArray`` of its own geometry, taken from ``joint_model.mic_array_for`` -- built by the
+    searching thread in the model's ``geometry`` mode, once per distinct array while it stays in the LRU.  With
+    ``None`` every search uses the array of ``joint_model.setup()``, as before."""
+    check_geometries(mixes, geometries)
     import torch
     spot = joint_model.spot_model
     mp = joint_model.Mic_processor
-    assert mp is not None, "call JointModel.setup() first"
+    assert mp is not None or geometries is not None, "call JointModel.setup() first"
+    method = mp.Prone_method if mp is not None else "SRP"
     dev = spot.device
     n = len(mixes)
     results = [None] * n
@@ -273,7 +320,8 @@ def search_batched(joint_model, mixes, concurrent=2):
     errors, todo, todo_lock = [], list(range(n)), threading.Lock()
 
     def search(k):
-        view, scorer = mixture_view(mp), batcher.proxy(k)
+        own = mp if geometries is None else joint_model.mic_array_for(geometries[k][0], geometries[k][1], method)
+        view, scorer = mixture_view(own), batcher.proxy(k)
         times = [0.0] * 5
         t0 = time.time()
         patch_list, _ = view.Apply_SRP_PHAT(hosts[k])
@@ -323,10 +371,11 @@ def search_batched(joint_model, mixes, concurrent=2):
     sys.setswitchinterval(min(switch, 2e-4))
     threads = [threading.Thread(target=work, name=f"asw-search-{w}") for w in range(n_workers)]
     try:
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
+        with (no_full_collections() if geometries is not None else contextlib.nullcontext()):
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join()
     finally:
         sys.setswitchinterval(switch)
     if errors:

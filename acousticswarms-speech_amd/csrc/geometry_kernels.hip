@@ -1,0 +1,386 @@
+// geometry_kernels.hip -- the one-off geometry tables of the SRP-PHAT stage built on the device.
+//
+// Replaces the host build of SRPPhat (srp.py: _lookup_grid, _valid_mask, _map_3d_tdoa and the tau / tops_delta /
+// dis_matrix statements; reference: SRP_PHAT.__init__, Map_3D_TDoA and search_cluster,
+// sep/Traditional_SP/SRP_Prunning.py:149-180,277-344,368-381) for arrays that change per mixture:
+//   lookup_planes   pair-major TDoA tables planes[P][ny][nx][nz] of the 5 cm / 1 cm lookup grids
+//   voxel_map       quantised TDoA vector and keep-out mask per voxel of the SRP grid, dis_matrix
+//   label           26-connected components of equal quantised vectors, label = smallest C-order voxel index
+//   compact         POWER_INDEX, cluster offsets, CSR member list, cluster centres, tau and tops_delta
+//
+// Exactness.  Every value is computed in double with the expression order of the numpy statements it
+// replaces -- norm = sqrt((dx*dx + dy*dy) + dz*dz), "/ C * FS" as two operations, centres as a sequential sum in
+// member order divided by the count -- with IEEE sqrt and divide and with contraction off for the whole file, so
+// no fma changes a rounding.  Nothing here accumulates through atomics and the sort is a stable radix sort: two
+// builds of one geometry are bit-identical.
+#pragma clang fp contract(off)
+#include <hipcub/hipcub.hpp>
+
+#include "asw_common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kMaxVoxels = 1 << 24;          // labels and CSR indices are int32
+constexpr int kLabelBurst = 4;               // propagation sweeps between two reads of the "changed" flag
+
+// |p - m| in numpy.linalg.norm's order for a length-3 axis: (s0 + s1) + s2
+__device__ __forceinline__ double norm3(double dx, double dy, double dz) {
+  return __dsqrt_rn((dx * dx + dy * dy) + dz * dz);
+}
+
+// thread = one lookup point ((y*nx + x)*nz + z); planes[p][point] = (|pt - m_{p+1}| - |pt - m_0|) / C * FS
+__global__ __launch_bounds__(kBlock) void lookup_planes_kernel(const double* __restrict__ ys, int ny,
+                                                               const double* __restrict__ xs, int nx,
+                                                               const double* __restrict__ zs, int nz,
+                                                               const double* __restrict__ mics, int M, double C, double FS,
+                                                               double* __restrict__ planes) {
+  const long total = (long)ny * nx * nz;
+  const long idx = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= total) return;
+  const int z = (int)(idx % nz);
+  const long yx = idx / nz;
+  const int x = (int)(yx % nx), y = (int)(yx / nx);
+  const double px = xs[x], py = ys[y], pz = zs[z];
+  const double d0 = norm3(px - mics[0], py - mics[1], pz - mics[2]) / C * FS;
+  for (int i = 1; i < M; ++i) {
+    const double d = norm3(px - mics[3 * i], py - mics[3 * i + 1], pz - mics[3 * i + 2]) / C * FS;
+    planes[(long)(i - 1) * total + idx] = d - d0;
+  }
+}
+
+// thread = one voxel (ix*Ly + iy)*Lz + iz.  q[v][p] = rint(((d_{p+1} - d_0) / C * FS) / res) * res (rint rounds
+// half to even, as numpy.round does); valid = outside the keep-out rectangle around the array (open interval).
+__global__ __launch_bounds__(kBlock) void voxel_map_kernel(const double* __restrict__ xs, int Lx,
+                                                           const double* __restrict__ ys, int Ly,
+                                                           const double* __restrict__ zs, int Lz,
+                                                           const double* __restrict__ mics, int M, double b0, double b1,
+                                                           double b2, double b3, double C, double FS, double res,
+                                                           int32_t* __restrict__ q, uint8_t* __restrict__ valid) {
+  const int n = Lx * Ly * Lz;
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= n) return;
+  const int iz = v % Lz, iy = (v / Lz) % Ly, ix = v / (Lz * Ly);
+  const double px = xs[ix], py = ys[iy], pz = zs[iz];
+  const double d0 = norm3(px - mics[0], py - mics[1], pz - mics[2]);
+  const int ires = (int)res;
+  for (int i = 1; i < M; ++i) {
+    const double d = norm3(px - mics[3 * i], py - mics[3 * i + 1], pz - mics[3 * i + 2]);
+    const double off = (d - d0) / C * FS;
+    q[(long)v * (M - 1) + (i - 1)] = (int32_t)rint(off / res) * ires;
+  }
+  const bool inside = px > b0 && px < b2 && py > b1 && py < b3;
+  valid[v] = inside ? 0 : 1;
+}
+
+// thread = one (ix, iy): sqrt((x - cx)^2 + (y - cy)^2) + 1e-8
+__global__ __launch_bounds__(kBlock) void dis_matrix_kernel(const double* __restrict__ xs, int Lx,
+                                                            const double* __restrict__ ys, int Ly, double cx, double cy,
+                                                            double* __restrict__ dis) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= Lx * Ly) return;
+  const double a = xs[i / Ly] - cx, b = ys[i % Ly] - cy;
+  dis[i] = __dsqrt_rn(a * a + b * b) + 1e-8;
+}
+
+// Neighbour k of 27 is (k/9 - 1, (k/3)%3 - 1, k%3 - 1).  adj bit k: that neighbour exists, is valid and has the same
+// quantised vector.  labels start at the voxel's own index (-1: invalid voxel).
+__global__ __launch_bounds__(kBlock) void label_init_kernel(const int32_t* __restrict__ q, const uint8_t* __restrict__ valid,
+                                                            int Lx, int Ly, int Lz, int P, uint32_t* __restrict__ adj,
+                                                            int32_t* __restrict__ labels) {
+  const int n = Lx * Ly * Lz;
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= n) return;
+  if (!valid[v]) {
+    adj[v] = 0;
+    labels[v] = -1;
+    return;
+  }
+  const int iz = v % Lz, iy = (v / Lz) % Ly, ix = v / (Lz * Ly);
+  uint32_t bits = 0;
+  for (int k = 0; k < 27; ++k) {
+    if (k == 13) continue;
+    const int jx = ix + k / 9 - 1, jy = iy + (k / 3) % 3 - 1, jz = iz + k % 3 - 1;
+    if (jx < 0 || jx >= Lx || jy < 0 || jy >= Ly || jz < 0 || jz >= Lz) continue;
+    const int u = (jx * Ly + jy) * Lz + jz;
+    if (!valid[u]) continue;
+    bool same = true;
+    for (int p = 0; p < P; ++p) same = same && q[(long)u * P + p] == q[(long)v * P + p];
+    if (same) bits |= 1u << k;
+  }
+  adj[v] = bits;
+  labels[v] = v;
+}
+
+// One sweep of min-label propagation with a pointer jump.  A voxel's label is written by its own thread only, always
+// with a smaller index of its own component, so the sweeps may read labels other threads are lowering: whatever they
+// see, the fixed point -- every voxel carrying the smallest index of its component -- is the same.
+__global__ __launch_bounds__(kBlock) void label_sweep_kernel(const uint32_t* __restrict__ adj, int Lx, int Ly, int Lz,
+                                                             volatile int32_t* labels, int32_t* __restrict__ changed) {
+  const int n = Lx * Ly * Lz;
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= n) return;
+  const int32_t cur = labels[v];
+  if (cur < 0) return;
+  const uint32_t bits = adj[v];
+  int32_t best = cur;
+  for (int k = 0; k < 27; ++k) {
+    if (!((bits >> k) & 1u)) continue;
+    const int u = v + ((k / 9 - 1) * Ly + ((k / 3) % 3 - 1)) * Lz + (k % 3 - 1);
+    const int32_t l = labels[u];
+    best = l < best ? l : best;
+  }
+  const int32_t up = labels[best];           // best is a voxel of this component, its label another one, not larger
+  best = up < best ? up : best;
+  if (best < cur) {
+    labels[v] = best;
+    *changed = 1;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void flags_kernel(const int32_t* __restrict__ labels, int n, int32_t* __restrict__ rootf,
+                                                       int32_t* __restrict__ validf) {
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= n) return;
+  const int32_t l = labels[v];
+  rootf[v] = l == v ? 1 : 0;
+  validf[v] = l >= 0 ? 1 : 0;
+}
+
+// rank = exclusive scan of the root flags: the component whose smallest voxel comes first in C order is cluster 0,
+// which is the order the reference's (ix, iy, iz) scan meets them in.
+__global__ __launch_bounds__(kBlock) void scatter_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ q, int n,
+                                                         int P, const int32_t* __restrict__ rank,
+                                                         const int32_t* __restrict__ vpos, int32_t* __restrict__ power_index,
+                                                         int32_t* __restrict__ valid_flat, int32_t* __restrict__ valid_cid,
+                                                         int32_t* __restrict__ offsets) {
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= n) return;
+  const int32_t l = labels[v];
+  if (l < 0 || l >= n) {                      // invalid voxel (a label outside the lattice cannot index rank[])
+    power_index[v] = 0;
+    return;
+  }
+  const int32_t cid = rank[l];
+  power_index[v] = cid;
+  const int32_t j = vpos[v];
+  valid_flat[j] = v;
+  valid_cid[j] = cid;
+  if (l == v)
+    for (int p = 0; p < P; ++p) offsets[(long)cid * P + p] = q[(long)v * P + p];
+}
+
+// bounds[g] = first position of cluster g in the sorted keys (g = G gives V)
+__global__ __launch_bounds__(kBlock) void bounds_kernel(const int32_t* __restrict__ keys, int V, int G, int32_t* __restrict__ bounds) {
+  const int g = blockIdx.x * kBlock + threadIdx.x;
+  if (g > G) return;
+  int lo = 0, hi = V;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (keys[mid] < g) lo = mid + 1; else hi = mid;
+  }
+  bounds[g] = lo;
+}
+
+// thread = one cluster: its members' positions summed one after the other in ascending voxel index, then / count
+__global__ __launch_bounds__(kBlock) void centres_kernel(const int32_t* __restrict__ members, const int32_t* __restrict__ bounds,
+                                                         int G, const double* __restrict__ xs, const double* __restrict__ ys,
+                                                         const double* __restrict__ zs, int Ly, int Lz,
+                                                         double* __restrict__ centres) {
+  const int g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= G) return;
+  const int b0 = bounds[g], b1 = bounds[g + 1];
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int j = b0; j < b1; ++j) {
+    const int v = members[j];
+    const double px = xs[v / (Lz * Ly)], py = ys[(v / Lz) % Ly], pz = zs[v % Lz];
+    if (j == b0) {
+      sx = px; sy = py; sz = pz;
+    } else {
+      sx = sx + px; sy = sy + py; sz = sz + pz;
+    }
+  }
+  const double cnt = (double)(b1 - b0);
+  centres[3 * (long)g] = sx / cnt;
+  centres[3 * (long)g + 1] = sy / cnt;
+  centres[3 * (long)g + 2] = sz / cnt;
+}
+
+// thread = one (cluster, mic).  tau ignores the mic's z and takes the point's z absolute (generate_mod_vector);
+// delta = |p - c| - |(p - c) - (m - c)| with c the mic mean (TOPS_block.py:45-48,105-112).
+__global__ __launch_bounds__(kBlock) void delays_kernel(const double* __restrict__ centres, int G, const double* __restrict__ mics,
+                                                        int M, double cx, double cy, double cz, double C,
+                                                        double* __restrict__ tau, double* __restrict__ delta) {
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= (long)G * M) return;
+  const int g = (int)(i / M), m = (int)(i % M);
+  const double gx = centres[3 * (long)g], gy = centres[3 * (long)g + 1], gz = centres[3 * (long)g + 2];
+  const double mx = mics[3 * m], my = mics[3 * m + 1], mz = mics[3 * m + 2];
+  const double dx = gx - mx, dy = gy - my;
+  tau[i] = __dsqrt_rn((dx * dx + dy * dy) + gz * gz) / C;
+  const double px = gx - cx, py = gy - cy, pz = gz - cz;
+  const double ex = px - (mx - cx), ey = py - (my - cy), ez = pz - (mz - cz);
+  delta[i] = norm3(px, py, pz) - norm3(ex, ey, ez);
+}
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int sort_bits(int G) {
+  int bits = 1;
+  while (bits < 31 && (1 << bits) < G) ++bits;
+  return bits;
+}
+
+// temporary storage of the scans and of the radix sort over n items (the larger of the two)
+hipError_t cub_temp_bytes(int n, size_t* bytes) {
+  size_t a = 0, b = 0;
+  hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, a, (const int32_t*)nullptr, (int32_t*)nullptr, n, (hipStream_t)0);
+  if (e != hipSuccess) return e;
+  e = hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr,
+                                         (int32_t*)nullptr, n, 0, 32, (hipStream_t)0);
+  *bytes = a > b ? a : b;
+  return e;
+}
+
+bool good_axes(int a, int b, int c) {
+  return a > 0 && b > 0 && c > 0 && (long)a * b * c <= kMaxVoxels;
+}
+
+}  // namespace
+
+extern "C" int asw_geom_lookup_planes(const double* ys, int ny, const double* xs, int nx, const double* zs, int nz,
+                                      const double* mics, int M, double C, double FS, double* planes, void* stream) {
+  ASW_CHECK_ARG(ys && xs && zs && mics && planes, "geom_lookup_planes: null pointer");
+  ASW_CHECK_ARG(ny > 0 && nx > 0 && nz > 0 && (long)ny * nx * nz <= 0x7fffffffL,
+                "geom_lookup_planes: bad grid %d x %d x %d (the cube scans index points with int32)", ny, nx, nz);
+  ASW_CHECK_ARG(M >= 2 && M <= 32, "geom_lookup_planes: M = %d outside 2..32", M);
+  ASW_CHECK_ARG(C > 0 && FS > 0, "geom_lookup_planes: C and FS must be positive");
+  const long total = (long)ny * nx * nz;
+  hipLaunchKernelGGL(lookup_planes_kernel, dim3(asw::cdiv(total, kBlock)), dim3(kBlock), 0, asw::as_stream(stream), ys, ny, xs,
+                     nx, zs, nz, mics, M, C, FS, planes);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+extern "C" int asw_geom_voxel_map(const double* xs, int Lx, const double* ys, int Ly, const double* zs, int Lz,
+                                  const double* mics, int M, const double* border, const double* centre, double C, double FS,
+                                  double resolution, int32_t* q, uint8_t* valid, double* dis_matrix, void* stream) {
+  ASW_CHECK_ARG(xs && ys && zs && mics && border && centre && q && valid && dis_matrix, "geom_voxel_map: null pointer");
+  ASW_CHECK_ARG(good_axes(Lx, Ly, Lz), "geom_voxel_map: bad lattice %d x %d x %d", Lx, Ly, Lz);
+  ASW_CHECK_ARG(M >= 2 && M <= 32, "geom_voxel_map: M = %d outside 2..32", M);
+  ASW_CHECK_ARG(C > 0 && FS > 0, "geom_voxel_map: C and FS must be positive");
+  ASW_CHECK_ARG(resolution >= 1 && resolution <= 1024 && resolution == (double)(int)resolution,
+                "geom_voxel_map: the sample resolution must be a whole number of samples in 1..1024");
+  hipStream_t s = asw::as_stream(stream);
+  const int n = Lx * Ly * Lz;
+  hipLaunchKernelGGL(voxel_map_kernel, dim3(asw::cdiv(n, kBlock)), dim3(kBlock), 0, s, xs, Lx, ys, Ly, zs, Lz, mics, M, border[0],
+                     border[1], border[2], border[3], C, FS, resolution, q, valid);
+  ASW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dis_matrix_kernel, dim3(asw::cdiv((long)Lx * Ly, kBlock)), dim3(kBlock), 0, s, xs, Lx, ys, Ly, centre[0],
+                     centre[1], dis_matrix);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+extern "C" int asw_geom_label(const int32_t* q, const uint8_t* valid, int Lx, int Ly, int Lz, int P, uint32_t* adj_scratch,
+                              int32_t* flag_scratch, int32_t* labels, int* sweeps, void* stream) {
+  ASW_CHECK_ARG(q && valid && adj_scratch && flag_scratch && labels, "geom_label: null pointer");
+  ASW_CHECK_ARG(good_axes(Lx, Ly, Lz), "geom_label: bad lattice %d x %d x %d", Lx, Ly, Lz);
+  ASW_CHECK_ARG(P >= 1 && P <= 31, "geom_label: P = %d outside 1..31", P);
+  hipStream_t s = asw::as_stream(stream);
+  const int n = Lx * Ly * Lz, blocks = asw::cdiv(n, kBlock);
+  hipLaunchKernelGGL(label_init_kernel, dim3(blocks), dim3(kBlock), 0, s, q, valid, Lx, Ly, Lz, P, adj_scratch, labels);
+  ASW_LAUNCH_CHECK();
+  int done = 0;
+  // a label falls at least once per sweep until the fixed point, so n sweeps are an upper bound no lattice reaches
+  for (long it = 0; it < (long)n + kLabelBurst; it += kLabelBurst) {
+    ASW_HIP(hipMemsetAsync(flag_scratch, 0, sizeof(int32_t), s));
+    for (int k = 0; k < kLabelBurst; ++k) {
+      hipLaunchKernelGGL(label_sweep_kernel, dim3(blocks), dim3(kBlock), 0, s, adj_scratch, Lx, Ly, Lz, labels, flag_scratch);
+      ASW_LAUNCH_CHECK();
+    }
+    done += kLabelBurst;
+    int32_t changed = 0;
+    ASW_HIP(hipMemcpyAsync(&changed, flag_scratch, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    ASW_HIP(hipStreamSynchronize(s));
+    if (!changed) {
+      if (sweeps) *sweeps = done;
+      return ASW_OK;
+    }
+  }
+  return asw::set_error(ASW_ERR_STATE, "geom_label: the labels did not settle within %d sweeps", done);
+}
+
+extern "C" int64_t asw_geom_workspace_bytes(int n_voxels) {
+  if (n_voxels <= 0 || n_voxels > kMaxVoxels) {
+    asw::set_error(ASW_ERR_ARG, "geom_workspace_bytes: %d voxels outside 1..%d", n_voxels, kMaxVoxels);
+    return ASW_ERR_ARG;
+  }
+  size_t temp = 0;
+  if (cub_temp_bytes(n_voxels, &temp) != hipSuccess) {
+    asw::set_error(ASW_ERR_HIP, "geom_workspace_bytes: the scan / sort size query failed");
+    return ASW_ERR_HIP;
+  }
+  return (int64_t)(5 * align256((size_t)n_voxels * sizeof(int32_t)) + align256(temp));
+}
+
+extern "C" int asw_geom_compact(const int32_t* labels, const int32_t* q, const double* xs, int Lx, const double* ys, int Ly,
+                                const double* zs, int Lz, const double* mics, int M, const double* centre, double C,
+                                void* workspace, int64_t workspace_bytes, int32_t* power_index, int32_t* valid_flat,
+                                int32_t* valid_cid, int32_t* members, int32_t* bounds, int32_t* offsets, double* centres,
+                                double* tau, double* delta, int* counts, void* stream) {
+  ASW_CHECK_ARG(labels && q && xs && ys && zs && mics && centre && workspace && counts, "geom_compact: null pointer");
+  ASW_CHECK_ARG(power_index && valid_flat && valid_cid && members && bounds && offsets && centres && tau && delta,
+                "geom_compact: null output pointer");
+  ASW_CHECK_ARG(good_axes(Lx, Ly, Lz), "geom_compact: bad lattice %d x %d x %d", Lx, Ly, Lz);
+  ASW_CHECK_ARG(M >= 2 && M <= 32, "geom_compact: M = %d outside 2..32", M);
+  ASW_CHECK_ARG(C > 0, "geom_compact: C must be positive");
+  const int n = Lx * Ly * Lz, P = M - 1, blocks = asw::cdiv(n, kBlock);
+  const size_t slot = align256((size_t)n * sizeof(int32_t));
+  ASW_CHECK_ARG(workspace_bytes >= (int64_t)(5 * slot), "geom_compact: workspace of %lld bytes is too small (asw_geom_workspace_bytes)",
+                (long long)workspace_bytes);
+  size_t temp = (size_t)workspace_bytes - 5 * slot;
+  hipStream_t s = asw::as_stream(stream);
+  size_t need = 0;
+  ASW_HIP(cub_temp_bytes(n, &need));
+  ASW_CHECK_ARG(temp >= need, "geom_compact: workspace of %lld bytes is too small (asw_geom_workspace_bytes)",
+                (long long)workspace_bytes);
+  char* base = static_cast<char*>(workspace);
+  int32_t* rootf = reinterpret_cast<int32_t*>(base);
+  int32_t* validf = reinterpret_cast<int32_t*>(base + slot);
+  int32_t* rank = reinterpret_cast<int32_t*>(base + 2 * slot);
+  int32_t* vpos = reinterpret_cast<int32_t*>(base + 3 * slot);
+  int32_t* keys = reinterpret_cast<int32_t*>(base + 4 * slot);
+  void* cub = base + 5 * slot;
+
+  hipLaunchKernelGGL(flags_kernel, dim3(blocks), dim3(kBlock), 0, s, labels, n, rootf, validf);
+  ASW_LAUNCH_CHECK();
+  size_t t = temp;
+  ASW_HIP(hipcub::DeviceScan::ExclusiveSum(cub, t, rootf, rank, n, s));
+  t = temp;
+  ASW_HIP(hipcub::DeviceScan::ExclusiveSum(cub, t, validf, vpos, n, s));
+  hipLaunchKernelGGL(scatter_kernel, dim3(blocks), dim3(kBlock), 0, s, labels, q, n, P, rank, vpos, power_index, valid_flat,
+                     valid_cid, offsets);
+  ASW_LAUNCH_CHECK();
+  int32_t last[4] = {0, 0, 0, 0};
+  ASW_HIP(hipMemcpyAsync(&last[0], rank + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipMemcpyAsync(&last[1], rootf + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipMemcpyAsync(&last[2], vpos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipMemcpyAsync(&last[3], validf + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipStreamSynchronize(s));
+  const int G = last[0] + last[1], V = last[2] + last[3];
+  counts[0] = G;
+  counts[1] = V;
+  if (G < 0 || V < G || V > n) return asw::set_error(ASW_ERR_STATE, "geom_compact: inconsistent labels (G = %d, V = %d, n = %d)", G, V, n);
+  if (G == 0) return ASW_OK;
+  t = temp;
+  ASW_HIP(hipcub::DeviceRadixSort::SortPairs(cub, t, valid_cid, keys, valid_flat, members, V, 0, sort_bits(G), s));
+  hipLaunchKernelGGL(bounds_kernel, dim3(asw::cdiv(G + 1, kBlock)), dim3(kBlock), 0, s, keys, V, G, bounds);
+  ASW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(centres_kernel, dim3(asw::cdiv(G, kBlock)), dim3(kBlock), 0, s, members, bounds, G, xs, ys, zs, Ly, Lz, centres);
+  ASW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(delays_kernel, dim3(asw::cdiv((long)G * M, kBlock)), dim3(kBlock), 0, s, centres, G, mics, M, centre[0],
+                     centre[1], centre[2], C, tau, delta);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}

@@ -10,7 +10,8 @@
 // (sep/training/JointModel/network.py:27-104), Network.forward
 // (sep/training/SpeakerLocalization/network.py:363-405), the host energy loops
 // (sep/helpers/local_utils_3d.py:13-17,349-354), si_sdr pairs (sep/helpers/eval_utils.py:11-82),
-// SRP_Map_WINDOW_torch (sep/Traditional_SP/SRP_Prunning.py:387-434), MUSIC_Map_WINDOW / TOPS_Map_WINDOW (:436-497) and the joint separation
+// SRP_Map_WINDOW_torch (sep/Traditional_SP/SRP_Prunning.py:387-434), MUSIC_Map_WINDOW / TOPS_Map_WINDOW (:436-497), the geometry
+// tables of SRP_PHAT.__init__ / Map_3D_TDoA / search_cluster (:149-180,277-344,368-381; geom_*) and the joint separation
 // network's infer_sample / forward (sep/training/SpeakerSeparation/network.py:418-548).
 //
 // Model handles (asw_spot*, asw_sep*) are created and loaded through the C ABI
@@ -326,6 +327,105 @@ std::tuple<Tensor, Tensor> tops_map(const Tensor& mix, const Tensor& delta, int6
   return {out, max_bin};
 }
 
+// ---- geometry tables built on the device (csrc/geometry_kernels.hip) ---------------------------------
+// The axis arrays and the microphones are float64 device tensors; border / centre are host scalars.
+void need_axes(const Tensor& a, const Tensor& b, const Tensor& c, const Tensor& mics) {
+  need(a, "first axis", at::kDouble, 1);
+  need(b, "second axis", at::kDouble, 1);
+  need(c, "third axis", at::kDouble, 1);
+  need(mics, "mics", at::kDouble, 2);
+  for (const Tensor* t : {&b, &c, &mics}) same_device(a, *t, "all geometry operands");
+  TORCH_CHECK(mics.size(1) == 3 && mics.size(0) >= 2 && mics.size(0) <= 32, "mics must be [M, 3] with 2 <= M <= 32");
+  TORCH_CHECK(a.numel() > 0 && b.numel() > 0 && c.numel() > 0, "empty axis");
+}
+
+Tensor geom_lookup_planes(const Tensor& ys, const Tensor& xs, const Tensor& zs, const Tensor& mics, double C, double FS) {
+  need_axes(ys, xs, zs, mics);
+  const int ny = checked_int(ys.size(0), "ny"), nx = checked_int(xs.size(0), "nx"), nz = checked_int(zs.size(0), "nz");
+  const int M = checked_int(mics.size(0), "M");
+  TORCH_CHECK((int64_t)ny * nx * nz <= INT32_MAX, "lookup grid too large");
+  Tensor planes = at::empty({M - 1, ny, nx, nz}, ys.options());
+  Launch l(ys);
+  check_status(asw_geom_lookup_planes(ys.data_ptr<double>(), ny, xs.data_ptr<double>(), nx, zs.data_ptr<double>(), nz,
+                                      mics.data_ptr<double>(), M, C, FS, planes.data_ptr<double>(), l.stream),
+               "asw_geom_lookup_planes");
+  return planes;
+}
+
+std::tuple<Tensor, Tensor, Tensor> geom_voxel_map(const Tensor& xs, const Tensor& ys, const Tensor& zs, const Tensor& mics,
+                                                  c10::ArrayRef<double> border, c10::ArrayRef<double> centre, double C, double FS,
+                                                  double resolution) {
+  need_axes(xs, ys, zs, mics);
+  TORCH_CHECK(border.size() == 4 && centre.size() == 3, "border must hold 4 values and centre 3");
+  const int Lx = checked_int(xs.size(0), "Lx"), Ly = checked_int(ys.size(0), "Ly"), Lz = checked_int(zs.size(0), "Lz");
+  const int M = checked_int(mics.size(0), "M");
+  const int64_t n = (int64_t)Lx * Ly * Lz;
+  TORCH_CHECK(n <= (1 << 24), "SRP lattice too large");
+  Tensor q = at::empty({n, M - 1}, xs.options().dtype(at::kInt));
+  Tensor valid = at::empty({n}, xs.options().dtype(at::kByte));
+  Tensor dis = at::empty({Lx, Ly}, xs.options());
+  Launch l(xs);
+  check_status(asw_geom_voxel_map(xs.data_ptr<double>(), Lx, ys.data_ptr<double>(), Ly, zs.data_ptr<double>(), Lz,
+                                  mics.data_ptr<double>(), M, border.data(), centre.data(), C, FS, resolution,
+                                  q.data_ptr<int32_t>(), valid.data_ptr<uint8_t>(), dis.data_ptr<double>(), l.stream),
+               "asw_geom_voxel_map");
+  return {q, valid, dis};
+}
+
+std::tuple<Tensor, int64_t> geom_label(const Tensor& q, const Tensor& valid, int64_t Lx, int64_t Ly, int64_t Lz) {
+  need(q, "q", at::kInt, 2);
+  need(valid, "valid", at::kByte, 1);
+  same_device(q, valid, "q and valid");
+  TORCH_CHECK(Lx > 0 && Ly > 0 && Lz > 0 && Lx * Ly * Lz == valid.size(0) && q.size(0) == valid.size(0) && valid.size(0) <= (1 << 24),
+              "q must be [Lx*Ly*Lz, P] and valid [Lx*Ly*Lz]");
+  TORCH_CHECK(q.size(1) >= 1 && q.size(1) <= 31, "q must hold 1..31 pairs");
+  Tensor labels = at::empty({valid.size(0)}, q.options());
+  Tensor adj = at::empty({valid.size(0)}, q.options());
+  Tensor flag = at::empty({1}, q.options());
+  int sweeps = 0;
+  Launch l(q);
+  check_status(asw_geom_label(q.data_ptr<int32_t>(), valid.data_ptr<uint8_t>(), checked_int(Lx, "Lx"), checked_int(Ly, "Ly"),
+                              checked_int(Lz, "Lz"), checked_int(q.size(1), "P"), reinterpret_cast<uint32_t*>(adj.data_ptr<int32_t>()),
+                              flag.data_ptr<int32_t>(), labels.data_ptr<int32_t>(), &sweeps, l.stream),
+               "asw_geom_label");
+  return {labels, (int64_t)sweeps};
+}
+
+// -> power_index [n], valid_flat [V], valid_cid [V], members [V], bounds [G+1], offsets [G,P], centres [G,3], tau [G,M], delta [G,M]
+std::vector<Tensor> geom_compact(const Tensor& labels, const Tensor& q, const Tensor& xs, const Tensor& ys, const Tensor& zs,
+                                 const Tensor& mics, c10::ArrayRef<double> centre, double C) {
+  need_axes(xs, ys, zs, mics);
+  need(labels, "labels", at::kInt, 1);
+  need(q, "q", at::kInt, 2);
+  same_device(xs, labels, "axes and labels");
+  same_device(xs, q, "axes and q");
+  TORCH_CHECK(centre.size() == 3, "centre must hold 3 values");
+  const int Lx = checked_int(xs.size(0), "Lx"), Ly = checked_int(ys.size(0), "Ly"), Lz = checked_int(zs.size(0), "Lz");
+  const int M = checked_int(mics.size(0), "M");
+  const int64_t n = (int64_t)Lx * Ly * Lz;
+  TORCH_CHECK(n <= (1 << 24) && labels.size(0) == n && q.size(0) == n && q.size(1) == M - 1,
+              "labels must be [Lx*Ly*Lz] and q [Lx*Ly*Lz, M-1]");
+  const int64_t ws_bytes = asw_geom_workspace_bytes((int)n);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_geom_workspace_bytes failed: ", asw_last_error());
+  auto i32 = labels.options();
+  Tensor ws = at::empty({ws_bytes}, i32.dtype(at::kByte));
+  Tensor power_index = at::empty({n}, i32), valid_flat = at::empty({n}, i32), valid_cid = at::empty({n}, i32);
+  Tensor members = at::empty({n}, i32), bounds = at::empty({n + 1}, i32), offsets = at::empty({n, M - 1}, i32);
+  Tensor centres = at::empty({n, 3}, xs.options()), tau = at::empty({n, M}, xs.options()), delta = at::empty({n, M}, xs.options());
+  int counts[2] = {0, 0};
+  Launch l(xs);
+  check_status(asw_geom_compact(labels.data_ptr<int32_t>(), q.data_ptr<int32_t>(), xs.data_ptr<double>(), Lx, ys.data_ptr<double>(), Ly,
+                                zs.data_ptr<double>(), Lz, mics.data_ptr<double>(), M, centre.data(), C, ws.data_ptr(), ws_bytes,
+                                power_index.data_ptr<int32_t>(), valid_flat.data_ptr<int32_t>(), valid_cid.data_ptr<int32_t>(),
+                                members.data_ptr<int32_t>(), bounds.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(),
+                                centres.data_ptr<double>(), tau.data_ptr<double>(), delta.data_ptr<double>(), counts, l.stream),
+               "asw_geom_compact");
+  const int64_t G = counts[0], V = counts[1];
+  // the [G, ...] tables outlive the build (tau and delta stay on the device for the maps): own storage, not a slice of [n, ...]
+  return {power_index, valid_flat.narrow(0, 0, V), valid_cid.narrow(0, 0, V), members.narrow(0, 0, V), bounds.narrow(0, 0, G + 1),
+          offsets.narrow(0, 0, G), centres.narrow(0, 0, G).clone(), tau.narrow(0, 0, G).clone(), delta.narrow(0, 0, G).clone()};
+}
+
 // ---- joint separation network ---------------------------------------------------------------------
 Tensor sep_infer(int64_t model, const Tensor& mix, const Tensor& offsets) {
   TORCH_CHECK(model != 0, "sep_infer: null model handle");
@@ -414,6 +514,11 @@ TORCH_LIBRARY(asw, m) {
         "int hop) -> Tensor");
   m.def("tops_map(Tensor mix, Tensor delta, int bin0, int nbins, float coef, int window, int step, "
         "int n_windows, int nfft, int hop) -> (Tensor, Tensor)");
+  m.def("geom_lookup_planes(Tensor ys, Tensor xs, Tensor zs, Tensor mics, float C, float FS) -> Tensor");
+  m.def("geom_voxel_map(Tensor xs, Tensor ys, Tensor zs, Tensor mics, float[] border, float[] centre, float C, float FS, "
+        "float resolution) -> (Tensor, Tensor, Tensor)");
+  m.def("geom_label(Tensor q, Tensor valid, int Lx, int Ly, int Lz) -> (Tensor, int)");
+  m.def("geom_compact(Tensor labels, Tensor q, Tensor xs, Tensor ys, Tensor zs, Tensor mics, float[] centre, float C) -> Tensor[]");
   m.def("sep_infer(int model, Tensor mix, Tensor offsets) -> Tensor");
   m.def("sep_forward(int model, Tensor mix, int n_speakers, int n_mics, int max_speakers) -> Tensor");
   m.def("sep_forward_counts(int model, Tensor mix, int[] counts, int n_mics, int max_speakers) -> Tensor");
@@ -433,6 +538,10 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("hermitian_eigh", &hermitian_eigh);
   m.impl("music_map", &music_map);
   m.impl("tops_map", &tops_map);
+  m.impl("geom_lookup_planes", &geom_lookup_planes);
+  m.impl("geom_voxel_map", &geom_voxel_map);
+  m.impl("geom_label", &geom_label);
+  m.impl("geom_compact", &geom_compact);
   m.impl("sep_infer", &sep_infer);
   m.impl("sep_forward", &sep_forward);
   m.impl("sep_forward_counts", &sep_forward_counts);

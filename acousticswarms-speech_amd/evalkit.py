@@ -5,10 +5,10 @@ record of ``sep/eval/eval_model.py``.
 Follows sep/eval/eval_model.py:18-91 (matching, metadata preprocessing), :129-249 (result
 record) and sep/eval/get_items.py:10-46 (directory layout written by
 datasets/generate_dataset.py:633-699: ``metadata.json`` + ``micNN_mixed.wav`` +
-``mic00_voiceNN.wav``).  Two third-party metrics the reference calls are absent here and are
-NOT restated: mir_eval's BSS-eval SDR (fields ``si_snr_in_mir`` / ``si_snri_mir`` are None) and
-asteroid's metric wrapper, whose SI-SDR is the plain scale-invariant SDR of
-``sep/helpers/eval_utils.py:11-39`` (``hostdsp.si_sdr``) -- "parity unpinned" for the wrapper.
+``mic00_voiceNN.wav``).  The two third-party metrics the reference calls are absent here: mir_eval's
+BSS-eval SDR is restated below from the published BSS-eval v3 algorithm (fields ``si_snr_in_mir`` /
+``si_snri_mir``), and asteroid's metric wrapper is not needed -- its SI-SDR is the plain scale-invariant
+SDR of ``sep/helpers/eval_utils.py:11-39`` (``hostdsp.si_sdr``).  Both are "parity unpinned".
 """
 import json
 import os

@@ -10,6 +10,8 @@ implementation of sep/training/SpeakerSeparation/network.py) or any object with
 ``infer(mix, patches)``; with ``sep_model=None`` the separation stage is skipped, ``audio`` is
 None and ``times[4]`` stays 0 (callers must then report a localize-only latency).
 """
+import collections
+import threading
 import time
 
 import numpy as np
@@ -37,32 +39,62 @@ def _sync():
         pass
 
 
+GEOMETRY_CACHE_SIZE = 8        # arrays kept by JointModel.mic_array_for (a 7-mic bench array: about 65 MB of tables)
+
+
+def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host"):
+    """The configuration string of the reference's ``setup`` (:125-131), extended by the pruning method and the
+    geometry mode when they are not the defaults."""
+    key = '~'.join([f"{x:.05f}" for x in np.asarray(mic_positions).flatten()]) \
+        + '|' + '~'.join([f"{x:.05f}" for x in speaker_range])
+    if prone_method != "SRP":
+        key += '|' + str(prone_method)
+    if geometry != "host":
+        key += '|geometry=' + str(geometry)
+    return key
+
+
+class _Pending(object):
+    """A geometry another thread is building (JointModel.mic_array_for)."""
+    __slots__ = ("done", "value", "error")
+
+    def __init__(self):
+        self.done, self.value, self.error = threading.Event(), None, None
+
+
 class JointModel(object):
-    def __init__(self, spot_model, sep_model=None, device=None):
+    def __init__(self, spot_model, sep_model=None, device=None, geometry="host"):
+        """``geometry``: default of ``setup``'s argument of that name and the mode of the per-mixture arrays of
+        ``mic_array_for`` -- "host" or "device" (see ``MicArray``)."""
+        if geometry not in ("host", "device"):
+            raise ValueError(f'geometry must be "host" or "device", got {geometry!r}')
         self.spot_model = spot_model
         self.sep_model = sep_model
         self.device = device
+        self.geometry = geometry
+        self._geometry_cache = collections.OrderedDict()      # config key -> MicArray | _Pending, least recent first
+        self._geometry_lock = threading.Lock()
+        self.geometry_stats = {"builds": 0, "hits": 0}
         self.times = [0, 0, 0, 0, 0]
         self.previous_config = None
         self.Mic_processor = None
         self._mix_dev = self._mix_src = None
 
-    def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP"):
+    def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP", geometry=None):
         """(Re)build the geometry tables unless the configuration is unchanged (:125-137).
         One-off per geometry and excluded from latency, as the reference's README notes.
         ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS") and is part of the
-        configuration."""
-        key = '~'.join([f"{x:.05f}" for x in np.asarray(mic_positions).flatten()]) \
-            + '|' + '~'.join([f"{x:.05f}" for x in speaker_range])
-        if prone_method != "SRP":
-            key += '|' + str(prone_method)
+        configuration, and so is ``geometry`` ("host" | "device", default: the model's): where the tables are
+        built."""
+        geometry = self.geometry if geometry is None else geometry
+        key = config_key(mic_positions, speaker_range, prone_method, geometry)
         if key == self.previous_config:
             print("reuse the previous recycle!")
             return
         import gc
         gc.unfreeze()                       # a previous geometry may go now
         self.Mic_processor = MicArray(mic_positions, Spk_Range=speaker_range, Prone_method=prone_method,
-                                      device=self.device)
+                                      device=self.device, geometry=geometry)
         self.previous_config = key
         # The geometry tables are tens of thousands of small arrays and lists that live as long as
         # this configuration.  Left in the collector's oldest generation they make every full
@@ -71,6 +103,60 @@ class JointModel(object):
         # generation: later collections only look at what a forward() itself allocates.
         gc.collect()
         gc.freeze()
+
+    def mic_array_for(self, mic_positions, speaker_range, prone_method="SRP"):
+        """The ``MicArray`` of one mixture's own geometry (batch path, ``geometries=``), built in the model's
+        ``geometry`` mode and kept in a small LRU keyed like ``previous_config``: an array that repeats within a
+        batch is built once, and two searches asking for the same array at the same time share one build (the
+        second waits for the first).  Thread-safe; ``geometry_stats`` counts builds and hits.
+
+        Unlike ``setup`` this does not run ``gc.collect()`` / ``gc.freeze()``: that pair walks the whole heap
+        (tens of ms) and a per-mixture array does not live long enough to be worth moving to the permanent
+        generation.  Instead the batch raises the collector's oldest-generation threshold while it runs
+        (``batching.no_full_collections``), so no full collection lands inside a search, and an evicted array is
+        released by reference counting alone -- its tables hold no reference cycle."""
+        key = config_key(mic_positions, speaker_range, prone_method, self.geometry)
+        with self._geometry_lock:
+            hit = self._geometry_cache.get(key)
+            if hit is None:
+                pending = _Pending()
+                self._geometry_cache[key] = pending
+            else:
+                self._geometry_cache.move_to_end(key)
+        if hit is not None:
+            if isinstance(hit, _Pending):
+                hit.done.wait()
+                if hit.error is not None:
+                    raise hit.error
+                hit = hit.value
+            with self._geometry_lock:
+                self.geometry_stats["hits"] += 1
+            return hit
+        try:
+            mp = MicArray(np.asarray(mic_positions), Spk_Range=speaker_range, Prone_method=prone_method,
+                          device=self.device, geometry=self.geometry)
+        except BaseException as exc:
+            with self._geometry_lock:
+                self._geometry_cache.pop(key, None)
+            pending.error = exc
+            pending.done.set()
+            raise
+        with self._geometry_lock:
+            self.geometry_stats["builds"] += 1
+            self._geometry_cache[key] = mp
+            ready = [k for k, v in self._geometry_cache.items() if not isinstance(v, _Pending)]
+            for k in ready[:max(0, len(ready) - GEOMETRY_CACHE_SIZE)]:
+                del self._geometry_cache[k]
+        pending.value = mp
+        pending.done.set()
+        return mp
+
+    def use_geometry(self, mic_positions, speaker_range):
+        """Make the cached array of this geometry (``mic_array_for``) the one ``forward`` searches with: the plain
+        per-mixture loop of ``shard.localize_batch(..., geometries=...)``."""
+        method = self.Mic_processor.Prone_method if self.Mic_processor is not None else "SRP"
+        self.Mic_processor = self.mic_array_for(mic_positions, speaker_range, method)
+        self.previous_config = config_key(mic_positions, speaker_range, method, self.geometry)
 
     def forward(self, mix_data):
         """-> (patches, audio_loc, audio, SRP_drop, stage1_drop, spot_times) (:142-149)."""

@@ -71,7 +71,10 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
 
 class MicArray(object):
     def __init__(self, mic_positions, demo=False, Spk_Range=None, grid_size=0.05, Prone_method="SRP",
-                 MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None):
+                 MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None,
+                 geometry="host"):
+        """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
+        (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture)."""
         if Prone_method not in PRONE_METHODS:
             # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
             raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
@@ -86,7 +89,8 @@ class MicArray(object):
         self.upper_bound_pairwise = (np.linalg.norm(mic_positions[1:] - mic_positions[0], axis=1) + 0.08) \
             / SPEED_OF_SOUND * FS
         self.SRP_node = SRPPhat(mic_pos=mic_positions, freq_bins=FREQ_BINS, Range_spk=Spk_Range, grid_size=grid_size,
-                                FS=FS, n_fft=N_FFT, threshold=[0.15, 0.015, 0.05], WIDTH=INIT_WIDTH, device=device)
+                                FS=FS, n_fft=N_FFT, threshold=[0.15, 0.015, 0.05], WIDTH=INIT_WIDTH, device=device,
+                                geometry=geometry)
         self.original_times = 0
         self.spotforming_times = 0
         self.big_spotforming_times = 0

@@ -15,9 +15,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ASW_LIB_PATH") or os.path.join(_HERE, "libasw_hip.so")   # env: A/B builds only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["asw_common.cpp", "convgemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip", "misc_kernels.hip", "attention_mfma.hip", "srp_kernels.hip",
-           "pruner_kernels.hip",
+           "pruner_kernels.hip", "geometry_kernels.hip",
            "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip"]
 HEADERS = ["asw_common.h", "model_common.h", "mfma_util.h"]
+# geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
+EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"]}
 OPS_PATH = os.path.join(_HERE, "libasw_torch_ops.so")      # TORCH_LIBRARY(asw, ...) adapters over the C ABI
 OPS_SOURCE = "torch_ops.cpp"
 
@@ -36,7 +38,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         op = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         objs.append(op)
         if force or not os.path.exists(op) or os.path.getmtime(op) < max(os.path.getmtime(sp), hdr_time):
-            jobs.append(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-c", sp, "-o", op])
+            jobs.append(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"] + EXTRA_FLAGS.get(src, [])
+                        + ["-c", sp, "-o", op])
     if not jobs and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(o) for o in objs):
         return LIB_PATH
 
@@ -235,6 +238,16 @@ SIGNATURES = {
                               c_void_p]),
     "asw_tops_map": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p,
                              c_void_p, c_void_p, c_void_p]),
+    "asw_geom_lookup_planes": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_double,
+                                       c_void_p, c_void_p]),
+    "asw_geom_voxel_map": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "asw_geom_label": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int),
+                               c_void_p]),
+    "asw_geom_workspace_bytes": (c_int64, [c_int]),
+    "asw_geom_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                 c_void_p, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
 }
 
 _lib = None

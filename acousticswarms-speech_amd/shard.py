@@ -213,7 +213,7 @@ class ShardedSpotModel:
         return sorted(merged, key=key)
 
 
-def localize_batch(joint_model, mixes, group=None, concurrent=2):
+def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None):
     """A batch of mixtures over the ranks of one node (BASELINE config "batch of 64 mixtures"):
     with at least as many mixtures as ranks the cheapest partition is by whole mixture --
     contiguous balanced blocks, each rank runs the complete search of its mixtures on its own
@@ -226,8 +226,17 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2):
     internal batches stay full and one search's host stages overlap the others' GPU work) when the spot
     model is the HIP model; ``concurrent=1`` or any other duck-typed model gives the plain loop.
 
+    ``geometries``: one ``(mic_positions, speaker_range)`` per mixture, for batches recorded with a different
+    array each (all mixtures then share M and T; ``ValueError`` otherwise, before any device work).  A mixture's
+    geometry goes to the rank that gets the mixture; there each search uses the ``MicArray`` of its own geometry
+    from ``JointModel.mic_array_for`` (built in the model's ``geometry`` mode, repeated arrays once), in the batched
+    form and in the plain loop alike.  ``None``: every mixture on the array of ``joint_model.setup()``.
+
     ``joint_model.spot_model`` must be the plain per-rank model here.  Returns, on every rank and
     in mixture order, a list of dicts {centres [K,3], powers [K], names, spot_times, times[5]}."""
+    from .batching import check_geometries, no_full_collections
+    check_geometries(mixes, geometries)
+    import contextlib
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -242,16 +251,28 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2):
     local = []
     if batched:
         from .batching import search_batched
-        res, stats = search_batched(joint_model, [mixes[k] for k in mine], concurrent=concurrent)
+        res, stats = search_batched(joint_model, [mixes[k] for k in mine], concurrent=concurrent,
+                                    geometries=None if geometries is None else [geometries[k] for k in mine])
         localize_batch.last_stats = stats                    # diagnostic: launches, candidates, GPU seconds inside them
         local = list(zip(mine, res))
     else:
-        for k in mine:
-            patches, _audio_loc, _audio, _d0, _d1, spot_times = joint_model.forward(mixes[k])
-            local.append((k, {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
-                              "powers": np.array([p[2] for p in patches]),
-                              "names": [p[3] for p in patches],
-                              "spot_times": spot_times, "times": list(joint_model.times)}))
+        own = geometries is not None and hasattr(joint_model, "use_geometry")
+        if geometries is not None and not own:
+            raise RuntimeError("geometries= needs a model with use_geometry() (JointModel)")
+        before = (joint_model.Mic_processor, joint_model.previous_config) if own else None
+        try:
+            with (no_full_collections() if own else contextlib.nullcontext()):
+                for k in mine:
+                    if own:
+                        joint_model.use_geometry(geometries[k][0], geometries[k][1])
+                    patches, _audio_loc, _audio, _d0, _d1, spot_times = joint_model.forward(mixes[k])
+                    local.append((k, {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
+                                      "powers": np.array([p[2] for p in patches]),
+                                      "names": [p[3] for p in patches],
+                                      "spot_times": spot_times, "times": list(joint_model.times)}))
+        finally:
+            if own:                                           # the array of setup() is the model's again
+                joint_model.Mic_processor, joint_model.previous_config = before
     if world == 1:
         return [r for _k, r in local]
     box = [None] * world

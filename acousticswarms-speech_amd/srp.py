@@ -1,4 +1,5 @@
-"""SRP-PHAT pruning stage: geometry tables on the host, steered-response map on the GPU.
+"""SRP-PHAT pruning stage: geometry tables on the host (or, with ``geometry="device"``, built on the
+GPU by csrc/geometry_kernels.hip), steered-response map on the GPU.
 
 Mirrors ``SRP_PHAT`` (sep/Traditional_SP/SRP_Prunning.py:101-643; SURVEY.md §8 a-O, a-P,
 a-Q) with the same method names used by the search (``reset``,
@@ -13,8 +14,15 @@ a-Q) with the same method names used by the search (``reset``,
   (csrc/srp_kernels.hip) -- there is no host fallback;
 * the alternative MUSIC and TOPS maps (``MUSIC_Map_WINDOW`` / ``TOPS_Map_WINDOW``, :436-497)
   run in csrc/pruner_kernels.hip.  Where the reference would divide 0/0 (no complete
-  window), they raise ``RuntimeError`` instead of leaving a NaN map.
+  window), they raise ``RuntimeError`` instead of leaving a NaN map;
+* ``SRPPhat(..., geometry="device")`` builds the same tables with the ``torch.ops.asw.geom_*`` kernels -- for
+  arrays that change from mixture to mixture, where the host build costs more than a batched search.  The
+  integer tables are equal and the float tables bit-identical to the host build (same float64 expression
+  order, no fma); ``clusters`` is then a lazy sequence over the CSR member arrays and ``Pos_5`` / ``Pos_1``
+  are generated from the point index.  ``"device"`` without a GPU raises ``RuntimeError``.
 """
+import threading
+
 import numpy as np
 from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
@@ -41,6 +49,93 @@ class GridCluster(object):
         return np.mean(self.grids, axis=0)
 
 
+class ClusterSeq(object):
+    """The cluster list of a device-built node: a read-only sequence whose items are ``GridCluster`` objects made
+    on demand from the CSR arrays (``offsets`` [G,P], ``bounds`` [G+1], ``members`` [V]: flat voxel indices,
+    ascending within a cluster) and the lattice axes.  Item i equals item i of the host-built list."""
+
+    def __init__(self, offsets, bounds, members, x_grids, y_grids, z_grids):
+        self.offsets = np.asarray(offsets, dtype=np.int64)
+        self.bounds = np.asarray(bounds, dtype=np.int64)
+        self.members = np.asarray(members, dtype=np.int64)
+        self.axes = (np.asarray(x_grids), np.asarray(y_grids), np.asarray(z_grids))
+        self.shape = tuple(len(a) for a in self.axes)
+
+    def __len__(self):
+        return self.offsets.shape[0]
+
+    def sizes(self):
+        return np.diff(self.bounds)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        i = int(i)
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError("cluster index out of range")
+        mem = self.members[self.bounds[i]:self.bounds[i + 1]]
+        ix, iy, iz = np.unravel_index(mem, self.shape)
+        pts = np.stack([self.axes[0][ix], self.axes[1][iy], self.axes[2][iz]], axis=1)
+        return GridCluster(self.offsets[i], pts, np.stack([ix, iy, iz], axis=1))
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+
+class LookupPositions(object):
+    """``Pos_5`` / ``Pos_1`` of a device-built node: the [ny,nx,nz,3] point table of a lookup grid, generated from
+    the flat point index ((y*nx + x)*nz + z) instead of stored.  Supports what the cube scans use:
+    ``pos.reshape(-1, 3)[idx]``; ``np.asarray(pos)`` materialises the table."""
+
+    def __init__(self, xx, yy, zz):
+        self.xx, self.yy, self.zz = xx, yy, zz
+        self.shape = (len(yy), len(xx), len(zz), 3)
+
+    def reshape(self, *shape):
+        if shape not in ((-1, 3), ((-1, 3),)):
+            return np.asarray(self).reshape(*shape)
+        return self
+
+    def __getitem__(self, idx):
+        y, x, z = np.unravel_index(np.asarray(idx, dtype=np.int64), self.shape[:3])
+        return np.stack([self.xx[x], self.yy[y], self.zz[z]], axis=-1)
+
+    def __array__(self, dtype=None, copy=None):
+        X, Y, Z = np.meshgrid(self.xx, self.yy, self.zz)
+        a = np.stack((X, Y, Z), axis=3)
+        return a if dtype is None else a.astype(dtype)
+
+
+_TWIDDLES = {}
+_TWIDDLES_LOCK = threading.Lock()
+
+
+def _twiddles(freq_bins, n_fft, dev):
+    """(nb_pad, DFT twiddle table on ``dev``) of a bin range.  The table does not depend on the array, so it is
+    uploaded once per device and bin range and shared by every node (with one array per mixture it would
+    otherwise cross PCIe once per mixture: 3.1 MB)."""
+    import torch
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    nb = len(freq_bins)
+    key = (index, int(n_fft), int(freq_bins[0]), nb, bool(np.array_equal(freq_bins, np.arange(freq_bins[0], freq_bins[0] + nb))))
+    with _TWIDDLES_LOCK:
+        hit = _TWIDDLES.get(key) if key[-1] else None
+        if hit is None:
+            nb_pad = ((nb + 63) // 64) * 64
+            k = freq_bins.astype(np.float64)[:, None]
+            nn = np.arange(n_fft, dtype=np.float64)[None, :]
+            ang = 2 * np.pi * k * nn / n_fft
+            tw = np.zeros((2 * nb_pad, n_fft), dtype=np.float32)
+            tw[:nb] = np.cos(ang)
+            tw[nb_pad:nb_pad + nb] = -np.sin(ang)
+            hit = (nb_pad, torch.from_numpy(tw).to(dev))
+            if key[-1]:
+                _TWIDDLES[key] = hit
+    return hit
+
+
 def _offsets_within(offsets, center, width):
     """All pairs within +-width/2 of ``center`` (hyperbola_offset / hyperbola_area_sample,
     SRP_Prunning.py:19-39); offsets [..., P].  The same comparisons as the all-pairs mask,
@@ -63,7 +158,10 @@ def _offsets_within(offsets, center, width):
 
 class SRPPhat(object):
     def __init__(self, mic_pos, freq_bins, Range_spk, C=343, FS=16000, n_fft=1024, grid_size=0.06,
-                 grid_size_z=0.1, sample_resolution=4, threshold=0.03, WIDTH=8, device=None):
+                 grid_size_z=0.1, sample_resolution=4, threshold=0.03, WIDTH=8, device=None, geometry="host"):
+        if geometry not in ("host", "device"):
+            raise ValueError(f'geometry must be "host" or "device", got {geometry!r}')
+        self.geometry = geometry
         self.device = device
         self.C, self.FS, self.n_fft = C, FS, n_fft
         self.freq_bins = np.asarray(freq_bins)
@@ -79,33 +177,16 @@ class SRPPhat(object):
         self.y_grids = np.arange(r[2], r[3], grid_size)
         self.z_grids = np.arange(r[4], r[5], grid_size_z)
         self.Lx, self.Ly, self.Lz = len(self.x_grids), len(self.y_grids), len(self.z_grids)
-        gx, gy = np.meshgrid(self.x_grids, self.y_grids, indexing="ij")
-        self.dis_matrix = np.sqrt((gx - self.mic_center[0]) ** 2 + (gy - self.mic_center[1]) ** 2) + 1e-8
         self.Axis_range = [[r[0], r[1]], [r[2], r[3]], [r[4], r[5]]]
-
-        # 5 cm and 1 cm lookup grids with their TDoA vectors (:149-170)
-        self.Pos_5, self.Offset_5 = self._lookup_grid(0.05)
-        self.Pos_1, self.Offset_1 = self._lookup_grid(0.01)
-        # pair-major copies for the cube scans (asw_cube_select_planes streams one pair's plane)
-        self._planes_5 = np.ascontiguousarray(np.moveaxis(self.Offset_5, 3, 0))
-        self._planes_1 = np.ascontiguousarray(np.moveaxis(self.Offset_1, 3, 0))
-
         keepout = 0.2                                       # :174-180
         self.array_border = [self.mic_pos[:, 0].min() - keepout, self.mic_pos[:, 1].min() - keepout,
                              self.mic_pos[:, 0].max() + keepout, self.mic_pos[:, 1].max() + keepout]
-        self._map_3d_tdoa()
-
-        # propagation delays used by the steering term; mic z is ignored and the point's z is
-        # taken absolute, exactly as generate_mod_vector does (:368-381)
-        dx = self.grids[:, None, 0] - self.mic_pos[None, :, 0]
-        dy = self.grids[:, None, 1] - self.mic_pos[None, :, 1]
-        self.tau = np.sqrt(dx ** 2 + dy ** 2 + self.grids[:, None, 2] ** 2) / self.C      # [G,M] seconds
         self.omega = 2 * np.pi * FS * self.freq_bins / n_fft
-        # TOPS path differences (TOPS_block.py:45-48,105-112): mics and points centred on the mic mean, in
-        # full 3-D; delta[g, m] = |p_g| - |p_g - m_m|.  The steering phase is tops_coef * (k - f0) * delta.
-        pc = self.grids - self.mic_center
-        mc = self.mic_pos - self.mic_center
-        self.tops_delta = np.linalg.norm(pc, axis=1)[:, None] - np.linalg.norm(pc[:, None, :] - mc[None], axis=2)
+        self._geom_dev = None
+        if geometry == "device":
+            self._build_on_device()
+        else:
+            self._build_on_host()
         self.tops_coef = 2 * np.pi * FS / (n_fft * C)
         self.tops_max_bin = None
         ii, jj = np.triu_indices(self.num_mic, k=1)          # row-major upper triangle == mask_triu order
@@ -115,6 +196,85 @@ class SRPPhat(object):
         self._dev = None
 
     # ---- one-off geometry ---------------------------------------------------------
+    def _build_on_host(self):
+        gx, gy = np.meshgrid(self.x_grids, self.y_grids, indexing="ij")
+        self.dis_matrix = np.sqrt((gx - self.mic_center[0]) ** 2 + (gy - self.mic_center[1]) ** 2) + 1e-8
+
+        # 5 cm and 1 cm lookup grids with their TDoA vectors (:149-170)
+        self.Pos_5, self.Offset_5 = self._lookup_grid(0.05)
+        self.Pos_1, self.Offset_1 = self._lookup_grid(0.01)
+        # pair-major copies for the cube scans (asw_cube_select_planes streams one pair's plane)
+        self._planes_5 = np.ascontiguousarray(np.moveaxis(self.Offset_5, 3, 0))
+        self._planes_1 = np.ascontiguousarray(np.moveaxis(self.Offset_1, 3, 0))
+
+        self._map_3d_tdoa()
+
+        # propagation delays used by the steering term; mic z is ignored and the point's z is
+        # taken absolute, exactly as generate_mod_vector does (:368-381)
+        dx = self.grids[:, None, 0] - self.mic_pos[None, :, 0]
+        dy = self.grids[:, None, 1] - self.mic_pos[None, :, 1]
+        self.tau = np.sqrt(dx ** 2 + dy ** 2 + self.grids[:, None, 2] ** 2) / self.C      # [G,M] seconds
+        # TOPS path differences (TOPS_block.py:45-48,105-112): mics and points centred on the mic mean, in
+        # full 3-D; delta[g, m] = |p_g| - |p_g - m_m|.  The steering phase is tops_coef * (k - f0) * delta.
+        pc = self.grids - self.mic_center
+        mc = self.mic_pos - self.mic_center
+        self.tops_delta = np.linalg.norm(pc, axis=1)[:, None] - np.linalg.norm(pc[:, None, :] - mc[None], axis=2)
+
+    def _build_on_device(self):
+        """The same tables from csrc/geometry_kernels.hip (``torch.ops.asw.geom_*``): the kernels get the axis arrays
+        computed here, so every position is the host's; tau and tops_delta also stay on the device for the map
+        kernels.  ``build_times`` keeps the split of the build: kernels (to the last synchronise), device-to-host
+        copies, host remainder, in seconds."""
+        import time
+        import torch
+        from . import native
+        dev = torch.device(self.device if self.device is not None else "cuda")
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError('geometry="device" builds the tables on the MI355X (no host fallback)')
+        t0 = time.perf_counter()
+        ops = native.torch_ops()
+        r = self.Range_spk
+        C, FS = float(self.C), float(self.FS)
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        mics = up(self.mic_pos)
+        zz = np.arange(r[4], r[5], 0.1)
+        zz_d = up(zz)
+        lookup = {}
+        for step in (0.05, 0.01):
+            xx, yy = np.arange(r[0], r[1], step), np.arange(r[2], r[3], step)
+            lookup[step] = (xx, yy, ops.geom_lookup_planes(up(yy), up(xx), zz_d, mics, C, FS))
+        xs, ys, zs = up(self.x_grids), up(self.y_grids), up(self.z_grids)
+        centre = [float(v) for v in self.mic_center]
+        q, valid, dis = ops.geom_voxel_map(xs, ys, zs, mics, [float(v) for v in self.array_border], centre, C, FS,
+                                           float(self.sample_resolution))
+        labels, self.label_sweeps = ops.geom_label(q, valid, self.Lx, self.Ly, self.Lz)
+        power_index, valid_flat, valid_cid, members, bounds, offsets, centres, tau, delta = \
+            ops.geom_compact(labels, q, xs, ys, zs, mics, centre, C)
+        G = int(offsets.shape[0])
+        if G == 0:
+            raise RuntimeError("the keep-out region covers the whole speaker range: no valid voxel")
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+
+        (xx5, yy5, p5), (xx1, yy1, p1) = lookup[0.05], lookup[0.01]
+        self._planes_5, self._planes_1 = native.to_host(p5), native.to_host(p1)     # one copy per table
+        small = [t.cpu().numpy() for t in (power_index, valid_flat, valid_cid, members, bounds, offsets, centres, tau, delta,
+                                            dis)]
+        t2 = time.perf_counter()
+
+        self.Offset_5, self.Offset_1 = np.moveaxis(self._planes_5, 0, 3), np.moveaxis(self._planes_1, 0, 3)   # views
+        self.Pos_5, self.Pos_1 = LookupPositions(xx5, yy5, zz), LookupPositions(xx1, yy1, zz)
+        self.POWER_MAP = np.zeros((self.Lx, self.Ly, self.Lz))
+        self.POWER_INDEX = small[0].astype(int).reshape(self.Lx, self.Ly, self.Lz)
+        self._valid_flat, self._valid_cid = small[1].astype(np.int64), small[2].astype(np.int64)
+        self.clusters = ClusterSeq(small[5], small[4], small[3], self.x_grids, self.y_grids, self.z_grids)
+        self.grids, self.tau, self.tops_delta, self.dis_matrix = small[6], small[7], small[8], small[9]
+        self.SRP_times = G
+        self._geom_dev = {"dev": dev, "tau": tau, "delta": delta}
+        self.build_times = {"kernels_s": t1 - t0, "d2h_s": t2 - t1, "host_s": time.perf_counter() - t2}
+
     def _lookup_grid(self, step):
         r = self.Range_spk
         xx, yy, zz = np.arange(r[0], r[1], step), np.arange(r[2], r[3], step), np.arange(r[4], r[5], 0.1)
@@ -197,20 +357,14 @@ class SRPPhat(object):
     def _device_tables(self, dev):
         import torch
         if self._dev is None or self._dev["dev"] != dev:
-            nb = len(self.freq_bins)
-            nb_pad = ((nb + 63) // 64) * 64
-            k = self.freq_bins.astype(np.float64)[:, None]
-            nn = np.arange(self.n_fft, dtype=np.float64)[None, :]
-            ang = 2 * np.pi * k * nn / self.n_fft
-            tw = np.zeros((2 * nb_pad, self.n_fft), dtype=np.float32)
-            tw[:nb] = np.cos(ang)
-            tw[nb_pad:nb_pad + nb] = -np.sin(ang)
-            self._dev = {"dev": dev, "nb_pad": nb_pad,
-                         "tw": torch.from_numpy(tw).to(dev),
-                         "tau": torch.from_numpy(np.ascontiguousarray(self.tau)).to(dev),
+            nb_pad, tw = _twiddles(self.freq_bins, self.n_fft, dev)
+            built = self._geom_dev if self._geom_dev is not None and self._geom_dev["dev"] == dev else None
+            self._dev = {"dev": dev, "nb_pad": nb_pad, "tw": tw,
+                         # a device-built node left its delays on the device: nothing to upload again
+                         "tau": built["tau"] if built else torch.from_numpy(np.ascontiguousarray(self.tau)).to(dev),
                          "omega": torch.from_numpy(np.ascontiguousarray(self.omega, dtype=np.float64)).to(dev),
                          "pi": torch.from_numpy(self.pair_i).to(dev), "pj": torch.from_numpy(self.pair_j).to(dev),
-                         "delta": torch.from_numpy(np.ascontiguousarray(self.tops_delta)).to(dev)}
+                         "delta": built["delta"] if built else torch.from_numpy(np.ascontiguousarray(self.tops_delta)).to(dev)}
         return self._dev
 
     def _device_signal(self, signal):

@@ -566,6 +566,48 @@ int asw_tops_map(const double* evecs, const double* magsum, int n_windows, int n
                  int M, const double* delta, int G, double coef, double* q_scratch,
                  int32_t* max_bin, float* out, void* stream);
 
+/* Geometry tables of the SRP-PHAT stage built on the device (csrc/geometry_kernels.hip; reference:
+ * SRP_PHAT.__init__, Map_3D_TDoA, search_cluster, sep/Traditional_SP/SRP_Prunning.py:149-180,277-344,368-381).
+ * All arithmetic is float64 in the expression order of the numpy statements of srp.py, contraction off; the
+ * axis arrays are the host's numpy.arange results.  mics [M][3], 2 <= M <= 32, P = M - 1.
+ *
+ * asw_geom_lookup_planes: planes[p][y][x][z] = (|pt - mics[p+1]| - |pt - mics[0]|) / C * FS with
+ * pt = (xs[x], ys[y], zs[z]) -- the pair-major table asw_cube_select_planes reads.
+ *
+ * asw_geom_voxel_map: per voxel v = (ix*Ly + iy)*Lz + iz of the SRP lattice the quantised TDoA vector
+ * q[v][p] = rint(off / resolution) * resolution (round half to even; resolution a whole number) and
+ * valid[v] = 0 inside the keep-out rectangle border = {x_lo, y_lo, x_hi, y_hi} (HOST pointer, open interval),
+ * 1 elsewhere; dis_matrix[ix][iy] = sqrt((x - centre[0])^2 + (y - centre[1])^2) + 1e-8 (centre: HOST, 3 doubles).
+ *
+ * asw_geom_label: labels[v] = smallest C-order index of v's component among the 26-connected valid voxels with
+ * an identical q vector, -1 for invalid voxels.  Min-label propagation with pointer jumping until a device flag
+ * reports no change (synchronises the stream); *sweeps (HOST, may be NULL) = sweeps run.
+ * adj_scratch uint32 [n], flag_scratch int32 [1].
+ *
+ * asw_geom_workspace_bytes: size of asw_geom_compact's workspace for an n-voxel lattice (negative: asw_status).
+ *
+ * asw_geom_compact: clusters ranked by their label (the order the reference's scan meets them in).  Every output
+ * is allocated for the lattice size n = Lx*Ly*Lz by the caller; counts (HOST, 2 ints) receives G clusters and
+ * V valid voxels (synchronises the stream).  power_index int32 [n] (0 on invalid voxels); valid_flat / valid_cid
+ * int32 [V]: valid voxels ascending and their cluster; members int32 [V] with bounds int32 [G+1]: CSR member
+ * lists, ascending voxel index within a cluster; offsets int32 [G][P]; centres [G][3]: sequential sum of the
+ * member positions in that order / count; tau [G][M] = sqrt((dx^2 + dy^2) + z^2) / C (mic z ignored);
+ * delta [G][M] = |c - centre| - |(c - centre) - (m - centre)|. */
+int asw_geom_lookup_planes(const double* ys, int ny, const double* xs, int nx, const double* zs, int nz,
+                           const double* mics, int M, double C, double FS, double* planes, void* stream);
+int asw_geom_voxel_map(const double* xs, int Lx, const double* ys, int Ly, const double* zs, int Lz,
+                       const double* mics, int M, const double* border, const double* centre, double C,
+                       double FS, double resolution, int32_t* q, uint8_t* valid, double* dis_matrix,
+                       void* stream);
+int asw_geom_label(const int32_t* q, const uint8_t* valid, int Lx, int Ly, int Lz, int P,
+                   uint32_t* adj_scratch, int32_t* flag_scratch, int32_t* labels, int* sweeps, void* stream);
+int64_t asw_geom_workspace_bytes(int n_voxels);
+int asw_geom_compact(const int32_t* labels, const int32_t* q, const double* xs, int Lx, const double* ys, int Ly,
+                     const double* zs, int Lz, const double* mics, int M, const double* centre, double C,
+                     void* workspace, int64_t workspace_bytes, int32_t* power_index, int32_t* valid_flat,
+                     int32_t* valid_cid, int32_t* members, int32_t* bounds, int32_t* offsets, double* centres,
+                     double* tau, double* delta, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
