@@ -111,17 +111,24 @@ extern "C" int asw_srp_cross_spectra(const float* mix, int M, int T, int window,
                                      int hop, int nbins, int nb_pad, float tol, const float* twiddle,
                                      const int32_t* pair_i, const int32_t* pair_j, int P, float* xf_scratch,
                                      float* cc, void* stream) {
+  // every refusal happens here, before the first launch (a one-microphone call has empty pair tables, so the
+  // microphone count is judged before the pointers)
+  ASW_CHECK_ARG(M >= 2 && M <= 32, "srp_cross_spectra: %d microphones (2..32 supported)", M);
   ASW_CHECK_ARG(mix && twiddle && pair_i && pair_j && xf_scratch && cc, "srp_cross_spectra: null pointer");
-  ASW_CHECK_ARG(M >= 2 && M <= 32 && window >= nfft && nfft % 32 == 0 && hop % 4 == 0 && step % 4 == 0 && T % 4 == 0,
-                "srp_cross_spectra: bad shape (T, step and hop must be multiples of 4)");
-  ASW_CHECK_ARG(nb_pad % 64 == 0 && nbins <= nb_pad && P == M * (M - 1) / 2, "srp_cross_spectra: bad bin/pair count");
+  ASW_CHECK_ARG(nfft > 0 && hop > 0 && window >= nfft, "srp_cross_spectra: window %d is shorter than one %d-sample frame",
+                window, nfft);
+  ASW_CHECK_ARG(nfft % 32 == 0 && hop % 4 == 0 && step % 4 == 0 && T % 4 == 0 && window % 4 == 0,
+                "srp_cross_spectra: bad shape (T, window, step and hop must be multiples of 4)");
+  ASW_CHECK_ARG(nb_pad % 64 == 0 && nbins > 0 && nbins <= nb_pad && P == M * (M - 1) / 2, "srp_cross_spectra: bad bin/pair count");
+  ASW_CHECK_ARG(n_windows <= 0 || (step >= 0 && (long)(n_windows - 1) * step + window <= T),
+                "srp_cross_spectra: %d windows of %d samples every %d run past the end of the %d-sample signal", n_windows,
+                window, step, T);
   const int F = asw_srp_frames(window, nfft, hop);
   hipStream_t s = asw::as_stream(stream);
   const size_t smem = (size_t)F * M * 2 * sizeof(float);
   ASW_CHECK_ARG(smem <= 64 * 1024, "srp_cross_spectra: %d frames x %d mics exceed the LDS tile", F, M);
   for (int w = 0; w < n_windows; ++w) {
     const long start = (long)w * step;
-    ASW_CHECK_ARG(start + window <= T, "srp_cross_spectra: window %d exceeds the signal", w);
     asw_convgemm_args a = {};
     a.A = mix + start; a.Wt = twiddle; a.out = xf_scratch;
     a.B = M; a.M_out = F; a.N = 2 * nb_pad; a.Cin = nfft; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
@@ -138,8 +145,9 @@ extern "C" int asw_srp_cross_spectra(const float* mix, int M, int T, int window,
 extern "C" int asw_srp_map(const float* cc, int n_windows, int nbins, int P, const double* tau, int G, int M,
                            const double* omega, const int32_t* pair_i, const int32_t* pair_j, float* part_scratch,
                            float* out, void* stream) {
+  ASW_CHECK_ARG(M >= 2 && M <= 32, "srp_map: %d microphones (2..32 supported)", M);
   ASW_CHECK_ARG(cc && tau && omega && pair_i && pair_j && part_scratch && out, "srp_map: null pointer");
-  ASW_CHECK_ARG(G > 0 && M >= 2 && M <= 32 && nbins > 0 && P > 0 && n_windows > 0, "srp_map: bad shape");
+  ASW_CHECK_ARG(G > 0 && nbins > 0 && P == M * (M - 1) / 2 && n_windows > 0, "srp_map: bad shape");
   hipStream_t s = asw::as_stream(stream);
   const int KS = 8, kps = asw::cdiv(nbins, KS);
   const float scale = 1.0f / ((float)nbins * (float)P);

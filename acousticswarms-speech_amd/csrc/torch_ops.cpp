@@ -217,7 +217,10 @@ Tensor srp_phat_map(const Tensor& mix, const Tensor& twiddle, const Tensor& pair
   const int M = checked_int(mix.size(0), "M"), T = checked_int(mix.size(1), "T");
   const int P = checked_int(pair_i.size(0), "P"), G = checked_int(tau.size(0), "G"), nbins = checked_int(omega.size(0), "nbins");
   const int nb_pad = checked_int(twiddle.size(0) / 2, "nb_pad"), nw = checked_int(n_windows, "n_windows");
+  TORCH_CHECK(M >= 2 && M <= 32, "srp_phat_map: ", M, " microphones (2..32 supported)");
   TORCH_CHECK(T % 4 == 0, "mix length must be a multiple of 4 (pad with zeros)");
+  TORCH_CHECK(nfft > 0 && hop > 0 && window >= nfft, "srp_phat_map: window ", window, " is shorter than one ", nfft,
+              "-sample frame");
   TORCH_CHECK(twiddle.size(1) == nfft && twiddle.size(0) == 2 * (int64_t)nb_pad && nb_pad >= nbins, "twiddle must be [2*nb_pad, nfft]");
   TORCH_CHECK(pair_j.size(0) == P && tau.size(1) == M, "pair_j must be [P], tau [G, M]");
   Tensor out = at::zeros({G}, mix.options());

@@ -249,6 +249,41 @@ def pair_sisdr(y):
     return out
 
 
+# ---- the two stages of the SRP-PHAT map (csrc/srp_kernels.hip) --------------------------------
+def srp_cross_spectra(mix, twiddle, pair_i, pair_j, nbins, window, step, n_windows, nfft, hop, tol=1e-8):
+    """DFT-GEMM + PHAT + frame-averaged cross-spectrum of every pair (asw_srp_cross_spectra).
+    mix [M][T], twiddle [2*nb_pad][nfft] (srp._twiddles) -> cc [n_windows][nbins][P][2]."""
+    M, T = mix.shape
+    P = pair_i.shape[0]
+    nb_pad = twiddle.shape[0] // 2
+    assert twiddle.shape == (2 * nb_pad, nfft), "twiddle must be [2*nb_pad, nfft]"
+    for t in (pair_i, pair_j):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == P, "pair tables: int32 [P]"
+    F = lib().asw_srp_frames(window, nfft, hop)
+    xf = torch.empty((M, max(F, 1), 2 * nb_pad), dtype=torch.float32, device=mix.device)
+    # NaN-filled, so that an entry the kernel leaves unwritten shows in a comparison whatever the allocator held
+    cc = torch.full((n_windows, nbins, P, 2), float("nan"), dtype=torch.float32, device=mix.device)
+    check(lib().asw_srp_cross_spectra(ptr(_f32(mix)), M, T, window, step, n_windows, nfft, hop, nbins, nb_pad, tol,
+                                      ptr(_f32(twiddle)), ptr(pair_i), ptr(pair_j), P, ptr(xf), ptr(cc),
+                                      current_stream()))
+    return cc
+
+
+def srp_map(cc, tau, omega, pair_i, pair_j):
+    """Steered-response map, running maximum over the windows of cc starting from zeros (asw_srp_map).
+    cc [n_windows][nbins][P][2], tau [G][M] and omega [nbins] float64 -> [G]."""
+    n_windows, nbins, P, _ = cc.shape
+    G, M = tau.shape
+    for t, dt, n in ((tau, torch.float64, G * M), (omega, torch.float64, nbins), (pair_i, torch.int32, P),
+                     (pair_j, torch.int32, P)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n, "srp_map: operand dtype / size"
+    part = torch.empty((8 * 8 * G,), dtype=torch.float32, device=cc.device)
+    out = torch.empty((G,), dtype=torch.float32, device=cc.device)
+    check(lib().asw_srp_map(ptr(_f32(cc)), n_windows, nbins, P, ptr(tau), G, M, ptr(omega), ptr(pair_i), ptr(pair_j),
+                            ptr(part), ptr(out), current_stream()))
+    return out
+
+
 # ---- kernels of the joint separation network (csrc/sep_kernels.hip) --------------------------
 def joint_shift_stats(mix, offsets):
     """mean / unbiased std of the all-channel average of the S*M zero-fill shifted channels."""
