@@ -81,4 +81,32 @@ struct ProfScope {
   int slot;
   hipStream_t stream;
 };
+
+// "[B.. M.. N.. K.. <key><val>]": the shape suffix of a GEMM launch name in the detailed profile (empty otherwise)
+struct ShapeTag {
+  char s[64] = "";
+  ShapeTag(const asw_convgemm_args& a, char key, int val) {
+    if (prof_detail()) snprintf(s, sizeof s, "[B%d M%d N%d K%d %c%d]", a.B, a.M_out, a.N, a.taps * a.Cin, key, val);
+  }
+};
+
+#ifdef __HIPCC__
+// The launch protocol of the kernels that come as a (one-term, three-term) pair of instantiations, K1 for the
+// single-pass f16 mode (precision 2) and K3 for everything else: pick the instantiation, raise its per-device
+// dynamic-LDS limit to lds_limit (one SmemAttr per device and instantiation), open the profiler scope under
+// `name` + `detail`, launch, check.  `detail` is the shape suffix of the detailed profile (asw_profile_enable(2)).
+template <auto K1, auto K3, typename... Args>
+int launch_pair(int precision, dim3 grid, dim3 block, size_t lds, size_t lds_limit, std::string name, const char* detail,
+                double flops, double bytes, hipStream_t s, const Args&... args) {
+  const bool x1 = precision == 2;
+  auto kern = x1 ? K1 : K3;
+  static SmemAttr attr[2];
+  if (int rc = attr[x1].ensure(reinterpret_cast<const void*>(kern), lds_limit)) return rc;
+  if (prof_detail()) name += detail;
+  ProfScope prof(s, name, flops, bytes);
+  hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+#endif
 }  // namespace asw

@@ -35,11 +35,10 @@
 // col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)), then each wave owns whole
 // rows: + residual, * gate tensor, LayerNorm over the row (two-pass, wave shuffles),
 // GroupNorm partial sums, coalesced row stores.
-#include <cstdlib>
 #include <type_traits>
 
 #include "asw_common.h"
-#include "mfma_util.h"
+#include "f16x3_tile.h"
 
 namespace {
 using namespace asw_mfma;
@@ -367,10 +366,9 @@ void convgemm16_kernel(const asw_convgemm_args p) {
   static_assert(BK % 16 == 0, "k-step of the f16 MFMA");
   constexpr int NT = 64 * WM * WN;           // threads
   constexpr int LDH = BK + 8;                // halves per staged row
-  constexpr int KV = BK / 4;                 // float4 (A, fp32) per row
   constexpr int KH = BK / 8;                 // 16-byte vectors (B, fp16) per row
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int A_VEC = (BM * KV + NT - 1) / NT, B_VEC = (BN * KH + NT - 1) / NT;
+  constexpr int B_VEC = (BN * KH + NT - 1) / NT;
 
   extern __shared__ __align__(16) float smem[];
   _Float16* Ah = reinterpret_cast<_Float16*>(smem);
@@ -380,43 +378,24 @@ void convgemm16_kernel(const asw_convgemm_args p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
-  // XCD-aware tile order.  The grid is 1-D; workgroup L goes to XCD L % 8 (the dispatcher deals
-  // consecutive workgroups round-robin over the 8 XCDs, each with its own L2).  Slot s = L / 8 of
-  // one XCD walks the column tiles of a row tile first: the ncol workgroups that read the same
-  // activation rows run back to back on ONE L2, so those rows come from HBM once instead of once
-  // per column tile.  The (batch item, row tile) pairs are dealt to the XCDs in groups of 8, so
-  // every XCD gets the same share whatever the number of row tiles per item; padded slots exit.
   const int ncol = p.N / BN, nrt = (p.M_out + BM - 1) / BM;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int R = (slot / ncol) * 8 + xcd;                      // (batch item, row tile) index
-  if (R >= p.B * nrt) return;
-  const dim3 tile(R % nrt, slot % ncol, R / nrt);
+  uint3 tl;
+  if (!xcd_tile_groups(p.B, nrt, ncol, tl)) return;           // XCD-aware order, groups of 8
+  const dim3 tile(tl.x, tl.y, tl.z);
   const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
   const int K = p.taps * p.Cin;
-  const int cpb = p.Cin / BK;
-  const int nk = p.taps * cpb;
-  const float* __restrict__ Ab = p.A + (long)b * p.a_batch_stride;
-  const float* __restrict__ A2b = p.A2 ? p.A2 + (long)b * p.a_batch_stride : nullptr;
+  const int nk = p.taps * (p.Cin / BK);
   const _Float16* __restrict__ Wh = reinterpret_cast<const _Float16*>(p.Wt_hi);
   const _Float16* __restrict__ Wl = reinterpret_cast<const _Float16*>(p.Wt_lo);
 
   // One staging register set (a second set, i.e. loads two chunks ahead, was measured: no
   // gain, and its 64 extra VGPRs cost a resident workgroup per CU).
-  float4 ra0[A_VEC];
+  ChunkedA<BM, BK, NT, A2F> A(p, b, m0, tid);
   half8 rbh0[B_VEC], rbl0[B_VEC];
 
-  // per-thread invariants of the staging addresses
-  long a_row[A_VEC];                         // element offset of (row, tap 0, c 0) + this thread's column
-  bool a_ok[A_VEC];
+  // per-thread invariants of the weight staging addresses
   long b_row[B_VEC];
   bool b_ok[B_VEC];
-#pragma unroll
-  for (int v = 0; v < A_VEC; ++v) {
-    const int idx = tid + v * NT;
-    const int row = idx / KV, cv = idx - row * KV;
-    a_row[v] = ((long)(m0 + row) * p.stride - p.pad) * p.a_row_stride + cv * 4;
-    a_ok[v] = (idx < BM * KV) && (m0 + row < p.M_out);
-  }
 #pragma unroll
   for (int v = 0; v < B_VEC; ++v) {
     const int idx = tid + v * NT;
@@ -424,23 +403,9 @@ void convgemm16_kernel(const asw_convgemm_args p) {
     b_row[v] = (long)(n0 + row) * K + cv * 8;
     b_ok[v] = (idx < BN * KH) && (n0 + row < p.N);
   }
-  const long tap_step = (long)p.dil * p.a_row_stride;
-  const __amdgpu_buffer_rsrc_t rA = act_rsrc(Ab, p.a_len);
-  const __amdgpu_buffer_rsrc_t rA2 = act_rsrc(A2F ? A2b : Ab, p.a_len);
 
-  auto gload = [&](int kc, float4 (&ra)[A_VEC], half8 (&rbh)[B_VEC], half8 (&rbl)[B_VEC]) {
-    const int tap = kc / cpb;
-    const long koff = tap * tap_step + (kc - tap * cpb) * BK;
-#pragma unroll
-    for (int v = 0; v < A_VEC; ++v) {
-      const long e = a_row[v] + koff;                   // padding / past-the-end offsets read as zeros
-      float4 x = act_load4(rA, e, a_ok[v]);
-      if (A2F) {
-        const float4 y = act_load4(rA2, e, a_ok[v]);
-        x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
-      }
-      ra[v] = x;
-    }
+  auto gload = [&](int kc, half8 (&rbh)[B_VEC], half8 (&rbl)[B_VEC]) {
+    A.load(kc);
 #pragma unroll
     for (int v = 0; v < B_VEC; ++v) {
       const long o = (b_ok[v] ? b_row[v] : 0) + (long)kc * BK;
@@ -448,18 +413,8 @@ void convgemm16_kernel(const asw_convgemm_args p) {
       if (NTERM == 3) rbl[v] = *reinterpret_cast<const half8*>(Wl + o);
     }
   };
-  auto lstore = [&](const float4 (&ra)[A_VEC], const half8 (&rbh)[B_VEC], const half8 (&rbl)[B_VEC]) {
-#pragma unroll
-    for (int v = 0; v < A_VEC; ++v) {
-      const int idx = tid + v * NT;
-      const int row = idx / KV, cv = idx - row * KV;
-      if (idx < BM * KV) {
-        half4 hi, lo;
-        split4t<NTERM>(ra[v], hi, lo);
-        *reinterpret_cast<half4*>(Ah + row * LDH + cv * 4) = hi;
-        if (NTERM == 3) *reinterpret_cast<half4*>(Al + row * LDH + cv * 4) = lo;
-      }
-    }
+  auto lstore = [&](const half8 (&rbh)[B_VEC], const half8 (&rbl)[B_VEC]) {
+    A.template deposit<NTERM>(Ah, Al);
 #pragma unroll
     for (int v = 0; v < B_VEC; ++v) {
       const int idx = tid + v * NT;
@@ -499,28 +454,22 @@ void convgemm16_kernel(const asw_convgemm_args p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          if (NTERM == 3) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          }
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < TN; ++j) mma3<NTERM>(acc[i][j], ah[i], al[i], bh[j], bl[j]);
     }
   };
 
 #ifdef ASW_PHASE_TIMING
   unsigned long long tg_wait = 0, tg_store = 0, tg_comp = 0;
 #endif
-  gload(0, ra0, rbh0, rbl0);
+  gload(0, rbh0, rbl0);
   for (int kc = 0; kc < nk; ++kc) {
     ASW_PHASE_MARK(g0);
     __syncthreads();
     ASW_PHASE_MARK(g1);
-    lstore(ra0, rbh0, rbl0);
+    lstore(rbh0, rbl0);
     __syncthreads();
     ASW_PHASE_MARK(g2);
-    if (kc + 1 < nk) gload(kc + 1, ra0, rbh0, rbl0);
+    if (kc + 1 < nk) gload(kc + 1, rbh0, rbl0);
     compute();
 #ifdef ASW_PHASE_TIMING
     {
@@ -560,9 +509,6 @@ void convgemm16_kernel(const asw_convgemm_args p) {
 // Same tiling (wave tile BM/2 x 64), same epilogue, same XCD-aware tile order as the kernel above.
 // Measured (T = 48 000, batch 64): mask encoder 312 -> 332 TFLOP/s, strided / transposed convolutions
 // +3-6 %.  64-wide chunks (half the barriers, 147 KB ring) spill and lose: 304.
-#ifndef ASW_PIPE_QDB
-#define ASW_PIPE_QDB 2
-#endif
 // Main loop of one 256-column tile: picks the tile of this workgroup (false: none, the whole workgroup
 // leaves), runs the K loop and returns the accumulators (wave (wm, wn) of WM x 4 holds rows
 // wm*BM/WM + 32*i.., columns wn*64 + 32*j..).  Ends on a barrier: the ring is free for the epilogue.
@@ -571,10 +517,10 @@ void convgemm16_kernel(const asw_convgemm_args p) {
 template <int BM, bool A2F, int BK, int NTERM = 3, int WM = 2>
 __device__ __forceinline__ bool pipe_mainloop(const asw_convgemm_args& p, float* smem, floatx16 (&acc)[BM / WM / 32][2],
                                               dim3& tile_out, int& ncol_out) {
-  constexpr int BN = 256, WN = 4, NT = 64 * WM * WN, QDB = ASW_PIPE_QDB;
-  constexpr int LDH = BK + 8, KV = BK / 4;
+  constexpr int BN = 256, WN = 4, NT = 64 * WM * WN;
+  constexpr int QDB = 2;                           // B fragments in flight, in k-steps
+  constexpr int LDH = BK + 8;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int A_VEC = (BM * KV + NT - 1) / NT;
   constexpr int STAGE = 2 * BM * LDH;              // halves per ring stage (hi image + lo image)
 
   _Float16* ring = reinterpret_cast<_Float16*>(smem);
@@ -582,72 +528,26 @@ __device__ __forceinline__ bool pipe_mainloop(const asw_convgemm_args& p, float*
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int ncol = p.N / BN, nrt = (p.M_out + BM - 1) / BM;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int R = (slot / ncol) * 8 + xcd;                      // (batch item, row tile) index, XCD-aware order
-  if (R >= p.B * nrt) return false;
-  const dim3 tile(R % nrt, slot % ncol, R / nrt);
+  uint3 tl;
+  if (!xcd_tile_groups(p.B, nrt, ncol, tl)) return false;     // XCD-aware order, groups of 8
+  const dim3 tile(tl.x, tl.y, tl.z);
   tile_out = tile;
   ncol_out = ncol;
   const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
-  const int cpb = p.Cin / BK;
-  const int nk = p.taps * cpb;
-  const float* __restrict__ Ab = p.A + (long)b * p.a_batch_stride;
-  const float* __restrict__ A2b = p.A2 ? p.A2 + (long)b * p.a_batch_stride : nullptr;
+  const int nk = p.taps * (p.Cin / BK);
   const half8* __restrict__ Wh = reinterpret_cast<const half8*>(p.Wf_hi);
   const half8* __restrict__ Wl = reinterpret_cast<const half8*>(p.Wf_lo);
   const int NTF = p.N / 32;                        // column fragments across N
   const int nt0 = n0 / 32 + wn * TN;
 
-  float4 ra[A_VEC];
-  long a_row[A_VEC];
-  bool a_ok[A_VEC];
-#pragma unroll
-  for (int v = 0; v < A_VEC; ++v) {
-    const int idx = tid + v * NT;
-    const int row = idx / KV, cv = idx - row * KV;
-    a_row[v] = ((long)(m0 + row) * p.stride - p.pad) * p.a_row_stride + cv * 4;
-    a_ok[v] = (idx < BM * KV) && (m0 + row < p.M_out);
-  }
-  const long tap_step = (long)p.dil * p.a_row_stride;
-  const __amdgpu_buffer_rsrc_t rA = act_rsrc(Ab, p.a_len);
-  const __amdgpu_buffer_rsrc_t rA2 = act_rsrc(A2F ? A2b : Ab, p.a_len);
-
-  auto gload = [&](int kc) {
-    const int tap = kc / cpb;
-    const long koff = tap * tap_step + (kc - tap * cpb) * BK;
-#pragma unroll
-    for (int v = 0; v < A_VEC; ++v) {
-      const long e = a_row[v] + koff;
-      float4 x = act_load4(rA, e, a_ok[v]);
-      if (A2F) {
-        const float4 y = act_load4(rA2, e, a_ok[v]);
-        x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
-      }
-      ra[v] = x;
-    }
-  };
+  ChunkedA<BM, BK, NT, A2F> A(p, b, m0, tid);
   auto deposit = [&](int stage) {
     _Float16* Ah = ring + stage * STAGE;
-    _Float16* Al = Ah + BM * LDH;
-#pragma unroll
-    for (int v = 0; v < A_VEC; ++v) {
-      const int idx = tid + v * NT;
-      const int row = idx / KV, cv = idx - row * KV;
-      if (idx < BM * KV) {
-        half4 hi, lo;
-        split4t<NTERM>(ra[v], hi, lo);
-        *reinterpret_cast<half4*>(Ah + row * LDH + cv * 4) = hi;
-        if (NTERM == 3) *reinterpret_cast<half4*>(Al + row * LDH + cv * 4) = lo;
-      }
-    }
+    A.template deposit<NTERM>(Ah, Ah + BM * LDH);
   };
   auto bload = [&](int kg, half8 (&bh)[TN], half8 (&bl)[TN]) {          // kg = global k-step (16 K each)
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const long o = ((long)kg * NTF + nt0 + j) * 64 + lane;
-      bh[j] = Wh[o];
-      if (NTERM == 3) bl[j] = Wl[o];
-    }
+    for (int j = 0; j < TN; ++j) frag_load<NTERM>(Wh, Wl, (long)kg * NTF + nt0 + j, lane, bh[j], bl[j]);
   };
 
 #pragma unroll
@@ -662,16 +562,16 @@ __device__ __forceinline__ bool pipe_mainloop(const asw_convgemm_args& p, float*
   const int nks = nk * (BK / 16);                  // k-steps in all
 #pragma unroll
   for (int q = 0; q < QDB; ++q) bload(q, qh[q], ql[q]);
-  gload(0);
+  A.load(0);
   deposit(0);
   __syncthreads();
   constexpr int KS = BK / 16;
-  static_assert(KS % QDB == 0 || QDB == 2 * KS, "the B ring is one or two chunks deep");
+  static_assert(KS % QDB == 0, "the B ring is one chunk deep");
   // One chunk; PAR = chunk parity, compile-time so that ring stage and B buffer indices are static
   // (the loop below is unrolled by two).
   auto chunk = [&](int kc, auto par) {
     constexpr int PAR = decltype(par)::value;
-    if (kc + 1 < nk) gload(kc + 1);                // in flight under the MFMAs of this chunk
+    if (kc + 1 < nk) A.load(kc + 1);               // in flight under the MFMAs of this chunk
     const _Float16* Ah = ring + PAR * STAGE;
     const _Float16* Al = Ah + BM * LDH;
 #pragma unroll
@@ -686,13 +586,7 @@ __device__ __forceinline__ bool pipe_mainloop(const asw_convgemm_args& p, float*
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          if (NTERM == 3) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], qh[q][j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], ql[q][j], acc[i][j], 0, 0, 0);
-          }
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], qh[q][j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < TN; ++j) mma3<NTERM>(acc[i][j], ah[i], al[i], qh[q][j], ql[q][j]);
       const int kg = kc * KS + ks + QDB;           // same slot, QDB k-steps ahead
       if (kg < nks) bload(kg, qh[q], ql[q]);
       // deposit of the next chunk between the k-steps: its conversions and LDS writes issue in the
@@ -764,10 +658,7 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
     const float bm = p.bias ? p.bias[col] : 0.f, bb = mf.byp_bias ? mf.byp_bias[col] : 0.f;
     half8 wh[KSB], wl[KSB];
 #pragma unroll
-    for (int ks = 0; ks < KSB; ++ks) {
-      wh[ks] = Bh[((long)ks * NTF + nt) * 64 + lane];
-      wl[ks] = Bl[((long)ks * NTF + nt) * 64 + lane];
-    }
+    for (int ks = 0; ks < KSB; ++ks) frag_load<NTERM>(Bh, Bl, (long)ks * NTF + nt, lane, wh[ks], wl[ks]);
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
       const int f = m0 + wm * (BM / 2) + tm * 32 + (lane & 31);
@@ -784,11 +675,7 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
         split4t<NTERM>(x1, h1, l1);
         const half8 ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
         const half8 al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-        if (NTERM == 3) {
-          bp = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wh[ks], bp, 0, 0, 0);
-          bp = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[ks], bp, 0, 0, 0);
-        }
-        bp = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[ks], bp, 0, 0, 0);
+        mma3<NTERM>(bp, ah, al, wh[ks], wl[ks]);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -831,18 +718,14 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
     for (int ks = 0; ks < BN / 16; ++ks) {
       const float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
       const float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
-      const long o = ((long)(n0 / 16 + ks) * 2 + tt) * 64 + lane;
-      const half8 dh = Dh[o], dl = Dl[o];
+      half8 dh, dl;
+      frag_load<NTERM>(Dh, Dl, (long)(n0 / 16 + ks) * 2 + tt, lane, dh, dl);
       half4 h0, l0, h1, l1;
       split4t<NTERM>(x0, h0, l0);
       split4t<NTERM>(x1, h1, l1);
       const half8 ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
       const half8 al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-      if (NTERM == 3) {
-        tp = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, dh, tp, 0, 0, 0);
-        tp = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, dl, tp, 0, 0, 0);
-      }
-      tp = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, dh, tp, 0, 0, 0);
+      mma3<NTERM>(tp, ah, al, dh, dl);
     }
     const int j = tt * 32 + (lane & 31);
     if (j < mf.dec_taps) {
@@ -873,30 +756,16 @@ int launch_mask_path(const asw_maskpath_args* args, void* stream) {
   ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(m.ref) & 15) == 0 && m.ref_batch_stride % 4 == 0,
                 "mask_path: reference rows must be 16-byte aligned");
   ASW_CHECK_ARG(a.precision == 1 || a.precision == 2, "mask_path: precision 1 (f16x3) or 2 (single-pass f16)");
-  const bool x1 = a.precision == 2;
   a.relu = 1;
   constexpr size_t ring = (size_t)2 * 2 * BM * (BK + 8) * sizeof(_Float16);
   constexpr size_t slab = (size_t)128 * (BN + 4) * sizeof(float);
   constexpr size_t smem = ring > slab ? ring : slab;
   static_assert(smem <= 160 * 1024, "LDS budget");
-  const void* kern = x1 ? reinterpret_cast<const void*>(maskpath16p_kernel<BM, KSB, 1>)
-                        : reinterpret_cast<const void*>(maskpath16p_kernel<BM, KSB, 3>);
-  static asw::SmemAttr attr[2];                         // per device and instantiation
-  if (int rc = attr[x1].ensure(kern, smem)) return rc;
-  const long nrt = asw::cdiv(a.M_out, BM);
-  dim3 grid(((nrt * a.B + 7) / 8) * 8 * (a.N / BN), 1, 1);
-  std::string pn = "maskpath16p<256,256,32>";
-  if (asw::prof_detail()) {
-    char sh[64];
-    snprintf(sh, sizeof sh, "[B%d M%d N%d K%d s%d]", a.B, a.M_out, a.N, a.taps * a.Cin, a.stride);
-    pn += sh;
-  }
   // mask encoder + bypass + decoder taps
-  asw::ProfScope prof(s, pn, 2.0 * a.B * (double)a.M_out * a.N * ((double)a.taps * a.Cin + m.byp_taps + m.dec_taps));
-  if (x1) hipLaunchKernelGGL((maskpath16p_kernel<BM, KSB, 1>), grid, dim3(512), smem, s, a, m);
-  else hipLaunchKernelGGL((maskpath16p_kernel<BM, KSB, 3>), grid, dim3(512), smem, s, a, m);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  return asw::launch_pair<maskpath16p_kernel<BM, KSB, 1>, maskpath16p_kernel<BM, KSB, 3>>(
+      a.precision, dim3(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN)), dim3(512), smem, smem,
+      "maskpath16p<256,256,32>", asw::ShapeTag(a, 's', a.stride).s,
+      2.0 * a.B * (double)a.M_out * a.N * ((double)a.taps * a.Cin + m.byp_taps + m.dec_taps), 0.0, s, a, m);
 }
 
 template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int WM = 2>
@@ -907,26 +776,12 @@ int launch_pipe(const asw_convgemm_args& a, hipStream_t s) {
   constexpr size_t smem = ring > slab ? ring : slab;
   static_assert(smem <= 160 * 1024, "LDS budget");
   static_assert(BM == 128 * WM, "wave tile 128 x 64");
-  const bool x1 = a.precision == 2;                     // single-pass f16: the one-term instantiation
-  const void* kern = x1 ? reinterpret_cast<const void*>(convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 1, WM>)
-                        : reinterpret_cast<const void*>(convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 3, WM>);
-  static asw::SmemAttr attr[2];                         // per device and instantiation
-  if (int rc = attr[x1].ensure(kern, smem)) return rc;
   ASW_CHECK_ARG(A2F == (a.A2 != nullptr), "convgemm: skip operand variant mismatch");
   ASW_CHECK_ARG(a.Cin % BK == 0 && a.N % BN == 0, "convgemm: pipelined tile needs Cin %% BK == 0 and N %% 256 == 0");
-  const long nrt = asw::cdiv(a.M_out, BM);
-  dim3 grid(((nrt * a.B + 7) / 8) * 8 * (a.N / BN), 1, 1);
-  std::string pn = asw::prof_name(MUL ? "convgemm16pm" : "convgemm16p", BM, BN, BK, false, STATS);
-  if (asw::prof_detail()) {
-    char sh[64];
-    snprintf(sh, sizeof sh, "[B%d M%d N%d K%d s%d]", a.B, a.M_out, a.N, a.taps * a.Cin, a.stride);
-    pn += sh;
-  }
-  asw::ProfScope prof(s, pn, 2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin);
-  if (x1) hipLaunchKernelGGL((convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 1, WM>), grid, dim3(256 * WM), smem, s, a);
-  else hipLaunchKernelGGL((convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 3, WM>), grid, dim3(256 * WM), smem, s, a);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  return asw::launch_pair<convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 1, WM>, convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 3, WM>>(
+      a.precision, dim3(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN)), dim3(256 * WM), smem, smem,
+      asw::prof_name(MUL ? "convgemm16pm" : "convgemm16p", BM, BN, BK, false, STATS), asw::ShapeTag(a, 's', a.stride).s,
+      2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin, 0.0, s, a);
 }
 
 // ------------------------------------------------------------------ halo-staged residual conv
@@ -948,9 +803,6 @@ int launch_pipe(const asw_convgemm_args& a, hipStream_t s) {
 // its B operand with one coalesced 1 KiB load per fragment, one k-step ahead of the MFMAs
 // (they are L2/L1-resident: a layer's weights are at most 7.3 MB and shared by every
 // workgroup).  No barrier inside the taps x k-steps of a slice.
-#ifndef ASW_RES128_WAVES
-#define ASW_RES128_WAVES 3
-#endif
 template <int BM, int PH, bool POLY>
 struct ResRows {
   static constexpr int BMJ = BM / PH;
@@ -965,14 +817,13 @@ struct ResRows {
 
 template <int BM, int C, int WM, int WN, int PH, int QD = 4, bool POLY = (PH > 1), bool GLU = false, int NTERM = 3>
 __global__ __launch_bounds__(64 * WM * WN)
-__attribute__((amdgpu_waves_per_eu(C == 64 ? 4 : WM * WN == 8 ? 2 : (QD == 2 ? (C >= 512 || (C == 256 && BM == 128) ? 2 : (C == 128 ? ASW_RES128_WAVES : 3)) : (C == 64 && WM * WN == 4 ? 4 : 1)))))
+__attribute__((amdgpu_waves_per_eu(C == 64 ? 4 : WM * WN == 8 ? 2 : (QD == 2 ? (C >= 512 || (C == 256 && BM == 128) ? 2 : 3) : (C == 64 && WM * WN == 4 ? 4 : 1)))))
 void resconv16_kernel(const asw_convgemm_args p) {
   static_assert(QD == 2 || QD == 4, "B prefetch depth in k-steps");
   static_assert(!GLU || (PH == 1 && !POLY), "GroupNorm + GLU on load: contiguous tiles only");
   static_assert(WM * WN == 2 || WM * WN == 4 || WM * WN == 8, "2, 4 or 8 waves per workgroup");
-  constexpr int NTHR = 64 * WM * WN, SROWS = NTHR / 16;   // staging: 16 threads per row
+  constexpr int NTHR = 64 * WM * WN;
   constexpr int TM = BM / WM / 32, TN = C / WN / 32;
-  constexpr int RS = 272;                    // bytes per staged row: 128 hi + 128 lo + 16 pad
   constexpr int NT = C / 32;                 // 32-column fragments across N
   constexpr int BMJ = BM / PH;
   constexpr int SU = (GLU && C > 64) ? 4 : 8;   // staging rows per thread in flight
@@ -1007,7 +858,7 @@ void resconv16_kernel(const asw_convgemm_args p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int srow = tid >> 4, sc4 = tid & 15;          // staging: 16 threads per row, SROWS rows per pass
+  const int sc4 = tid & 15;                           // staging: 16 threads per row
   int a_base[TM];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
@@ -1016,92 +867,47 @@ void resconv16_kernel(const asw_convgemm_args p) {
   }
   const int nt0 = wn * TN;                            // first N fragment of this wave
 
-  float gm0 = 0.f, gr0 = 0.f, gm1 = 0.f, gr1 = 0.f;
-  float4 gga, gba, ggg, gbg;
-  if (GLU) {
-    gm0 = p.glu_mr[b * 4 + 0]; gr0 = p.glu_mr[b * 4 + 1]; gm1 = p.glu_mr[b * 4 + 2]; gr1 = p.glu_mr[b * 4 + 3];
-  }
+  GluCoef gc;
+  if (GLU) gc.stats(p.glu_mr, b);
   ASW_PHASE_MARK(t_begin);
 #ifdef ASW_PHASE_TIMING
   unsigned long long t_stage = 0, t_loop = 0;
 #endif
+  // (the two slices at C = 128 are unrolled -- not in the one-term kernels without GLU -- and no others: what hipcc
+  // chose on its own while the staging loop was written out here)
+#pragma unroll(C == 128 && (NTERM == 3 || GLU) ? 2 : 1)
   for (int cc = 0; cc < C / 64; ++cc) {
     ASW_PHASE_MARK(t_s0);
-    if (GLU) {
-      gga = *reinterpret_cast<const float4*>(p.glu_gamma + cc * 64 + sc4 * 4);
-      gba = *reinterpret_cast<const float4*>(p.glu_beta + cc * 64 + sc4 * 4);
-      ggg = *reinterpret_cast<const float4*>(p.glu_gamma + C + cc * 64 + sc4 * 4);
-      gbg = *reinterpret_cast<const float4*>(p.glu_beta + C + cc * 64 + sc4 * 4);
-    }
+    if (GLU) gc.affine(p.glu_gamma, p.glu_beta, C, cc * 64 + sc4 * 4);
     __syncthreads();                                   // previous slice fully consumed
     // ---- stage + split the image of this channel slice (8 loads per thread in flight: 8 rows, or 4 rows of value + gate
     // halves where the accumulators leave no room for more)
-    for (int r0 = 0; r0 < R; r0 += SROWS * SU) {
-      float4 buf[SU];
-      float4 gate[GLU ? SU : 1];
-      bool okr[GLU ? SU : 1];
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int row = r0 + u * SROWS + srow;
-        int g;
-        bool ok = row < R;
-        if (!POLY) {
-          g = m0 - pad + row;
-        } else {
-          const int ph = pb * PH + row / RJ;
-          g = dil * (jb * BMJ + row % RJ - (taps - 1) / 2) + ph;
-          ok = ok && ph < dil && (jb * BMJ + row % RJ - (taps - 1) / 2) >= 0;
-        }
-        ok = ok && g >= 0 && g < T;
-        if (GLU) {
-          buf[u] = act_load4(rX, (long)g * 2 * C + cc * 64 + sc4 * 4, ok);
-          gate[u] = act_load4(rX, (long)g * 2 * C + C + cc * 64 + sc4 * 4, ok);
-          okr[u] = ok;
-        } else {
-          buf[u] = act_load4(rX, (long)g * C + cc * 64 + sc4 * 4, ok);
-        }
-      }
-      if (GLU) {
-        // the arithmetic of gn_glu_kernel, expression for expression; rows outside the sequence stay zero
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          float4 o;
-#define ASW_GLU(f)                                                       \
-  {                                                                      \
-    const float gl = asw::gn_glu_value(buf[u].f, gate[u].f, gm0, gr0, gm1, gr1, gga.f, gba.f, ggg.f, gbg.f); \
-    o.f = okr[u] ? gl : 0.f;                                             \
-  }
-          ASW_GLU(x) ASW_GLU(y) ASW_GLU(z) ASW_GLU(w)
-#undef ASW_GLU
-          buf[u] = o;
-          // the normalised rows of the tile's own output range go out once as well: the skip connection of an
-          // encoder block, and (C > 64, where the image holds one channel slice at a time) this layer's residual
-          const int g = m0 - pad + r0 + u * SROWS + srow;
-          if (p.glu_out && okr[u] && g >= m0 && g < m0 + BM)
+    stage_image<NTHR, C, SU, GLU, NTERM, C == 64>(
+        img, R, rX, cc * 64, gc,
+        [&](int row) __attribute__((always_inline)) {
+          int g;
+          bool ok = row < R;
+          if (!POLY) {
+            g = m0 - pad + row;
+          } else {
+            const int ph = pb * PH + row / RJ;
+            g = dil * (jb * BMJ + row % RJ - (taps - 1) / 2) + ph;
+            ok = ok && ph < dil && (jb * BMJ + row % RJ - (taps - 1) / 2) >= 0;
+          }
+          return ImgSrc{g, ok && g >= 0 && g < T};
+        },
+        // the normalised rows of the tile's own output range go out once as well: the skip connection of an
+        // encoder block, and (C > 64, where the image holds one channel slice at a time) this layer's residual
+        [&](int g, bool ok, const float4& o) __attribute__((always_inline)) {
+          if (p.glu_out && ok && g >= m0 && g < m0 + BM)
             *reinterpret_cast<float4*>(p.glu_out + ((long)b * T + g) * C + cc * 64 + sc4 * 4) = o;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int row = r0 + u * SROWS + srow;
-        if (row < R) {
-          half4 hi, lo;
-          split4t<NTERM>(buf[u], hi, lo);
-          *reinterpret_cast<half4*>(img + row * RS + sc4 * 8) = hi;
-          if (NTERM == 3 || C == 64) *reinterpret_cast<half4*>(img + row * RS + 128 + sc4 * 8) = lo;
-        }
-      }
-    }
+        });
     __syncthreads();
     // ---- taps x k-steps, B fragments double-buffered in registers
     auto bload = [&](int tap, int ks, half8 (&bh)[TN], half8 (&bl)[TN]) {
       const long kg = (long)tap * (C / 16) + cc * 4 + ks;          // global k-step
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const long o = (kg * NT + nt0 + j) * 64 + lane;
-        bh[j] = Wh[o];
-        if (NTERM == 3) bl[j] = Wl[o];
-      }
+      for (int j = 0; j < TN; ++j) frag_load<NTERM>(Wh, Wl, kg * NT + nt0 + j, lane, bh[j], bl[j]);
     };
     // A fragments are double buffered in registers, one k-step ahead: left to itself the compiler
     // keeps ONE fragment register and waits for every ds_read right before its MFMA
@@ -1111,21 +917,15 @@ void resconv16_kernel(const asw_convgemm_args p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const char* q = img + a_base[i] + tap * tapstep * RS + ks * 32;
-        ah[i] = *reinterpret_cast<const half8*>(q);
-        if (NTERM == 3) al[i] = *reinterpret_cast<const half8*>(q + 128);
+        ah[i] = *reinterpret_cast<const half8*>(q + IMG_HI);
+        if (NTERM == 3) al[i] = *reinterpret_cast<const half8*>(q + IMG_LO);
       }
     };
     auto mma = [&](const half8 (&ah)[TM], const half8 (&al)[TM], const half8 (&bh)[TN], const half8 (&bl)[TN]) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          if (NTERM == 3) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          }
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < TN; ++j) mma3<NTERM>(acc[i][j], ah[i], al[i], bh[j], bl[j]);
     };
     // One B register buffer per k-step of a tap: the fragment for (tap+1, ks) is requested
     // right after (tap, ks) has been multiplied, i.e. three k-steps (600-1200 MFMA cycles)
@@ -1189,8 +989,8 @@ void resconv16_kernel(const asw_convgemm_args p) {
 #pragma unroll
         for (int q = 0; q < G::VPL; ++q) {
           const int col = (lc + q * G::LPR) * 4;
-          const half4 hi = *reinterpret_cast<const half4*>(img + irow * RS + col * 2);
-          const half4 lo = *reinterpret_cast<const half4*>(img + irow * RS + 128 + col * 2);
+          const half4 hi = *reinterpret_cast<const half4*>(img + irow * RS + IMG_HI + col * 2);
+          const half4 lo = *reinterpret_cast<const half4*>(img + irow * RS + IMG_LO + col * 2);
           rpre[(tm * G::NSTEP + st) * G::VPL + q] = make_float4((float)hi[0] + (float)lo[0], (float)hi[1] + (float)lo[1],
                                                                 (float)hi[2] + (float)lo[2], (float)hi[3] + (float)lo[3]);
         }
@@ -1219,32 +1019,23 @@ template <int BM, int C, int WM, int WN, int PH, int QD = 4, bool POLY = (PH > 1
 int launch_res(const asw_convgemm_args& a, hipStream_t s) {
   constexpr int BMJ = BM / PH;
   const int RJ = BMJ + (!POLY ? (a.taps - 1) * a.dil : a.taps - 1);
-  const size_t img = (size_t)PH * RJ * 272;
+  const size_t img = (size_t)PH * RJ * RS;
   const size_t slab = (size_t)(WM * 32) * (C + 4) * sizeof(float);
   const size_t smem = img > slab ? img : slab;
   if (smem > 160 * 1024) return 1;                     // caller falls back to the generic kernel
-  const bool x1 = a.precision == 2;                     // single-pass f16: the one-term instantiation
-  auto kern = x1 ? resconv16_kernel<BM, C, WM, WN, PH, QD, POLY, GLU, 1> : resconv16_kernel<BM, C, WM, WN, PH, QD, POLY, GLU, 3>;
-  static asw::SmemAttr attr[2];                         // per device and instantiation
-  if (int rc = attr[x1].ensure(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
   const int gx = !POLY ? asw::cdiv(a.M_out, BM)
                        : asw::cdiv(asw::cdiv(a.M_out, a.dil), BMJ) * asw::cdiv(a.dil, PH);
-  dim3 grid(gx, 1, a.B);
   char nm[96];
-  int nl = snprintf(nm, sizeof nm, "resconv16<%d,%d,%s%d%s%s>", BM, C, POLY ? "poly" : "ph", PH, QD == 2 ? ",q2" : "", GLU ? ",glu" : "");
-  if (asw::prof_detail()) snprintf(nm + nl, sizeof nm - nl, "[B%d M%d N%d K%d d%d]", a.B, a.M_out, a.N, a.taps * a.Cin, a.dil);
-  asw::ProfScope prof(s, nm, 2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin);
+  snprintf(nm, sizeof nm, "resconv16<%d,%d,%s%d%s%s>", BM, C, POLY ? "poly" : "ph", PH, QD == 2 ? ",q2" : "", GLU ? ",glu" : "");
   asw_convgemm_args k = a;
   // C > 64: the image holds one 64-channel slice at a time, so the residual (= the normalised input) is read back
   // from glu_out: the rows a workgroup reads in its epilogue are the ones it stored while staging (same CU, after
   // the barriers of the k-loop)
   if (GLU && C > 64) k.resid = a.glu_out;
-  hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), smem, s, k);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  return asw::launch_pair<resconv16_kernel<BM, C, WM, WN, PH, QD, POLY, GLU, 1>, resconv16_kernel<BM, C, WM, WN, PH, QD, POLY, GLU, 3>>(
+      a.precision, dim3(gx, 1, a.B), dim3(64 * WM * WN), smem, 160 * 1024, nm, asw::ShapeTag(a, 'd', a.dil).s,
+      2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin, 0.0, s, k);
 }
-
-
 
 // returns 1 when the layer is not a halo-kernel case (or does not fit LDS)
 int try_resconv(const asw_convgemm_args& a, hipStream_t s) {
@@ -1331,34 +1122,21 @@ int launch(const asw_convgemm_args& a, hipStream_t s) {
   constexpr size_t slab = (size_t)(WM * 32) * (BN + 4) * sizeof(float);
   constexpr size_t smem = stage > slab ? stage : slab;
   static_assert(smem <= 160 * 1024, "LDS budget");
-  const bool x1 = F16 && a.precision == 2;              // single-pass f16: the one-term instantiation
-  const void* kern;
-  if constexpr (F16)
-    kern = x1 ? reinterpret_cast<const void*>(convgemm16_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F, 1>)
-              : reinterpret_cast<const void*>(convgemm16_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F, 3>);
-  else kern = reinterpret_cast<const void*>(convgemm_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F>);
-  static asw::SmemAttr attr[2];                         // per device and instantiation
-  if (int rc = attr[x1].ensure(kern, smem)) return rc;
   ASW_CHECK_ARG(A2F == (a.A2 != nullptr), "convgemm: the skip operand is fused only in the 128-wide statistics tile");
   ASW_CHECK_ARG(a.Cin % BK == 0, "convgemm: Cin=%d not a multiple of BK=%d", a.Cin, BK);
   ASW_CHECK_ARG(a.N % BN == 0, "convgemm: N=%d not a multiple of BN=%d", a.N, BN);
-  dim3 grid(asw::cdiv(a.M_out, BM), a.N / BN, a.B);
-  if constexpr (F16) grid = dim3((((long)grid.x * a.B + 7) / 8) * 8 * grid.y, 1, 1);   // XCD-aware 1-D order, see the kernel
-  std::string pn = asw::prof_name(F16 ? (MUL ? "convgemm16m" : "convgemm16") : (MUL ? "convgemm_m" : "convgemm"),
-                                  BM, BN, BK, LN, STATS);
-  if (asw::prof_detail()) {
-    char sh[64];
-    snprintf(sh, sizeof sh, "[B%d M%d N%d K%d s%d]", a.B, a.M_out, a.N, a.taps * a.Cin, a.stride);
-    pn += sh;
-  }
-  asw::ProfScope prof(s, pn, 2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin);
-  if constexpr (F16) {
-    if (x1) hipLaunchKernelGGL((convgemm16_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F, 1>), grid, dim3(64 * WM * WN), smem, s, a);
-    else hipLaunchKernelGGL((convgemm16_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F, 3>), grid, dim3(64 * WM * WN), smem, s, a);
-  } else
-    hipLaunchKernelGGL((convgemm_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F>), grid, dim3(256), smem, s, a);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  const int nrt = asw::cdiv(a.M_out, BM), ncol = a.N / BN;
+  const std::string pn = asw::prof_name(F16 ? (MUL ? "convgemm16m" : "convgemm16") : (MUL ? "convgemm_m" : "convgemm"),
+                                        BM, BN, BK, LN, STATS);
+  const asw::ShapeTag tag(a, 's', a.stride);
+  const double flops = 2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin;
+  if constexpr (F16)
+    return asw::launch_pair<convgemm16_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F, 1>,
+                            convgemm16_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F, 3>>(
+        a.precision, dim3(xcd_grid_groups((long)nrt * a.B, ncol)), dim3(64 * WM * WN), smem, smem, pn, tag.s, flops, 0.0, s, a);
+  else   // exact fp32: one instantiation
+    return asw::launch_pair<convgemm_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F>, convgemm_kernel<BM, BN, BK, WM, WN, LN, STATS, MUL, A2F>>(
+        0, dim3(nrt, ncol, a.B), dim3(256), smem, smem, pn, tag.s, flops, 0.0, s, a);
 }
 
 template <int BM, int BN, int BK, int WM, int WN, bool LN, bool STATS, bool MUL = false>
@@ -1366,6 +1144,27 @@ int launch_prec(const asw_convgemm_args& a, hipStream_t s) {
   return a.precision >= 1 ? launch<BM, BN, BK, WM, WN, LN, STATS, MUL, true>(a, s)
                           : launch<BM, BN, BK, WM, WN, LN, STATS, MUL, false>(a, s);
 }
+
+// The epilogue variants of a non-LayerNorm tile: gate tensor (MUL), GroupNorm partial sums with the skip operand added
+// on load (STATS + A2F), partial sums alone, plain.  A tile is a type with run<STATS, MUL, A2F>(a, s).
+template <typename Tile, bool HAS_MUL = true>
+int launch_variant(const asw_convgemm_args& a, hipStream_t s) {
+  const bool stats = a.stats != nullptr;
+  if constexpr (HAS_MUL)
+    if (a.mul) return Tile::template run<false, true, false>(a, s);
+  if (stats && a.A2) return Tile::template run<true, false, true>(a, s);
+  return stats ? Tile::template run<true, false, false>(a, s) : Tile::template run<false, false, false>(a, s);
+}
+template <int BM, int BN, int WM, int WN, bool F16>
+struct GemmTile {                        // two-barrier kernels: convgemm16 / convgemm, 32-wide chunks
+  template <bool STATS, bool MUL, bool A2F>
+  static int run(const asw_convgemm_args& a, hipStream_t s) { return launch<BM, BN, 32, WM, WN, false, STATS, MUL, F16, A2F>(a, s); }
+};
+template <int BM, int WM>
+struct PipeTile {                        // pipelined 256-column kernel: convgemm16p
+  template <bool STATS, bool MUL, bool A2F>
+  static int run(const asw_convgemm_args& a, hipStream_t s) { return launch_pipe<BM, STATS, MUL, A2F, 32, WM>(a, s); }
+};
 
 // tile choice for the non-LayerNorm variants; must match asw_convgemm_stats_tiles
 inline bool wide_tile(int N) { return N % 128 == 0; }
@@ -1377,8 +1176,7 @@ inline bool wide_tile(int N) { return N % 128 == 0; }
 // that leave a 256-row tile a quarter or more empty (the bottleneck-side convolutions: 188 rows at
 // T = 48 000, 563 at T = 144 000 -> 2 % instead of 27 % of the MFMAs on padding rows).
 inline int wide_tile_kind(int B, int M_out, int N, int K) {
-  static const int min_k = getenv("ASW_WIDE_MIN_K") ? atoi(getenv("ASW_WIDE_MIN_K")) : 256;   // A/B measurements
-  if (M_out <= 128 || N % 256 != 0 || K < min_k) return 0;
+  if (M_out <= 128 || N % 256 != 0 || K < 256) return 0;
   const long blocks = (long)asw::cdiv(M_out, 256) * (N / 256) * B;
   if (blocks < 512) return 0;
   const long pad256 = (long)asw::cdiv(M_out, 256) * 256, pad192 = (long)asw::cdiv(M_out, 192) * 192;
@@ -1529,49 +1327,22 @@ extern "C" int asw_convgemm_f32(const asw_convgemm_args* args, void* stream) {
   if (wide_tile(a.N)) {
     if (a.precision >= 1) {
       // f16x3 is bound by the bytes each CU can pull per cycle, so take the largest tile the
-      // shape fills: 256x256 (8 waves, 1/32 B per MAC), 256x128, else 128x128 (1/16 B per MAC)
+      // shape fills: 256x256 or 192x256 (8 waves, 1/32 B per MAC), else 128x128 (1/16 B per MAC)
       const int t = wide_tile_kind(a.B, a.M_out, a.N, a.taps * a.Cin);
-      static const bool no_pipe = getenv("ASW_NO_PIPE") != nullptr;           // A/B switch for measurements
       // (192-row tiles, i.e. a single row tile per item and a long K, stay on the two-barrier kernel:
       // with so little reuse of a weight fragment the global B path loses, 296 vs 322 TFLOP/s)
-      if (!no_pipe && a.Wf_hi && a.Wf_lo && t == 2 && (a.taps * a.Cin) % 16 == 0 && a.N % 32 == 0) {
+      if (a.Wf_hi && a.Wf_lo && t == 2 && (a.taps * a.Cin) % 16 == 0 && a.N % 32 == 0) {
         // Short K (the decoder's transposed convolutions): two independent 4-wave workgroups of 128 rows per CU, same
         // wave tile -- one drains its tile while the other computes (K = 512: 234 -> 260 TFLOP/s, K = 256: 186 -> 193;
-        // at K >= 896 and in the mask path the 8-wave tile is 2-4 % ahead).  ASW_PIPE_HALF_TILE=0 / 1 forces one form.
-        static const int force = getenv("ASW_PIPE_HALF_TILE") ? atoi(getenv("ASW_PIPE_HALF_TILE")) : -1;
-        const bool half_tile = force >= 0 ? force == 1 : a.taps * a.Cin <= 512;
-        if (half_tile && !a.mul) {
-          if (stats && a.A2) return launch_pipe<128, true, false, true, 32, 1>(a, s);
-          return stats ? launch_pipe<128, true, false, false, 32, 1>(a, s) : launch_pipe<128, false, false, false, 32, 1>(a, s);
-        }
-        if (a.mul) return launch_pipe<256, false, true, false>(a, s);
-        if (stats && a.A2) return launch_pipe<256, true, false, true>(a, s);
-        return stats ? launch_pipe<256, true, false, false>(a, s) : launch_pipe<256, false, false, false>(a, s);
+        // at K >= 896 and in the mask path the 8-wave tile is 2-4 % ahead).
+        if (a.taps * a.Cin <= 512 && !a.mul) return launch_variant<PipeTile<128, 1>, false>(a, s);
+        return launch_variant<PipeTile<256, 2>>(a, s);
       }
-      if (t == 3) {
-        if (a.mul) return launch<192, 256, 32, 2, 4, false, false, true, true>(a, s);
-        if (stats && a.A2) return launch<192, 256, 32, 2, 4, false, true, false, true, true>(a, s);
-        return stats ? launch<192, 256, 32, 2, 4, false, true, false, true>(a, s)
-                     : launch<192, 256, 32, 2, 4, false, false, false, true>(a, s);
-      }
-      if (t == 2) {
-        if (a.mul) return launch<256, 256, 32, 2, 4, false, false, true, true>(a, s);
-        if (stats && a.A2) return launch<256, 256, 32, 2, 4, false, true, false, true, true>(a, s);
-        return stats ? launch<256, 256, 32, 2, 4, false, true, false, true>(a, s)
-                     : launch<256, 256, 32, 2, 4, false, false, false, true>(a, s);
-      }
-      if (t == 1) {
-        if (a.mul) return launch<256, 128, 32, 4, 2, false, false, true, true>(a, s);
-        if (stats && a.A2) return launch<256, 128, 32, 4, 2, false, true, false, true, true>(a, s);
-        return stats ? launch<256, 128, 32, 4, 2, false, true, false, true>(a, s)
-                     : launch<256, 128, 32, 4, 2, false, false, false, true>(a, s);
-      }
+      if (t == 3) return launch_variant<GemmTile<192, 256, 2, 4, true>>(a, s);
+      if (t == 2) return launch_variant<GemmTile<256, 256, 2, 4, true>>(a, s);
+      return launch_variant<GemmTile<128, 128, 2, 2, true>>(a, s);
     }
-    if (a.mul) return launch_prec<128, 128, 32, 2, 2, false, false, true>(a, s);
-    if (stats && a.A2)
-      return a.precision >= 1 ? launch<128, 128, 32, 2, 2, false, true, false, true, true>(a, s)
-                              : launch<128, 128, 32, 2, 2, false, true, false, false, true>(a, s);
-    return stats ? launch_prec<128, 128, 32, 2, 2, false, true>(a, s) : launch_prec<128, 128, 32, 2, 2, false, false>(a, s);
+    return launch_variant<GemmTile<128, 128, 2, 2, false>>(a, s);
   }
   ASW_CHECK_ARG(a.N % 64 == 0, "convgemm: N=%d must be a multiple of 64", a.N);
   return stats ? launch_prec<256, 64, 32, 4, 1, false, true>(a, s) : launch_prec<256, 64, 32, 4, 1, false, false>(a, s);

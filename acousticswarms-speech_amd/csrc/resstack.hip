@@ -29,16 +29,14 @@
 // 16 B pad (272 B: the 16-byte fragment reads of 32 consecutive rows are bank-conflict free).  Weights
 // never touch LDS: MFMA-fragment order (asw_pack_fragments_f16), one coalesced 1 KiB load per fragment,
 // QD k-steps ahead.
-#include <cstdlib>
 #include <type_traits>
 
 #include "asw_common.h"
-#include "mfma_util.h"
+#include "f16x3_tile.h"
 
 namespace {
 using namespace asw_mfma;
 
-constexpr int RS = 272;                  // bytes per image row
 constexpr int C = 64;
 constexpr int MAXL = 3;
 
@@ -77,65 +75,6 @@ struct KArgs {
   LayerDev L[MAXL];
 };
 
-// taps x 4 k-steps of one layer for NF row fragments of this wave: acc[i][cb] += W(cb) . X(i)^T
-template <int NF, int QD, int NTERM>
-__device__ __forceinline__ void kloop(floatx16 (&acc)[NF][2], const char* img, const int (&xb)[NF], int taps, int tapstep,
-                                      const half8* __restrict__ Wh, const half8* __restrict__ Wl, int lane) {
-  auto wload = [&](int kg, half8 (&h)[2], half8 (&l)[2]) {
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const long o = ((long)kg * 2 + cb) * 64 + lane;
-      h[cb] = Wh[o];
-      if (NTERM == 3) l[cb] = Wl[o];
-    }
-  };
-  auto xload = [&](int tap, int ks, half8 (&h)[NF], half8 (&l)[NF]) {
-#pragma unroll
-    for (int i = 0; i < NF; ++i) {
-      const char* q = img + xb[i] + tap * tapstep + ks * 32;
-      h[i] = *reinterpret_cast<const half8*>(q);
-      if (NTERM == 3) l[i] = *reinterpret_cast<const half8*>(q + 128);
-    }
-  };
-  half8 wh[QD][2], wl[QD][2];
-  half8 xh[2][NF], xl[2][NF];
-#pragma unroll
-  for (int q = 0; q < QD; ++q) wload(q, wh[q], wl[q]);
-  xload(0, 0, xh[0], xl[0]);
-  // Every load in the loop body is UNCONDITIONAL (past-the-end indices are clamped to the last fragment, which
-  // is simply fetched again): a load inside an `if` sits in its own basic block, and at the join hipcc waits
-  // vmcnt(0) -- i.e. for the weight fragments requested one k-step earlier -- once per tap, instead of counting.
-  const int nks = taps * 4;
-  for (int tap = 0; tap < taps; ++tap) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int nk = (ks + 1) & 3;
-      int nt = tap + (ks == 3 ? 1 : 0);
-      nt = nt < taps ? nt : taps - 1;
-      xload(nt, nk, xh[(ks + 1) & 1], xl[(ks + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);       // (the next k-step's LDS reads go out BEFORE this k-step's MFMAs, not after)
-      const int s = ks % QD, xbuf = ks & 1;
-#pragma unroll
-      for (int i = 0; i < NF; ++i)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          if (NTERM == 3) {
-            // same term order as the row-major kernels: x_lo * w_hi, x_hi * w_lo, x_hi * w_hi
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[s][cb], xl[xbuf][i], acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[s][cb], xh[xbuf][i], acc[i][cb], 0, 0, 0);
-          }
-          acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[s][cb], xh[xbuf][i], acc[i][cb], 0, 0, 0);
-        }
-      int kg = tap * 4 + ks + QD;
-      kg = kg < nks ? kg : nks - 1;
-      wload(kg, wh[s], wl[s]);
-      // pin the k-step order: left alone, hipcc sinks the four k-steps' weight loads to the end of the tap body and
-      // waits for them at the top of the next one -- the L2 latency of the weight stream exposed once per tap
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
 // NL fused layers (contiguous row tiles) or one layer on polyphase row sets (POLY, NL == 1).
 // NW waves, each owning TM 32-row fragments x all 64 channels.
 template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int NTERM, int QD>
@@ -153,12 +92,8 @@ void resstack64_kernel(const KArgs p) {
   float* tab = reinterpret_cast<float*>(smem + (size_t)p.img_rows * RS);       // [NL][bias | gamma | beta][64]
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  // XCD-aware tile order: workgroup L runs on XCD L % 8 (round-robin dispatch); XCD x walks a CONTIGUOUS
-  // run of (item, row tile) pairs, so the halo rows two neighbouring tiles share meet in one L2.
-  const int total = p.B * p.ntile;
-  const int per = (total + 7) >> 3;
-  const int idx = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-  if (idx >= total) return;
+  int idx;
+  if (!xcd_tile_run(p.B * p.ntile, idx)) return;        // XCD-aware order: a contiguous run of (item, row tile) pairs
   const int b = idx / p.ntile, tile = idx - b * p.ntile;
   const int T = p.T, taps = p.taps;
   const int dil0 = p.L[0].dil, pad0 = p.L[0].pad;
@@ -180,15 +115,13 @@ void resstack64_kernel(const KArgs p) {
     const __amdgpu_buffer_rsrc_t rX = GLU ? act_rsrc(p.glu_raw + (long)b * T * 2 * C, (long)T * 2 * C)
                                           : act_rsrc(p.x + (long)b * T * C, (long)T * C);
     const int srow = tid >> 4, sc4 = tid & 15;
-    float gm0 = 0.f, gr0 = 0.f, gm1 = 0.f, gr1 = 0.f;
-    float4 gga, gba, ggg, gbg;
+    GluCoef gc;
     if (GLU) {
-      gm0 = p.glu_mr[b * 4 + 0]; gr0 = p.glu_mr[b * 4 + 1]; gm1 = p.glu_mr[b * 4 + 2]; gr1 = p.glu_mr[b * 4 + 3];
-      gga = *reinterpret_cast<const float4*>(p.glu_gamma + sc4 * 4);
-      gba = *reinterpret_cast<const float4*>(p.glu_beta + sc4 * 4);
-      ggg = *reinterpret_cast<const float4*>(p.glu_gamma + C + sc4 * 4);
-      gbg = *reinterpret_cast<const float4*>(p.glu_beta + C + sc4 * 4);
+      gc.stats(p.glu_mr, b);
+      gc.affine(p.glu_gamma, p.glu_beta, C, sc4 * 4);
     }
+    // (This loop stays here instead of calling stage_image of f16x3_tile.h, which resconv16 and downconv64 use: through
+    // the shared routine the GLU variant of the fused pair measured 0.7 % slower, 11.11 -> 11.21 ms per bench step.)
     // the whole image is requested before the first row is converted: one exposed memory latency per tile (with 8
     // rows per thread in flight the three rounds of a 262-row image took 17 % of a workgroup's time)
     constexpr int SU = GLU ? 9 : 18;
@@ -219,17 +152,9 @@ void resstack64_kernel(const KArgs p) {
         }
       }
       if (GLU) {
-        // the arithmetic of gn_glu_kernel, expression for expression; rows outside the sequence stay zero
 #pragma unroll
         for (int u = 0; u < SU; ++u) {
-          float4 o;
-#define ASW_GLU(f)                                                       \
-  {                                                                      \
-    const float gl = asw::gn_glu_value(buf[u].f, gate[u].f, gm0, gr0, gm1, gr1, gga.f, gba.f, ggg.f, gbg.f); \
-    o.f = okr[u] ? gl : 0.f;                                             \
-  }
-          ASW_GLU(x) ASW_GLU(y) ASW_GLU(z) ASW_GLU(w)
-#undef ASW_GLU
+          const float4 o = gn_glu4(buf[u], gate[u], gc, okr[u]);
           buf[u] = o;
           // the normalised tensor is also a skip connection: each tile writes the rows of its own output range once
           if (p.glu_out && okr[u]) {
@@ -245,8 +170,8 @@ void resstack64_kernel(const KArgs p) {
         if (row < R_img) {
           half4 hi, lo;
           split4t<NTERM>(buf[u], hi, lo);
-          *reinterpret_cast<half4*>(img + row * RS + sc4 * 8) = hi;
-          *reinterpret_cast<half4*>(img + row * RS + 128 + sc4 * 8) = lo;      // (the residual reads it in every mode)
+          *reinterpret_cast<half4*>(img + row * RS + IMG_HI + sc4 * 8) = hi;
+          *reinterpret_cast<half4*>(img + row * RS + IMG_LO + sc4 * 8) = lo;      // (the residual reads it in every mode)
         }
       }
     }
@@ -285,7 +210,9 @@ void resstack64_kernel(const KArgs p) {
         a[i][0] = acc[i][0];
         a[i][1] = acc[i][1];
       }
-      kloop<NF, QD, NTERM>(a, img, xb, taps, tapstep, Ld.Wh, Ld.Wl, lane);
+      kloop<NF, 2, QD, NTERM>(
+          a, taps, [&](int tap, int i) __attribute__((always_inline)) { return img + xb[i] + tap * tapstep; }, Ld.Wh, Ld.Wl,
+          [](int kg, int cb) __attribute__((always_inline)) { return (long)kg * 2 + cb; }, lane);
 #pragma unroll
       for (int i = 0; i < NF; ++i) { acc[i][0] = a[i][0]; acc[i][1] = a[i][1]; }
     };
@@ -319,8 +246,8 @@ void resstack64_kernel(const KArgs p) {
           for (int q = 0; q < 4; ++q) {
             const int c0 = cb * 32 + q * 8 + h * 4;
             const float4 bi = *reinterpret_cast<const float4*>(tb + c0);
-            const half4 rh = *reinterpret_cast<const half4*>(rrow + c0 * 2);
-            const half4 rl = *reinterpret_cast<const half4*>(rrow + 128 + c0 * 2);
+            const half4 rh = *reinterpret_cast<const half4*>(rrow + IMG_HI + c0 * 2);
+            const half4 rl = *reinterpret_cast<const half4*>(rrow + IMG_LO + c0 * 2);
             const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -371,8 +298,8 @@ void resstack64_kernel(const KArgs p) {
               if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);
               half4 hi, lo;
               split4t<NTERM>(v, hi, lo);
-              *reinterpret_cast<half4*>(wrow + c0 * 2) = hi;
-              *reinterpret_cast<half4*>(wrow + 128 + c0 * 2) = lo;
+              *reinterpret_cast<half4*>(wrow + IMG_HI + c0 * 2) = hi;
+              *reinterpret_cast<half4*>(wrow + IMG_LO + c0 * 2) = lo;
             }
         }
       }
@@ -433,21 +360,14 @@ void resstack64_kernel(const KArgs p) {
 
 template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int QD>
 int launch_stack(const KArgs& k, int precision, size_t smem, double flops, const char* tag, hipStream_t s) {
-  const bool x1 = precision == 2;
-  auto kern = x1 ? resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 1, QD> : resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD>;
-  static asw::SmemAttr attr[2];                         // per device and instantiation
-  if (int rc = attr[x1].ensure(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
-  const int total = k.B * k.ntile;
-  dim3 grid(((total + 7) / 8) * 8);
-  char nm[128];
-  int nl = snprintf(nm, sizeof nm, "resstack64<%s,%dx%d%s%s>", tag, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
-                    GLU ? ",glu" : "");
-  if (asw::prof_detail()) snprintf(nm + nl, sizeof nm - nl, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
+  char nm[128], detail[48] = "";
+  snprintf(nm, sizeof nm, "resstack64<%s,%dx%d%s%s>", tag, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
+           GLU ? ",glu" : "");
+  if (asw::prof_detail()) snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
   // algorithmic bytes: the stack's input read once, its output written once
-  asw::ProfScope prof(s, nm, flops, (double)k.B * k.T * C * 4 * (GLU ? 3 : 2));
-  hipLaunchKernelGGL(kern, grid, dim3(64 * NW), smem, s, k);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 1, QD>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD>>(
+      precision, dim3(xcd_grid_run(k.B * k.ntile)), dim3(64 * NW), smem, 160 * 1024, nm, detail, flops,
+      (double)k.B * k.T * C * 4 * (GLU ? 3 : 2), s, k);
 }
 
 template <int NW, int TM>
@@ -536,13 +456,5 @@ extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream)
     halo += L.pad;
   }
   const double flops = 2.0 * a.B * (double)a.T * C * C * a.taps * a.n_layers;
-  // tile variants (waves x 32-row fragments per wave); ASW_RESSTACK_TILE=<NW><TM> picks one for measurements
-  static const int tile_env = getenv("ASW_RESSTACK_TILE") ? atoi(getenv("ASW_RESSTACK_TILE")) : 0;
-  const int variant = tile_env == 24 || tile_env == 44 || tile_env == 82 ? tile_env : 42;
-  switch (variant) {
-    case 24: return dispatch<2, 4>(a, k, glu, flops, s);
-    case 44: return dispatch<4, 4>(a, k, glu, flops, s);
-    case 82: return dispatch<8, 2>(a, k, glu, flops, s);
-    default: return dispatch<4, 2>(a, k, glu, flops, s);
-  }
+  return dispatch<4, 2>(a, k, glu, flops, s);            // 4 waves x 2 row fragments: 256 rows computed by layer 0
 }

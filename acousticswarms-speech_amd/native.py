@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["asw_common.cpp", "convgemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip", "misc_kernels.hip", "attention_mfma.hip", "srp_kernels.hip",
            "pruner_kernels.hip", "geometry_kernels.hip",
            "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip"]
-HEADERS = ["asw_common.h", "model_common.h", "mfma_util.h"]
+HEADERS = ["asw_common.h", "model_common.h", "mfma_util.h", "f16x3_tile.h"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
 EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"]}
 OPS_PATH = os.path.join(_HERE, "libasw_torch_ops.so")      # TORCH_LIBRARY(asw, ...) adapters over the C ABI

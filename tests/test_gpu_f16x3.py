@@ -61,8 +61,8 @@ def test_residual_layer_f16x3(C, T, dil, frag):
 def test_stride2_conv_of_64_channels_f16x3(Cout, T, K):
     """EncoderBlock tail of the two full-rate levels -- gate * x -> Conv1d(stride 2) -> GroupNorm(2) -> GLU
     (network.py:101-113) -- through the halo-staged stride-2 kernel (csrc/downconv.hip: even / odd row images,
-    transposed accumulators) in f16x3 arithmetic, against torch fp32 and against the generic GEMM (ASW_NO_DOWNCONV is
-    read once per process, so the generic path is reached here through the fragment-free call)."""
+    transposed accumulators) in f16x3 arithmetic, against torch fp32 and against the generic GEMM (which the
+    fragment-free call reaches: the stride-2 kernel needs fragment-order weights)."""
     from acousticswarms_speech_amd import ops
     B, Cin = 3, 64
     x = _rand(B, Cin, T, seed=8)
@@ -142,6 +142,132 @@ def test_pipelined_wide_tiles_f16x3(M, N, K, skip):
     np.testing.assert_allclose(s[:, 0].numpy(), want[..., :N // 2].sum((1, 2)).numpy(), rtol=1e-5, atol=1e-2)
     np.testing.assert_allclose(s[:, 1].numpy(), (want[..., :N // 2] ** 2).sum((1, 2)).numpy(), rtol=1e-5)
     np.testing.assert_allclose(s[:, 3].numpy(), (want[..., N // 2:] ** 2).sum((1, 2)).numpy(), rtol=1e-5)
+
+
+# ---- which kernel a shape is sent to.  (arguments -> launch name in the detailed profile), the names recorded from the
+# dispatcher as it stood before its launch functions and its variant cascade were folded into shared helpers.
+_DISPATCH = []
+
+
+def _row(kind, expected, **kw):
+    _DISPATCH.append(pytest.param(kind, kw, expected, id=kind + "-" + "-".join(f"{k}{v}" for k, v in kw.items())))
+
+
+for _N in (64, 128, 256, 512, 1024):                    # LayerNorm epilogue on the generic tiles (one tap: no halo kernel)
+    _bk = 32 if _N <= 256 else 16
+    _bm = {64: 256, 128: 128, 256: 64, 512: 64, 1024: 32}[_N]
+    _row("ln", f"convgemm<{_bm},{_N},{_bk},ln>[B2 M70 N{_N} K{_N} s1]", N=_N, prec="f32")
+    _row("ln", f"convgemm16<{_bm},{_N},{_bk},ln>[B2 M70 N{_N} K{_N} s1]", N=_N, prec="f16x3")
+for _C, _T, _d, _nm in ((64, 300, 1, "128,64,ph1"), (64, 777, 7, "128,64,poly1"), (64, 4800, 49, "128,64,poly1"),
+                        (64, 2400, 49, "128,64,poly2"), (64, 1800, 49, "128,64,poly4"), (64, 900, 49, "128,64,ph1"),
+                        (64, 100, 49, "128,64,ph1"), (128, 520, 7, "128,128,ph1,q2"), (128, 2400, 49, "128,128,poly2,q2"),
+                        (256, 300, 7, "64,256,ph1,q2"), (512, 200, 1, "64,512,ph1,q2"), (512, 200, 49, "64,512,ph1")):
+    _row("res", f"resconv16<{_nm}>[B2 M{_T} N{_C} K{7 * _C} d{_d}]", C=_C, T=_T, dil=_d)      # halo kernel, 7 taps
+_row("res", "resconv16<128,64,ph1,glu>[B2 M300 N64 K448 d1]", C=64, T=300, dil=1, glu=True)
+_row("down", "downconv64<128x128,stats>[B2 M129 N128 K448 s2]", N=128, T=258)
+# wide tiles need B x tiles >= 512; M = 500: two 256-row tiles per item, M = 300: one 192-row tile and a half
+for _K, _forms in ((256, ("plain", "stats", "stats+A2")), (1024, ("plain", "stats", "stats+A2", "mul"))):
+    for _f in _forms:
+        _ep = "plain" if _f in ("plain", "mul") else "stats"
+        _m = "m" if _f == "mul" else ""
+        _row("gemm", f"convgemm16p{_m}<{128 if _K <= 512 else 256},256,32,{_ep}>[B256 M500 N256 K{_K} s1]",
+             B=256, M=500, N=256, K=_K, prec="f16x3", form=_f)
+        _row("gemm", f"convgemm16{_m}<256,256,32,{_ep}>[B256 M500 N256 K{_K} s1]",
+             B=256, M=500, N=256, K=_K, prec="f16x3", form=_f, frag=False)
+_row("gemm", "convgemm16<192,256,32,plain>[B256 M300 N256 K256 s1]", B=256, M=300, N=256, K=256, prec="f16x3", form="plain")
+_row("gemm", "convgemm16m<192,256,32,plain>[B256 M300 N256 K256 s1]", B=256, M=300, N=256, K=256, prec="f16x3", form="mul")
+for _prec, _k in (("f32", "convgemm"), ("f16x3", "convgemm16")):
+    for _f in ("plain", "stats", "stats+A2", "mul"):                                      # 128 x 128
+        _nm = f"{_k}{'' if _f != 'mul' else '_m' if _prec == 'f32' else 'm'}<128,128,32,{'plain' if _f in ('plain', 'mul') else 'stats'}>"
+        _row("gemm", _nm + "[B2 M300 N256 K128 s1]", B=2, M=300, N=256, K=128, prec=_prec, form=_f)
+    for _f in ("plain", "stats"):                                                         # 256 x 64
+        _row("gemm", f"{_k}<256,64,32,{_f}>[B2 M300 N192 K128 s1]", B=2, M=300, N=192, K=128, prec=_prec, form=_f)
+
+
+def _grand(*shape, seed, scale=1.0):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return torch.randn(*shape, generator=g, device="cuda") * scale
+
+
+_gemm_cache = {}
+
+
+def _gemm_case(B, M, N, K):
+    """Inputs and float64 references of one GEMM shape, shared by the rows of that shape (one shape kept at a time)."""
+    key = (B, M, N, K)
+    if key not in _gemm_cache:
+        _gemm_cache.clear()
+        x, x2 = _grand(B, M, K, seed=41), _grand(B, M, K, seed=42)
+        w, bias, mul = _grand(N, K, seed=43, scale=1 / math.sqrt(K)), _grand(N, seed=44, scale=0.1), _grand(B, M, N, seed=45)
+        want = F.linear(x.double(), w.double(), bias.double())
+        want2 = F.linear(x.double() + x2.double(), w.double(), bias.double())
+        _gemm_cache[key] = dict(x=x, x2=x2, w=w, bias=bias, mul=mul, want=want, want2=want2)
+    return _gemm_cache[key]
+
+
+@pytest.mark.parametrize("kind,kw,expected", _DISPATCH)
+def test_convgemm_dispatch_table(kind, kw, expected):
+    """Every branch of asw_convgemm_f32's dispatch at the smallest shape that reaches it: the launch it makes (read
+    from the detailed profile) and its output against torch in float64, at the bounds this file and
+    test_gpu_kernels.py use per kernel: 2e-5 relative L2 for f16x3 (operands carry ~21 bits), 2e-6 for exact f32."""
+    import ctypes
+    import json
+    from acousticswarms_speech_amd import native, ops
+    prec = kw.get("prec", "f16x3")
+    if kind == "ln":                                   # LN(ReLU(x W^T + b) + x), one tap
+        N = kw["N"]
+        x = _grand(2, 70, N, seed=51)
+        w, b = _grand(N, N, seed=52, scale=1 / math.sqrt(N)), _grand(N, seed=53, scale=0.1)
+        g, be = 1 + _grand(N, seed=54, scale=0.1), _grand(N, seed=55, scale=0.1)
+        want = F.layer_norm(F.relu(F.linear(x.double(), w.double(), b.double())) + x.double(), (N,), g.double(), be.double())
+        call = lambda: ops.convgemm(x, w, 70, N, N, bias=b, relu=True, resid=x, ln=(g, be), precision=prec, use_fragments=False)
+    elif kind == "res":                                # DilatedResidualLayer, 7 taps, fragment-order weights
+        C, T, dil = kw["C"], kw["T"], kw["dil"]
+        w = _grand(C, C, 7, seed=62, scale=1 / math.sqrt(7 * C))
+        b, g, be = _grand(C, seed=63, scale=0.1), 1 + _grand(C, seed=64, scale=0.1), _grand(C, seed=65, scale=0.1)
+        args = dict(taps=7, dil=dil, pad=3 * dil, bias=b, relu=True, ln=(g, be), precision=prec)
+        if kw.get("glu"):                              # the input is GLU(GroupNorm(2)(raw)), applied while staging
+            raw = _grand(2, T, 2 * C, seed=61) * 1.7 + 0.3
+            gg, gb = 1 + _grand(2 * C, seed=66, scale=0.2), _grand(2 * C, seed=67, scale=0.1)
+            r = raw.double()
+            stats = torch.stack([r[..., :C].sum((1, 2)), (r[..., :C] ** 2).sum((1, 2)), r[..., C:].sum((1, 2)),
+                                 (r[..., C:] ** 2).sum((1, 2))], dim=1).float().view(2, 1, 4).contiguous()
+            mr = ops.gn_finalize(stats, T, C)
+            xd = F.glu(F.group_norm(r.transpose(1, 2), 2, gg.double(), gb.double(), 1e-5), dim=1)      # [B, C, T]
+            call = lambda: ops.convgemm(raw, ops.pack_conv_weight(w), T, C, C, resid=raw, a_batch_stride=T * C, a_len=T * C,
+                                        B=2, glu=(raw, mr, gg, gb), **args)
+        else:
+            x = _grand(2, T, C, seed=61)
+            xd = x.double().transpose(1, 2)
+            call = lambda: ops.convgemm(x, ops.pack_conv_weight(w), T, C, C, resid=x, **args)
+        want = F.layer_norm((F.relu(F.conv1d(xd, w.double(), b.double(), dilation=dil, padding=3 * dil)) + xd).transpose(1, 2),
+                            (C,), g.double(), be.double())
+    elif kind == "down":                               # stride-2 convolution of a 64-channel tensor, with partial sums
+        N, T = kw["N"], kw["T"]
+        x = _grand(2, T, 64, seed=71)
+        w, b = _grand(N, 64, 7, seed=72, scale=1 / math.sqrt(7 * 64)), _grand(N, seed=73, scale=0.1)
+        want = F.conv1d(x.double().transpose(1, 2), w.double(), b.double(), stride=2, padding=3).transpose(1, 2)
+        call = lambda: ops.convgemm(x, ops.pack_conv_weight(w), want.shape[1], N, 64, taps=7, stride=2, pad=3, bias=b,
+                                    stats_chan_mod=N, precision=prec)
+    else:                                              # plain GEMM tiles: x W^T + b, optionally (x + x2), * mul, partial sums
+        B, M, N, K, form = kw["B"], kw["M"], kw["N"], kw["K"], kw["form"]
+        c = _gemm_case(B, M, N, K)
+        want = c["want2"] if form == "stats+A2" else c["want"] * c["mul"].double() if form == "mul" else c["want"]
+        call = lambda: ops.convgemm(c["x"], c["w"], M, N, K, bias=c["bias"], precision=prec, use_fragments=kw.get("frag", True),
+                                    stats_chan_mod=N if form.startswith("stats") else 0,
+                                    A2=c["x2"] if form == "stats+A2" else None, mul=c["mul"] if form == "mul" else None)
+    L = native.lib()
+    L.asw_profile_enable(2)
+    out, _ = call()
+    torch.cuda.synchronize()
+    buf = ctypes.create_string_buffer(1 << 16)
+    native.check(L.asw_profile_report(buf, len(buf)))
+    L.asw_profile_enable(0)
+    names = list(json.loads(buf.value.decode()))
+    r = float((out.double() - want).norm() / want.norm())
+    _log(f"dispatch {kind} {kw}: {names} rel={r:.3e}")
+    assert names == [expected]
+    assert r < (2e-6 if prec == "f32" else 2e-5)
 
 
 def _model(cfg, seed, batch=32):
