@@ -7,6 +7,7 @@
 //   voxel_map       quantised TDoA vector and keep-out mask per voxel of the SRP grid, dis_matrix
 //   label           26-connected components of equal quantised vectors, label = smallest C-order voxel index
 //   compact         POWER_INDEX, cluster offsets, CSR member list, cluster centres, tau and tops_delta
+//   lattice         the coarse TDoA lattice of the 1 cm lookup grid (dense_grid.coarse_lattice): stage 1 without a pruner
 //
 // Exactness.  Every value is computed in double with the expression order of the numpy statements it
 // replaces -- norm = sqrt((dx*dx + dy*dy) + dz*dz), "/ C * FS" as two operations, centres as a sequential sum in
@@ -381,6 +382,195 @@ extern "C" int asw_geom_compact(const int32_t* labels, const int32_t* q, const d
   ASW_LAUNCH_CHECK();
   hipLaunchKernelGGL(delays_kernel, dim3(asw::cdiv((long)G * M, kBlock)), dim3(kBlock), 0, s, centres, G, mics, M, centre[0],
                      centre[1], centre[2], C, tau, delta);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+// ---- coarse TDoA lattice of the 1 cm lookup grid (dense_grid.coarse_lattice) -------------------------------------
+// Every lookup point outside the keep-out rectangle belongs to the cube its TDoA vector rounds to; the cubes come out
+// in lexicographic order of their cell vectors and the members of a cube in ascending point index.  The cell vector
+// of 16 microphones is 15 int32 fields (up to 31): it is ordered by one stable radix pass per pair, last pair first.
+namespace {
+
+// thread = one lookup point i = (iy*nx + ix)*nz + iz: keep[i] = outside the keep-out rectangle (open interval, the
+// comparisons of SRPPhat._valid_mask), cellp[p][i] = rint(planes[p][i] / width) (IEEE divide, round half to even)
+__global__ __launch_bounds__(kBlock) void lattice_cells_kernel(const double* __restrict__ planes, int P, long n, int nx, int nz,
+                                                               const double* __restrict__ xs, const double* __restrict__ ys,
+                                                               double b0, double b1, double b2, double b3, double width,
+                                                               int32_t* __restrict__ cellp, int32_t* __restrict__ keep) {
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const long yx = i / nz;
+  const double px = xs[yx % nx], py = ys[yx / nx];
+  const bool inside = px > b0 && px < b2 && py > b1 && py < b3;
+  keep[i] = inside ? 0 : 1;
+  for (int p = 0; p < P; ++p) cellp[(long)p * n + i] = (int32_t)rint(planes[(long)p * n + i] / width);
+}
+
+// kept points in ascending index: perm[pos[i]] = i
+__global__ __launch_bounds__(kBlock) void lattice_compact_kernel(const int32_t* __restrict__ keep, const int32_t* __restrict__ pos,
+                                                                 long n, int32_t* __restrict__ perm) {
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  if (keep[i]) perm[pos[i]] = (int32_t)i;
+}
+
+// keys of one radix pass: the cell of pair p of the points in their current order
+__global__ __launch_bounds__(kBlock) void lattice_keys_kernel(const int32_t* __restrict__ plane, const int32_t* __restrict__ perm,
+                                                              int K, int32_t* __restrict__ keys) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= K) return;
+  keys[j] = plane[perm[j]];
+}
+
+// head[j] = 1 where sorted point j opens a cube (its cell vector differs from its predecessor's)
+__global__ __launch_bounds__(kBlock) void lattice_heads_kernel(const int32_t* __restrict__ cellp, int P, long n,
+                                                               const int32_t* __restrict__ perm, int K, int32_t* __restrict__ head) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= K) return;
+  int32_t h = 1;
+  if (j > 0) {
+    const int32_t a = perm[j], b = perm[j - 1];
+    h = 0;
+    for (int p = 0; p < P; ++p) h |= cellp[(long)p * n + a] != cellp[(long)p * n + b] ? 1 : 0;
+  }
+  head[j] = h;
+}
+
+// rank = exclusive scan of head: a head is cube rank[j]; it writes the cube's first position and cell vector
+__global__ __launch_bounds__(kBlock) void lattice_scatter_kernel(const int32_t* __restrict__ cellp, int P, long n,
+                                                                 const int32_t* __restrict__ perm, int K,
+                                                                 const int32_t* __restrict__ head, const int32_t* __restrict__ rank,
+                                                                 int32_t* __restrict__ cells, int32_t* __restrict__ bounds) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= K) return;
+  if (head[j]) {
+    const int32_t g = rank[j], a = perm[j];
+    bounds[g] = j;
+    for (int p = 0; p < P; ++p) cells[(long)g * P + p] = cellp[(long)p * n + a];
+  }
+  if (j == K - 1) bounds[rank[j] + head[j]] = K;
+}
+
+// thread = one cube: its members' positions summed one after the other in member order, then / count (centres_kernel
+// with the lookup grid's point index)
+__global__ __launch_bounds__(kBlock) void lattice_centres_kernel(const int32_t* __restrict__ members, const int32_t* __restrict__ bounds,
+                                                                 int N, const double* __restrict__ xs, const double* __restrict__ ys,
+                                                                 const double* __restrict__ zs, int nx, int nz,
+                                                                 double* __restrict__ centres) {
+  const int g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= N) return;
+  const int b0 = bounds[g], b1 = bounds[g + 1];
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int j = b0; j < b1; ++j) {
+    const int i = members[j];
+    const int yx = i / nz;
+    const double px = xs[yx % nx], py = ys[yx / nx], pz = zs[i % nz];
+    if (j == b0) {
+      sx = px; sy = py; sz = pz;
+    } else {
+      sx = sx + px; sy = sy + py; sz = sz + pz;
+    }
+  }
+  const double cnt = (double)(b1 - b0);
+  centres[3 * (long)g] = sx / cnt;
+  centres[3 * (long)g + 1] = sy / cnt;
+  centres[3 * (long)g + 2] = sz / cnt;
+}
+
+constexpr int kLatticeSlots = 6;             // keep / head, pos / rank, two permutations, two key arrays
+
+}  // namespace
+
+extern "C" int64_t asw_geom_lattice_workspace_bytes(int n_points, int P) {
+  if (n_points <= 0 || P < 1 || P > 31) {
+    asw::set_error(ASW_ERR_ARG, "geom_lattice_workspace_bytes: %d points, %d pairs (need points > 0, 1 <= pairs <= 31)", n_points, P);
+    return ASW_ERR_ARG;
+  }
+  size_t temp = 0;
+  if (cub_temp_bytes(n_points, &temp) != hipSuccess) {
+    asw::set_error(ASW_ERR_HIP, "geom_lattice_workspace_bytes: the scan / sort size query failed");
+    return ASW_ERR_HIP;
+  }
+  return (int64_t)((size_t)(P + kLatticeSlots) * align256((size_t)n_points * sizeof(int32_t)) + align256(temp));
+}
+
+extern "C" int asw_geom_lattice(const double* planes, int P, int ny, int nx, int nz, const double* xs, const double* ys,
+                                const double* zs, const double* border, double width, void* workspace, int64_t workspace_bytes,
+                                int32_t* cells, int32_t* bounds, int32_t* members, double* centres, int* counts, void* stream) {
+  ASW_CHECK_ARG(planes && xs && ys && zs && border && workspace && counts, "geom_lattice: null pointer");
+  ASW_CHECK_ARG(cells && bounds && members && centres, "geom_lattice: null output pointer");
+  ASW_CHECK_ARG(ny > 0 && nx > 0 && nz > 0 && (long)ny * nx * nz <= 0x7fffffffL,
+                "geom_lattice: bad grid %d x %d x %d (points are indexed with int32)", ny, nx, nz);
+  ASW_CHECK_ARG(P >= 1 && P <= 31, "geom_lattice: P = %d outside 1..31", P);
+  ASW_CHECK_ARG(width >= 1.0 / 1024 && width <= 1024, "geom_lattice: the cube width must lie in 1/1024..1024 samples");
+  const long n = (long)ny * nx * nz;
+  const size_t slot = align256((size_t)n * sizeof(int32_t));
+  const size_t fixed = (size_t)(P + kLatticeSlots) * slot;
+  size_t need = 0;
+  ASW_HIP(cub_temp_bytes((int)n, &need));
+  ASW_CHECK_ARG(workspace_bytes >= (int64_t)(fixed + need),
+                "geom_lattice: workspace of %lld bytes is too small (asw_geom_lattice_workspace_bytes)", (long long)workspace_bytes);
+  const size_t temp = (size_t)workspace_bytes - fixed;
+  hipStream_t s = asw::as_stream(stream);
+  char* base = static_cast<char*>(workspace);
+  int32_t* cellp = reinterpret_cast<int32_t*>(base);
+  char* rest = base + (size_t)P * slot;
+  int32_t* keep = reinterpret_cast<int32_t*>(rest);                 // later: head flags of the sorted points
+  int32_t* pos = reinterpret_cast<int32_t*>(rest + slot);           // later: their exclusive scan
+  int32_t* perm_a = reinterpret_cast<int32_t*>(rest + 2 * slot);
+  int32_t* perm_b = reinterpret_cast<int32_t*>(rest + 3 * slot);
+  int32_t* keys_a = reinterpret_cast<int32_t*>(rest + 4 * slot);
+  int32_t* keys_b = reinterpret_cast<int32_t*>(rest + 5 * slot);
+  void* cub = rest + kLatticeSlots * slot;
+  const int blocks = asw::cdiv(n, kBlock);
+
+  counts[0] = counts[1] = 0;
+  ASW_HIP(hipMemsetAsync(bounds, 0, sizeof(int32_t), s));           // bounds[0] of an empty lattice
+  hipLaunchKernelGGL(lattice_cells_kernel, dim3(blocks), dim3(kBlock), 0, s, planes, P, n, nx, nz, xs, ys, border[0], border[1],
+                     border[2], border[3], width, cellp, keep);
+  ASW_LAUNCH_CHECK();
+  size_t t = temp;
+  ASW_HIP(hipcub::DeviceScan::ExclusiveSum(cub, t, keep, pos, (int)n, s));
+  int32_t last[2] = {0, 0};
+  ASW_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipMemcpyAsync(&last[1], keep + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipStreamSynchronize(s));
+  const int K = last[0] + last[1];
+  if (K < 0 || K > n) return asw::set_error(ASW_ERR_STATE, "geom_lattice: inconsistent keep flags (%d kept of %ld points)", K, n);
+  counts[1] = K;
+  if (K == 0) return ASW_OK;
+  hipLaunchKernelGGL(lattice_compact_kernel, dim3(blocks), dim3(kBlock), 0, s, keep, pos, n, perm_a);
+  ASW_LAUNCH_CHECK();
+
+  // least significant field first; every pass is stable, so the points end up ordered by the whole cell vector with
+  // ties (one cube) left in ascending point index
+  const int kblocks = asw::cdiv(K, kBlock);
+  int32_t *cur = perm_a, *spare = perm_b;
+  for (int p = P - 1; p >= 0; --p) {
+    int32_t* out = p == 0 ? members : spare;                        // the last pass leaves the member list in place
+    hipLaunchKernelGGL(lattice_keys_kernel, dim3(kblocks), dim3(kBlock), 0, s, cellp + (long)p * n, cur, K, keys_a);
+    ASW_LAUNCH_CHECK();
+    t = temp;
+    ASW_HIP(hipcub::DeviceRadixSort::SortPairs(cub, t, keys_a, keys_b, cur, out, K, 0, 32, s));
+    spare = cur;
+    cur = out;
+  }
+  int32_t *head = keep, *rank = pos;
+  hipLaunchKernelGGL(lattice_heads_kernel, dim3(kblocks), dim3(kBlock), 0, s, cellp, P, n, members, K, head);
+  ASW_LAUNCH_CHECK();
+  t = temp;
+  ASW_HIP(hipcub::DeviceScan::ExclusiveSum(cub, t, head, rank, K, s));
+  hipLaunchKernelGGL(lattice_scatter_kernel, dim3(kblocks), dim3(kBlock), 0, s, cellp, P, n, members, K, head, rank, cells, bounds);
+  ASW_LAUNCH_CHECK();
+  ASW_HIP(hipMemcpyAsync(&last[0], rank + (K - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipMemcpyAsync(&last[1], head + (K - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ASW_HIP(hipStreamSynchronize(s));
+  const int N = last[0] + last[1];
+  if (N < 1 || N > K) return asw::set_error(ASW_ERR_STATE, "geom_lattice: inconsistent head flags (N = %d, kept = %d)", N, K);
+  counts[0] = N;
+  hipLaunchKernelGGL(lattice_centres_kernel, dim3(asw::cdiv(N, kBlock)), dim3(kBlock), 0, s, members, bounds, N, xs, ys, zs, nx, nz,
+                     centres);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

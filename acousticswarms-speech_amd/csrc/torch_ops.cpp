@@ -429,6 +429,38 @@ std::vector<Tensor> geom_compact(const Tensor& labels, const Tensor& q, const Te
           offsets.narrow(0, 0, G), centres.narrow(0, 0, G).clone(), tau.narrow(0, 0, G).clone(), delta.narrow(0, 0, G).clone()};
 }
 
+// -> cells [N,P] int32, bounds [N+1] int32, members [K] int32, centres [N,3] double: the coarse TDoA lattice of a lookup grid
+// (dense_grid.coarse_lattice).  planes [P,ny,nx,nz] stays where it is: the device build hands over the tensor it made.
+std::vector<Tensor> geom_lattice(const Tensor& planes, const Tensor& xs, const Tensor& ys, const Tensor& zs,
+                                 c10::ArrayRef<double> border, double width) {
+  need(planes, "planes", at::kDouble, 4);
+  need(xs, "xs", at::kDouble, 1);
+  need(ys, "ys", at::kDouble, 1);
+  need(zs, "zs", at::kDouble, 1);
+  for (const Tensor* t : {&xs, &ys, &zs}) same_device(planes, *t, "planes and axes");
+  TORCH_CHECK(border.size() == 4, "border must hold 4 values");
+  const int P = checked_int(planes.size(0), "P"), ny = checked_int(planes.size(1), "ny"), nx = checked_int(planes.size(2), "nx");
+  const int nz = checked_int(planes.size(3), "nz");
+  TORCH_CHECK(P >= 1 && P <= 31, "planes must hold 1..31 pairs");
+  TORCH_CHECK(ys.size(0) == ny && xs.size(0) == nx && zs.size(0) == nz, "planes must be [P, len(ys), len(xs), len(zs)]");
+  const int64_t n = (int64_t)ny * nx * nz;
+  TORCH_CHECK(n > 0 && n <= INT32_MAX, "lookup grid empty or too large");
+  const int64_t ws_bytes = asw_geom_lattice_workspace_bytes((int)n, P);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_geom_lattice_workspace_bytes failed: ", asw_last_error());
+  auto i32 = planes.options().dtype(at::kInt);
+  Tensor ws = at::empty({ws_bytes}, i32.dtype(at::kByte));
+  Tensor cells = at::empty({n, P}, i32), bounds = at::empty({n + 1}, i32), members = at::empty({n}, i32);
+  Tensor centres = at::empty({n, 3}, planes.options());
+  int counts[2] = {0, 0};
+  Launch l(planes);
+  check_status(asw_geom_lattice(planes.data_ptr<double>(), P, ny, nx, nz, xs.data_ptr<double>(), ys.data_ptr<double>(),
+                                zs.data_ptr<double>(), border.data(), width, ws.data_ptr(), ws_bytes, cells.data_ptr<int32_t>(),
+                                bounds.data_ptr<int32_t>(), members.data_ptr<int32_t>(), centres.data_ptr<double>(), counts, l.stream),
+               "asw_geom_lattice");
+  const int64_t N = counts[0], K = counts[1];
+  return {cells.narrow(0, 0, N), bounds.narrow(0, 0, N + 1), members.narrow(0, 0, K), centres.narrow(0, 0, N)};
+}
+
 // ---- joint separation network ---------------------------------------------------------------------
 Tensor sep_infer(int64_t model, const Tensor& mix, const Tensor& offsets) {
   TORCH_CHECK(model != 0, "sep_infer: null model handle");
@@ -522,6 +554,7 @@ TORCH_LIBRARY(asw, m) {
         "float resolution) -> (Tensor, Tensor, Tensor)");
   m.def("geom_label(Tensor q, Tensor valid, int Lx, int Ly, int Lz) -> (Tensor, int)");
   m.def("geom_compact(Tensor labels, Tensor q, Tensor xs, Tensor ys, Tensor zs, Tensor mics, float[] centre, float C) -> Tensor[]");
+  m.def("geom_lattice(Tensor planes, Tensor xs, Tensor ys, Tensor zs, float[] border, float width) -> Tensor[]");
   m.def("sep_infer(int model, Tensor mix, Tensor offsets) -> Tensor");
   m.def("sep_forward(int model, Tensor mix, int n_speakers, int n_mics, int max_speakers) -> Tensor");
   m.def("sep_forward_counts(int model, Tensor mix, int[] counts, int n_mics, int max_speakers) -> Tensor");
@@ -545,6 +578,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("geom_voxel_map", &geom_voxel_map);
   m.impl("geom_label", &geom_label);
   m.impl("geom_compact", &geom_compact);
+  m.impl("geom_lattice", &geom_lattice);
   m.impl("sep_infer", &sep_infer);
   m.impl("sep_forward", &sep_forward);
   m.impl("sep_forward_counts", &sep_forward_counts);

@@ -11,6 +11,8 @@ so every point belongs to exactly one cube).  The reference has no function for 
 configuration; it only defines the stress workload, so there is no fixture to pin and the
 enumeration is checked by its own invariants (tests/test_search_host.py).
 """
+import collections
+
 import numpy as np
 
 from .patch import Patch, pair_offsets
@@ -50,3 +52,81 @@ def dense_tdoa_candidates(mic_positions, roi, width=2, step=0.02, chunk=1 << 20,
         for k, (a, c) in enumerate(zip(first, counts)):
             patches.append(Patch(offsets[k].astype(np.float64), np.full(P, float(width)), pts[:, order[a:a + c]]))
     return offsets, counts, patches
+
+
+# ---- the coarse lattice of an array: stage 1 without a pruner (Prone_method="DENSE") ---------------------------
+class Lattice(collections.namedtuple("Lattice", "cells bounds members centres")):
+    """``cells`` int32 [N,P], ``bounds`` int32 [N+1], ``members`` int32 [n_kept], ``centres`` float64 [N,3] of
+    ``coarse_lattice``; ``width`` is the cube width the cells were taken at."""
+
+    def __new__(cls, cells, bounds, members, centres, width):
+        self = super().__new__(cls, cells, bounds, members, centres)
+        self.width = width
+        return self
+
+    @property
+    def n_cubes(self):
+        return int(self.cells.shape[0])
+
+
+def lookup_axes(node):
+    """(xs, ys, zs) of the 1 cm lookup grid of an ``SRPPhat`` node, host- or device-built."""
+    pos = node.Pos_1
+    if hasattr(pos, "xx"):
+        return pos.xx, pos.yy, pos.zz
+    return pos[0, :, 0, 0], pos[:, 0, 0, 1], pos[0, 0, :, 2]
+
+
+def lattice_keep_mask(node):
+    """bool [ny*nx*nz]: lookup points outside the keep-out rectangle around the array -- the comparisons of
+    ``SRPPhat._valid_mask`` on the lookup grid's own axes."""
+    xs, ys, zs = lookup_axes(node)
+    b = node.array_border
+    inside = ((xs[None, :] > b[0]) & (xs[None, :] < b[2]) & (ys[:, None] > b[1]) & (ys[:, None] < b[3]))
+    return np.broadcast_to(~inside[:, :, None], (len(ys), len(xs), len(zs))).reshape(-1)
+
+
+def coarse_lattice(node, width=8):
+    """Every non-empty width-``width`` TDoA cube of the 1 cm lookup grid of ``node`` (an ``SRPPhat``): the stage-1
+    candidate list of a search with the pruner taken out.
+
+    Points: ``Pos_1`` / ``_planes_1`` [P,ny,nx,nz], point index i = (iy*nx + ix)*nz + iz, without the points whose x
+    lies strictly inside (array_border[0], array_border[2]) and whose y strictly inside (array_border[1],
+    array_border[3]).  The cell of point i on pair p is rint(planes[p][i] / width) (IEEE divide, round half to
+    even); a cube is a distinct cell vector.  Cubes are ordered lexicographically (pair 0 most significant, signed),
+    the members of a cube in ascending i, and a centre is the sequential float64 sum of the member positions in
+    that order divided by their number.  csrc/geometry_kernels.hip (``asw_geom_lattice``) builds the same tables on
+    the GPU, bit for bit; this is their statement."""
+    planes = node._planes_1
+    P = planes.shape[0]
+    flat = planes.reshape(P, -1)
+    kept = np.flatnonzero(lattice_keep_mask(node))
+    cells = np.empty((kept.shape[0], P), dtype=np.int32)
+    for p in range(P):                                       # bounded temporaries: one plane at a time
+        cells[:, p] = np.rint(flat[p, kept] / width)
+    if kept.shape[0] == 0:
+        return Lattice(np.zeros((0, P), np.int32), np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros((0, 3)), width)
+    order = np.lexsort(cells.T[::-1])                        # stable; the last key given is the most significant
+    sc = cells[order]
+    first = np.flatnonzero(np.concatenate([[True], np.any(sc[1:] != sc[:-1], axis=1)]))
+    bounds = np.concatenate([first, [kept.shape[0]]]).astype(np.int32)
+    members = kept[order].astype(np.int32)
+    pos = node.Pos_1.reshape(-1, 3)[members]
+    centres = np.empty((first.shape[0], 3))
+    for g in range(first.shape[0]):
+        a, b = bounds[g], bounds[g + 1]
+        centres[g] = np.cumsum(pos[a:b], axis=0)[-1] / float(b - a)      # one member after the other
+    return Lattice(np.ascontiguousarray(sc[first]), bounds, members, centres, width)
+
+
+def lattice_patches(node, lattice):
+    """The lattice as the patch list of stage 1: one fresh ``Patch`` per cube (``check_out`` mutates its offsets and
+    widths) holding the cube's 1 cm points, with the cube's centre as ``peak_pos`` -- the fine stage builds its
+    centre candidate from it."""
+    cells, bounds, members, centres = lattice
+    width = lattice.width
+    P = cells.shape[1]
+    pos = node.Pos_1.reshape(-1, 3)[members]
+    offsets = cells.astype(np.float64) * width
+    return [Patch(offsets[g].copy(), np.full(P, width), pos[bounds[g]:bounds[g + 1]].T, centres[g].copy())
+            for g in range(cells.shape[0])]

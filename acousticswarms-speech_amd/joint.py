@@ -83,9 +83,9 @@ class JointModel(object):
     def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP", geometry=None):
         """(Re)build the geometry tables unless the configuration is unchanged (:125-137).
         One-off per geometry and excluded from latency, as the reference's README notes.
-        ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS") and is part of the
-        configuration, and so is ``geometry`` ("host" | "device", default: the model's): where the tables are
-        built."""
+        ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS"; "DENSE": no pruner, the whole
+        coarse TDoA lattice of the array) and is part of the configuration, and so is ``geometry`` ("host" |
+        "device", default: the model's): where the tables are built."""
         geometry = self.geometry if geometry is None else geometry
         key = config_key(mic_positions, speaker_range, prone_method, geometry)
         if key == self.previous_config:

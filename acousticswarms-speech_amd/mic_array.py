@@ -7,6 +7,7 @@ reference including its order-dependent quirks (documented inline).
 """
 import numpy as np
 
+from .dense_grid import lattice_patches
 from .hostdsp import max_avg_power, si_sdr, split_wav, split_wise_sisdr
 from .patch import FS, SPEED_OF_SOUND, Patch, pair_offsets
 from .search import (INIT_WIDTH, SPOT_POWER_THRESHOLD2, USE_RELATIVE_SPOT_POWER, binary_search_baseline,
@@ -19,8 +20,9 @@ FINE_CHUNK_EDGES = (0.0, 0.07, 0.40, 0.73, 0.93, 1.0)      # pipelined fine stag
 BIN0, BIN1, N_FFT = 2, 200, 2048
 FREQ_BINS = np.arange(BIN0, BIN1)
 
-# pruning map of stage 1 per Prone_method (sep/Mic_Array.py:165-170)
-PRONE_METHODS = {"SRP": "SRP_Map_WINDOW_new", "MUSIC": "MUSIC_Map_WINDOW", "TOPS": "TOPS_Map_WINDOW"}
+# pruning map of stage 1 per Prone_method (sep/Mic_Array.py:165-170).  "DENSE" has none: stage 1 is then the whole
+# coarse TDoA lattice of the array (dense_grid.coarse_lattice), built once with the geometry
+PRONE_METHODS = {"SRP": "SRP_Map_WINDOW_new", "MUSIC": "MUSIC_Map_WINDOW", "TOPS": "TOPS_Map_WINDOW", "DENSE": None}
 
 
 def check_sisnr_win(sisnr_list, SISNR_THRESHOLD=-2, SISNR_THRESHOLD2=-7):
@@ -74,7 +76,9 @@ class MicArray(object):
                  MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None,
                  geometry="host"):
         """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
-        (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture)."""
+        (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture).
+        ``Prone_method="DENSE"`` takes the pruner out: ``Apply_SRP_PHAT`` returns every width-``INIT_WIDTH`` cube of
+        the array's TDoA lattice, and the later stages run on that list unchanged."""
         if Prone_method not in PRONE_METHODS:
             # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
             raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
@@ -90,7 +94,9 @@ class MicArray(object):
             / SPEED_OF_SOUND * FS
         self.SRP_node = SRPPhat(mic_pos=mic_positions, freq_bins=FREQ_BINS, Range_spk=Spk_Range, grid_size=grid_size,
                                 FS=FS, n_fft=N_FFT, threshold=[0.15, 0.015, 0.05], WIDTH=INIT_WIDTH, device=device,
-                                geometry=geometry)
+                                geometry=geometry, lattice_width=INIT_WIDTH if Prone_method == "DENSE" else None)
+        if Prone_method == "DENSE" and self.SRP_node.lattice.n_cubes == 0:
+            raise RuntimeError("the keep-out region covers the whole speaker range: the TDoA lattice is empty")
         self.original_times = 0
         self.spotforming_times = 0
         self.big_spotforming_times = 0
@@ -107,6 +113,10 @@ class MicArray(object):
         self.SRP_node.reset()
         self.spotforming_times = 0
         self.original_times = 0
+        if self.Prone_method == "DENSE":
+            # no map, so the mixture is not read and no window length is required; fresh Patch objects per call,
+            # because check_out mutates them
+            return lattice_patches(self.SRP_node, self.SRP_node.lattice), np.zeros((3, 3))
         mix_np = mix_data.numpy() if hasattr(mix_data, "numpy") else np.asarray(mix_data)
         win = 36000 if mix_np.shape[1] >= 72000 else 24000
         getattr(self.SRP_node, PRONE_METHODS[self.Prone_method])(mix_np, window=win)

@@ -19,7 +19,10 @@ a-Q) with the same method names used by the search (``reset``,
   arrays that change from mixture to mixture, where the host build costs more than a batched search.  The
   integer tables are equal and the float tables bit-identical to the host build (same float64 expression
   order, no fma); ``clusters`` is then a lazy sequence over the CSR member arrays and ``Pos_5`` / ``Pos_1``
-  are generated from the point index.  ``"device"`` without a GPU raises ``RuntimeError``.
+  are generated from the point index.  ``"device"`` without a GPU raises ``RuntimeError``;
+* ``lattice_width=`` also builds the coarse TDoA lattice of the 1 cm lookup grid (``dense_grid.coarse_lattice``, the
+  stage-1 list of ``Prone_method="DENSE"``) in the node's geometry mode: numpy on the host, ``geom_lattice`` on
+  the planes tensor the device build made.
 """
 import threading
 
@@ -158,10 +161,13 @@ def _offsets_within(offsets, center, width):
 
 class SRPPhat(object):
     def __init__(self, mic_pos, freq_bins, Range_spk, C=343, FS=16000, n_fft=1024, grid_size=0.06,
-                 grid_size_z=0.1, sample_resolution=4, threshold=0.03, WIDTH=8, device=None, geometry="host"):
+                 grid_size_z=0.1, sample_resolution=4, threshold=0.03, WIDTH=8, device=None, geometry="host",
+                 lattice_width=None):
         if geometry not in ("host", "device"):
             raise ValueError(f'geometry must be "host" or "device", got {geometry!r}')
         self.geometry = geometry
+        self.lattice_width = lattice_width
+        self.lattice = None
         self.device = device
         self.C, self.FS, self.n_fft = C, FS, n_fft
         self.freq_bins = np.asarray(freq_bins)
@@ -187,6 +193,8 @@ class SRPPhat(object):
             self._build_on_device()
         else:
             self._build_on_host()
+            if lattice_width is not None:
+                self.lattice = self.coarse_lattice(lattice_width)
         self.tops_coef = 2 * np.pi * FS / (n_fft * C)
         self.tops_max_bin = None
         ii, jj = np.triu_indices(self.num_mic, k=1)          # row-major upper triangle == mask_triu order
@@ -242,9 +250,11 @@ class SRPPhat(object):
         zz = np.arange(r[4], r[5], 0.1)
         zz_d = up(zz)
         lookup = {}
+        axes_1 = None
         for step in (0.05, 0.01):
             xx, yy = np.arange(r[0], r[1], step), np.arange(r[2], r[3], step)
-            lookup[step] = (xx, yy, ops.geom_lookup_planes(up(yy), up(xx), zz_d, mics, C, FS))
+            axes_1 = (up(xx), up(yy), zz_d)
+            lookup[step] = (xx, yy, ops.geom_lookup_planes(axes_1[1], axes_1[0], zz_d, mics, C, FS))
         xs, ys, zs = up(self.x_grids), up(self.y_grids), up(self.z_grids)
         centre = [float(v) for v in self.mic_center]
         q, valid, dis = ops.geom_voxel_map(xs, ys, zs, mics, [float(v) for v in self.array_border], centre, C, FS,
@@ -274,6 +284,29 @@ class SRPPhat(object):
         self.SRP_times = G
         self._geom_dev = {"dev": dev, "tau": tau, "delta": delta}
         self.build_times = {"kernels_s": t1 - t0, "d2h_s": t2 - t1, "host_s": time.perf_counter() - t2}
+        if self.lattice_width is not None:
+            # the lattice is made of the 1 cm planes: they stay on the device (P x points x 8 bytes) for as long as the
+            # node lives, so another width costs no upload either
+            t3 = time.perf_counter()
+            self._geom_dev.update(planes_1=p1, axes_1=axes_1)
+            self.lattice = self.coarse_lattice(self.lattice_width)
+            self.build_times["lattice_s"] = time.perf_counter() - t3
+
+    def coarse_lattice(self, width):
+        """``dense_grid.coarse_lattice`` of this node in its geometry mode.  A host-built node evaluates the numpy
+        statement; a device-built one runs ``torch.ops.asw.geom_lattice`` on the planes tensor its build left on the
+        GPU (a node made with ``lattice_width=``) and copies only cells, bounds, members and centres to the host."""
+        from .dense_grid import Lattice, coarse_lattice
+        if self.geometry != "device":
+            return coarse_lattice(self, width)
+        from . import native
+        g = self._geom_dev
+        if g is None or g.get("planes_1") is None:
+            raise RuntimeError("a device-built node keeps its 1 cm planes on the GPU only when made with lattice_width=")
+        xs, ys, zs = g["axes_1"]
+        out = native.torch_ops().geom_lattice(g["planes_1"], xs, ys, zs, [float(v) for v in self.array_border], float(width))
+        cells, bounds, members, centres = (t.cpu().numpy() for t in out)
+        return Lattice(cells, bounds, members, centres, width)
 
     def _lookup_grid(self, step):
         r = self.Range_spk
@@ -324,6 +357,8 @@ class SRPPhat(object):
         graph = coo_matrix((np.ones(len(rows), dtype=np.int8), (rows, cols)), shape=(n, n))
         _, lab = connected_components(graph, directed=False)
         vid = np.flatnonzero(flat_valid)
+        if vid.shape[0] == 0:                                # the device build's message for G == 0
+            raise RuntimeError("the keep-out region covers the whole speaker range: no valid voxel")
         vlab = lab[vid]
         _, first = np.unique(vlab, return_index=True)        # first voxel (scan order) of each label
         order = np.argsort(first)

@@ -592,7 +592,20 @@ int asw_tops_map(const double* evecs, const double* magsum, int n_windows, int n
  * int32 [V]: valid voxels ascending and their cluster; members int32 [V] with bounds int32 [G+1]: CSR member
  * lists, ascending voxel index within a cluster; offsets int32 [G][P]; centres [G][3]: sequential sum of the
  * member positions in that order / count; tau [G][M] = sqrt((dx^2 + dy^2) + z^2) / C (mic z ignored);
- * delta [G][M] = |c - centre| - |(c - centre) - (m - centre)|. */
+ * delta [G][M] = |c - centre| - |(c - centre) - (m - centre)|.
+ *
+ * asw_geom_lattice_workspace_bytes: size of asw_geom_lattice's workspace for a lookup grid of n_points points and P
+ * pairs (negative: asw_status).
+ *
+ * asw_geom_lattice: the coarse TDoA lattice of a lookup grid (dense_grid.coarse_lattice).  planes [P][ny][nx][nz] as
+ * asw_geom_lookup_planes writes them, point i = (iy*nx + ix)*nz + iz.  Points inside the keep-out rectangle border
+ * (HOST, 4 doubles, open interval) are left out; the cell of a kept point on pair p is rint(planes[p][i] / width)
+ * (round half to even) and a cube is a distinct cell vector.  cells int32 [N][P]: the cubes in lexicographic order
+ * (pair 0 most significant, signed); members int32 [K] with bounds int32 [N+1]: CSR member lists, ascending point
+ * index within a cube; centres [N][3]: sequential sum of the member positions in that order / count.  Every output
+ * is allocated for the grid size n = ny*nx*nz by the caller (bounds: n + 1); counts (HOST, 2 ints) receives N cubes
+ * and K kept points (synchronises the stream).  N = 0 (every point inside the keep-out) is a valid result: bounds[0]
+ * = 0 and nothing else is written.  No atomics, stable radix passes: two builds are bit-identical. */
 int asw_geom_lookup_planes(const double* ys, int ny, const double* xs, int nx, const double* zs, int nz,
                            const double* mics, int M, double C, double FS, double* planes, void* stream);
 int asw_geom_voxel_map(const double* xs, int Lx, const double* ys, int Ly, const double* zs, int Lz,
@@ -607,6 +620,11 @@ int asw_geom_compact(const int32_t* labels, const int32_t* q, const double* xs, 
                      void* workspace, int64_t workspace_bytes, int32_t* power_index, int32_t* valid_flat,
                      int32_t* valid_cid, int32_t* members, int32_t* bounds, int32_t* offsets, double* centres,
                      double* tau, double* delta, int* counts, void* stream);
+int64_t asw_geom_lattice_workspace_bytes(int n_points, int P);
+int asw_geom_lattice(const double* planes, int P, int ny, int nx, int nz, const double* xs, const double* ys,
+                     const double* zs, const double* border, double width, void* workspace,
+                     int64_t workspace_bytes, int32_t* cells, int32_t* bounds, int32_t* members, double* centres,
+                     int* counts, void* stream);
 
 #ifdef __cplusplus
 }
