@@ -252,6 +252,7 @@ def mixture_view(mic_array):
     v._side_stream = None
     v._seg_cache, v._dev_cache = {}, {}
     v.trace = {"coarse_kept": [], "fine_clusters": {}, "final_clusters": []}
+    v.lattice_nms = None
     return v
 
 

@@ -8,6 +8,7 @@
 //   label           26-connected components of equal quantised vectors, label = smallest C-order voxel index
 //   compact         POWER_INDEX, cluster offsets, CSR member list, cluster centres, tau and tops_delta
 //   lattice         the coarse TDoA lattice of the 1 cm lookup grid (dense_grid.coarse_lattice): stage 1 without a pruner
+//   lattice_nms     local maxima of scores over that lattice (dense_grid.lattice_local_maxima): Prone_method="DENSE_NMS"
 //
 // Exactness.  Every value is computed in double with the expression order of the numpy statements it
 // replaces -- norm = sqrt((dx*dx + dy*dy) + dz*dz), "/ C * FS" as two operations, centres as a sequential sum in
@@ -571,6 +572,170 @@ extern "C" int asw_geom_lattice(const double* planes, int P, int ny, int nx, int
   counts[0] = N;
   hipLaunchKernelGGL(lattice_centres_kernel, dim3(asw::cdiv(N, kBlock)), dim3(kBlock), 0, s, members, bounds, N, xs, ys, zs, nx, nz,
                      centres);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+// ---- non-maximum suppression over the lattice (dense_grid.lattice_local_maxima) ----------------------------------
+// Cube j is near cube i when every pair's cells differ by at most `radius`; best[i] is the near cube with the largest
+// score (lowest index among equals), degree[i] the number of near cubes other than i.  An all-pairs test: one thread
+// owns cube i (cells and running champion in registers), the cubes j pass by in LDS tiles, and the j range is split
+// over gridDim.y so that a few thousand cubes still fill the device.  Integer compares and exact float64 compares
+// only, no atomics: a split leaves a partial champion and a partial degree per cube in the workspace (every slot is
+// written, so what the workspace held before does not matter) and a second kernel combines them in split order.
+namespace {
+
+constexpr int kNmsTile = 256;                // cubes j per LDS tile, and cubes i per block (one per thread)
+constexpr int kNmsStride = kNmsTile + 1;     // row stride of the transposed tile: the staging writes spread over the banks
+constexpr int kNmsMaxSplits = 32;
+constexpr int kNmsMaxCubes = kMaxVoxels;     // int32 indices and int arithmetic on them with room to spare
+// LDS per block: cells [PB][kNmsStride] int32 + scores [kNmsTile] float64 + the j range.  For P = 31 (PB = 31) that is
+// 31 * 257 * 4 + 256 * 8 + 8 = 33 924 bytes of the CU's 160 KiB: four blocks per CU.
+
+// splits of the j range: enough blocks for 256 CUs several times over, never less than one tile of j per split
+int nms_splits(int N) {
+  const int rows = asw::cdiv(N, kNmsTile);
+  const int want = asw::cdiv(1024, rows > 0 ? rows : 1);
+  const int s = want < rows ? want : rows;
+  return s < 1 ? 1 : (s > kNmsMaxSplits ? kNmsMaxSplits : s);
+}
+
+// |a - b| of two int32 without overflow
+__device__ __forceinline__ uint32_t cell_distance(int32_t a, int32_t b) {
+  return a >= b ? (uint32_t)a - (uint32_t)b : (uint32_t)b - (uint32_t)a;
+}
+
+// block (x, y): cubes i = x * kNmsTile + thread against split y of the cubes j that can be near them.  The table is
+// sorted with pair 0 most significant, so the cubes whose pair-0 cell lies within `radius` of the block's are one
+// contiguous range [jlo, jhi), found by bisection in column 0; split y takes its share of that range in whole tiles.
+// PB >= P is the compile-time bound that keeps the cube's own cells in registers.
+template <int PB>
+__global__ __launch_bounds__(kNmsTile) void lattice_nms_kernel(const int32_t* __restrict__ cells, int N, int P,
+                                                               const double* __restrict__ scores, uint32_t radius,
+                                                               int32_t* __restrict__ part_best, int32_t* __restrict__ part_degree) {
+  __shared__ int32_t s_cells[PB * kNmsStride];
+  __shared__ double s_scores[kNmsTile];
+  __shared__ int s_range[2];
+  const int t = threadIdx.x;
+  const int i0 = blockIdx.x * kNmsTile;
+  const int i = i0 + t;
+  if (t == 0) {
+    const int i_last = (i0 + kNmsTile < N ? i0 + kNmsTile : N) - 1;
+    const long lo_v = (long)cells[(long)i0 * P] - (long)radius, hi_v = (long)cells[(long)i_last * P] + (long)radius;
+    int a = 0, b = N;                                        // first j with cells[j][0] >= lo_v
+    while (a < b) {
+      const int m = a + (b - a) / 2;
+      if ((long)cells[(long)m * P] < lo_v) a = m + 1; else b = m;
+    }
+    s_range[0] = a;
+    b = N;                                                   // first j with cells[j][0] > hi_v
+    while (a < b) {
+      const int m = a + (b - a) / 2;
+      if ((long)cells[(long)m * P] <= hi_v) a = m + 1; else b = m;
+    }
+    s_range[1] = a;
+  }
+  __syncthreads();
+  const int jlo = s_range[0], jhi = s_range[1];
+  const int tiles = (jhi - jlo + kNmsTile - 1) / kNmsTile, ny = (int)gridDim.y;
+  const int per = (tiles + ny - 1) / ny * kNmsTile;                  // j per split, whole tiles
+  const long jb_l = (long)jlo + (long)blockIdx.y * per;
+  const int jbeg = jb_l < jhi ? (int)jb_l : jhi;
+  const int jend = jhi - jbeg < per ? jhi : jbeg + per;
+
+  int32_t mine[PB];
+#pragma unroll
+  for (int p = 0; p < PB; ++p) mine[p] = (i < N && p < P) ? cells[(long)i * P + p] : 0;
+  int best = -1, deg = 0;
+  double best_sc = 0.0;
+  for (int jb = jbeg; jb < jend; jb += kNmsTile) {
+    const int cnt = jend - jb < kNmsTile ? jend - jb : kNmsTile;      // rows past the range are neither read nor counted
+    __syncthreads();                                                  // the previous tile has been consumed
+    for (int e = t; e < cnt * P; e += kNmsTile) {                     // coalesced read of cnt rows, transposed into LDS
+      const int row = e / P, p = e - row * P;
+      s_cells[p * kNmsStride + row] = cells[(long)jb * P + e];
+    }
+    if (t < cnt) s_scores[t] = scores[jb + t];
+    __syncthreads();
+    for (int jj = 0; jj < cnt; ++jj) {                                // every lane reads the same j: LDS broadcasts
+      bool near = true;
+#pragma unroll
+      for (int p = 0; p < PB; ++p)
+        if (p < P) near &= cell_distance(mine[p], s_cells[p * kNmsStride + jj]) <= radius;
+      const int j = jb + jj;
+      const double sc = s_scores[jj];
+      deg += (near && j != i) ? 1 : 0;
+      if (near && (best < 0 || sc > best_sc)) {                       // j ascends: an equal score keeps the lower index
+        best = j;
+        best_sc = sc;
+      }
+    }
+  }
+  if (i < N) {
+    part_best[(long)blockIdx.y * N + i] = best;                       // -1: no near cube in this split
+    part_degree[(long)blockIdx.y * N + i] = deg;
+  }
+}
+
+// thread = one cube: the partial champions in split order (largest score, lowest index among equals), degrees summed
+__global__ __launch_bounds__(kBlock) void lattice_nms_combine_kernel(const int32_t* __restrict__ part_best,
+                                                                     const int32_t* __restrict__ part_degree,
+                                                                     const double* __restrict__ scores, int N, int splits,
+                                                                     int32_t* __restrict__ best, int32_t* __restrict__ degree) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  int b = -1, d = 0;
+  double bs = 0.0;
+  for (int s = 0; s < splits; ++s) {
+    const int j = part_best[(long)s * N + i];
+    d += part_degree[(long)s * N + i];
+    if (j < 0) continue;
+    const double sc = scores[j];
+    if (b < 0 || sc > bs || (sc == bs && j < b)) {
+      b = j;
+      bs = sc;
+    }
+  }
+  best[i] = b < 0 ? i : b;                   // a cube is near itself; b < 0 only on a table that breaks the sort order
+  degree[i] = d;
+}
+
+}  // namespace
+
+extern "C" int64_t asw_lattice_nms_workspace_bytes(int N, int P) {
+  if (N < 0 || N > kNmsMaxCubes || P < 1 || P > 31) {
+    asw::set_error(ASW_ERR_ARG, "lattice_nms_workspace_bytes: %d cubes, %d pairs (need 0 <= cubes <= %d, 1 <= pairs <= 31)", N, P,
+                   kNmsMaxCubes);
+    return ASW_ERR_ARG;
+  }
+  return (int64_t)(2 * align256((size_t)nms_splits(N) * (size_t)N * sizeof(int32_t)));
+}
+
+extern "C" int asw_lattice_nms(const int32_t* cells, int N, int P, const double* scores, int radius, void* workspace,
+                               int64_t workspace_bytes, int32_t* best, int32_t* degree, void* stream) {
+  ASW_CHECK_ARG(N >= 0 && N <= kNmsMaxCubes, "lattice_nms: N = %d outside 0..%d", N, kNmsMaxCubes);
+  ASW_CHECK_ARG(P >= 1 && P <= 31, "lattice_nms: P = %d outside 1..31", P);
+  ASW_CHECK_ARG(radius >= 1, "lattice_nms: radius = %d, must be at least 1", radius);
+  if (N == 0) return ASW_OK;
+  ASW_CHECK_ARG(cells && scores && workspace, "lattice_nms: null pointer");
+  ASW_CHECK_ARG(best && degree, "lattice_nms: null output pointer");
+  const int splits = nms_splits(N);
+  const size_t slot = align256((size_t)splits * (size_t)N * sizeof(int32_t));
+  ASW_CHECK_ARG(workspace_bytes >= (int64_t)(2 * slot),
+                "lattice_nms: workspace of %lld bytes is too small (asw_lattice_nms_workspace_bytes)", (long long)workspace_bytes);
+  hipStream_t s = asw::as_stream(stream);
+  int32_t* part_best = static_cast<int32_t*>(workspace);
+  int32_t* part_degree = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + slot);
+  const dim3 grid(asw::cdiv(N, kNmsTile), splits);
+  if (P <= 8)
+    hipLaunchKernelGGL(lattice_nms_kernel<8>, grid, dim3(kNmsTile), 0, s, cells, N, P, scores, (uint32_t)radius, part_best, part_degree);
+  else if (P <= 16)
+    hipLaunchKernelGGL(lattice_nms_kernel<16>, grid, dim3(kNmsTile), 0, s, cells, N, P, scores, (uint32_t)radius, part_best, part_degree);
+  else
+    hipLaunchKernelGGL(lattice_nms_kernel<31>, grid, dim3(kNmsTile), 0, s, cells, N, P, scores, (uint32_t)radius, part_best, part_degree);
+  ASW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lattice_nms_combine_kernel, dim3(asw::cdiv(N, kBlock)), dim3(kBlock), 0, s, part_best, part_degree, scores, N,
+                     splits, best, degree);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

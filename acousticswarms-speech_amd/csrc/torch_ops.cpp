@@ -461,6 +461,27 @@ std::vector<Tensor> geom_lattice(const Tensor& planes, const Tensor& xs, const T
   return {cells.narrow(0, 0, N), bounds.narrow(0, 0, N + 1), members.narrow(0, 0, K), centres.narrow(0, 0, N)};
 }
 
+// -> best [N] int32, degree [N] int32: non-maximum suppression over a lattice (dense_grid.lattice_local_maxima).  cells [N,P]
+// is the table geom_lattice returned, read where it is; column 0 must be non-decreasing (the caller checks it).
+std::vector<Tensor> lattice_nms(const Tensor& cells, const Tensor& scores, int64_t radius) {
+  need(cells, "cells", at::kInt, 2);
+  need(scores, "scores", at::kDouble, 1);
+  same_device(cells, scores, "cells and scores");
+  const int N = checked_int(cells.size(0), "N"), P = checked_int(cells.size(1), "P");
+  TORCH_CHECK(P >= 1 && P <= 31, "cells must hold 1..31 pairs");
+  TORCH_CHECK(scores.size(0) == N, "scores must be [N] = [", N, "], got [", scores.size(0), "]");
+  TORCH_CHECK(radius >= 1, "radius must be at least 1");
+  const int64_t ws_bytes = asw_lattice_nms_workspace_bytes(N, P);
+  TORCH_CHECK(ws_bytes >= 0, "libasw_hip: asw_lattice_nms_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({ws_bytes}, cells.options().dtype(at::kByte));
+  Tensor best = at::empty({N}, cells.options()), degree = at::empty({N}, cells.options());
+  Launch l(cells);
+  check_status(asw_lattice_nms(cells.data_ptr<int32_t>(), N, P, scores.data_ptr<double>(), checked_int(radius, "radius"),
+                               ws.data_ptr(), ws_bytes, best.data_ptr<int32_t>(), degree.data_ptr<int32_t>(), l.stream),
+               "asw_lattice_nms");
+  return {best, degree};
+}
+
 // ---- joint separation network ---------------------------------------------------------------------
 Tensor sep_infer(int64_t model, const Tensor& mix, const Tensor& offsets) {
   TORCH_CHECK(model != 0, "sep_infer: null model handle");
@@ -555,6 +576,7 @@ TORCH_LIBRARY(asw, m) {
   m.def("geom_label(Tensor q, Tensor valid, int Lx, int Ly, int Lz) -> (Tensor, int)");
   m.def("geom_compact(Tensor labels, Tensor q, Tensor xs, Tensor ys, Tensor zs, Tensor mics, float[] centre, float C) -> Tensor[]");
   m.def("geom_lattice(Tensor planes, Tensor xs, Tensor ys, Tensor zs, float[] border, float width) -> Tensor[]");
+  m.def("lattice_nms(Tensor cells, Tensor scores, int radius) -> Tensor[]");
   m.def("sep_infer(int model, Tensor mix, Tensor offsets) -> Tensor");
   m.def("sep_forward(int model, Tensor mix, int n_speakers, int n_mics, int max_speakers) -> Tensor");
   m.def("sep_forward_counts(int model, Tensor mix, int[] counts, int n_mics, int max_speakers) -> Tensor");
@@ -579,6 +601,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("geom_label", &geom_label);
   m.impl("geom_compact", &geom_compact);
   m.impl("geom_lattice", &geom_lattice);
+  m.impl("lattice_nms", &lattice_nms);
   m.impl("sep_infer", &sep_infer);
   m.impl("sep_forward", &sep_forward);
   m.impl("sep_forward_counts", &sep_forward_counts);

@@ -130,3 +130,54 @@ def lattice_patches(node, lattice):
     offsets = cells.astype(np.float64) * width
     return [Patch(offsets[g].copy(), np.full(P, width), pos[bounds[g]:bounds[g + 1]].T, centres[g].copy())
             for g in range(cells.shape[0])]
+
+
+# ---- non-maximum suppression over the lattice (Prone_method="DENSE_NMS") ---------------------------------------
+def lattice_local_maxima(cells, scores, radius=1, chunk=1 << 22):
+    """(best int32 [N], degree int32 [N]) of the cubes ``cells`` int32 [N,P] (as ``coarse_lattice`` /
+    ``dense_tdoa_candidates`` return them) under ``scores`` float64 [N], all finite.
+
+    Cube j is near cube i when max_p |cells[i,p] - cells[j,p]| <= ``radius`` (Chebyshev distance in cell space; i is
+    near itself).  ``degree[i]`` counts the near cubes other than i; ``best[i]`` is the near cube with the largest
+    score, the lowest index among equals (-0.0 equals 0.0).  Cube i is a local maximum when ``best[i] == i``.
+    csrc/geometry_kernels.hip (``asw_lattice_nms``) computes the same two arrays on the GPU, exactly; this is their
+    statement.  Rows are taken ``chunk // N`` at a time, so the [rows, N] temporaries stay bounded."""
+    cells = np.asarray(cells)
+    scores = np.asarray(scores, dtype=np.float64)
+    if cells.ndim != 2 or scores.shape != (cells.shape[0],):
+        raise ValueError(f"cells must be [N, P] and scores [N], got {cells.shape} and {scores.shape}")
+    if int(radius) != radius or radius < 1:
+        raise ValueError(f"radius must be a whole number >= 1, got {radius!r}")
+    if not np.all(np.isfinite(scores)):
+        raise ValueError("every score must be finite")
+    N, P = cells.shape
+    best, degree = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+    wide = cells.astype(np.int64)                            # differences of int32 cells cannot overflow
+    rows = max(1, int(chunk) // max(N, 1))
+    for lo in range(0, N, rows):
+        hi = min(N, lo + rows)
+        near = np.ones((hi - lo, N), dtype=bool)
+        for p in range(P):                                   # one pair at a time
+            near &= np.abs(wide[lo:hi, p, None] - wide[None, :, p]) <= radius
+        degree[lo:hi] = near.sum(axis=1) - 1
+        best[lo:hi] = np.argmax(np.where(near, scores[None, :], -np.inf), axis=1)     # first of the largest
+    return best, degree
+
+
+def lattice_local_maxima_device(cells_dev, scores, radius=1):
+    """``lattice_local_maxima`` by ``torch.ops.asw.lattice_nms`` on a cells tensor that lives on the GPU: only the N
+    scores go up, ``best`` and ``degree`` come back.  Refuses what the statement refuses, and a table whose column 0
+    decreases somewhere -- the kernel finds the cubes near a block of rows by bisection in that column."""
+    import torch
+    from . import native
+    scores = np.ascontiguousarray(scores, dtype=np.float64)
+    if cells_dev.dim() != 2 or scores.shape != (int(cells_dev.shape[0]),):
+        raise ValueError(f"cells must be [N, P] and scores [N], got {tuple(cells_dev.shape)} and {scores.shape}")
+    if int(radius) != radius or radius < 1:
+        raise ValueError(f"radius must be a whole number >= 1, got {radius!r}")
+    if not np.all(np.isfinite(scores)):
+        raise ValueError("every score must be finite")
+    if cells_dev.shape[0] > 1 and not bool((cells_dev[1:, 0] >= cells_dev[:-1, 0]).all()):
+        raise ValueError("column 0 of cells must be non-decreasing (the lattice is sorted with pair 0 most significant)")
+    best, degree = native.torch_ops().lattice_nms(cells_dev, torch.from_numpy(scores).to(cells_dev.device), int(radius))
+    return best.cpu().numpy(), degree.cpu().numpy()

@@ -10,6 +10,7 @@ import numpy as np
 from .dense_grid import lattice_patches
 from .hostdsp import max_avg_power, si_sdr, split_wav, split_wise_sisdr
 from .patch import FS, SPEED_OF_SOUND, Patch, pair_offsets
+from . import search
 from .search import (INIT_WIDTH, SPOT_POWER_THRESHOLD2, USE_RELATIVE_SPOT_POWER, binary_search_baseline,
                      search_area)
 from .srp import SRPPhat
@@ -21,8 +22,11 @@ BIN0, BIN1, N_FFT = 2, 200, 2048
 FREQ_BINS = np.arange(BIN0, BIN1)
 
 # pruning map of stage 1 per Prone_method (sep/Mic_Array.py:165-170).  "DENSE" has none: stage 1 is then the whole
-# coarse TDoA lattice of the array (dense_grid.coarse_lattice), built once with the geometry
-PRONE_METHODS = {"SRP": "SRP_Map_WINDOW_new", "MUSIC": "MUSIC_Map_WINDOW", "TOPS": "TOPS_Map_WINDOW", "DENSE": None}
+# coarse TDoA lattice of the array (dense_grid.coarse_lattice), built once with the geometry.  "DENSE_NMS" is "DENSE"
+# with a coarse stage that keeps only the lattice's local maxima (dense_grid.lattice_local_maxima)
+PRONE_METHODS = {"SRP": "SRP_Map_WINDOW_new", "MUSIC": "MUSIC_Map_WINDOW", "TOPS": "TOPS_Map_WINDOW", "DENSE": None,
+                 "DENSE_NMS": None}
+LATTICE_METHODS = ("DENSE", "DENSE_NMS")
 
 
 def check_sisnr_win(sisnr_list, SISNR_THRESHOLD=-2, SISNR_THRESHOLD2=-7):
@@ -78,7 +82,9 @@ class MicArray(object):
         """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
         (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture).
         ``Prone_method="DENSE"`` takes the pruner out: ``Apply_SRP_PHAT`` returns every width-``INIT_WIDTH`` cube of
-        the array's TDoA lattice, and the later stages run on that list unchanged."""
+        the array's TDoA lattice, and the later stages run on that list unchanged.  ``"DENSE_NMS"`` has the same
+        stage 1; its coarse stage keeps a cube only if no cube within ``search.LATTICE_NMS_RADIUS`` cells on every
+        pair scored higher, and ``lattice_nms`` = {"radius", "best", "degree"} records the latest search."""
         if Prone_method not in PRONE_METHODS:
             # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
             raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
@@ -94,8 +100,8 @@ class MicArray(object):
             / SPEED_OF_SOUND * FS
         self.SRP_node = SRPPhat(mic_pos=mic_positions, freq_bins=FREQ_BINS, Range_spk=Spk_Range, grid_size=grid_size,
                                 FS=FS, n_fft=N_FFT, threshold=[0.15, 0.015, 0.05], WIDTH=INIT_WIDTH, device=device,
-                                geometry=geometry, lattice_width=INIT_WIDTH if Prone_method == "DENSE" else None)
-        if Prone_method == "DENSE" and self.SRP_node.lattice.n_cubes == 0:
+                                geometry=geometry, lattice_width=INIT_WIDTH if Prone_method in LATTICE_METHODS else None)
+        if Prone_method in LATTICE_METHODS and self.SRP_node.lattice.n_cubes == 0:
             raise RuntimeError("the keep-out region covers the whole speaker range: the TDoA lattice is empty")
         self.original_times = 0
         self.spotforming_times = 0
@@ -107,13 +113,14 @@ class MicArray(object):
         # parity tests): coarse kept indices, per coarse patch {head: members} of the fine-stage
         # clustering, and the global clusters as lists of "g_head" names
         self.trace = {"coarse_kept": [], "fine_clusters": {}, "final_clusters": []}
+        self.lattice_nms = None         # DENSE_NMS: radius, best and degree of the latest coarse stage
 
     # ---- stage 1: SRP-PHAT / MUSIC / TOPS pruning (sep/Mic_Array.py:152-194) --------------
     def Apply_SRP_PHAT(self, mix_data):
         self.SRP_node.reset()
         self.spotforming_times = 0
         self.original_times = 0
-        if self.Prone_method == "DENSE":
+        if self.Prone_method in LATTICE_METHODS:
             # no map, so the mixture is not read and no window length is required; fresh Patch objects per call,
             # because check_out mutates them
             return lattice_patches(self.SRP_node, self.SRP_node.lattice), np.zeros((3, 3))
@@ -126,12 +133,20 @@ class MicArray(object):
     # ---- stage 2: coarse Spotforming, relaxed window (sep/Mic_Array.py:196-222) ---------
     def Spotform_Big_Patch(self, mix_data, patch_list, spot_model):
         self.big_spotforming_times = len(patch_list)
-        kept, _powers_with_dis, rel_thr = binary_search_baseline(mix_data, spot_model, patch_list,
-                                                                 self.mic_positions)
+        kept, _powers_with_dis, rel_thr = binary_search_baseline(
+            mix_data, spot_model, patch_list, self.mic_positions,
+            survivors=self._lattice_survivors if self.Prone_method == "DENSE_NMS" else None)
         self.Relative_Threshold = rel_thr
         pos = {id(p): i for i, p in enumerate(patch_list)}
         self.trace = {"coarse_kept": [pos[id(p)] for p in kept], "fine_clusters": {}, "final_clusters": []}
         return kept
+
+    def _lattice_survivors(self, powers_win):
+        """DENSE_NMS: one flag per cube of the lattice, true for its local maxima under the windowed powers."""
+        radius = search.LATTICE_NMS_RADIUS
+        best, degree = self.SRP_node.lattice_local_maxima(powers_win, radius)
+        self.lattice_nms = {"radius": radius, "best": best, "degree": degree}
+        return best == np.arange(best.shape[0])
 
     # ---- stage 3: fine Spotforming, strict window (sep/Mic_Array.py:225-395) ------------
     def _subdivide(self, big):

@@ -251,6 +251,8 @@ SIGNATURES = {
     "asw_geom_lattice_workspace_bytes": (c_int64, [c_int, c_int]),
     "asw_geom_lattice": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                  c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
+    "asw_lattice_nms_workspace_bytes": (c_int64, [c_int, c_int]),
+    "asw_lattice_nms": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@ SPOT_POWER_THRESHOLD1 = 0.008
 SPOT_POWER_THRESHOLD2 = 0.01
 SI_SNR_POWER_THRESHOLD = 4e-3
 INIT_WIDTH = 8
+LATTICE_NMS_RADIUS = 1      # cells; the neighbourhood of Prone_method="DENSE_NMS" (dense_grid.lattice_local_maxima), read per call
 
 
 def _halve(patch, samples, dim):
@@ -158,12 +159,15 @@ def stage_energies(spot_model, mix_data, patch_list, strict):
     return np.array(p), np.array(pw)
 
 
-def binary_search_baseline(mix_data, spot_model, patch_list, mic_positions):
+def binary_search_baseline(mix_data, spot_model, patch_list, mic_positions, survivors=None):
     """Coarse stage scoring (local_utils_3d.py:339-388): run the spot model with the relaxed
     window on every SRP patch, weight the windowed RMS by (1 + distance to mic 0), keep
     those above SPOT_POWER_THRESHOLD1 in descending windowed-RMS order, at most
-    MAX_BIG_PATCH.  Returns (kept patches, powers_with_dis, relative_threshold*1.2)."""
+    MAX_BIG_PATCH.  Returns (kept patches, powers_with_dis, relative_threshold*1.2).
+    ``survivors`` (not in the reference): a function of the windowed powers returning one flag per patch; a patch
+    whose flag is false is passed over after the threshold test and does not count towards the cap."""
     _, powers_win = stage_energies(spot_model, mix_data, patch_list, 0)
+    alive = None if survivors is None else survivors(powers_win)
     with_dis = []
     for i, p in enumerate(patch_list):
         c = p.center_pos()
@@ -177,6 +181,8 @@ def binary_search_baseline(mix_data, spot_model, patch_list, mic_positions):
     kept = []
     for i in order:
         if with_dis[i] < thr:
+            continue
+        if alive is not None and not alive[i]:
             continue
         if len(kept) >= MAX_BIG_PATCH:
             print("warning too many patch remaining, only keep the best 30")

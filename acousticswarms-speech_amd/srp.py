@@ -22,7 +22,8 @@ a-Q) with the same method names used by the search (``reset``,
   are generated from the point index.  ``"device"`` without a GPU raises ``RuntimeError``;
 * ``lattice_width=`` also builds the coarse TDoA lattice of the 1 cm lookup grid (``dense_grid.coarse_lattice``, the
   stage-1 list of ``Prone_method="DENSE"``) in the node's geometry mode: numpy on the host, ``geom_lattice`` on
-  the planes tensor the device build made.
+  the planes tensor the device build made.  ``lattice_local_maxima`` (``Prone_method="DENSE_NMS"``) then runs on it: the
+  numpy statement on the host, ``lattice_nms`` on the cells tensor a device build keeps on the GPU.
 """
 import threading
 
@@ -306,7 +307,25 @@ class SRPPhat(object):
         xs, ys, zs = g["axes_1"]
         out = native.torch_ops().geom_lattice(g["planes_1"], xs, ys, zs, [float(v) for v in self.array_border], float(width))
         cells, bounds, members, centres = (t.cpu().numpy() for t in out)
+        if width == self.lattice_width:
+            # the node's own lattice: its cells stay on the device for lattice_local_maxima (N x P x 4 bytes of their
+            # own -- the op's result is a slice of a table sized for every lookup point)
+            g["cells"] = out[0].clone()
         return Lattice(cells, bounds, members, centres, width)
+
+    def lattice_local_maxima(self, scores, radius=1):
+        """``dense_grid.lattice_local_maxima`` of this node's lattice (a node made with ``lattice_width=``) under
+        ``scores`` [n_cubes], in the node's geometry mode: the numpy statement on a host-built node,
+        ``torch.ops.asw.lattice_nms`` on the cells tensor the lattice build left on the GPU on a device-built one --
+        the scores go up, (best, degree) come back, same values."""
+        from .dense_grid import lattice_local_maxima, lattice_local_maxima_device
+        if self.lattice is None:
+            raise RuntimeError("this node has no lattice: make it with lattice_width=")
+        if np.shape(scores) != (self.lattice.n_cubes,):
+            raise ValueError(f"scores must hold one value per cube ({self.lattice.n_cubes}), got shape {np.shape(scores)}")
+        if self.geometry != "device":
+            return lattice_local_maxima(self.lattice.cells, scores, radius)
+        return lattice_local_maxima_device(self._geom_dev["cells"], scores, radius)
 
     def _lookup_grid(self, step):
         r = self.Range_spk

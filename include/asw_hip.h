@@ -605,7 +605,22 @@ int asw_tops_map(const double* evecs, const double* magsum, int n_windows, int n
  * index within a cube; centres [N][3]: sequential sum of the member positions in that order / count.  Every output
  * is allocated for the grid size n = ny*nx*nz by the caller (bounds: n + 1); counts (HOST, 2 ints) receives N cubes
  * and K kept points (synchronises the stream).  N = 0 (every point inside the keep-out) is a valid result: bounds[0]
- * = 0 and nothing else is written.  No atomics, stable radix passes: two builds are bit-identical. */
+ * = 0 and nothing else is written.  No atomics, stable radix passes: two builds are bit-identical.
+ *
+ * asw_lattice_nms_workspace_bytes: size of asw_lattice_nms's workspace for N cubes of P pairs, 0 <= N <= 2^24
+ * (negative: asw_status; 0 for N = 0).
+ *
+ * asw_lattice_nms: non-maximum suppression over a lattice (dense_grid.lattice_local_maxima).  cells int32 [N][P] as
+ * asw_geom_lattice writes them, scores float64 [N], both on the device; 1 <= P <= 31, radius >= 1.  Cube j is near
+ * cube i when |cells[i][p] - cells[j][p]| <= radius on every pair (the differences are formed without overflow: any
+ * int32 cells, any radius); a cube is near itself.  degree[i] = near cubes other than i; best[i] = the near cube with
+ * the largest score, the lowest index among equal scores (-0.0 equals 0.0); i is a local maximum when best[i] == i.
+ * RELIES ON column 0 of cells being non-decreasing, as in a table sorted with pair 0 most significant: the cubes that
+ * can be near a block of rows are found by bisection in that column.  On a table that breaks the order, or with
+ * non-finite scores, the result is unspecified but every access stays in bounds.  Integer and exact float64 compares,
+ * partial results per split of the j range combined in a fixed order, no atomics: two calls are bit-identical, and
+ * the result does not depend on what the workspace held.  Every refusal (null pointer, N < 0 or > 2^24, P outside
+ * 1..31, radius < 1, short workspace) happens before the first launch; N = 0 succeeds and launches nothing. */
 int asw_geom_lookup_planes(const double* ys, int ny, const double* xs, int nx, const double* zs, int nz,
                            const double* mics, int M, double C, double FS, double* planes, void* stream);
 int asw_geom_voxel_map(const double* xs, int Lx, const double* ys, int Ly, const double* zs, int Lz,
@@ -625,6 +640,9 @@ int asw_geom_lattice(const double* planes, int P, int ny, int nx, int nz, const 
                      const double* zs, const double* border, double width, void* workspace,
                      int64_t workspace_bytes, int32_t* cells, int32_t* bounds, int32_t* members, double* centres,
                      int* counts, void* stream);
+int64_t asw_lattice_nms_workspace_bytes(int N, int P);
+int asw_lattice_nms(const int32_t* cells, int N, int P, const double* scores, int radius, void* workspace,
+                    int64_t workspace_bytes, int32_t* best, int32_t* degree, void* stream);
 
 #ifdef __cplusplus
 }
