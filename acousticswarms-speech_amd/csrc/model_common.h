@@ -173,25 +173,37 @@ inline bool resstack_ok(const std::vector<ResLayer>& res, int prec, int ch, int 
   return true;
 }
 
+// how many layers from layer j on share one resstack launch
+inline size_t resstack_fuse_count(const std::vector<ResLayer>& res, size_t j, int K) {
+  static const bool nofuse = getenv("ASW_RESSTACK_NOFUSE") != nullptr;
+  size_t n = 1;
+  int halo = 0;
+  while (!nofuse && j + n < res.size() && n < 3) {
+    const int pad = res[j + n].dil * (K - 1) / 2;
+    if (halo + pad > 64) break;
+    halo += pad;
+    ++n;
+  }
+  return n;
+}
+
+// Input of a residual stack given as the 8-channel source of the 1x1 convolution in front of it (asw_resstack_args.src_hi):
+// the two fp16 planes, the composed layer-0 weight and the 1x1 weight that rebuilds the residual.
+struct SrcFeed { const void* hi; const void* lo; const WBuf* comp; const WBuf* pre; };
+
 inline int run_res(const std::vector<ResLayer>& res, int prec, int B, int T, int ch, int K, float* x, float* p, float* q,
-            float** final_out, hipStream_t s, const GluSrc* glu = nullptr) {
+            float** final_out, hipStream_t s, const GluSrc* glu = nullptr, const SrcFeed* feed = nullptr) {
   // ping-pong: layer 0 reads x (kept intact), later layers alternate p/q
   const float* in = glu ? glu->raw : x;
   float* outb = p;
+  if (feed && !(resstack_ok(res, prec, ch, K) && prec == 1 && resstack_fuse_count(res, 0, K) == 2))
+    return asw::set_error(ASW_ERR_STATE, "run_res: the source-fed form needs the fused f16x3 pair");
   if (resstack_ok(res, prec, ch, K)) {
-    static const bool nofuse = getenv("ASW_RESSTACK_NOFUSE") != nullptr;
     size_t j = 0;
     while (j < res.size()) {
-      size_t n = 1;
-      int halo = 0;
-      while (!nofuse && j + n < res.size() && n < 3) {
-        const int pad = res[j + n].dil * (K - 1) / 2;
-        if (halo + pad > 64) break;
-        halo += pad;
-        ++n;
-      }
+      const size_t n = resstack_fuse_count(res, j, K);
       asw_resstack_args a = {};
-      a.x = (glu && j == 0) ? nullptr : in;
+      a.x = ((glu || feed) && j == 0) ? nullptr : in;
       a.out = outb;
       a.B = B; a.T = T; a.C = ch; a.taps = K; a.n_layers = (int)n; a.precision = prec; a.ln_eps = 1e-5f;
       for (size_t i = 0; i < n; ++i) {
@@ -201,6 +213,11 @@ inline int run_res(const std::vector<ResLayer>& res, int prec, int B, int T, int
       }
       if (glu && j == 0) {
         a.glu_raw = glu->raw; a.glu_mr = glu->mr; a.glu_gamma = glu->gamma; a.glu_beta = glu->beta; a.glu_out = glu->side_out;
+      }
+      if (feed && j == 0) {
+        a.src_hi = feed->hi; a.src_lo = feed->lo;
+        a.layer[0].Wf_hi = feed->comp->fhi; a.layer[0].Wf_lo = feed->comp->flo; a.layer[0].w_shift = feed->comp->shift;
+        a.pre_hi = feed->pre->fhi; a.pre_lo = feed->pre->flo; a.pre_shift = feed->pre->shift;
       }
       int rc = asw_resstack64_f16x3(&a, s);
       if (rc) return rc;
@@ -316,6 +333,7 @@ struct TrunkPlan {
   int B, T, Tp, F, RL;                     // B: sequences in this batch
   std::vector<int> Tl;                     // length at level 0..depth
   float *mean, *stdv, *refn;
+  uint16_t *src_hi = nullptr, *src_lo = nullptr;   // the 8-channel network input as fp16 planes (source-fed block 0)
   std::vector<float*> X, Pb, Qb, raw_dn, raw_up, st_dn, st_up, mr_dn, mr_up;
   float *Y, *D, *ywave;
 };
@@ -328,12 +346,15 @@ struct Trunk {
   int device = 0;                          // HIP device the weights and the workspace live on
   int precision = 0;                       // 0 = exact f32 MFMA, 1 = f16x3 split MFMA, 2 = single-pass f16
   bool fuse_mask = true;                   // f16x3: GroupNorm + GLU on load; bypass + mask encoder + decoder taps in one launch
+  bool want_src = false;                   // the network has a source-fed front end (the spot network's candidate loop)
+  bool src_stack = true;                   // ... and uses it (asw_spot_set_source_stack)
 
   std::vector<int> enc_cin, enc_cout;      // per encoder block
   std::vector<int> dec_cin, dec_cout, dec_stride;   // per decoder block, in execution order
   int stride_product = 1;
 
   DevBuf pre_w, pre_b;
+  WBuf src_wt, src_pre;                    // preproc folded into encoder block 0's first layer: composed weight, [W | b]
   std::vector<EncBlock> enc;
   std::vector<DecBlock> dec;
   WBuf byp_wt, mask_wt, dec_wt;
@@ -442,6 +463,18 @@ struct Trunk {
       UP(enc[i].gn_g, P(p + ".norm1.weight"));
       UP(enc[i].gn_b, P(p + ".norm1.bias"));
     }
+    if (want_src && tc.channels == 64 && tc.n_mics <= 7 && K <= 7 && enc[0].res[0].wt.fhi) {
+      // No non-linearity separates preproc (1x1, n_mics -> 64) from the first residual layer's convolution:
+      // conv(preproc(u)) is a convolution of u~ = (u_0 .. u_6, 1) with Wc_k [W | b], composed here in double.  The
+      // last channel carries the bias, so the rows next to the zero padding come out right without a special case.
+      // No window gate enters encoder block 0's residual layers: one composed weight serves every gate set.
+      std::vector<float> pre16((size_t)64 * 16), comp((size_t)64 * 64);
+      if ((rc = asw_compose_source_weights(P("encoder.module_list.0.res.seq.0.conv.weight").data(), P("preproc.weight").data(),
+                                           P("preproc.bias").data(), tc.n_mics, K, comp.data(), pre16.data())))
+        return rc;
+      if ((rc = src_wt.upload_gemm(comp, 64, 64))) return rc;
+      if ((rc = src_pre.upload_gemm(pre16, 64, 16))) return rc;
+    }
     for (int i = 0; i < tc.depth; ++i) {
       const std::string p = "decoder.module_list." + std::to_string(i);
       if ((rc = pack_res_layers(raw, p, dec_cout[i], K, RL, RD, dec[i].res))) return rc;
@@ -511,6 +544,12 @@ struct Trunk {
     return fuse_mask && precision >= 1 && tc.encoder_channels % 256 == 0 && tc.channels % 32 == 0 &&
            tc.encoder_kernel_size <= 48 && tc.encoder_stride % 4 == 0 && byp_wt48.fhi && dec_wt.fhi && mask_wt.fhi;
   }
+  // the candidate loop feeds encoder block 0 from the network input (f16x3, the fused pair as its first launch)
+  bool src_path() const {
+    return want_src && src_stack && precision == 1 && src_wt.fhi && src_pre.fhi && !enc.empty() &&
+           resstack_ok(enc[0].res, precision, enc_cin[0], tc.kernel_size) &&
+           resstack_fuse_count(enc[0].res, 0, tc.kernel_size) == 2;
+  }
   // the shape of a batch of B sequences of T samples and its level buffers: the head of the workspace
   void layout_levels(int B, int T, Arena& a, TrunkPlan& pl) const {
     const int depth = tc.depth, EK = tc.encoder_kernel_size, ES = tc.encoder_stride;
@@ -523,6 +562,10 @@ struct Trunk {
     pl.mean = a.take<float>(B);
     pl.stdv = a.take<float>(B);
     pl.refn = a.take<float>((size_t)B * pl.RL);
+    if (want_src) {
+      pl.src_hi = a.take<uint16_t>((size_t)B * pl.Tp * 8);
+      pl.src_lo = a.take<uint16_t>((size_t)B * pl.Tp * 8);
+    }
     pl.X.resize(depth + 1); pl.Pb.resize(depth); pl.Qb.resize(depth);
     pl.raw_dn.resize(depth); pl.raw_up.resize(depth); pl.st_dn.resize(depth); pl.st_up.resize(depth);
     pl.mr_up.resize(depth); pl.mr_dn.resize(depth);
@@ -556,19 +599,21 @@ struct Trunk {
     pl.ywave = a.take<float>((size_t)pl.B * pl.T);
   }
 
-  // ---- run; pl.X[0] / pl.refn are filled
+  // ---- run; pl.X[0] (or the source planes) / pl.refn are filled
   // encoder (network.py:98-113,146-156): X[0] -> X[depth]
-  int encode(TrunkPlan& pl, const GatedConvs& g, hipStream_t s) {
+  // src0: pl.src_hi / pl.src_lo are filled instead of pl.X[0] (src_path()); X[0] is neither read nor written
+  int encode(TrunkPlan& pl, const GatedConvs& g, hipStream_t s, bool src0 = false) {
     const int B = pl.B, K = tc.kernel_size;
     taps.clear();
-    taps["preproc"] = {pl.X[0], (size_t)B * pl.Tl[0] * tc.channels};
+    if (!src0) taps["preproc"] = {pl.X[0], (size_t)B * pl.Tl[0] * tc.channels};
     int rc;
     GluSrc src = {};
+    const SrcFeed feed = {pl.src_hi, pl.src_lo, &src_wt, &src_pre};
     bool glu = false;                        // X[i] is still un-normalised in raw_dn[i-1]: block i applies GroupNorm + GLU
     for (int i = 0; i < tc.depth; ++i) {
       float* r = nullptr;
       if ((rc = run_res(enc[i].res, precision, B, pl.Tl[i], enc_cin[i], K, pl.X[i], pl.Pb[i], pl.Qb[i], &r, s,
-                        glu ? &src : nullptr)))
+                        glu ? &src : nullptr, (src0 && i == 0) ? &feed : nullptr)))
         return rc;
       asw_convgemm_args a = {};
       a.A = r; g.down_wt[i].bind(a, precision); a.bias = enc[i].bias.p; a.out = pl.raw_dn[i]; a.stats = pl.st_dn[i];

@@ -9,6 +9,7 @@
 // mixture at shifted addresses and writes only the channels-last [N][T_pad][C]
 // network input plus the normalised reference channel.
 #include "asw_common.h"
+#include "mfma_util.h"
 
 namespace {
 
@@ -147,6 +148,64 @@ __global__ __launch_bounds__(256) void preproc_kernel(const float* __restrict__ 
   }
 }
 
+// The source-fed form of the first residual pair (resstack.hip, SRC) takes the network input itself instead of the
+// preproc output: u~[tp] = (u_0 .. u_{M-1}, 0 .., 1) for every row of [0, T_pad) -- the aligned, quantised, normalised
+// samples (zeros in the left pad) and a last channel that is 1 and carries the preproc bias -- already split into the
+// fp16 hi / lo halves of the f16x3 operands (the conversion of split4t<3>, saturating), 16 bytes per row and plane.
+// grid (row tiles of 256, N): (1) one (row, mic) pair per thread into LDS, exactly as preproc_kernel computes it;
+// (2) one row per thread, a wave writes 1 KiB per plane back to back.  refn as preproc_kernel writes it.
+__global__ __launch_bounds__(256) void src_planes_kernel(const float* __restrict__ srcs, int M, int T, int T_pad,
+                                                         const int32_t* __restrict__ offsets,
+                                                         const int32_t* __restrict__ mix_index, int circular,
+                                                         const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                         asw_mfma::half8* __restrict__ src_hi,
+                                                         asw_mfma::half8* __restrict__ src_lo, float* __restrict__ refn,
+                                                         long refn_stride) {
+  constexpr int ROWS = 256;
+  __shared__ int off[8];
+  __shared__ float vs[ROWS * 7];            // [row][m], M <= 7
+  const int n = blockIdx.y;
+  const float* __restrict__ src = srcs + (mix_index ? (long)mix_index[n] * M * T : 0);
+  if (threadIdx.x < M) {
+    int o = 0;
+    if (threadIdx.x > 0) {
+      o = offsets[(long)n * (M - 1) + threadIdx.x - 1];
+      if (circular) { o %= T; if (o < 0) o += T; }
+    }
+    off[threadIdx.x] = o;
+  }
+  __syncthreads();
+  const int pad = T_pad - T;
+  const float mu = mean[n], sg = stdv[n];
+  const int row0 = blockIdx.x * ROWS;
+  for (int it = threadIdx.x; it < ROWS * M; it += blockDim.x) {
+    const int m = it / ROWS, r = it - m * ROWS;           // consecutive lanes -> consecutive samples
+    const int tp = row0 + r;
+    float x = 0.f;
+    if (tp >= pad && tp < T_pad) {
+      int i = tp - pad + off[m];
+      if (circular) { if (i >= T) i -= T; x = src[(long)m * T + i]; }
+      else x = (i >= 0 && i < T) ? src[(long)m * T + i] : 0.f;
+      x = (quant16(x) - mu) / sg;
+    }
+    vs[r * M + m] = x;
+  }
+  __syncthreads();
+  const int r = threadIdx.x, tp = row0 + r;
+  if (tp >= T_pad) return;
+  float u[8];
+#pragma unroll
+  for (int m = 0; m < 7; ++m) u[m] = m < M ? vs[r * M + m] : 0.f;
+  u[7] = 1.0f;
+  asw_mfma::half4 h0, l0, h1, l1;
+  asw_mfma::split4t<3>(make_float4(u[0], u[1], u[2], u[3]), h0, l0);
+  asw_mfma::split4t<3>(make_float4(u[4], u[5], u[6], u[7]), h1, l1);
+  const long o = (long)n * T_pad + tp;
+  src_hi[o] = asw_mfma::half8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+  src_lo[o] = asw_mfma::half8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+  refn[(long)n * refn_stride + tp] = u[0];
+}
+
 }  // namespace
 
 extern "C" int asw_shift_stats(const float* mix, int M, int T, const int32_t* offsets, int N, int circular,
@@ -190,6 +249,23 @@ extern "C" int asw_shift_norm_preproc_multi(const float* mix, int M, int T, int 
   asw::ProfScope prof(asw::as_stream(stream), "preproc", 0.0, (double)M * T * 4 + (double)N * T_pad * (C + 1) * 4);
   hipLaunchKernelGGL(preproc_kernel<true>, grid, dim3(256), 0, asw::as_stream(stream), mix, M, T, T_pad, offsets, mix_index,
                      circular, mean, std, w, b, C, x0, refn, refn_stride, rows);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+extern "C" int asw_shift_norm_src_multi(const float* mix, int M, int T, int T_pad, const int32_t* offsets,
+                                        const int32_t* mix_index, int N, int circular, const float* mean, const float* std,
+                                        void* src_hi, void* src_lo, float* refn, long refn_stride, void* stream) {
+  ASW_CHECK_ARG(refn_stride >= T_pad, "shift_norm_src: refn_stride < T_pad");
+  ASW_CHECK_ARG(mix && offsets && mean && std && src_hi && src_lo && refn, "shift_norm_src: null pointer");
+  ASW_CHECK_ARG(M >= 1 && M <= 7 && T >= 1 && T_pad >= T, "shift_norm_src: bad shape M=%d T=%d T_pad=%d (M <= 7)", M, T, T_pad);
+  if (N == 0) return ASW_OK;
+  dim3 grid(asw::cdiv(T_pad, 256), N);
+  // algorithmic bytes: the mixture once + the two [N][T_pad][8] fp16 planes and the reference channel written
+  asw::ProfScope prof(asw::as_stream(stream), "preproc_src", 0.0, (double)M * T * 4 + (double)N * T_pad * (32 + 4));
+  hipLaunchKernelGGL(src_planes_kernel, grid, dim3(256), 0, asw::as_stream(stream), mix, M, T, T_pad, offsets, mix_index,
+                     circular, mean, std, reinterpret_cast<asw_mfma::half8*>(src_hi), reinterpret_cast<asw_mfma::half8*>(src_lo),
+                     refn, refn_stride);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

@@ -70,17 +70,38 @@ struct KArgs {
   const float* glu_gamma;
   const float* glu_beta;
   float* glu_out;                        // optional: the GroupNorm + GLU rows of this tile's own output range, fp32
+  const half8* src_h;                    // SRC: the 8-channel source rows [B][T][8], fp16 hi / lo planes (16 B per row each)
+  const half8* src_l;
+  const half8* Pre_h;                    // SRC: the 1x1 weight [64][16] that rebuilds layer 0's residual, fragment order
+  const half8* Pre_l;
+  float pre_up, pre_down;                // SRC: 2^pre_shift and its inverse
   int B, T, taps, ntile, BM, img_rows;
   float eps;
   LayerDev L[MAXL];
 };
 
+// One 16-byte row of a source plane through its buffer descriptor: rows outside [0, T) read as zeros.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t src_rsrc(const half8* base, long rows) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<half8*>(base), 0, (int)(rows * 16), 0x00020000);
+}
+__device__ __forceinline__ half8 src_load(__amdgpu_buffer_rsrc_t r, int row) {
+  return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(r, row >= 0 ? row * 16 : (int)0x80000000, 0, 0));
+}
+
 // NL fused layers (contiguous row tiles) or one layer on polyphase row sets (POLY, NL == 1).
 // NW waves, each owning TM 32-row fragments x all 64 channels.
-template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int NTERM, int QD>
+//
+// SRC: layer 0's input x0 is itself a 1x1 convolution of an 8-channel source u~ = (u_0 .. u_6, 1) (zero outside the
+// sequence), x0[t] = Wpre~ u~[t], which nothing non-linear separates from layer 0's convolution.  Layer 0 then runs
+// on u~ with the composed weights Wc_k Wpre~ (k index = tap * 8 + channel: 4 k-steps of two taps each instead of
+// taps x 4), its B operand loaded straight from the two fp16 planes of u~ -- a fragment is 32 consecutive 16-byte
+// rows -- with no LDS image and no staging pass; the residual x0 is one more k-step with Wpre~ (K = 8 padded to 16)
+// accumulated onto the ReLU'd accumulators.  x0 is never materialised.
+template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int NTERM, int QD, bool SRC = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(TM >= 4 ? 1 : 2)))
 void resstack64_kernel(const KArgs p) {
   static_assert(!POLY || NL == 1, "polyphase row sets: single layers only");
+  static_assert(!SRC || (!POLY && !GLU && NTERM == 3), "source-fed layer 0: contiguous tiles, f16x3");
   static_assert(QD == 2 || QD == 4, "weight prefetch depth in k-steps");
   constexpr int NTHR = 64 * NW, SROWS = NTHR / 16;
   constexpr int R0 = 32 * NW * TM;                      // rows layer 0 computes
@@ -105,13 +126,15 @@ void resstack64_kernel(const KArgs p) {
 
   RS_MARK(t_start);
   // ---- per-layer vectors -> LDS
-  for (int i = tid; i < NL * 3 * 16; i += NTHR) {
-    const int li = i / 48, w = (i - li * 48) / 16, c4 = i & 15;
-    const float* src = w == 0 ? p.L[li].bias : w == 1 ? p.L[li].gamma : p.L[li].beta;
-    reinterpret_cast<float4*>(tab)[i] = *reinterpret_cast<const float4*>(src + c4 * 4);
+  if constexpr (!SRC) {                  // (SRC: after layer 0's operand loads are out, under the same wait)
+    for (int i = tid; i < NL * 3 * 16; i += NTHR) {
+      const int li = i / 48, w = (i - li * 48) / 16, c4 = i & 15;
+      const float* src = w == 0 ? p.L[li].bias : w == 1 ? p.L[li].gamma : p.L[li].beta;
+      reinterpret_cast<float4*>(tab)[i] = *reinterpret_cast<const float4*>(src + c4 * 4);
+    }
   }
   // ---- stage + split the input rows of layer 0 (16 threads per row, 8 rows per thread in flight)
-  {
+  if constexpr (!SRC) {
     const __amdgpu_buffer_rsrc_t rX = GLU ? act_rsrc(p.glu_raw + (long)b * T * 2 * C, (long)T * 2 * C)
                                           : act_rsrc(p.x + (long)b * T * C, (long)T * C);
     const int srow = tid >> 4, sc4 = tid & 15;
@@ -176,7 +199,7 @@ void resstack64_kernel(const KArgs p) {
       }
     }
   }
-  __syncthreads();
+  if constexpr (!SRC) __syncthreads();
   RS_MARK(t_staged);
 #ifdef ASW_PHASE_TIMING
   unsigned long long t_marks[2 * MAXL + 1];
@@ -216,6 +239,76 @@ void resstack64_kernel(const KArgs p) {
 #pragma unroll
       for (int i = 0; i < NF; ++i) { acc[i][0] = a[i][0]; acc[i][1] = a[i][1]; }
     };
+    if constexpr (SRC && li == 0) {
+      // Layer 0 on the source planes (every wave owns TM whole fragments here: nfrag == NW * TM, checked by the host).
+      // Lane (row r, half h) holds, for k-step ks, the 8 source channels of row r + tap, tap = 2 ks + h: one 16-byte
+      // load per plane.  Tap 7 does not exist -- its weights are zero -- but its rows are read and are finite (data or
+      // the descriptor's zeros).  Everything is requested before the first MFMA: one exposed latency per tile.
+      const __amdgpu_buffer_rsrc_t rH = src_rsrc(p.src_h + (long)b * T, T), rL = src_rsrc(p.src_l + (long)b * T, T);
+      const int g0 = m0 - Ld.halo - Ld.pad + wid * TM * 32 + (lane & 31);       // global row of this lane's row at tap 0
+      half8 xh[4][TM], xl[4][TM], rh[TM], rl[TM];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          xh[ks][i] = src_load(rH, g0 + i * 32 + 2 * ks + h);
+          xl[ks][i] = src_load(rL, g0 + i * 32 + 2 * ks + h);
+        }
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {                    // the residual's rows (centre tap); the half h == 1 meets zero weights
+        rh[i] = src_load(rH, g0 + i * 32 + Ld.pad);
+        rl[i] = src_load(rL, g0 + i * 32 + Ld.pad);
+      }
+      // weight stream: k-steps 0..3 of the composed weight, then the 1x1 weight as "k-step 4"; two slots
+      half8 wh[2][2], wl[2][2];
+      auto wload = [&](auto kgc, int slot) {
+        constexpr int kg = decltype(kgc)::value;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          if constexpr (kg < 4) frag_load<3>(Ld.Wh, Ld.Wl, (long)kg * 2 + cb, lane, wh[slot][cb], wl[slot][cb]);
+          else frag_load<3>(p.Pre_h, p.Pre_l, (long)cb, lane, wh[slot][cb], wl[slot][cb]);
+        }
+      };
+      wload(std::integral_constant<int, 0>{}, 0);
+      wload(std::integral_constant<int, 1>{}, 1);
+      for (int i = tid; i < NL * 3 * 16; i += NTHR) {   // per-layer vectors -> LDS
+        const int lj = i / 48, w = (i - lj * 48) / 16, c4 = i & 15;
+        const float* src = w == 0 ? p.L[lj].bias : w == 1 ? p.L[lj].gamma : p.L[lj].beta;
+        reinterpret_cast<float4*>(tab)[i] = *reinterpret_cast<const float4*>(src + c4 * 4);
+      }
+      __syncthreads();
+      auto kstep = [&](auto ksc) {
+        constexpr int ks = decltype(ksc)::value;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) mma3<3, true>(acc[i][cb], xh[ks][i], xl[ks][i], wh[ks & 1][cb], wl[ks & 1][cb]);
+        if constexpr (ks + 2 <= 4) wload(std::integral_constant<int, ks + 2>{}, ks & 1);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      kstep(std::integral_constant<int, 0>{});
+      kstep(std::integral_constant<int, 1>{});
+      kstep(std::integral_constant<int, 2>{});
+      kstep(std::integral_constant<int, 3>{});
+      // + bias, ReLU -- brought to the units of the 1x1 weight (both weights carry a power-of-two pre-scale, so the
+      // rescaling is exact) -- then the residual x0 = Wpre~ u~ accumulated on top: no second accumulator set
+      const float* tb0 = tab;
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4 bi = *reinterpret_cast<const float4*>(tb0 + cb * 32 + q * 8 + h * 4);
+            const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              acc[i][cb][q * 4 + j] = fmaxf(acc[i][cb][q * 4 + j] * Ld.scale + bv[j], 0.f) * p.pre_up;
+          }
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) mma3<3, true>(acc[i][cb], rh[i], rl[i], wh[0][cb], wl[0][cb]);
+      }
+    } else {
     if (nf >= TM) run(std::integral_constant<int, TM>{});
     else if constexpr (TM > 1) {
       if (nf == 1) run(std::integral_constant<int, 1>{});
@@ -223,6 +316,7 @@ void resstack64_kernel(const KArgs p) {
         if (nf == 2) run(std::integral_constant<int, 2>{});
         if (nf == 3) run(std::integral_constant<int, 3>{});
       }
+    }
     }
 #ifdef ASW_PHASE_TIMING
     {
@@ -251,8 +345,13 @@ void resstack64_kernel(const KArgs p) {
             const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              float v = fmaxf(acc[i][cb][q * 4 + j] * Ld.scale + bv[j], 0.f);
-              v += (float)rh[j] + (float)rl[j];
+              float v;
+              if constexpr (SRC && li == 0) {
+                v = acc[i][cb][q * 4 + j] * p.pre_down;          // bias, ReLU and residual are in the accumulators
+              } else {
+                v = fmaxf(acc[i][cb][q * 4 + j] * Ld.scale + bv[j], 0.f);
+                v += (float)rh[j] + (float)rl[j];
+              }
               acc[i][cb][q * 4 + j] = v;
               s += v;
             }
@@ -281,7 +380,7 @@ void resstack64_kernel(const KArgs p) {
     }
     if constexpr (!last) {
       // the next layer's input replaces this layer's in the image: rows outside the sequence are its zero padding
-      __syncthreads();                                  // every wave is done reading the old image
+      if constexpr (!(SRC && li == 0)) __syncthreads(); // every wave is done reading the old image
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         if (i < nf) {
@@ -358,16 +457,23 @@ void resstack64_kernel(const KArgs p) {
 #endif
 }
 
-template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int QD>
+template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int QD, bool SRC = false>
 int launch_stack(const KArgs& k, int precision, size_t smem, double flops, const char* tag, hipStream_t s) {
   char nm[128], detail[48] = "";
-  snprintf(nm, sizeof nm, "resstack64<%s,%dx%d%s%s>", tag, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
-           GLU ? ",glu" : "");
+  snprintf(nm, sizeof nm, "resstack64<%s,%dx%d%s%s%s>", tag, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
+           GLU ? ",glu" : "", SRC ? ",src" : "");
   if (asw::prof_detail()) snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
+  if constexpr (SRC) {
+    // f16x3 only; algorithmic bytes: the two source planes read once, the output written once
+    return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, true>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, true>>(
+        1, dim3(xcd_grid_run(k.B * k.ntile)), dim3(64 * NW), smem, 160 * 1024, nm, detail, flops,
+        (double)k.B * k.T * (32 + C * 4), s, k);
+  } else {
   // algorithmic bytes: the stack's input read once, its output written once
   return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 1, QD>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD>>(
       precision, dim3(xcd_grid_run(k.B * k.ntile)), dim3(64 * NW), smem, 160 * 1024, nm, detail, flops,
       (double)k.B * k.T * C * 4 * (GLU ? 3 : 2), s, k);
+  }
 }
 
 template <int NW, int TM>
@@ -405,6 +511,10 @@ int dispatch(const asw_resstack_args& a, KArgs& k, bool glu, double flops, hipSt
   const size_t smem = (size_t)rows * RS + (size_t)a.n_layers * 3 * 64 * sizeof(float);
   ASW_CHECK_ARG(smem <= 160 * 1024, "resstack: image of %d rows exceeds LDS (dilation %d x %d taps too wide for a contiguous tile)",
                 rows, dil0, a.taps);
+  if (k.src_h) {
+    ASW_CHECK_ARG(k.L[0].nfrag == NW * TM, "resstack: source-fed layer 0 computes %d of %d fragments", k.L[0].nfrag, NW * TM);
+    return launch_stack<2, NW, TM, 1, false, false, 4, true>(k, a.precision, smem, flops, "2", s);
+  }
   switch (a.n_layers) {
     case 1: return glu ? launch_stack<1, NW, TM, 1, false, true, 4>(k, a.precision, smem, flops, "1", s)
                        : launch_stack<1, NW, TM, 1, false, false, 4>(k, a.precision, smem, flops, "1", s);
@@ -428,6 +538,26 @@ extern "C" int asw_debug_resstack_cycles(unsigned long long* out6, int reset) {
 }
 #endif
 
+extern "C" int asw_compose_source_weights(const float* wc, const float* wpre, const float* bpre, int M, int taps, float* comp,
+                                          float* pre16) {
+  ASW_CHECK_ARG(wc && wpre && bpre && comp && pre16, "compose_source_weights: null pointer");
+  ASW_CHECK_ARG(M >= 1 && M <= 7 && taps >= 1 && taps <= 7, "compose_source_weights: M=%d taps=%d (at most 7 each)", M, taps);
+  for (int i = 0; i < C * 16; ++i) pre16[i] = 0.f;
+  for (int i = 0; i < C * 64; ++i) comp[i] = 0.f;
+  for (int c = 0; c < C; ++c) {
+    for (int m = 0; m < M; ++m) pre16[c * 16 + m] = wpre[c * M + m];
+    pre16[c * 16 + 7] = bpre[c];                         // the channel that is 1 on every row carries the bias
+  }
+  for (int n = 0; n < C; ++n)
+    for (int k = 0; k < taps; ++k)
+      for (int j = 0; j < 8; ++j) {
+        double acc = 0.0;
+        for (int c = 0; c < C; ++c) acc += (double)wc[((size_t)n * C + c) * taps + k] * (double)pre16[c * 16 + j];
+        comp[n * 64 + k * 8 + j] = (float)acc;
+      }
+  return ASW_OK;
+}
+
 extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream) {
   ASW_CHECK_ARG(args != nullptr, "resstack: null args");
   const asw_resstack_args& a = *args;
@@ -437,7 +567,7 @@ extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream)
   ASW_CHECK_ARG(a.taps >= 3 && a.taps <= 15 && a.taps % 2 == 1, "resstack: taps=%d (odd, 3..15)", a.taps);
   ASW_CHECK_ARG(a.precision == 1 || a.precision == 2, "resstack: precision 1 (f16x3) or 2 (single-pass f16)");
   ASW_CHECK_ARG(a.B > 0 && a.B <= (1 << 20) && a.T > 0 && (int64_t)a.T * 2 * C < ((int64_t)1 << 29), "resstack: bad B / T");
-  ASW_CHECK_ARG(a.out && (a.x || a.glu_raw), "resstack: null tensor");
+  ASW_CHECK_ARG(a.out && (a.x || a.glu_raw || a.src_hi), "resstack: null tensor");
   const bool glu = a.glu_raw != nullptr;
   if (glu) ASW_CHECK_ARG(a.glu_mr && a.glu_gamma && a.glu_beta, "resstack: GroupNorm + GLU on load needs the statistics / affine arrays");
   KArgs k = {};
@@ -455,6 +585,16 @@ extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream)
     L.scale = ldexpf(1.0f, -d.w_shift);
     halo += L.pad;
   }
-  const double flops = 2.0 * a.B * (double)a.T * C * C * a.taps * a.n_layers;
+  double flops = 2.0 * a.B * (double)a.T * C * C * a.taps * a.n_layers;
+  if (a.src_hi) {
+    ASW_CHECK_ARG(a.src_lo && a.pre_hi && a.pre_lo && !a.x && !glu, "resstack: the source-fed form takes src_hi / src_lo / pre_hi / pre_lo and no x");
+    ASW_CHECK_ARG(a.precision == 1 && a.n_layers == 2 && a.taps <= 7 && a.layer[0].dil == 1,
+                  "resstack: source-fed layer 0 is f16x3, two layers, dilation 1, at most 7 taps");
+    k.src_h = reinterpret_cast<const half8*>(a.src_hi); k.src_l = reinterpret_cast<const half8*>(a.src_lo);
+    k.Pre_h = reinterpret_cast<const half8*>(a.pre_hi); k.Pre_l = reinterpret_cast<const half8*>(a.pre_lo);
+    k.pre_up = ldexpf(1.0f, a.pre_shift); k.pre_down = ldexpf(1.0f, -a.pre_shift);
+    // the FLOPs executed: layer 0 is K = 64 (8 taps x 8 channels) plus the K = 16 residual step, layer 1 as always
+    flops = 2.0 * a.B * (double)a.T * C * (64 + 16 + C * a.taps);
+  }
   return dispatch<4, 2>(a, k, glu, flops, s);            // 4 waves x 2 row fragments: 256 rows computed by layer 0
 }

@@ -45,6 +45,7 @@ struct asw_spot : Trunk {
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
+  asw_spot() { want_src = true; }
   ~asw_spot() {
     for (char* w : ws) if (w) (void)hipFree(w);
     if (side) (void)hipStreamDestroy(side);
@@ -165,12 +166,12 @@ int ensure_ws(asw_spot* m, int B, int T, Plan& pl, int lane = 0) {
   return ASW_OK;
 }
 
-// everything after the preproc stage; pl.X[0] / pl.refn are filled
+// everything after the preproc stage; pl.X[0] (src0: the source planes instead) / pl.refn are filled
 int run_network(asw_spot* m, Plan& pl, GateSet* gs, const float* mean, const float* stdv, float* out_wave,
-                hipStream_t s) {
+                hipStream_t s, bool src0 = false) {
   const asw_spot_config& c = m->cfg;
   int rc;
-  if ((rc = m->encode(pl, *gs, s))) return rc;
+  if ((rc = m->encode(pl, *gs, s, src0))) return rc;
   // ---- bottleneck (network.py:240-265): post-norm transformer layers, batch-first rows
   const int L = pl.Tl[c.depth], d = m->enc_cout.back(), rows = pl.B * L;
   const float* h = pl.X[c.depth];
@@ -292,6 +293,7 @@ extern "C" int asw_spot_shift_and_sep_multi(asw_spot* m, const float* mix, int K
     ASW_HIP(hipStreamWaitEvent(m->side, m->ev_fork, 0));
   }
   const int C = m->cfg.channels, pad_l = m->cfg.encoder_kernel_size / 2;
+  const bool src0 = m->src_path();
   // The caller's stream continues after BOTH lanes on every exit path: when a launch fails half way the side
   // lane may still be writing out_wave / out_energy (the caller's buffers), so the join is not skipped -- and if
   // the join itself cannot be queued the side lane is drained before the status is returned.
@@ -307,11 +309,17 @@ extern "C" int asw_spot_shift_and_sep_multi(asw_spot* m, const float* mix, int K
       ASW_HIP(hipMemsetAsync(p.refn, 0, (size_t)B * p.RL * sizeof(float), q));
       int r;
       if ((r = asw_shift_stats_multi(mix, M, T, off, mi, B, circular, p.mean, p.stdv, q))) return r;
-      if ((r = asw_shift_norm_preproc_multi(mix, M, T, p.Tp, off, mi, B, circular, p.mean, p.stdv, m->pre_w.p, m->pre_b.p, C,
-                                            p.X[0], p.refn + pad_l, p.RL, q)))
+      if (src0) {
+        // preproc folded into encoder block 0's first layer: the 8-channel input goes out, X[0] is never written
+        if ((r = asw_shift_norm_src_multi(mix, M, T, p.Tp, off, mi, B, circular, p.mean, p.stdv, p.src_hi, p.src_lo,
+                                          p.refn + pad_l, p.RL, q)))
+          return r;
+      } else if ((r = asw_shift_norm_preproc_multi(mix, M, T, p.Tp, off, mi, B, circular, p.mean, p.stdv, m->pre_w.p,
+                                                   m->pre_b.p, C, p.X[0], p.refn + pad_l, p.RL, q))) {
         return r;
+      }
       float* y = out_wave ? out_wave + (size_t)i0 * T : p.ywave;
-      if ((r = run_network(m, p, gs, p.mean, p.stdv, y, q))) return r;
+      if ((r = run_network(m, p, gs, p.mean, p.stdv, y, q, src0))) return r;
       if (out_energy && (r = asw_energies(y, B, T, energy_window, p.escr, out_energy + (size_t)i0 * 2, q))) return r;
     }
     return ASW_OK;
@@ -362,6 +370,12 @@ extern "C" int asw_spot_forward(asw_spot* m, const float* mix_norm, int B, int M
 extern "C" int asw_spot_set_fused_mask(asw_spot* m, int on) {
   ASW_CHECK_ARG(m, "set_fused_mask: null model handle");
   m->fuse_mask = on != 0;
+  return ASW_OK;
+}
+
+extern "C" int asw_spot_set_source_stack(asw_spot* m, int on) {
+  ASW_CHECK_ARG(m, "set_source_stack: null model handle");
+  m->src_stack = on != 0;
   return ASW_OK;
 }
 

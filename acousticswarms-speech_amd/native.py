@@ -146,7 +146,8 @@ class ResStackArgs(Structure):
     _fields_ = [("x", c_void_p), ("out", c_void_p), ("B", c_int32), ("T", c_int32), ("C", c_int32), ("taps", c_int32),
                 ("n_layers", c_int32), ("precision", c_int32), ("ln_eps", c_float), ("layer", ResLayerDesc * 3),
                 ("glu_raw", c_void_p), ("glu_mr", c_void_p), ("glu_gamma", c_void_p), ("glu_beta", c_void_p),
-                ("glu_out", c_void_p)]
+                ("glu_out", c_void_p), ("src_hi", c_void_p), ("src_lo", c_void_p), ("pre_hi", c_void_p), ("pre_lo", c_void_p),
+                ("pre_shift", c_int32)]
 
 
 # name -> (restype, argtypes); must list every symbol declared in include/asw_hip.h
@@ -170,6 +171,7 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_int, c_void_p]),
     "asw_spot_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), c_void_p, c_void_p]),
     "asw_spot_set_fused_mask": (c_int, [c_void_p, c_int]),
+    "asw_spot_set_source_stack": (c_int, [c_void_p, c_int]),
     "asw_spot_get_tap": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
     "asw_sep_create": (c_int, [POINTER(SepConfigC), POINTER(c_void_p)]),
     "asw_sep_destroy": (None, [c_void_p]),
@@ -197,11 +199,14 @@ SIGNATURES = {
     "asw_shift_stats_multi": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "asw_shift_norm_preproc_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "asw_shift_norm_src_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "asw_pad_preproc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                 c_void_p, c_long, c_void_p]),
     "asw_convgemm_f32": (c_int, [POINTER(ConvGemmArgs), c_void_p]),
     "asw_mask_path_f16x3": (c_int, [POINTER(MaskPathArgs), c_void_p]),
     "asw_resstack64_f16x3": (c_int, [POINTER(ResStackArgs), c_void_p]),
+    "asw_compose_source_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "asw_convgemm_stats_tiles": (c_int, [c_int, c_int]),
     "asw_f16x3_overflow_count": (c_int, [c_int, POINTER(c_int32)]),
     "asw_gn_glu": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,

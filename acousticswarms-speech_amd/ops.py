@@ -99,6 +99,42 @@ def resstack(x, layers, taps=7, precision="f16x3", eps=1e-5, glu=None, out=None,
     return out
 
 
+def resstack_src(src_hi, src_lo, pre_w, pre_b, layers, taps=7, eps=1e-5, out=None):
+    """The fused pair with its first layer fed by the 8-channel source of the 1x1 convolution (pre_w [64][M], pre_b [64])
+    in front of it (include/asw_hip.h:asw_resstack_args.src_hi).  src_hi / src_lo: the planes of shift_norm_src;
+    layers: [(conv weight [64][64][taps] torch layout, bias, gamma, beta, dil)] * 2."""
+    import ctypes
+    import numpy as np
+    B, T = src_hi.shape[0], src_hi.shape[1]
+    dev = src_hi.device
+    if out is None:
+        out = torch.empty((B, T, 64), dtype=torch.float32, device=dev)
+    M = pre_w.shape[1]
+    wc = np.ascontiguousarray(layers[0][0].detach().cpu().numpy(), dtype=np.float32)
+    wp = np.ascontiguousarray(pre_w.detach().cpu().numpy(), dtype=np.float32).reshape(64, M)
+    bp = np.ascontiguousarray(pre_b.detach().cpu().numpy(), dtype=np.float32)
+    comp, pre16 = np.empty((64, 64), dtype=np.float32), np.empty((64, 16), dtype=np.float32)
+    check(lib().asw_compose_source_weights(ctypes.c_void_p(wc.ctypes.data), ctypes.c_void_p(wp.ctypes.data),
+                                           ctypes.c_void_p(bp.ctypes.data), M, taps, ctypes.c_void_p(comp.ctypes.data),
+                                           ctypes.c_void_p(pre16.ctypes.data)))
+    a = ResStackArgs()
+    a.out = out.data_ptr()
+    a.B, a.T, a.C, a.taps, a.n_layers, a.precision, a.ln_eps = B, T, 64, taps, len(layers), 1, eps
+    keep = []
+    for i, (w, bias, gamma, beta, dil) in enumerate(layers):
+        Wt = torch.from_numpy(comp).to(dev) if i == 0 else pack_conv_weight(w).to(dev)
+        fh, fl, sh = pack_fragments_f16(Wt, 64, Wt.shape[1])
+        keep.append((fh, fl))
+        d = a.layer[i]
+        d.Wf_hi, d.Wf_lo, d.w_shift, d.dil = fh.data_ptr(), fl.data_ptr(), sh, dil
+        d.bias, d.ln_gamma, d.ln_beta = _f32(bias).data_ptr(), _f32(gamma).data_ptr(), _f32(beta).data_ptr()
+    ph, pl, psh = pack_fragments_f16(torch.from_numpy(pre16).to(dev), 64, 16)
+    a.src_hi, a.src_lo, a.pre_hi, a.pre_lo, a.pre_shift = src_hi.data_ptr(), src_lo.data_ptr(), ph.data_ptr(), pl.data_ptr(), psh
+    check(lib().asw_resstack64_f16x3(byref(a), current_stream()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
 def pack_fragments_f16(Wt, N, K):
     """fp32 device Wt[N][K] -> fragment-major (hi, lo) device tensors + shift (asw_pack_fragments_f16)."""
     import ctypes
@@ -182,6 +218,18 @@ def shift_norm_preproc(mix, offsets, mean, std, w, b, T_pad, circular=True):
                                        ptr(std), ptr(_f32(w)), ptr(_f32(b)), C, ptr(x0), ptr(refn), T_pad,
                                        current_stream()))
     return x0, refn
+
+
+def shift_norm_src(mix, offsets, mean, std, T_pad, circular=True):
+    """asw_shift_norm_src_multi on one mixture: (src_hi, src_lo) [N][T_pad][8] fp16 planes and refn [N][T_pad]."""
+    M, T = mix.shape
+    N = offsets.shape[0]
+    hi = torch.empty((N, T_pad, 8), dtype=torch.float16, device=mix.device)
+    lo = torch.empty((N, T_pad, 8), dtype=torch.float16, device=mix.device)
+    refn = torch.zeros((N, T_pad), dtype=torch.float32, device=mix.device)
+    check(lib().asw_shift_norm_src_multi(ptr(_f32(mix)), M, T, T_pad, ptr(offsets), None, N, int(circular), ptr(mean),
+                                         ptr(std), ptr(hi), ptr(lo), ptr(refn), T_pad, current_stream()))
+    return hi, lo, refn
 
 
 def overlap_add_unnorm(D, taps, hop, t, trim_left, trim_right, bias, mean=None, std=None):

@@ -283,6 +283,13 @@ class SpotModel:
         native.check(native.lib().asw_spot_set_fused_mask(self._h, int(bool(on))))
         return self
 
+    def set_source_stack(self, on: bool = True):
+        """f16x3 mode: shift_and_sep folds the 1x1 preproc into encoder block 0's first residual layer (default;
+        the "preproc" tap does not exist then) or runs the separate preproc pass (asw_spot_set_source_stack)."""
+        self._need()
+        native.check(native.lib().asw_spot_set_source_stack(self._h, int(bool(on))))
+        return self
+
     def get_tap(self, name: str, shape=None):
         """Intermediate activation of the last forward (channels-last), for parity tests."""
         import torch

@@ -134,9 +134,19 @@ int asw_spot_forward(asw_spot* m, const float* mix_norm, int B, int M, int t,
  * pass everywhere (default: on). */
 int asw_spot_set_fused_mask(asw_spot* m, int on);
 
+/* f16x3 mode, 64 channels at level 0, n_mics <= 7, kernel_size <= 7: asw_spot_shift_and_sep[_multi] folds the 1x1
+ * preproc convolution into the first residual layer of encoder block 0 (no non-linearity separates them): the front end
+ * writes the 8-channel network input (asw_shift_norm_src_multi) instead of the 64-channel preproc output, and the
+ * block's first fused pair runs source-fed (asw_resstack_args.src_hi).  The preproc output is then never written and
+ * the "preproc" tap does not exist after such a call.  on = 0 selects the separate preproc pass (default: on).
+ * asw_spot_forward, the f32 and the single-pass f16 modes always take the separate pass. */
+int asw_spot_set_source_stack(asw_spot* m, int on);
+
 /* Debug/parity tap: copy an intermediate activation of the LAST forward to `dst`
  * (channels-last [B][T_l][C] float32).  names: "preproc", "enc0".., "bottleneck",
- * "dec0".., "latent" (three-GEMM mask path only).  Returns the element count through *numel (dst may be NULL). */
+ * "dec0".., "latent" (three-GEMM mask path only); "preproc" does not exist after a
+ * shift_and_sep call that took the source-fed path (asw_spot_set_source_stack): the call then fails with "no
+ * activation named preproc".  Returns the element count through *numel (dst may be NULL). */
 int asw_spot_get_tap(asw_spot* m, const char* name, float* dst, size_t capacity, size_t* numel,
                      void* stream);
 
@@ -264,6 +274,15 @@ int asw_shift_norm_preproc_multi(const float* mix, int M, int T, int T_pad, cons
                                  const int32_t* mix_index, int N, int circular, const float* mean, const float* std,
                                  const float* w, const float* b, int C, float* x0, float* refn, long refn_stride,
                                  void* stream);
+
+/* asw_shift_norm_preproc_multi without the 1x1 convolution, for the source-fed first residual pair
+ * (asw_resstack_args.src_hi): the same shift, quantisation, normalisation and left pad, the same refn, and instead of
+ * x0 the network input itself as u~ [N][T_pad][8] = (u_0 .. u_{M-1}, 0 .., 1) -- the last channel is 1 on every row and
+ * carries the preproc bias -- already split into the two fp16 halves of the f16x3 operands (saturating at +-65504 like
+ * every activation split): src_hi / src_lo, 16 bytes per row each.  M <= 7. */
+int asw_shift_norm_src_multi(const float* mix, int M, int T, int T_pad, const int32_t* offsets,
+                             const int32_t* mix_index, int N, int circular, const float* mean, const float* std,
+                             void* src_hi, void* src_lo, float* refn, long refn_stride, void* stream);
 
 /* Normalised input variant used by asw_spot_forward: x [B][M][t] -> x0, refn. */
 int asw_pad_preproc(const float* x, int B, int M, int t, int T_pad, const float* w,
@@ -406,8 +425,26 @@ typedef struct asw_resstack_args {
   const float* glu_beta;
   float* glu_out;         /* optional with glu_raw: [B][T][64], receives GLU(GroupNorm(glu_raw)) -- the stack's input --
                              for a caller that needs it as a tensor as well (the encoder's skip connection) */
+  /* Optional, instead of x (precision 1, n_layers == 2, layer 0 of dilation 1, taps <= 7): the stack's input is
+   * x[t] = Wpre~ u~[t], a 1x1 convolution of the 8-channel source u~ = (u_0 .. u_6, 1) written by
+   * asw_shift_norm_src_multi, and is never materialised.  src_hi / src_lo: [B][T][8] fp16 planes of u~;
+   * layer[0].Wf_hi / Wf_lo / w_shift: the COMPOSED weight Wt[64][64], column tap*8 + j = sum_c Wc[n][c][tap] Wpre~[c][j]
+   * (tap 7 zero), in fragment order; pre_hi / pre_lo / pre_shift: Wpre~ as Wt[64][16] (columns 8..15 zero), fragment
+   * order.  Layer 0's bias and LayerNorm and all of layer 1 as above.  Launch name resstack64<2,4x2,src>. */
+  const void* src_hi;
+  const void* src_lo;
+  const void* pre_hi;
+  const void* pre_lo;
+  int32_t pre_shift;
 } asw_resstack_args;
 int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream);
+/* Host helper: the weights of the source-fed form (asw_resstack_args.src_hi) from the torch-layout parameters, composed
+ * in double: wc [64][64][taps] (the first layer's Conv1d weight), wpre [64][M] and bpre [64] (the 1x1 convolution in
+ * front of it), M <= 7, taps <= 7 -> comp Wt[64][64] (column tap*8 + j; j == 7 multiplies the constant channel and
+ * carries the bias; tap 7 zero) and pre16 Wt[64][16] = [wpre | 0 | bpre | 0 x 8], both to be packed with
+ * asw_pack_fragments_f16. */
+int asw_compose_source_weights(const float* wc, const float* wpre, const float* bpre, int M, int taps, float* comp,
+                               float* pre16);
 /* Host helper: split n fp32 weights into the fp16 hi/lo pair used by precision 1 with the
  * power-of-two pre-scale that keeps the lo parts out of the fp16 subnormal range; returns
  * the shift through *w_shift.  hi/lo: n uint16 each (host). */
