@@ -241,6 +241,12 @@ class MixtureScorer(object):
     def segment_sisdr(self, waves, segments):
         return self.inner_model.segment_sisdr(waves, segments)
 
+    def voiced_segments(self, waves):
+        return self.inner_model.voiced_segments(waves)
+
+    def segment_sisdr_device(self, waves, seg_dev, cnt_dev):
+        return self.inner_model.segment_sisdr_device(waves, seg_dev, cnt_dev)
+
 
 def mixture_view(mic_array):
     """A per-search view of a MicArray: the geometry tables (tens of MB, read-only) are shared, everything a

@@ -522,6 +522,150 @@ __global__ __launch_bounds__(256) void seg_sisdr_kernel(const float* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------
+// Voiced segments (split_wav, sep/helpers/eval_utils.py:43-70) as hostdsp.voiced_segments_f64 states them: float64,
+// no logarithm, one fixed order of additions -- every value below is the statement's value to the bit.  A float32
+// squared is exact in double, so contracting a square into the add that follows rounds the same value once either way.
+//
+// voiced_block_sums_kernel: one wavefront per 256-sample block.  Lane l sums the squares of samples 4l .. 4l+3 left to
+// right (samples past T count as 0), then the statement's butterfly p[l] += p[l+s], s = 32 .. 1; lane 0 holds the sum.
+// `vec4`: every row is 16-byte aligned (T % 4 == 0 and an aligned base), so a lane's four samples are one load and lie
+// inside or outside the row together.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void voiced_block_sums_kernel(const float* __restrict__ y, int T, int nblk, int vec4,
+                                                                double* __restrict__ bsum) {
+  const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= nblk) return;                                        // whole wavefronts leave; no barrier below
+  const float* __restrict__ row = y + (long)blockIdx.y * T;
+  const long t = (long)j * 256 + lane * 4;
+  float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+  if (vec4) {
+    if (t < T) {
+      const float4 v = *reinterpret_cast<const float4*>(row + t);
+      v0 = v.x; v1 = v.y; v2 = v.z; v3 = v.w;
+    }
+  } else {
+    if (t < T) v0 = row[t];
+    if (t + 1 < T) v1 = row[t + 1];
+    if (t + 2 < T) v2 = row[t + 2];
+    if (t + 3 < T) v3 = row[t + 3];
+  }
+  const double q0 = (double)v0 * (double)v0, q1 = (double)v1 * (double)v1, q2 = (double)v2 * (double)v2,
+               q3 = (double)v3 * (double)v3;
+  double p = ((q0 + q1) + q2) + q3;
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) p = p + __shfl_down(p, s, 64);   // lanes < s hold the statement's p[:s]
+  if (lane == 0) bsum[(long)blockIdx.y * nblk + j] = p;
+}
+
+// ms[f] of the statement from one waveform's block sums; blocks outside [0, nblk) are 0
+__device__ __forceinline__ double voiced_frame_ms(const double* __restrict__ b, int nblk, int f) {
+  const double b0 = (f >= 2 && f - 2 < nblk) ? b[f - 2] : 0.0, b1 = (f >= 1 && f - 1 < nblk) ? b[f - 1] : 0.0;
+  const double b2 = f < nblk ? b[f] : 0.0, b3 = f + 1 < nblk ? b[f + 1] : 0.0;
+  return (((b0 + b1) + b2) + b3) / 1024.0;
+}
+
+// voiced_decide_kernel: one workgroup per waveform.  Frame values and their maximum (exact in any order), then the
+// frames in chunks of 256, one per thread.  The thread of a run's LAST frame owns the run: it needs the run's first
+// frame -- an inclusive max-scan over "f where a run starts, else -1" -- and the number of segments the earlier runs
+// gave -- an exclusive sum-scan over the runs' segment counts; both scans run in LDS and carry over from chunk to
+// chunk, so a run may span any number of chunks and T is not bounded by the LDS.  Every slot of the row is written:
+// the segments by their owners, [0, 0] from `count` on.  The segments are disjoint and at least 1000 samples long
+// whatever the flags are, so count <= T / 1000 <= kcap; the stores are guarded all the same.
+__global__ __launch_bounds__(256) void voiced_decide_kernel(const double* __restrict__ bsum, int T, int nblk, double thr,
+                                                            double Q, int* __restrict__ seg, int kcap,
+                                                            int* __restrict__ counts, double* __restrict__ ms_out) {
+  constexpr double A2 = 1e-10;
+  __shared__ double redmax[4];
+  __shared__ int scan_start[2][256], scan_cnt[2][256];
+  __shared__ int carry_start, carry_cnt;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nfr = 1 + T / 256;
+  const double* __restrict__ b = bsum + (long)blockIdx.x * nblk;
+  int* __restrict__ row = seg + (long)blockIdx.x * kcap * 2;
+
+  double peak = 0.0;                                            // ms >= 0
+  for (int f = tid; f < nfr; f += 256) {
+    const double v = voiced_frame_ms(b, nblk, f);
+    if (ms_out) ms_out[(long)blockIdx.x * nfr + f] = v;
+    peak = v > peak ? v : peak;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(peak, o, 64);
+    peak = w > peak ? w : peak;
+  }
+  if (lane == 0) redmax[wid] = peak;
+  if (tid == 0) { carry_start = -1; carry_cnt = 0; }
+  __syncthreads();
+  double peak2 = redmax[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) peak2 = redmax[w] > peak2 ? redmax[w] : peak2;
+  const double ref2 = peak2 < Q ? (A2 > Q ? A2 : Q) : (A2 > peak2 ? A2 : peak2);
+  const double level = thr * ref2;
+  auto voiced = [&](int f) -> bool {
+    if (f < 0 || f >= nfr) return false;
+    const double v = voiced_frame_ms(b, nblk, f);
+    return (A2 > v ? A2 : v) > level;
+  };
+
+  for (int f0c = 0; f0c < nfr; f0c += 256) {
+    const int f = f0c + tid;
+    const bool on = voiced(f);
+    const bool first = on && !voiced(f - 1), last = on && !voiced(f + 1);
+    scan_start[0][tid] = first ? f : -1;
+    __syncthreads();                                            // also: the previous chunk's carries are written
+    int cur = 0;
+    for (int d = 1; d < 256; d <<= 1) {                         // inclusive max-scan of the run starts
+      const int v = scan_start[cur][tid], u = tid >= d ? scan_start[cur][tid - d] : -1;
+      scan_start[cur ^ 1][tid] = u > v ? u : v;
+      cur ^= 1;
+      __syncthreads();
+    }
+    const int s_in = scan_start[cur][tid];
+    const int run_first = s_in >= 0 ? s_in : carry_start;       // a run that began in an earlier chunk
+    int m = 0, a = 0, e = 0;
+    if (last) {
+      const long a_l = (long)(run_first > 0 ? run_first : 0) * 256, e_l = (long)(f + 1) * 256;
+      a = (int)(a_l < T ? a_l : T);
+      e = (int)(e_l < T ? e_l : T);
+      const int len = e - a;
+      m = len < 1000 ? 0 : (len > 4000 ? len / 4000 : 1);
+    }
+    scan_cnt[0][tid] = m;
+    __syncthreads();
+    cur = 0;
+    for (int d = 1; d < 256; d <<= 1) {                         // inclusive sum-scan of the segment counts
+      const int v = scan_cnt[cur][tid], u = tid >= d ? scan_cnt[cur][tid - d] : 0;
+      scan_cnt[cur ^ 1][tid] = u + v;
+      cur ^= 1;
+      __syncthreads();
+    }
+    const int base = carry_cnt + scan_cnt[cur][tid] - m;
+    for (int i = 0; i < m; ++i) {
+      const int k = base + i;
+      if (k < kcap) {
+        row[2 * k] = a + 4000 * i;
+        row[2 * k + 1] = i == m - 1 ? e : a + 4000 * (i + 1);
+      }
+    }
+    const int chunk_cnt = scan_cnt[cur][tid];                   // thread 255: the whole chunk's
+    __syncthreads();                                            // every thread has read the carries
+    if (tid == 255) {
+      carry_cnt += chunk_cnt;
+      if (s_in >= 0) carry_start = s_in;                        // the latest run start so far
+    }
+  }
+  __syncthreads();
+  int count = carry_cnt;
+  count = count < kcap ? count : kcap;
+  for (int k = count + tid; k < kcap; k += 256) {
+    row[2 * k] = 0;
+    row[2 * k + 1] = 0;
+  }
+  if (tid == 0) counts[blockIdx.x] = count;
+}
+
 // x[b][:] -= mean(x[b][:])   (sep/Mic_Array.py:291: the stage loops centre every candidate
 // output before measuring / comparing it); mean accumulated in double, applied as float32
 __global__ __launch_bounds__(1024) void center_rows_kernel(float* __restrict__ y, int T) {
@@ -725,6 +869,41 @@ extern "C" int asw_pair_sisdr(const float* y, int n, int T, double* out, void* s
   else
     hipLaunchKernelGGL(pair_sisdr_kernel, dim3(asw::cdiv(n, 16), asw::cdiv(n, 16)), dim3(256), 0, asw::as_stream(stream), y, n, T,
                        out);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+extern "C" size_t asw_voiced_segments_workspace_bytes(int n, int T) {
+  if (n < 0 || n > 65535 || T < 1) {
+    asw::set_error(ASW_ERR_ARG, "voiced_segments_workspace_bytes: n = %d outside 0..65535 or T = %d < 1", n, T);
+    return 0;
+  }
+  return (size_t)n * (size_t)asw::cdiv(T, 256) * sizeof(double);
+}
+
+extern "C" int asw_voiced_segments(const float* y, int n, int T, double thr, double Q, int32_t* segments, int kcap,
+                                   int32_t* counts, double* ms, void* workspace, size_t workspace_bytes, void* stream) {
+  ASW_CHECK_ARG(n >= 0 && n <= 65535, "voiced_segments: n = %d outside 0..65535", n);
+  ASW_CHECK_ARG(T >= 1, "voiced_segments: T = %d < 1", T);
+  const int need_k = T / 1000 > 1 ? T / 1000 : 1;
+  ASW_CHECK_ARG(kcap >= need_k, "voiced_segments: kcap = %d, a waveform of %d samples can hold %d segments", kcap, T, need_k);
+  if (n == 0) return ASW_OK;
+  ASW_CHECK_ARG(y && workspace, "voiced_segments: null pointer");
+  ASW_CHECK_ARG(segments && counts, "voiced_segments: null output");
+  const int nblk = asw::cdiv(T, 256);
+  const size_t need = (size_t)n * (size_t)nblk * sizeof(double);
+  ASW_CHECK_ARG(workspace_bytes >= need, "voiced_segments: workspace of %zu bytes too small, %zu needed", workspace_bytes, need);
+  ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "voiced_segments: workspace not 8-byte aligned");
+  hipStream_t s = asw::as_stream(stream);
+  double* bsum = static_cast<double*>(workspace);
+  const int vec4 = (T % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
+  {
+    asw::ProfScope prof(s, "voiced_block_sums", 0.0, (double)n * T * 4);
+    hipLaunchKernelGGL(voiced_block_sums_kernel, dim3(asw::cdiv(nblk, 4), n), dim3(256), 0, s, y, T, nblk, vec4, bsum);
+    ASW_LAUNCH_CHECK();
+  }
+  asw::ProfScope prof(s, "voiced_decide", 0.0, (double)n * nblk * 8);
+  hipLaunchKernelGGL(voiced_decide_kernel, dim3(n), dim3(256), 0, s, bsum, T, nblk, thr, Q, segments, kcap, counts, ms);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

@@ -21,6 +21,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
+#include <cmath>
 #include <tuple>
 #include <vector>
 
@@ -192,6 +193,30 @@ Tensor segment_sisdr(const Tensor& y, const Tensor& segments, const Tensor& coun
                                  out.data_ptr<double>(), l.stream),
                "asw_segment_sisdr");
   return out;
+}
+
+// -> segments [n, kcap, 2] int32, counts [n] int32, ms [n, 1 + T/256] float64 (empty unless want_ms): the voiced segments
+// of every row (hostdsp.voiced_segments_f64), kcap = max(1, T / 1000).  The threshold and the quiet bound are formed here
+// in double as the statement forms them: 10 ** (-top_db / 10) and 0.04 * 0.04.
+std::tuple<Tensor, Tensor, Tensor> voiced_segments(const Tensor& y, double top_db, bool want_ms) {
+  need(y, "y", at::kFloat, 2);
+  const int n = checked_int(y.size(0), "n"), T = checked_int(y.size(1), "T");
+  TORCH_CHECK(T >= 1, "y must hold at least one sample per row");
+  TORCH_CHECK(n <= 65535, "voiced_segments takes at most 65535 waveforms, got ", n);
+  const int64_t kcap = T / 1000 > 1 ? T / 1000 : 1, nfr = 1 + T / 256;
+  Tensor segments = at::empty({n, kcap, 2}, y.options().dtype(at::kInt));
+  Tensor counts = at::empty({n}, y.options().dtype(at::kInt));
+  Tensor ms = at::empty({want_ms ? n : 0, nfr}, y.options().dtype(at::kDouble));
+  if (n == 0) return {segments, counts, ms};
+  const size_t ws_bytes = asw_voiced_segments_workspace_bytes(n, T);
+  Tensor ws = at::empty({static_cast<int64_t>(ws_bytes / sizeof(double))}, y.options().dtype(at::kDouble));
+  const double thr = std::pow(10.0, -top_db / 10.0), Q = 0.04 * 0.04;
+  Launch l(y);
+  check_status(asw_voiced_segments(y.data_ptr<float>(), n, T, thr, Q, segments.data_ptr<int32_t>(), static_cast<int>(kcap),
+                                   counts.data_ptr<int32_t>(), want_ms ? ms.data_ptr<double>() : nullptr, ws.data_ptr(),
+                                   ws_bytes, l.stream),
+               "asw_voiced_segments");
+  return {segments, counts, ms};
 }
 
 Tensor center_rows_(Tensor y) {
@@ -560,6 +585,7 @@ TORCH_LIBRARY(asw, m) {
   m.def("energies(Tensor y, int window) -> Tensor");
   m.def("pair_sisdr(Tensor y) -> Tensor");
   m.def("segment_sisdr(Tensor y, Tensor segments, Tensor counts) -> Tensor");
+  m.def("voiced_segments(Tensor y, float top_db=18.0, bool want_ms=False) -> (Tensor, Tensor, Tensor)");
   m.def("center_rows_(Tensor(a!) y) -> Tensor(a!)");
   m.def("srp_phat_map(Tensor mix, Tensor twiddle, Tensor pair_i, Tensor pair_j, Tensor tau, Tensor omega, int window, "
         "int step, int n_windows, int nfft, int hop, float tol) -> Tensor");
@@ -590,6 +616,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("energies", &energies);
   m.impl("pair_sisdr", &pair_sisdr);
   m.impl("segment_sisdr", &segment_sisdr);
+  m.impl("voiced_segments", &voiced_segments);
   m.impl("center_rows_", &center_rows_);
   m.impl("srp_phat_map", &srp_phat_map);
   m.impl("pruner_covariance", &pruner_covariance);

@@ -89,6 +89,78 @@ def split_wav(wav: np.ndarray, top_db: float = 18):
     return segs
 
 
+# ---- voiced segments, stated for a kernel (csrc/misc_kernels.hip: asw_voiced_segments) --------
+VOICED_A2 = 1e-10                       # amin**2 of nonsilent_intervals
+VOICED_Q = 0.04 * 0.04                  # split_wav's quiet bound on the peak RMS, squared
+
+
+def _frame_ms_f64(wav: np.ndarray) -> np.ndarray:
+    """Mean square of librosa's centred, zero-padded 1024 / 256 frames, [1 + T//256] float64, in one fixed order of
+    additions: the 256-sample block sums come from 64 partial sums of 4 consecutive samples each and a six-step
+    butterfly over them (what a 64-lane wavefront does), and a frame is the sum of its four blocks, left to right."""
+    y = np.ascontiguousarray(wav, dtype=np.float32).astype(np.float64)
+    T = y.shape[0]
+    nblk = -(-T // 256)
+    q = np.zeros(nblk * 256, dtype=np.float64)
+    q[:T] = y * y                                   # exact: a float32 squared fits a double
+    q = q.reshape(nblk, 64, 4)
+    p = ((q[:, :, 0] + q[:, :, 1]) + q[:, :, 2]) + q[:, :, 3]
+    for s in (32, 16, 8, 4, 2, 1):
+        p = p[:, :s] + p[:, s:2 * s]
+    nfr = 1 + T // 256
+    b = np.zeros(nfr + 3, dtype=np.float64)         # b[k] = block k - 2; blocks outside [0, nblk) are 0
+    b[2:2 + nblk] = p[:, 0]
+    return (((b[0:nfr] + b[1:nfr + 1]) + b[2:nfr + 2]) + b[3:nfr + 3]) / 1024.0
+
+
+def _voiced_reference(ms: np.ndarray, top_db: float):
+    """(thr, ref2) of the decision ``max(A2, ms[f]) > thr * ref2``."""
+    thr = 10.0 ** (-float(top_db) / 10.0)
+    peak2 = float(np.max(ms))
+    ref2 = max(VOICED_A2, VOICED_Q) if peak2 < VOICED_Q else max(VOICED_A2, peak2)
+    return thr, ref2
+
+
+def voiced_segments_f64(wav: np.ndarray, top_db: float = 18.0):
+    """``split_wav`` restated in float64 without logarithms, so that a kernel reproduces it bit for bit: returns
+    (segments as a list of [start, end], ms [1 + T//256] float64).  Frame f is voiced iff
+    ``max(A2, ms[f]) > thr * ref2`` with ``thr = 10 ** (-top_db / 10)`` and ``ref2`` the peak mean square (``Q`` when the
+    peak lies below it); maximal voiced runs [f0, f1) become the intervals [min(256 f0, T), min(256 f1, T)), and
+    the intervals are cut as in ``split_wav``: shorter than 1000 samples dropped, longer than 4000 cut into
+    ``n // 4000`` pieces of which the last takes the remainder.  The segments are ascending, disjoint and at least
+    1000 samples long, so there are at most ``T // 1000`` of them."""
+    T = int(np.shape(wav)[0])
+    ms = _frame_ms_f64(wav)
+    thr, ref2 = _voiced_reference(ms, top_db)
+    voiced = np.maximum(VOICED_A2, ms) > thr * ref2
+    edges = np.flatnonzero(np.diff(np.concatenate([[False], voiced, [False]]).astype(np.int8)))
+    segs = []
+    for f0, f1 in edges.reshape(-1, 2):
+        a, b = min(256 * int(f0), T), min(256 * int(f1), T)
+        n = b - a
+        if n < 1000:
+            continue
+        if n > 4000:
+            k = n // 4000
+            for i in range(k):
+                segs.append([a + 4000 * i, b if i == k - 1 else a + 4000 * (i + 1)])
+        else:
+            segs.append([a, b])
+    return segs, ms
+
+
+def voiced_margin_db(wav: np.ndarray, top_db: float = 18.0) -> float:
+    """Smallest distance in dB (float64) of any frame's level from the decision threshold of
+    ``voiced_segments_f64`` and of the peak from the quiet bound ``Q``: how far a waveform is from a decision that
+    another rounding of the same levels could take differently.  For the tests."""
+    ms = _frame_ms_f64(wav)
+    thr, ref2 = _voiced_reference(ms, top_db)
+    with np.errstate(divide="ignore"):
+        frames = np.abs(10.0 * np.log10(np.maximum(VOICED_A2, ms) / (thr * ref2)))
+        peak = abs(10.0 * np.log10(np.float64(np.max(ms)) / VOICED_Q))
+    return float(min(np.min(frames), peak))
+
+
 def split_wise_sisdr(est, ref, segments):
     """sep/helpers/eval_utils.py:73-82."""
     assert len(segments) > 0

@@ -42,15 +42,17 @@ def _sync():
 GEOMETRY_CACHE_SIZE = 8        # arrays kept by JointModel.mic_array_for (a 7-mic bench array: about 65 MB of tables)
 
 
-def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host"):
-    """The configuration string of the reference's ``setup`` (:125-131), extended by the pruning method and the
-    geometry mode when they are not the defaults."""
+def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host", segments="host"):
+    """The configuration string of the reference's ``setup`` (:125-131), extended by the pruning method, the
+    geometry mode and the segments mode when they are not the defaults."""
     key = '~'.join([f"{x:.05f}" for x in np.asarray(mic_positions).flatten()]) \
         + '|' + '~'.join([f"{x:.05f}" for x in speaker_range])
     if prone_method != "SRP":
         key += '|' + str(prone_method)
     if geometry != "host":
         key += '|geometry=' + str(geometry)
+    if segments != "host":
+        key += '|segments=' + str(segments)
     return key
 
 
@@ -63,11 +65,15 @@ class _Pending(object):
 
 
 class JointModel(object):
-    def __init__(self, spot_model, sep_model=None, device=None, geometry="host"):
+    def __init__(self, spot_model, sep_model=None, device=None, geometry="host", segments="host"):
         """``geometry``: default of ``setup``'s argument of that name and the mode of the per-mixture arrays of
-        ``mic_array_for`` -- "host" or "device" (see ``MicArray``)."""
+        ``mic_array_for`` -- "host" or "device" (see ``MicArray``).  ``segments``: the same for where the clustering
+        finds the voiced segments of the cluster heads."""
         if geometry not in ("host", "device"):
             raise ValueError(f'geometry must be "host" or "device", got {geometry!r}')
+        if segments not in ("host", "device"):
+            raise ValueError(f'segments must be "host" or "device", got {segments!r}')
+        self.segments = segments
         self.spot_model = spot_model
         self.sep_model = sep_model
         self.device = device
@@ -80,21 +86,24 @@ class JointModel(object):
         self.Mic_processor = None
         self._mix_dev = self._mix_src = None
 
-    def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP", geometry=None):
+    def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP", geometry=None,
+              segments=None):
         """(Re)build the geometry tables unless the configuration is unchanged (:125-137).
         One-off per geometry and excluded from latency, as the reference's README notes.
         ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS"; "DENSE": no pruner, the whole
         coarse TDoA lattice of the array) and is part of the configuration, and so is ``geometry`` ("host" |
-        "device", default: the model's): where the tables are built."""
+        "device", default: the model's): where the tables are built.  ``segments`` ("host" | "device", default: the
+        model's): where the voiced segments of the cluster heads are found."""
         geometry = self.geometry if geometry is None else geometry
-        key = config_key(mic_positions, speaker_range, prone_method, geometry)
+        segments = self.segments if segments is None else segments
+        key = config_key(mic_positions, speaker_range, prone_method, geometry, segments)
         if key == self.previous_config:
             print("reuse the previous recycle!")
             return
         import gc
         gc.unfreeze()                       # a previous geometry may go now
         self.Mic_processor = MicArray(mic_positions, Spk_Range=speaker_range, Prone_method=prone_method,
-                                      device=self.device, geometry=geometry)
+                                      device=self.device, geometry=geometry, segments=segments)
         self.previous_config = key
         # The geometry tables are tens of thousands of small arrays and lists that live as long as
         # this configuration.  Left in the collector's oldest generation they make every full
@@ -115,7 +124,7 @@ class JointModel(object):
         generation.  Instead the batch raises the collector's oldest-generation threshold while it runs
         (``batching.no_full_collections``), so no full collection lands inside a search, and an evicted array is
         released by reference counting alone -- its tables hold no reference cycle."""
-        key = config_key(mic_positions, speaker_range, prone_method, self.geometry)
+        key = config_key(mic_positions, speaker_range, prone_method, self.geometry, self.segments)
         with self._geometry_lock:
             hit = self._geometry_cache.get(key)
             if hit is None:
@@ -134,7 +143,7 @@ class JointModel(object):
             return hit
         try:
             mp = MicArray(np.asarray(mic_positions), Spk_Range=speaker_range, Prone_method=prone_method,
-                          device=self.device, geometry=self.geometry)
+                          device=self.device, geometry=self.geometry, segments=self.segments)
         except BaseException as exc:
             with self._geometry_lock:
                 self._geometry_cache.pop(key, None)
@@ -156,7 +165,7 @@ class JointModel(object):
         per-mixture loop of ``shard.localize_batch(..., geometries=...)``."""
         method = self.Mic_processor.Prone_method if self.Mic_processor is not None else "SRP"
         self.Mic_processor = self.mic_array_for(mic_positions, speaker_range, method)
-        self.previous_config = config_key(mic_positions, speaker_range, method, self.geometry)
+        self.previous_config = config_key(mic_positions, speaker_range, method, self.geometry, self.segments)
 
     def forward(self, mix_data):
         """-> (patches, audio_loc, audio, SRP_drop, stage1_drop, spot_times) (:142-149)."""

@@ -78,13 +78,19 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
 class MicArray(object):
     def __init__(self, mic_positions, demo=False, Spk_Range=None, grid_size=0.05, Prone_method="SRP",
                  MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None,
-                 geometry="host"):
+                 geometry="host", segments="host"):
         """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
         (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture).
         ``Prone_method="DENSE"`` takes the pruner out: ``Apply_SRP_PHAT`` returns every width-``INIT_WIDTH`` cube of
         the array's TDoA lattice, and the later stages run on that list unchanged.  ``"DENSE_NMS"`` has the same
         stage 1; its coarse stage keeps a cube only if no cube within ``search.LATTICE_NMS_RADIUS`` cells on every
-        pair scored higher, and ``lattice_nms`` = {"radius", "best", "degree"} records the latest search."""
+        pair scored higher, and ``lattice_nms`` = {"radius", "best", "degree"} records the latest search.
+        ``segments``: where the global clustering finds the voiced segments of the cluster heads -- "host"
+        (``hostdsp.split_wav`` per head) or "device" (one ``voiced_segments`` call of the scorer for all heads, the
+        tables handed to its ``segment_sisdr_device`` where they are; needs the HIP spot model)."""
+        if segments not in ("host", "device"):
+            raise ValueError(f'segments must be "host" or "device", got {segments!r}')
+        self.segments = segments
         if Prone_method not in PRONE_METHODS:
             # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
             raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
@@ -231,7 +237,8 @@ class MicArray(object):
         out = self._cluster_group(g, big, patches, list(energies_g[:, 0]), list(energies_g[:, 1]), area, centre,
                                   T_len, thr_new, sample_gt, sim_of, audio_of)
         for n, pair in enumerate(out):     # the global clustering needs these; here they hide behind the GPU
-            self._seg_cache[id(pair[1])] = (pair[1], split_wav(pair[1]))
+            if self.segments != "device":  # (device mode: the clustering finds all heads' segments in one launch)
+                self._seg_cache[id(pair[1])] = (pair[1], split_wav(pair[1]))
             self._dev_cache[id(pair[1])] = (pair[1], kept["rows"][n])      # the same waveform, still on the GPU
         return out
 
@@ -242,6 +249,8 @@ class MicArray(object):
         resident = hasattr(spot_model, "shift_and_sep_resident")
         inner = getattr(spot_model, "inner", spot_model)                 # ShardedSpotModel wraps the scorer
         self._device_scorer = inner if (resident and hasattr(inner, "segment_sisdr")) else None
+        if self.segments == "device" and not hasattr(self._device_scorer, "voiced_segments"):
+            raise RuntimeError('segments="device" needs a spot model with voiced_segments() (the HIP SpotModel)')
         sharded = getattr(spot_model, "world", 1) > 1
         n_groups = len(candidate_finished)
         self.spotforming_times = 0
@@ -312,7 +321,8 @@ class MicArray(object):
                 lambda k, h, sep=sep: si_sdr(sep[k, :], sep[h]), lambda heads, sep=sep: [sep[h, :] for h in heads]))
         if sharded:
             # the voiced segments of every head travel with its tuple: the global clustering of every rank
-            # then finds them cached for the remote heads too, as it does for its own
+            # then finds them cached for the remote heads too, as it does for its own (segments="device": the cache
+            # is empty, None travels in their place and every rank finds them on its GPU)
             tagged = [p + (self._seg_cache.get(id(p[1]), (None, None))[1],) for p in output_pair]
             merged = spot_model.gather_pairs(tagged)
             output_pair = [t[:-1] for t in merged]
@@ -341,7 +351,8 @@ class MicArray(object):
             gbounds.append(gbounds[-1] + n)
         self.fine_energies = spot_model.all_gather_groups(energies, mine, gbounds, owners=owners)
         # the voiced segments of every head travel with its tuple: the global clustering of every rank
-        # then finds them cached for the remote heads too, as it does for its own
+        # then finds them cached for the remote heads too, as it does for its own (segments="device": the cache
+        # is empty, None travels in their place and every rank finds them on its GPU)
         tagged = [p + (self._seg_cache.get(id(p[1]), (None, None))[1],) for p in output_pair]
         merged = spot_model.gather_pairs(tagged)
         output_pair = [t[:-1] for t in merged]
@@ -430,12 +441,15 @@ class MicArray(object):
         # (SURVEY.md §8f-2).  Any other model keeps the reference's host loops.
         scorer = getattr(self, "_device_scorer", None)
         cache = getattr(self, "_seg_cache", {})
+        on_device = getattr(self, "segments", "host") == "device"
+        if on_device and not hasattr(scorer, "voiced_segments"):
+            raise RuntimeError('segments="device" needs a spot model with voiced_segments() (the HIP SpotModel)')
         seg_all = []
-        for c in cands:
+        for c in ([] if on_device else cands):
             hit = cache.get(id(c[1]))
             seg_all.append(hit[1] if hit is not None and hit[0] is c[1] else split_wav(c[1]))
         full_dev = seg_dev = None
-        if scorer is not None and len(cands) > 1:
+        if scorer is not None and (len(cands) > 1 or (on_device and len(cands) > 0)):
             import torch
             dev_rows = [getattr(self, "_dev_cache", {}).get(id(c[1])) for c in cands]
             if all(r is not None and r[0] is c[1] for r, c in zip(dev_rows, cands)):
@@ -443,8 +457,20 @@ class MicArray(object):
             else:
                 waves = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(c[1], dtype=np.float32) for c in cands])))
                 waves = waves.to(scorer.device if getattr(scorer, "device", None) is not None else "cuda")
-            full_dev = scorer.pair_sisdr(waves)
-            seg_dev, _ = scorer.segment_sisdr(waves, seg_all)
+            if on_device:
+                # one launch pair finds every head's segments; the tables stay where segment_sisdr reads them and
+                # only they (a few KB) come back, for len(segs) and the seg_tab slices below
+                seg_tab_dev, cnt_dev = scorer.voiced_segments(waves)
+                if len(cands) > 1:
+                    full_dev = scorer.pair_sisdr(waves)
+                    seg_dev, cnt = scorer.segment_sisdr_device(waves, seg_tab_dev, cnt_dev)
+                else:
+                    cnt = cnt_dev.cpu().numpy()
+                seg_host = seg_tab_dev.cpu().numpy()
+                seg_all = [seg_host[i, :int(cnt[i])] for i in range(len(cands))]
+            else:
+                full_dev = scorer.pair_sisdr(waves)
+                seg_dev, _ = scorer.segment_sisdr(waves, seg_all)
         clusters = {}
         wrong = []
         centres = [c[0].center_pos() for c in cands]

@@ -252,6 +252,24 @@ class SpotModel:
                                                torch.from_numpy(cnt).to(waves.device))
         return out.cpu().numpy(), cnt
 
+    def voiced_segments(self, waves, top_db: float = 18.0):
+        """The voiced segments of every row of ``waves`` (device tensor [n,T] float32) found on the GPU
+        (``hostdsp.voiced_segments_f64``, the float64 statement of ``split_wav``): returns the device tensors
+        (segments [n, max(1, T//1000), 2] int32 with [0, 0] beyond a row's count, counts [n] int32).  Nothing is
+        copied and nothing waits for the device."""
+        seg, cnt, _ms = native.torch_ops().voiced_segments(waves.contiguous(), float(top_db), False)
+        return seg, cnt
+
+    def segment_sisdr_device(self, waves, seg_dev, cnt_dev):
+        """``segment_sisdr`` on tables that are already on the device (``voiced_segments``): the same op, the same
+        return -- (host ndarray [n,n,kmax] float64 with kmax = max(1, largest count), counts [n]).  Only the counts
+        come to the host before the launch: they size the result, so the slots no waveform uses are not computed,
+        filled with NaN and read back."""
+        cnt = cnt_dev.cpu().numpy()
+        kmax = max(1, int(cnt.max()) if cnt.size else 1)
+        out = native.torch_ops().segment_sisdr(waves.contiguous(), seg_dev[:, :kmax].contiguous(), cnt_dev)
+        return out.cpu().numpy(), cnt
+
     def forward(self, mix, window_embedding):
         """Network.forward: mix [B,M,t] (already normalised), window_embedding [B,2] -> [B,1,t]
         (device tensor).  Rows are grouped by identical embedding because the window gate

@@ -521,6 +521,27 @@ int asw_pair_sisdr(const float* y, int n, int T, double* out, void* stream);
 int asw_segment_sisdr(const float* y, int n, int T, const int32_t* segments, const int32_t* seg_count,
                       int kmax, double* out, void* stream);
 
+/* Voiced segments of n waveforms on the device (split_wav, eval_utils.py:43-70; call sites Mic_Array.py:399-500), as
+ * hostdsp.voiced_segments_f64 states them and equal to that statement bit for bit: y [n][T] float32, any T >= 1 (a
+ * row need not be 16-byte aligned).  The mean square of librosa's centred, zero-padded 1024 / 256 frames is formed in
+ * float64 in one fixed order -- per 256-sample block 64 partial sums of 4 consecutive squares, a six-step butterfly
+ * over them, a frame = its four blocks left to right, / 1024 -- and frame f of nfr = 1 + T/256 is voiced iff
+ * max(1e-10, ms[f]) > thr * ref2, ref2 = max(1e-10, Q) when the peak max_f ms[f] < Q and max(1e-10, peak) otherwise.
+ * thr = 10^(-top_db/10) and Q = 0.04 * 0.04 are the caller's doubles.  Maximal voiced runs [f0, f1) give the
+ * intervals [min(256 f0, T), min(256 f1, T)); one shorter than 1000 samples is dropped, one longer than 4000 is cut
+ * into len / 4000 pieces of 4000 of which the last takes the remainder.  segments int32 [n][kcap][2] receives the
+ * [start, end) pairs of waveform i in ascending order and [0, 0] in every slot from counts[i] on (so every slot is
+ * written), counts int32 [n]; kcap >= max(1, T / 1000) always suffices and is required.  ms [n][nfr] float64 receives
+ * the frame values, or NULL.  workspace: asw_voiced_segments_workspace_bytes(n, T) bytes, 8-byte aligned (the block
+ * sums, [n][ceil(T/256)] float64; 0 with the error message set for n outside 0..65535 or T < 1).  No atomics, no
+ * device-side assert: two calls give identical bytes, and the result does not depend on what the outputs or the
+ * workspace held.  With NaN or Inf samples the result is unspecified but every access stays in bounds.  Every refusal
+ * (n < 0 or > 65535, T < 1, kcap too small, null pointer, short workspace) happens before the first launch; n = 0
+ * succeeds and launches nothing.  The tables are what asw_segment_sisdr reads. */
+size_t asw_voiced_segments_workspace_bytes(int n, int T);
+int asw_voiced_segments(const float* y, int n, int T, double thr, double Q, int32_t* segments, int kcap,
+                        int32_t* counts, double* ms, void* workspace, size_t workspace_bytes, void* stream);
+
 /* HOST function (no GPU): breadth-first subdivision of one coarse hypercube into the fine
  * candidate hypercubes -- search_area / binary_area_divide_width
  * (sep/helpers/local_utils_3d.py:212-335) with Patch.check_out / hyperbola_sample
