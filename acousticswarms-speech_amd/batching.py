@@ -247,6 +247,9 @@ class MixtureScorer(object):
     def segment_sisdr_device(self, waves, seg_dev, cnt_dev):
         return self.inner_model.segment_sisdr_device(waves, seg_dev, cnt_dev)
 
+    def fine_clusters(self, waves, bounds, en_dev, gate, group_gate, min_trigger):
+        return self.inner_model.fine_clusters(waves, bounds, en_dev, gate, group_gate, min_trigger)
+
 
 def mixture_view(mic_array):
     """A per-search view of a MicArray: the geometry tables (tens of MB, read-only) are shared, everything a

@@ -1,0 +1,242 @@
+// cluster_kernels.hip -- the fine stage's per-coarse-patch clustering (MicArray._cluster_group,
+// sep/Mic_Array.py:283-383) for all coarse patches of a call, as fine_cluster.fine_clusters_f64 states it: float64, no
+// logarithm, one fixed order of additions -- every value below is the statement's value to the bit.
+#include "asw_common.h"
+
+#include <vector>
+
+namespace {
+
+constexpr int GR = 8;                            // a workgroup of group_gram_kernel owns GR x GR row pairs
+constexpr long GRAM_MAX_ELEMS = 1L << 27;        // cap of sum n_g^2 per call (1 GiB of float64)
+
+// ---------------------------------------------------------------------------
+// group_gram_kernel: G[a][b] = sum_t double(y_a[t]) * double(y_b[t]) for the row pairs of every group, one launch.
+// Workgroup w reads (group, tile row ta, tile column tb >= ta) from tiles[2w], tiles[2w + 1] = ta << 16 | tb.  Thread l
+// sums t = l, l + 256, ... from 0.0 with 4-byte loads -- coalesced whatever the alignment of a row --, a float32 x
+// float32 product being exact in double so that the fused multiply-add rounds the statement's sum.  Then the
+// statement's reduction: the butterfly p[l] += p[l + s], s = 32 .. 1, inside each wavefront (one 64-wide quarter), and
+// (w0 + w1) + (w2 + w3) over the four through LDS.  A row past the ragged edge of the group repeats the group's last
+// row and its pairs are not stored, so the kept pairs do not see the edge.  Both halves of an off-diagonal tile are
+// stored from the one sum; inside a diagonal tile [i][j] and [j][i] add the same products in the same order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void group_gram_kernel(const float* __restrict__ y, int T, const int* __restrict__ bounds,
+                                                         const int* __restrict__ goff, const int* __restrict__ tiles,
+                                                         double* __restrict__ gram) {
+  __shared__ double red[4][GR * GR];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int g = tiles[2 * blockIdx.x], tt = tiles[2 * blockIdx.x + 1];
+  const int ta = tt >> 16, tb = tt & 0xffff;
+  const int b0 = bounds[g], n = bounds[g + 1] - b0;
+  const float* ra[GR];
+  const float* rb[GR];
+#pragma unroll
+  for (int i = 0; i < GR; ++i) {
+    const int a = ta * GR + i, b = tb * GR + i;
+    ra[i] = y + (long)(b0 + (a < n ? a : n - 1)) * T;
+    rb[i] = y + (long)(b0 + (b < n ? b : n - 1)) * T;
+  }
+  double acc[GR][GR];
+#pragma unroll
+  for (int i = 0; i < GR; ++i)
+#pragma unroll
+    for (int j = 0; j < GR; ++j) acc[i][j] = 0.0;
+  for (int t = tid; t < T; t += 256) {
+    double va[GR], vb[GR];
+#pragma unroll
+    for (int i = 0; i < GR; ++i) {
+      va[i] = (double)ra[i][t];
+      vb[i] = (double)rb[i][t];
+    }
+#pragma unroll
+    for (int i = 0; i < GR; ++i)
+#pragma unroll
+      for (int j = 0; j < GR; ++j) acc[i][j] = __builtin_fma(va[i], vb[j], acc[i][j]);
+  }
+#pragma unroll
+  for (int i = 0; i < GR; ++i)
+#pragma unroll
+    for (int j = 0; j < GR; ++j) {
+      double p = acc[i][j];
+#pragma unroll
+      for (int s = 32; s > 0; s >>= 1) p = p + __shfl_down(p, s, 64);     // lanes < s hold the statement's p[:s]
+      if (lane == 0) red[wid][i * GR + j] = p;
+    }
+  __syncthreads();
+  if (tid < GR * GR) {
+    const double v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    const int a = ta * GR + tid / GR, b = tb * GR + tid % GR;
+    if (a < n && b < n) {
+      double* __restrict__ out = gram + goff[g];
+      out[(long)a * n + b] = v;
+      if (ta != tb) out[(long)b * n + a] = v;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// fine_cluster_kernel: one wavefront per group.  (1) order[] of the group := its rows in index order, so that every
+// slot holds a row of the group whatever the powers are; the open flag: max power2 >= group_gate.  (2) each candidate's
+// place in the visiting order by counting the candidates that go before it -- larger power, or equal power and a lower
+// index -- O(n^2), any n.  (3) the greedy loop over the visiting order, serial in the candidates: the lanes test the
+// current one against 64 heads at a time, the ballot's lowest set bit is the first head in creation order; a group
+// with more heads takes more rounds.  The head list is `heads` (workspace, the group's own n slots): nothing is sized
+// by LDS.  The wavefront is the whole workgroup, so __syncthreads() here is the fence that lets every lane read what
+// another lane stored to global memory.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void fine_cluster_kernel(const double* __restrict__ energies, const double* __restrict__ gate,
+                                                          const double* __restrict__ group_gate, double min_trigger, double ratio,
+                                                          const int* __restrict__ bounds, const int* __restrict__ goff,
+                                                          const double* __restrict__ gram, int* __restrict__ heads,
+                                                          int* __restrict__ order, int* __restrict__ label) {
+  const int lane = threadIdx.x, g = blockIdx.x;
+  const int b0 = bounds[g], n = bounds[g + 1] - b0;
+  if (n <= 0) return;                                               // the whole workgroup leaves
+  const double* __restrict__ en = energies + (long)b0 * 2;
+  double top = -__builtin_inf();
+  for (int i = lane; i < n; i += 64) {
+    order[b0 + i] = b0 + i;
+    label[b0 + i] = -1;
+    const double v = en[2 * i + 1];
+    top = v > top ? v : top;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(top, o, 64);
+    top = w > top ? w : top;
+  }
+  const bool open = !(top < group_gate[g]);
+  __syncthreads();
+  for (int i = lane; i < n; i += 64) {
+    const double p = en[2 * i];
+    int before = 0;
+    for (int j = 0; j < n; ++j) {
+      const double q = en[2 * j];
+      before += (q > p || (q == p && j < i)) ? 1 : 0;
+    }
+    if (before < n) order[b0 + before] = b0 + i;                    // always true; spelled out for the reader of bounds
+  }
+  __syncthreads();
+  if (!open) return;
+  const double* __restrict__ G = gram + goff[g];
+  int* __restrict__ hd = heads + b0;
+  int nh = 0;
+  for (int r = 0; r < n; ++r) {
+    int k = order[b0 + r] - b0;
+    k = k < 0 ? 0 : (k >= n ? n - 1 : k);                           // (a row of the group by construction)
+    if (en[2 * k + 1] < gate[b0 + k] || en[2 * k] < min_trigger) continue;    // wave-uniform
+    const double ee = G[(long)k * n + k];
+    int home = -1;
+    for (int c = 0; c < nh && home < 0; c += 64) {
+      const int h = c + lane < nh ? hd[c + lane] : -1;
+      bool same = false;
+      if (h >= 0) {
+        const double ss = G[(long)h * n + h], es = G[(long)k * n + h];
+        const double sss = es * es / ss;
+        double snn = ee - sss;
+        snn = (snn > 0.0 ? snn : 0.0) + 1e-8;
+        same = sss > ratio * snn;
+      }
+      const unsigned long long hit = __ballot(same);
+      if (hit) home = __shfl(h, __builtin_ctzll(hit), 64);
+    }
+    if (home < 0) {
+      if (lane == 0) {
+        hd[nh] = k;
+        label[b0 + k] = b0 + k;
+      }
+      ++nh;
+      __syncthreads();                                              // the next candidate's lanes read hd[]
+    } else if (lane == 0) {
+      label[b0 + k] = b0 + home;
+    }
+  }
+}
+
+// bounds[G + 1] checked: starts at 0, does not decrease, ends at N; -> sum n_g^2 and the number of tiles
+int check_bounds(const char* who, const int32_t* bounds, int G, long N, long* elems, long* n_tiles) {
+  ASW_CHECK_ARG(G >= 0 && G <= 65535, "%s: G = %d outside 0..65535", who, G);
+  ASW_CHECK_ARG(bounds, "%s: null bounds", who);
+  ASW_CHECK_ARG(bounds[0] == 0, "%s: bounds[0] = %d, not 0", who, bounds[0]);
+  long e = 0, nt = 0;
+  for (int g = 0; g < G; ++g) {
+    const long n = (long)bounds[g + 1] - bounds[g];
+    ASW_CHECK_ARG(n >= 0, "%s: bounds decrease at group %d (%d after %d)", who, g, bounds[g + 1], bounds[g]);
+    e += n * n;
+    ASW_CHECK_ARG(e <= GRAM_MAX_ELEMS, "%s: sum of n_g^2 exceeds the cap of %ld elements at group %d", who, GRAM_MAX_ELEMS, g);
+    const long t = (n + GR - 1) / GR;
+    nt += t * (t + 1) / 2;
+  }
+  ASW_CHECK_ARG(N < 0 || bounds[G] == N, "%s: bounds[G] = %d, not N = %ld", who, bounds[G], N);
+  *elems = e;
+  *n_tiles = nt;
+  return ASW_OK;
+}
+
+// workspace: [elems] float64 Gram | int32: bounds [G + 1] | goff [G + 1] | tiles [2 n_tiles] | heads [N]
+size_t workspace_need(long elems, int G, long n_tiles, long N) {
+  return (size_t)elems * sizeof(double) + ((size_t)2 * (G + 1) + (size_t)2 * n_tiles + (size_t)N) * sizeof(int32_t);
+}
+
+}  // namespace
+
+extern "C" size_t asw_fine_clusters_workspace_bytes(const int32_t* bounds_host, int G) {
+  long elems = 0, n_tiles = 0;
+  if (check_bounds("fine_clusters_workspace_bytes", bounds_host, G, -1, &elems, &n_tiles) != ASW_OK) return 0;
+  return workspace_need(elems, G, n_tiles, bounds_host[G]);
+}
+
+extern "C" int asw_fine_clusters(const float* y, int N, int T, const int32_t* bounds_host, int G, const double* energies,
+                                 const double* gate, const double* group_gate, double min_trigger, double ratio,
+                                 void* workspace, size_t workspace_bytes, int32_t* order, int32_t* label, double* gram,
+                                 void* stream) {
+  ASW_CHECK_ARG(N >= 0, "fine_clusters: N = %d < 0", N);
+  ASW_CHECK_ARG(T >= 1, "fine_clusters: T = %d < 1", T);
+  long elems = 0, n_tiles = 0;
+  if (int rc = check_bounds("fine_clusters", bounds_host, G, N, &elems, &n_tiles)) return rc;
+  if (N == 0 || G == 0) return ASW_OK;
+  ASW_CHECK_ARG(y && energies && gate && group_gate && workspace, "fine_clusters: null pointer");
+  ASW_CHECK_ARG(order && label, "fine_clusters: null output");
+  const size_t need = workspace_need(elems, G, n_tiles, N);
+  ASW_CHECK_ARG(workspace_bytes >= need, "fine_clusters: workspace of %zu bytes too small, %zu needed", workspace_bytes, need);
+  ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "fine_clusters: workspace not 8-byte aligned");
+
+  // the small table both kernels read: group bounds, Gram offsets, workgroup -> (group, tile)
+  std::vector<int32_t> table((size_t)2 * (G + 1) + (size_t)2 * n_tiles);
+  int32_t* hb = table.data();
+  int32_t* ho = hb + (G + 1);
+  int32_t* ht = ho + (G + 1);
+  long e = 0, w = 0;
+  for (int g = 0; g <= G; ++g) {
+    hb[g] = bounds_host[g];
+    ho[g] = (int32_t)e;
+    if (g == G) break;
+    const long n = (long)bounds_host[g + 1] - bounds_host[g], t = (n + GR - 1) / GR;
+    for (long a = 0; a < t; ++a)
+      for (long b = a; b < t; ++b) {
+        ht[2 * w] = g;
+        ht[2 * w + 1] = (int32_t)(a << 16 | b);                     // t <= 1449 under the cap
+        ++w;
+      }
+    e += n * n;
+  }
+  hipStream_t s = asw::as_stream(stream);
+  double* gram_ws = static_cast<double*>(workspace);
+  int32_t* db = reinterpret_cast<int32_t*>(gram_ws + elems);
+  int32_t* dofs = db + (G + 1);
+  int32_t* dt = dofs + (G + 1);
+  int32_t* heads = dt + 2 * n_tiles;
+  double* gm = gram ? gram : gram_ws;
+  // pageable source: the runtime has taken the table before the call returns
+  ASW_HIP(hipMemcpyAsync(db, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  {
+    asw::ProfScope prof(s, "group_gram", 2.0 * (double)elems * T, 0.0);
+    hipLaunchKernelGGL(group_gram_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, y, T, db, dofs, dt, gm);
+    ASW_LAUNCH_CHECK();
+  }
+  asw::ProfScope prof(s, "fine_cluster", 0.0, (double)elems * 8);
+  hipLaunchKernelGGL(fine_cluster_kernel, dim3(G), dim3(64), 0, s, energies, gate, group_gate, min_trigger, ratio, db, dofs,
+                     gm, heads, order, label);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}

@@ -219,6 +219,49 @@ std::tuple<Tensor, Tensor, Tensor> voiced_segments(const Tensor& y, double top_d
   return {segments, counts, ms};
 }
 
+// -> order [N] int32, label [N] int32, gram [sum n_g^2] float64 (empty unless want_gram): the fine stage's clustering of
+// every group of rows (fine_cluster.fine_clusters_f64).  bounds is a CPU tensor [G + 1] int32: the C entry point checks
+// it on the host.  ratio is formed here in double as the statement forms it: 10 ** (sim_db / 10).
+std::tuple<Tensor, Tensor, Tensor> fine_clusters(const Tensor& y, const Tensor& bounds, const Tensor& energies,
+                                                 const Tensor& gate, const Tensor& group_gate, double min_trigger,
+                                                 double sim_db, bool want_gram) {
+  need(y, "y", at::kFloat, 2);
+  need(energies, "energies", at::kDouble, 2);
+  need(gate, "gate", at::kDouble, 1);
+  need(group_gate, "group_gate", at::kDouble, 1);
+  same_device(y, energies, "y and energies");
+  same_device(y, gate, "y and gate");
+  same_device(y, group_gate, "y and group_gate");
+  TORCH_CHECK(bounds.is_cpu() && bounds.scalar_type() == at::kInt && bounds.dim() == 1 && bounds.is_contiguous() &&
+                  bounds.size(0) >= 1,
+              "bounds must be a contiguous CPU Int tensor [G + 1]");
+  const int N = checked_int(y.size(0), "N"), T = checked_int(y.size(1), "T");
+  const int G = checked_int(bounds.size(0) - 1, "G");
+  TORCH_CHECK(T >= 1, "y must hold at least one sample per row");
+  TORCH_CHECK(energies.size(0) == N && energies.size(1) == 2, "energies must be [N, 2]");
+  TORCH_CHECK(gate.size(0) == N, "gate must be [N]");
+  TORCH_CHECK(group_gate.size(0) == G, "group_gate must be [G]");
+  const int32_t* b = bounds.data_ptr<int32_t>();
+  const size_t ws_bytes = asw_fine_clusters_workspace_bytes(b, G);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_fine_clusters_workspace_bytes failed: ", asw_last_error());   // never 0 for valid bounds
+  TORCH_CHECK(b[G] == N, "bounds must end at the number of rows ", N, ", got ", b[G]);
+  int64_t elems = 0;
+  for (int g = 0; g < G; ++g) elems += static_cast<int64_t>(b[g + 1] - b[g]) * (b[g + 1] - b[g]);
+  Tensor order = at::empty({N}, y.options().dtype(at::kInt));
+  Tensor label = at::empty({N}, y.options().dtype(at::kInt));
+  Tensor gram = at::empty({want_gram ? elems : 0}, y.options().dtype(at::kDouble));
+  if (N == 0 || G == 0) return {order, label, gram};
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, y.options().dtype(at::kDouble));
+  const double ratio = std::pow(10.0, sim_db / 10.0);
+  Launch l(y);
+  check_status(asw_fine_clusters(y.data_ptr<float>(), N, T, b, G, energies.data_ptr<double>(), gate.data_ptr<double>(),
+                                 group_gate.data_ptr<double>(), min_trigger, ratio, ws.data_ptr(), ws_bytes,
+                                 order.data_ptr<int32_t>(), label.data_ptr<int32_t>(),
+                                 want_gram ? gram.data_ptr<double>() : nullptr, l.stream),
+               "asw_fine_clusters");
+  return {order, label, gram};
+}
+
 Tensor center_rows_(Tensor y) {
   need(y, "y", at::kFloat, 2);
   if (y.size(0) == 0) return y;
@@ -586,6 +629,8 @@ TORCH_LIBRARY(asw, m) {
   m.def("pair_sisdr(Tensor y) -> Tensor");
   m.def("segment_sisdr(Tensor y, Tensor segments, Tensor counts) -> Tensor");
   m.def("voiced_segments(Tensor y, float top_db=18.0, bool want_ms=False) -> (Tensor, Tensor, Tensor)");
+  m.def("fine_clusters(Tensor y, Tensor bounds, Tensor energies, Tensor gate, Tensor group_gate, float min_trigger, "
+        "float sim_db=-4.0, bool want_gram=False) -> (Tensor, Tensor, Tensor)");
   m.def("center_rows_(Tensor(a!) y) -> Tensor(a!)");
   m.def("srp_phat_map(Tensor mix, Tensor twiddle, Tensor pair_i, Tensor pair_j, Tensor tau, Tensor omega, int window, "
         "int step, int n_windows, int nfft, int hop, float tol) -> Tensor");
@@ -617,6 +662,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("pair_sisdr", &pair_sisdr);
   m.impl("segment_sisdr", &segment_sisdr);
   m.impl("voiced_segments", &voiced_segments);
+  m.impl("fine_clusters", &fine_clusters);
   m.impl("center_rows_", &center_rows_);
   m.impl("srp_phat_map", &srp_phat_map);
   m.impl("pruner_covariance", &pruner_covariance);

@@ -8,6 +8,7 @@ reference including its order-dependent quirks (documented inline).
 import numpy as np
 
 from .dense_grid import lattice_patches
+from .fine_cluster import clusters_of_group
 from .hostdsp import max_avg_power, si_sdr, split_wav, split_wise_sisdr
 from .patch import FS, SPEED_OF_SOUND, Patch, pair_offsets
 from . import search
@@ -78,7 +79,7 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
 class MicArray(object):
     def __init__(self, mic_positions, demo=False, Spk_Range=None, grid_size=0.05, Prone_method="SRP",
                  MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None,
-                 geometry="host", segments="host"):
+                 geometry="host", segments="host", clustering="host"):
         """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
         (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture).
         ``Prone_method="DENSE"`` takes the pruner out: ``Apply_SRP_PHAT`` returns every width-``INIT_WIDTH`` cube of
@@ -87,10 +88,17 @@ class MicArray(object):
         pair scored higher, and ``lattice_nms`` = {"radius", "best", "degree"} records the latest search.
         ``segments``: where the global clustering finds the voiced segments of the cluster heads -- "host"
         (``hostdsp.split_wav`` per head) or "device" (one ``voiced_segments`` call of the scorer for all heads, the
-        tables handed to its ``segment_sisdr_device`` where they are; needs the HIP spot model)."""
+        tables handed to its ``segment_sisdr_device`` where they are; needs the HIP spot model).
+        ``clustering``: where the fine stage clusters the candidates of its coarse patches -- "host" (per patch:
+        sort, thresholds, the greedy SI-SDR loop on one ``pair_sisdr`` read-back, one copy of the heads) or "device"
+        (per chunk of patches: one ``fine_clusters`` call of the scorer, ``fine_cluster.fine_clusters_f64`` on the
+        GPU, then one read-back of the decisions and one copy of all heads; needs the HIP spot model)."""
         if segments not in ("host", "device"):
             raise ValueError(f'segments must be "host" or "device", got {segments!r}')
+        if clustering not in ("host", "device"):
+            raise ValueError(f'clustering must be "host" or "device", got {clustering!r}')
         self.segments = segments
+        self.clustering = clustering
         if Prone_method not in PRONE_METHODS:
             # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
             raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
@@ -173,17 +181,9 @@ class MicArray(object):
         """Thresholding + SI-SDR clustering of the candidates of ONE coarse patch and the output
         tuples of its cluster heads (sep/Mic_Array.py:283-383).  ``sim_of(k, h)`` gives
         si_sdr(candidate k, candidate h); ``audio_of(heads)`` the heads' waveforms."""
-        out = []
-        big_label = -1
-        if sample_gt is not None:
-            for k in range(sample_gt.shape[1]):
-                if np.amax(np.abs(big.sample_offset - sample_gt[:, k])) < 3.5:
-                    big_label = k
-                    break
-        c = big.center_pos()
-        d = np.linalg.norm(c - self.mic_positions[0]) if c.shape[0] == 3 else 4
-        if np.amax(powers2) < thr_new / (1 + d):
-            return out
+        big_label = self._big_label(big, sample_gt)
+        if np.amax(powers2) < self._group_gate(big, thr_new):
+            return []
         order = np.argsort(-1 * np.array(powers))                           # sorted by total power (:339)
         clusters = {}
         # the reference scales the trigger by the length of the LAST candidate row (:343)
@@ -201,6 +201,28 @@ class MicArray(object):
                 clusters[k] = [k]
             else:
                 clusters[home].append(k)
+        return self._cluster_outputs(g, patches, powers, clusters, area, centre, big_label, audio_of)
+
+    @staticmethod
+    def _big_label(big, sample_gt):
+        """Index of the ground-truth source within 3.5 samples of the coarse patch, or -1 (sep/Mic_Array.py:283-289)."""
+        if sample_gt is not None:
+            for k in range(sample_gt.shape[1]):
+                if np.amax(np.abs(big.sample_offset - sample_gt[:, k])) < 3.5:
+                    return k
+        return -1
+
+    def _group_gate(self, big, thr_new):
+        """The level the best candidate of a coarse patch must reach for the patch to be clustered at all."""
+        c = big.center_pos()
+        d = np.linalg.norm(c - self.mic_positions[0]) if c.shape[0] == 3 else 4
+        return thr_new / (1 + d)
+
+    def _cluster_outputs(self, g, patches, powers, clusters, area, centre, big_label, audio_of):
+        """The tail of ``_cluster_group`` both clustering modes share: the trace entry of an open coarse patch and the
+        output tuples of its cluster heads.  ``clusters`` = {head: members}, heads in creation order, members in
+        visiting order (``weight_mean_pos`` sums in that order)."""
+        out = []
         self.trace["fine_clusters"][int(g)] = {int(h): [int(k) for k in m] for h, m in clusters.items()}
         if len(clusters) == 0:
             return out
@@ -242,6 +264,65 @@ class MicArray(object):
             self._dev_cache[id(pair[1])] = (pair[1], kept["rows"][n])      # the same waveform, still on the GPU
         return out
 
+    def _fine_gates(self, bigs, fines, thr_new):
+        """(bounds [G+1], gate [N], group_gate [G]) of a chunk of coarse patches for ``fine_clusters``: the very
+        thresholds ``_cluster_group`` forms, which depend on the patch geometry and ``thr_new`` only."""
+        bounds = np.zeros(len(fines) + 1, dtype=np.int32)
+        bounds[1:] = np.cumsum([len(f) for f in fines])
+        gate = np.empty(int(bounds[-1]), dtype=np.float64)
+        k = 0
+        for fine in fines:
+            for p in fine:
+                d = np.linalg.norm(p.center_pos() - self.mic_positions[0])
+                gate[k] = thr_new / (1 + d)
+                k += 1
+        group_gate = np.array([self._group_gate(big, thr_new) for big in bigs], dtype=np.float64).reshape(-1)
+        return bounds, gate, group_gate
+
+    def _device_groups(self, groups, bigs, fines, centres, waves, en_dev, gates, T_len, sample_gt, scorer):
+        """A chunk of coarse patches with the waveforms on the GPU and the clustering there too: one
+        ``fine_clusters`` call, one read-back of (energies, order, label), one gather and copy of all heads' rows;
+        then the bookkeeping of ``_cluster_group`` per patch.  -> (output tuples, host energies [N, 2])."""
+        import torch
+        bounds, gate, group_gate = gates
+        N = int(bounds[-1])
+        # the reference scales the trigger by the length of the LAST candidate row (:343)
+        min_trigger = self.MIN_TRIGGER_POWER / (3 * 48000) * T_len
+        order_d, label_d = scorer.fine_clusters(waves, bounds, en_dev, gate, group_gate, min_trigger)
+        # int32 is exact in float64: the three tables come back in one copy
+        back = torch.cat([en_dev.reshape(-1), order_d.to(torch.float64), label_d.to(torch.float64)]).cpu().numpy()
+        energies = back[:2 * N].reshape(N, 2)
+        order, label = back[2 * N:3 * N].astype(np.int64), back[3 * N:].astype(np.int64)
+        opened = []                                        # (position in the chunk, clusters) of the open patches
+        head_rows = []
+        for i in range(len(groups)):
+            b0, n = int(bounds[i]), int(bounds[i + 1] - bounds[i])
+            if n == 0 or np.amax(energies[b0:b0 + n, 1]) < group_gate[i]:
+                continue
+            clusters = clusters_of_group(order, label, b0, n)
+            opened.append((i, clusters))
+            head_rows.extend(b0 + h for h in clusters)
+        if head_rows:
+            idx = torch.from_numpy(np.asarray(head_rows, dtype=np.int64))
+            if waves.is_cuda:
+                idx = idx.pin_memory().to(waves.device, non_blocking=True)
+            rows_dev = waves.index_select(0, idx)
+            rows = rows_dev.cpu().numpy()
+        out, pos = [], 0
+        for i, clusters in opened:
+            b0, n = int(bounds[i]), int(bounds[i + 1] - bounds[i])
+            first = pos
+            pos += len(clusters)
+            pairs = self._cluster_outputs(groups[i], fines[i], list(energies[b0:b0 + n, 0]), clusters,
+                                          bigs[i].area_points, centres[i], self._big_label(bigs[i], sample_gt),
+                                          lambda heads, first=first: rows[first:first + len(heads)])
+            for m, pair in enumerate(pairs):
+                if self.segments != "device":
+                    self._seg_cache[id(pair[1])] = (pair[1], split_wav(pair[1]))
+                self._dev_cache[id(pair[1])] = (pair[1], rows_dev[first + m])
+            out.extend(pairs)
+        return out, energies
+
     def Spotform_Small_Patch_Parallel(self, mix_data, candidate_finished, spot_model, sample_gt=None,
                                       run_demo_folder=None):
         thr_new = min([SPOT_POWER_THRESHOLD2, self.Relative_Threshold]) if USE_RELATIVE_SPOT_POWER \
@@ -251,6 +332,9 @@ class MicArray(object):
         self._device_scorer = inner if (resident and hasattr(inner, "segment_sisdr")) else None
         if self.segments == "device" and not hasattr(self._device_scorer, "voiced_segments"):
             raise RuntimeError('segments="device" needs a spot model with voiced_segments() (the HIP SpotModel)')
+        on_device = self.clustering == "device"
+        if on_device and not (resident and hasattr(inner, "fine_clusters")):
+            raise RuntimeError('clustering="device" needs a spot model with fine_clusters() (the HIP SpotModel)')
         sharded = getattr(spot_model, "world", 1) > 1
         n_groups = len(candidate_finished)
         self.spotforming_times = 0
@@ -292,16 +376,23 @@ class MicArray(object):
             waves_dev, energies, sep_all = None, np.zeros((0, 2)), None
             T_len = int(mix_data.shape[1])
         elif resident:
-            waves_dev, energies = spot_model.shift_and_sep_resident(mix_data, total_patch, Strict=1)
+            waves_dev, energies = spot_model.shift_and_sep_resident(mix_data, total_patch, Strict=1,
+                                                                    device_energies=on_device)
             T_len = int(waves_dev.shape[1])
         else:
             sep_all = spot_model.shift_and_sep(mix_data, total_patch, Strict=1)
             T_len = int(sep_all.shape[1])
+        output_pair = []
+        if on_device and len(total_patch) > 0:
+            bigs = [candidate_finished[g] for g in mine]
+            fines = [total_patch[bounds[slot[g]]:bounds[slot[g] + 1]] for g in mine]
+            output_pair, energies = self._device_groups(
+                list(mine), bigs, fines, [centers[g] for g in mine], waves_dev, energies,
+                self._fine_gates(bigs, fines, thr_new), T_len, sample_gt, inner)
         if sharded and resident:
             self.fine_energies = spot_model.all_gather_groups(energies, mine, gbounds)
 
-        output_pair = []
-        for g in mine:
+        for g in ([] if on_device and len(total_patch) > 0 else mine):
             i = slot[g]                                                     # local slot of coarse patch g
             big = candidate_finished[g]
             patches = total_patch[bounds[i]:bounds[i + 1]]
@@ -367,10 +458,12 @@ class MicArray(object):
         the host subdivides the patches of chunk c+1, and the clustering of chunk c (energies,
         Gram launches, head copies -- issued on a side stream that only waits for chunk c) runs
         while the GPU is already on chunk c+1.  Same candidates, same order, same output.
+        With ``clustering="device"`` the clustering of chunk c is one ``fine_clusters`` call and two read-backs.
         ``owned`` (sharded use): the coarse patches this rank owns; the call then returns (output_pair,
         energies of these groups in that order) and reports their subdivision sizes in ``sizes_out``."""
         import torch
         dev = getattr(spot_model, "inner", spot_model).device
+        scorer = getattr(spot_model, "inner", spot_model) if self.clustering == "device" else None
         mix_dev = torch.as_tensor(mix_data).to(dev, dtype=torch.float32).contiguous()
         T_len = int(mix_dev.shape[1])
         order = list(range(len(candidate_finished))) if owned is None else [int(g) for g in owned]
@@ -393,11 +486,17 @@ class MicArray(object):
         output_pair, inflight = [], None
 
         def finish(job):
-            groups, fines, centres, waves, en_dev, ev = job
+            groups, fines, centres, waves, en_dev, ev, gates = job
             with torch.cuda.stream(side):
                 side.wait_event(ev)
                 waves.record_stream(side)
                 en_dev.record_stream(side)
+                if gates is not None:                          # clustering="device": the whole chunk in one call
+                    pairs, energies = self._device_groups(groups, [candidate_finished[g] for g in groups], fines, centres,
+                                                          waves, en_dev, gates, T_len, sample_gt, scorer)
+                    local_energies.append(energies)
+                    output_pair.extend(pairs)
+                    return
                 energies = en_dev.cpu().numpy()
                 local_energies.append(energies)
                 pos = 0
@@ -424,9 +523,11 @@ class MicArray(object):
             waves, en_dev = spot_model.shift_and_sep_resident(mix_dev, flat, Strict=1, device_energies=True)
             ev = torch.cuda.Event()
             ev.record(main)
+            # (device clustering: the thresholds are geometry alone, formed while the GPU runs this chunk)
+            gates = self._fine_gates([candidate_finished[g] for g in groups], fines, thr_new) if scorer is not None else None
             if inflight is not None:
                 finish(inflight)                               # host clustering of the previous chunk
-            inflight = (groups, fines, centres, waves, en_dev, ev)
+            inflight = (groups, fines, centres, waves, en_dev, ev, gates)
         if inflight is not None:
             finish(inflight)
         if owned is not None:

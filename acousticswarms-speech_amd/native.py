@@ -15,11 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ASW_LIB_PATH") or os.path.join(_HERE, "libasw_hip.so")   # env: A/B builds only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["asw_common.cpp", "convgemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip", "misc_kernels.hip", "attention_mfma.hip", "srp_kernels.hip",
-           "pruner_kernels.hip", "geometry_kernels.hip",
+           "pruner_kernels.hip", "geometry_kernels.hip", "cluster_kernels.hip",
            "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip"]
 HEADERS = ["asw_common.h", "model_common.h", "mfma_util.h", "f16x3_tile.h"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
-EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"]}
+# (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out)
+EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"], "cluster_kernels.hip": ["-ffp-contract=off"]}
 OPS_PATH = os.path.join(_HERE, "libasw_torch_ops.so")      # TORCH_LIBRARY(asw, ...) adapters over the C ABI
 OPS_SOURCE = "torch_ops.cpp"
 
@@ -225,6 +226,9 @@ SIGNATURES = {
     "asw_voiced_segments_workspace_bytes": (c_size_t, [c_int, c_int]),
     "asw_voiced_segments": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    "asw_fine_clusters_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "asw_fine_clusters": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double,
+                                  c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "asw_add_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "asw_search_area": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double,
                                 POINTER(c_int), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -260,6 +260,22 @@ class SpotModel:
         seg, cnt, _ms = native.torch_ops().voiced_segments(waves.contiguous(), float(top_db), False)
         return seg, cnt
 
+    def fine_clusters(self, waves, bounds, en_dev, gate, group_gate, min_trigger, sim_db: float = -4.0):
+        """The fine stage's clustering of every group of rows of ``waves`` (device tensor [N,T] float32) on the GPU
+        (``fine_cluster.fine_clusters_f64``): ``bounds`` host ints [G+1], ``en_dev`` the device energies [N,2] float64,
+        ``gate`` [N] and ``group_gate`` [G] host float64.  Returns the device tensors (order [N] int32, label [N]
+        int32).  The bounds and the gates (a few KB) go up through pinned memory; nothing comes back and nothing
+        waits for the device."""
+        import torch
+        b = torch.from_numpy(np.ascontiguousarray(bounds, dtype=np.int32))
+        gates = np.concatenate([np.asarray(gate, dtype=np.float64).reshape(-1),
+                                np.asarray(group_gate, dtype=np.float64).reshape(-1)])
+        gates_d = torch.from_numpy(gates).pin_memory().to(waves.device, non_blocking=True)
+        n = int(waves.shape[0])
+        order, label, _gram = native.torch_ops().fine_clusters(waves.contiguous(), b, en_dev.contiguous(), gates_d[:n],
+                                                               gates_d[n:], float(min_trigger), float(sim_db), False)
+        return order, label
+
     def segment_sisdr_device(self, waves, seg_dev, cnt_dev):
         """``segment_sisdr`` on tables that are already on the device (``voiced_segments``): the same op, the same
         return -- (host ndarray [n,n,kmax] float64 with kmax = max(1, largest count), counts [n]).  Only the counts

@@ -542,6 +542,38 @@ size_t asw_voiced_segments_workspace_bytes(int n, int T);
 int asw_voiced_segments(const float* y, int n, int T, double thr, double Q, int32_t* segments, int kcap,
                         int32_t* counts, double* ms, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The fine stage's per-coarse-patch clustering of N candidate outputs in G groups on the device (the thresholds and
+ * the greedy SI-SDR loop of Mic_Array.py:283-383), as fine_cluster.fine_clusters_f64 states it and equal to that
+ * statement bit for bit.  y [N][T] float32 (device), the mean-removed outputs, any T >= 1 (a row need not be 16-byte
+ * aligned).  bounds_host int32 [G + 1] is a HOST array and is read before the call returns: group g = rows
+ * bounds[g] .. bounds[g + 1], bounds[0] = 0, non-decreasing, bounds[G] = N; empty groups are allowed.  energies
+ * float64 [N][2] = (power, power2), gate float64 [N], group_gate float64 [G] (device); min_trigger and ratio =
+ * 10^(sim_db / 10) are the caller's doubles.
+ *   Gram: for rows a, b of one group G[a][b] = sum_t double(y_a[t]) * double(y_b[t]) in one fixed order -- 256
+ *   partial sums p[l] over t = l, l + 256, ... from 0.0; each 64-wide quarter reduced by p[:s] += p[s:2s], s = 32 .. 1;
+ *   the four quarter sums as (w0 + w1) + (w2 + w3) -- which depends neither on the group size nor on the tile or the
+ *   workgroup a pair falls in; G[a][b] and G[b][a] are the same bits.
+ *   Group g is open unless it is empty or max power2 of the group < group_gate[g]; every candidate of a closed group
+ *   gets label -1.  order int32 [N]: order[bounds[g] + r] = global row of the r-th candidate of group g by descending
+ *   power, equal powers by ascending row (closed groups too).  Candidate k is skipped (label -1) iff power2[k] <
+ *   gate[k] or power[k] < min_trigger; any other joins the first head h in creation order with
+ *   sss > ratio * snn, sss = es * es / ss, snn = max(ee - sss, 0) + 1e-8 (ee = G[k][k], ss = G[h][h], es = G[k][h]) --
+ *   label[k] = h, a global row -- or becomes a head, label[k] = k.  label int32 [N].
+ * gram float64 [sum n_g^2] receives the block-diagonal Gram matrix, group g row-major n_g x n_g at element offset
+ * sum_{h<g} n_h^2, or NULL.  workspace: asw_fine_clusters_workspace_bytes(bounds_host, G) bytes, 8-byte aligned (the
+ * Gram matrix, the group / tile table of the launch and one head slot per candidate; 0 with the error message set
+ * for bounds this call would refuse).  Two launches (group_gram, fine_cluster) and one small host-to-device copy of
+ * the table; no atomics, no device-side assert, plain vector stores: two calls give identical bytes, every slot of
+ * order and label is written, and the result does not depend on what the outputs or the workspace held.  With NaN
+ * or Inf in y or energies the result is unspecified but every access stays in bounds.  Every refusal -- null pointer,
+ * N < 0, T < 1, G outside 0..65535, bounds that do not start at 0, decrease or do not end at N, sum n_g^2 above 2^27
+ * elements, a short or misaligned workspace -- happens on the host before the copy and the first launch; N = 0 or
+ * G = 0 (with valid bounds) succeeds and launches nothing. */
+size_t asw_fine_clusters_workspace_bytes(const int32_t* bounds_host, int G);
+int asw_fine_clusters(const float* y, int N, int T, const int32_t* bounds_host, int G, const double* energies,
+                      const double* gate, const double* group_gate, double min_trigger, double ratio, void* workspace,
+                      size_t workspace_bytes, int32_t* order, int32_t* label, double* gram, void* stream);
+
 /* HOST function (no GPU): breadth-first subdivision of one coarse hypercube into the fine
  * candidate hypercubes -- search_area / binary_area_divide_width
  * (sep/helpers/local_utils_3d.py:212-335) with Patch.check_out / hyperbola_sample
