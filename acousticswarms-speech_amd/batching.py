@@ -250,6 +250,15 @@ class MixtureScorer(object):
     def fine_clusters(self, waves, bounds, en_dev, gate, group_gate, min_trigger):
         return self.inner_model.fine_clusters(waves, bounds, en_dev, gate, group_gate, min_trigger)
 
+    def pair_sisdr_device(self, waves):
+        return self.inner_model.pair_sisdr_device(waves)
+
+    def segment_sisdr_resident(self, waves, seg_dev, cnt_dev):
+        return self.inner_model.segment_sisdr_resident(waves, seg_dev, cnt_dev)
+
+    def global_clusters(self, full_dev, seg_dev, cnt_dev, near):
+        return self.inner_model.global_clusters(full_dev, seg_dev, cnt_dev, near)
+
 
 def mixture_view(mic_array):
     """A per-search view of a MicArray: the geometry tables (tens of MB, read-only) are shared, everything a

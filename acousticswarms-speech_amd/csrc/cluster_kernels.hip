@@ -1,6 +1,7 @@
 // cluster_kernels.hip -- the fine stage's per-coarse-patch clustering (MicArray._cluster_group,
 // sep/Mic_Array.py:283-383) for all coarse patches of a call, as fine_cluster.fine_clusters_f64 states it: float64, no
-// logarithm, one fixed order of additions -- every value below is the statement's value to the bit.
+// logarithm, one fixed order of additions -- every value below is the statement's value to the bit.  The second half of
+// the file is the global clustering's walk (MicArray.Clustering_new) as global_cluster.global_clusters_f64 states it.
 #include "asw_common.h"
 
 #include <vector>
@@ -237,6 +238,168 @@ extern "C" int asw_fine_clusters(const float* y, int N, int T, const int32_t* bo
   asw::ProfScope prof(s, "fine_cluster", 0.0, (double)elems * 8);
   hipLaunchKernelGGL(fine_cluster_kernel, dim3(G), dim3(64), 0, s, energies, gate, group_gate, min_trigger, ratio, db, dofs,
                      gm, heads, order, label);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+// ===========================================================================
+// The global clustering (MicArray.Clustering_new, sep/Mic_Array.py:399-500) as global_cluster.global_clusters_f64 states
+// it: comparisons of the float64 values pair_sisdr and segment_sisdr wrote, a first-hit scan and a running maximum.
+// There is no arithmetic, so every decision below is the statement's on every input, NaN and Inf included (a NaN
+// compares false on both sides of every test, as in numpy).
+// ===========================================================================
+namespace {
+
+constexpr int GLOBAL_MAX_ROWS = 8192;            // n * n bytes of merge matrix: 64 MiB at the cap
+
+__device__ __forceinline__ int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---------------------------------------------------------------------------
+// global_merge_kernel: one wavefront per ordered pair (i, j), four pairs per workgroup.  The lanes stride over the
+// used slots k < c_i of seg[i][j][.] -- contiguous doubles, so a wavefront's load is coalesced --, the two "any" flags
+// meet by ballot, and lane 0 stores merge[i][j] = full > sim_db or (any > win_hi and no < win_lo) or near.  Slots from
+// c_i on are never read.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void global_merge_kernel(const double* __restrict__ full, const double* __restrict__ seg,
+                                                           const int* __restrict__ counts, const unsigned char* __restrict__ near,
+                                                           int n, int K, double sim_db, double win_hi, double win_lo,
+                                                           unsigned char* __restrict__ merge) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const long pair = (long)blockIdx.x * 4 + wid;
+  if (pair >= (long)n * n) return;                                  // a whole wavefront leaves; no barrier follows
+  const int i = (int)(pair / n);
+  const int c = clamp_int(counts[i], 0, K);
+  const double* __restrict__ row = seg + pair * K;
+  bool hi = false, lo = false;
+  for (int k = lane; k < c; k += 64) {
+    const double v = row[k];
+    hi = hi || v > win_hi;
+    lo = lo || v < win_lo;
+  }
+  const bool any_hi = __ballot(hi) != 0ull, any_lo = __ballot(lo) != 0ull;
+  if (lane == 0) merge[pair] = (full[pair] > sim_db || (any_hi && !any_lo) || near[pair] != 0) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------
+// global_walk_kernel: one workgroup of 256 threads walks the candidates in order.  The head list is `heads` (workspace,
+// one int per candidate), so nothing is sized by LDS and any n and K run.  Per candidate i with c_i > 0:
+//   A. the threads stride over the head positions and keep the lowest p with merge[i][heads[p]] set; a wavefront
+//      minimum by shuffles, then the minimum of the four through LDS: the first head in creation order.
+//   B. no hit and at least one head: the threads stride over k < c_i; each loops over ALL heads and keeps the maximum of
+//      seg[i][h][k] that propagates NaN (consecutive lanes read consecutive doubles).  The two flags of the second
+//      window test meet by ballot and through LDS.
+// Every branch on c_i, the hit and the flags is uniform over the workgroup, so every thread meets the same barriers.
+// Thread 0 stores label[i] and the new head; the barrier that ends the step is the fence that lets the other threads
+// read heads[] and lets the LDS words be reused.  Every head index read back from memory is clamped to 0 .. n - 1.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void global_walk_kernel(const double* __restrict__ seg, const int* __restrict__ counts,
+                                                          const unsigned char* __restrict__ merge, int n, int K,
+                                                          double best_hi, double best_lo, int* __restrict__ heads,
+                                                          int* __restrict__ label) {
+  __shared__ int first[4];
+  __shared__ int flag[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int nh = 0;
+  for (int i = 0; i < n; ++i) {
+    const int c = clamp_int(counts[i], 0, K);
+    if (c == 0) {
+      if (tid == 0) label[i] = -1;
+      continue;
+    }
+    const unsigned char* __restrict__ mrow = merge + (long)i * n;
+    int pos = nh;                                                   // nh = "no hit"
+    for (int p = tid; p < nh; p += 256) {
+      const int h = clamp_int(heads[p], 0, n - 1);
+      if (mrow[h] != 0) {
+        pos = p;
+        break;                                                      // this thread's later positions are larger
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int w = __shfl_xor(pos, o, 64);
+      pos = w < pos ? w : pos;
+    }
+    if (lane == 0) first[wid] = pos;
+    __syncthreads();
+    {
+      const int a = first[0] < first[1] ? first[0] : first[1], b = first[2] < first[3] ? first[2] : first[3];
+      pos = a < b ? a : b;
+    }
+    if (pos < nh) {
+      if (tid == 0) label[i] = clamp_int(heads[pos], 0, n - 1);
+      __syncthreads();                                              // first[] is free again
+      continue;
+    }
+    bool shadowed = false;
+    if (nh > 0) {
+      bool hi = false, lo = false;
+      const double* __restrict__ srow = seg + (long)i * n * K;
+      for (int k = tid; k < c; k += 256) {
+        double best = srow[(long)clamp_int(heads[0], 0, n - 1) * K + k];
+        for (int p = 1; p < nh; ++p) {
+          const double v = srow[(long)clamp_int(heads[p], 0, n - 1) * K + k];
+          best = (v > best || v != v) ? v : best;                   // a NaN stays, as in np.amax
+        }
+        hi = hi || best > best_hi;
+        lo = lo || best < best_lo;
+      }
+      const int f = (__ballot(hi) != 0ull ? 1 : 0) | (__ballot(lo) != 0ull ? 2 : 0);
+      if (lane == 0) flag[wid] = f;
+      __syncthreads();
+      const int all = flag[0] | flag[1] | flag[2] | flag[3];
+      shadowed = (all & 1) != 0 && (all & 2) == 0;
+    }
+    if (tid == 0) {
+      if (shadowed) {
+        label[i] = -2;
+      } else {
+        label[i] = i;
+        heads[nh] = i;                                              // nh < n: at most one head per candidate
+      }
+    }
+    if (!shadowed) ++nh;
+    __syncthreads();                                                // heads[nh - 1] is visible; first[] and flag[] are free
+  }
+}
+
+// workspace: heads [n] int32 | merge [n * n] uint8 (used when the caller passes no merge), rounded up to 8 bytes
+size_t global_workspace_need(int n) { return ((size_t)n * sizeof(int32_t) + (size_t)n * n + 7) & ~(size_t)7; }
+
+}  // namespace
+
+extern "C" size_t asw_global_clusters_workspace_bytes(int n) {
+  if (n < 0 || n > GLOBAL_MAX_ROWS) {
+    asw::set_error(ASW_ERR_ARG, "global_clusters_workspace_bytes: n = %d outside 0..%d", n, GLOBAL_MAX_ROWS);
+    return 0;
+  }
+  return global_workspace_need(n);
+}
+
+extern "C" int asw_global_clusters(const double* full, const double* seg, const int32_t* counts, const uint8_t* near, int n,
+                                   int K, double sim_db, double win_hi, double win_lo, double best_hi, double best_lo,
+                                   void* workspace, size_t workspace_bytes, int32_t* label, uint8_t* merge, void* stream) {
+  ASW_CHECK_ARG(n >= 0 && n <= GLOBAL_MAX_ROWS, "global_clusters: n = %d outside 0..%d", n, GLOBAL_MAX_ROWS);
+  ASW_CHECK_ARG(K >= 1, "global_clusters: K = %d < 1", K);
+  if (n == 0) return ASW_OK;
+  ASW_CHECK_ARG(full && seg && counts && near && workspace, "global_clusters: null pointer");
+  ASW_CHECK_ARG(label, "global_clusters: null output");
+  const size_t need = global_workspace_need(n);
+  ASW_CHECK_ARG(workspace_bytes >= need, "global_clusters: workspace of %zu bytes too small, %zu needed", workspace_bytes, need);
+  ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "global_clusters: workspace not 8-byte aligned");
+
+  hipStream_t s = asw::as_stream(stream);
+  int32_t* heads = static_cast<int32_t*>(workspace);
+  uint8_t* mg = merge ? merge : reinterpret_cast<uint8_t*>(heads + n);
+  const long pairs = (long)n * n;
+  {
+    asw::ProfScope prof(s, "global_merge", 0.0, (double)pairs * K * 8);
+    hipLaunchKernelGGL(global_merge_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, full, seg, counts, near, n, K,
+                       sim_db, win_hi, win_lo, mg);
+    ASW_LAUNCH_CHECK();
+  }
+  asw::ProfScope prof(s, "global_walk", 0.0, (double)pairs);
+  hipLaunchKernelGGL(global_walk_kernel, dim3(1), dim3(256), 0, s, seg, counts, mg, n, K, best_hi, best_lo, heads, label);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

@@ -262,6 +262,38 @@ std::tuple<Tensor, Tensor, Tensor> fine_clusters(const Tensor& y, const Tensor& 
   return {order, label, gram};
 }
 
+// -> label [n] int32, merge [n, n] uint8 (empty [0, n] unless want_merge): the global clustering's decisions over the
+// tensors pair_sisdr and segment_sisdr wrote (global_cluster.global_clusters_f64).  Nothing is read back.
+std::tuple<Tensor, Tensor> global_clusters(const Tensor& full, const Tensor& seg, const Tensor& counts, const Tensor& near,
+                                           double sim_db, double win_hi, double win_lo, double best_hi, double best_lo,
+                                           bool want_merge) {
+  need(full, "full", at::kDouble, 2);
+  need(seg, "seg", at::kDouble, 3);
+  need(counts, "counts", at::kInt, 1);
+  need(near, "near", at::kByte, 2);
+  same_device(full, seg, "full and seg");
+  same_device(full, counts, "full and counts");
+  same_device(full, near, "full and near");
+  const int n = checked_int(full.size(0), "n"), K = checked_int(seg.size(2), "K");
+  TORCH_CHECK(full.size(1) == n, "full must be [n, n]");
+  TORCH_CHECK(seg.size(0) == n && seg.size(1) == n && K >= 1, "seg must be [n, n, K] with K >= 1");
+  TORCH_CHECK(counts.size(0) == n, "counts must be [n]");
+  TORCH_CHECK(near.size(0) == n && near.size(1) == n, "near must be [n, n]");
+  TORCH_CHECK(n <= 8192, "global_clusters takes at most 8192 candidates, got ", n);
+  Tensor label = at::empty({n}, full.options().dtype(at::kInt));
+  Tensor merge = at::empty({want_merge ? n : 0, n}, full.options().dtype(at::kByte));
+  if (n == 0) return {label, merge};
+  const size_t ws_bytes = asw_global_clusters_workspace_bytes(n);
+  Tensor ws = at::empty({static_cast<int64_t>(ws_bytes / 8)}, full.options().dtype(at::kDouble));
+  Launch l(full);
+  check_status(asw_global_clusters(full.data_ptr<double>(), seg.data_ptr<double>(), counts.data_ptr<int32_t>(),
+                                   near.data_ptr<uint8_t>(), n, K, sim_db, win_hi, win_lo, best_hi, best_lo, ws.data_ptr(),
+                                   ws_bytes, label.data_ptr<int32_t>(), want_merge ? merge.data_ptr<uint8_t>() : nullptr,
+                                   l.stream),
+               "asw_global_clusters");
+  return {label, merge};
+}
+
 Tensor center_rows_(Tensor y) {
   need(y, "y", at::kFloat, 2);
   if (y.size(0) == 0) return y;
@@ -631,6 +663,8 @@ TORCH_LIBRARY(asw, m) {
   m.def("voiced_segments(Tensor y, float top_db=18.0, bool want_ms=False) -> (Tensor, Tensor, Tensor)");
   m.def("fine_clusters(Tensor y, Tensor bounds, Tensor energies, Tensor gate, Tensor group_gate, float min_trigger, "
         "float sim_db=-4.0, bool want_gram=False) -> (Tensor, Tensor, Tensor)");
+  m.def("global_clusters(Tensor full, Tensor seg, Tensor counts, Tensor near, float sim_db=-1.0, float win_hi=-2.0, "
+        "float win_lo=-7.0, float best_hi=-1.0, float best_lo=-5.0, bool want_merge=False) -> (Tensor, Tensor)");
   m.def("center_rows_(Tensor(a!) y) -> Tensor(a!)");
   m.def("srp_phat_map(Tensor mix, Tensor twiddle, Tensor pair_i, Tensor pair_j, Tensor tau, Tensor omega, int window, "
         "int step, int n_windows, int nfft, int hop, float tol) -> Tensor");
@@ -663,6 +697,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("segment_sisdr", &segment_sisdr);
   m.impl("voiced_segments", &voiced_segments);
   m.impl("fine_clusters", &fine_clusters);
+  m.impl("global_clusters", &global_clusters);
   m.impl("center_rows_", &center_rows_);
   m.impl("srp_phat_map", &srp_phat_map);
   m.impl("pruner_covariance", &pruner_covariance);

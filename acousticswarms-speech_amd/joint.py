@@ -42,9 +42,11 @@ def _sync():
 GEOMETRY_CACHE_SIZE = 8        # arrays kept by JointModel.mic_array_for (a 7-mic bench array: about 65 MB of tables)
 
 
-def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host", segments="host", clustering="host"):
+def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host", segments="host", clustering="host",
+               global_clustering="host"):
     """The configuration string of the reference's ``setup`` (:125-131), extended by the pruning method, the
-    geometry mode, the segments mode and the clustering mode when they are not the defaults."""
+    geometry mode, the segments mode, the clustering mode and the global clustering mode when they are not the
+    defaults."""
     key = '~'.join([f"{x:.05f}" for x in np.asarray(mic_positions).flatten()]) \
         + '|' + '~'.join([f"{x:.05f}" for x in speaker_range])
     if prone_method != "SRP":
@@ -55,6 +57,8 @@ def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host"
         key += '|segments=' + str(segments)
     if clustering != "host":
         key += '|clustering=' + str(clustering)
+    if global_clustering != "host":
+        key += '|global_clustering=' + str(global_clustering)
     return key
 
 
@@ -67,19 +71,26 @@ class _Pending(object):
 
 
 class JointModel(object):
-    def __init__(self, spot_model, sep_model=None, device=None, geometry="host", segments="host", clustering="host"):
+    def __init__(self, spot_model, sep_model=None, device=None, geometry="host", segments="host", clustering="host",
+                 global_clustering="host"):
         """``geometry``: default of ``setup``'s argument of that name and the mode of the per-mixture arrays of
         ``mic_array_for`` -- "host" or "device" (see ``MicArray``).  ``segments``: the same for where the clustering
         finds the voiced segments of the cluster heads, and ``clustering`` for where the fine stage clusters the
-        candidates of its coarse patches."""
+        candidates of its coarse patches, and ``global_clustering`` for where the global clustering decides (``"device"``
+        needs ``segments="device"``)."""
         if geometry not in ("host", "device"):
             raise ValueError(f'geometry must be "host" or "device", got {geometry!r}')
         if segments not in ("host", "device"):
             raise ValueError(f'segments must be "host" or "device", got {segments!r}')
         if clustering not in ("host", "device"):
             raise ValueError(f'clustering must be "host" or "device", got {clustering!r}')
+        if global_clustering not in ("host", "device"):
+            raise ValueError(f'global_clustering must be "host" or "device", got {global_clustering!r}')
+        if global_clustering == "device" and segments != "device":
+            raise ValueError('global_clustering="device" needs segments="device"')
         self.segments = segments
         self.clustering = clustering
+        self.global_clustering = global_clustering
         self.spot_model = spot_model
         self.sep_model = sep_model
         self.device = device
@@ -93,18 +104,20 @@ class JointModel(object):
         self._mix_dev = self._mix_src = None
 
     def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP", geometry=None,
-              segments=None, clustering=None):
+              segments=None, clustering=None, global_clustering=None):
         """(Re)build the geometry tables unless the configuration is unchanged (:125-137).
         One-off per geometry and excluded from latency, as the reference's README notes.
         ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS"; "DENSE": no pruner, the whole
         coarse TDoA lattice of the array) and is part of the configuration, and so is ``geometry`` ("host" |
         "device", default: the model's): where the tables are built.  ``segments`` ("host" | "device", default: the
         model's): where the voiced segments of the cluster heads are found; ``clustering`` ("host" | "device",
-        default: the model's): where the fine stage clusters the candidates of its coarse patches."""
+        default: the model's): where the fine stage clusters the candidates of its coarse patches; ``global_clustering``
+        ("host" | "device", default: the model's): where the global clustering decides."""
         geometry = self.geometry if geometry is None else geometry
         segments = self.segments if segments is None else segments
         clustering = self.clustering if clustering is None else clustering
-        key = config_key(mic_positions, speaker_range, prone_method, geometry, segments, clustering)
+        global_clustering = self.global_clustering if global_clustering is None else global_clustering
+        key = config_key(mic_positions, speaker_range, prone_method, geometry, segments, clustering, global_clustering)
         if key == self.previous_config:
             print("reuse the previous recycle!")
             return
@@ -112,7 +125,7 @@ class JointModel(object):
         gc.unfreeze()                       # a previous geometry may go now
         self.Mic_processor = MicArray(mic_positions, Spk_Range=speaker_range, Prone_method=prone_method,
                                       device=self.device, geometry=geometry, segments=segments,
-                                      clustering=clustering)
+                                      clustering=clustering, global_clustering=global_clustering)
         self.previous_config = key
         # The geometry tables are tens of thousands of small arrays and lists that live as long as
         # this configuration.  Left in the collector's oldest generation they make every full
@@ -133,7 +146,8 @@ class JointModel(object):
         generation.  Instead the batch raises the collector's oldest-generation threshold while it runs
         (``batching.no_full_collections``), so no full collection lands inside a search, and an evicted array is
         released by reference counting alone -- its tables hold no reference cycle."""
-        key = config_key(mic_positions, speaker_range, prone_method, self.geometry, self.segments, self.clustering)
+        key = config_key(mic_positions, speaker_range, prone_method, self.geometry, self.segments, self.clustering,
+                         self.global_clustering)
         with self._geometry_lock:
             hit = self._geometry_cache.get(key)
             if hit is None:
@@ -153,7 +167,7 @@ class JointModel(object):
         try:
             mp = MicArray(np.asarray(mic_positions), Spk_Range=speaker_range, Prone_method=prone_method,
                           device=self.device, geometry=self.geometry, segments=self.segments,
-                          clustering=self.clustering)
+                          clustering=self.clustering, global_clustering=self.global_clustering)
         except BaseException as exc:
             with self._geometry_lock:
                 self._geometry_cache.pop(key, None)
@@ -176,7 +190,7 @@ class JointModel(object):
         method = self.Mic_processor.Prone_method if self.Mic_processor is not None else "SRP"
         self.Mic_processor = self.mic_array_for(mic_positions, speaker_range, method)
         self.previous_config = config_key(mic_positions, speaker_range, method, self.geometry, self.segments,
-                                          self.clustering)
+                                          self.clustering, self.global_clustering)
 
     def forward(self, mix_data):
         """-> (patches, audio_loc, audio, SRP_drop, stage1_drop, spot_times) (:142-149)."""

@@ -9,6 +9,7 @@ import numpy as np
 
 from .dense_grid import lattice_patches
 from .fine_cluster import clusters_of_group
+from .global_cluster import clusters_of_labels
 from .hostdsp import max_avg_power, si_sdr, split_wav, split_wise_sisdr
 from .patch import FS, SPEED_OF_SOUND, Patch, pair_offsets
 from . import search
@@ -79,7 +80,7 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
 class MicArray(object):
     def __init__(self, mic_positions, demo=False, Spk_Range=None, grid_size=0.05, Prone_method="SRP",
                  MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None,
-                 geometry="host", segments="host", clustering="host"):
+                 geometry="host", segments="host", clustering="host", global_clustering="host"):
         """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
         (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture).
         ``Prone_method="DENSE"`` takes the pruner out: ``Apply_SRP_PHAT`` returns every width-``INIT_WIDTH`` cube of
@@ -92,13 +93,22 @@ class MicArray(object):
         ``clustering``: where the fine stage clusters the candidates of its coarse patches -- "host" (per patch:
         sort, thresholds, the greedy SI-SDR loop on one ``pair_sisdr`` read-back, one copy of the heads) or "device"
         (per chunk of patches: one ``fine_clusters`` call of the scorer, ``fine_cluster.fine_clusters_f64`` on the
-        GPU, then one read-back of the decisions and one copy of all heads; needs the HIP spot model)."""
+        GPU, then one read-back of the decisions and one copy of all heads; needs the HIP spot model).
+        ``global_clustering``: where the global clustering decides -- "host" (the SI-SDR matrix, the segment tensor and
+        the segment tables are read back and walked in numpy) or "device" (the three SI-SDR ops leave their results on
+        the GPU, one ``global_clusters`` call of the scorer, ``global_cluster.global_clusters_f64`` on the GPU, decides
+        there, and only the [n] labels come back; needs ``segments="device"`` and the HIP spot model)."""
         if segments not in ("host", "device"):
             raise ValueError(f'segments must be "host" or "device", got {segments!r}')
         if clustering not in ("host", "device"):
             raise ValueError(f'clustering must be "host" or "device", got {clustering!r}')
+        if global_clustering not in ("host", "device"):
+            raise ValueError(f'global_clustering must be "host" or "device", got {global_clustering!r}')
+        if global_clustering == "device" and segments != "device":
+            raise ValueError('global_clustering="device" needs segments="device"')
         self.segments = segments
         self.clustering = clustering
+        self.global_clustering = global_clustering
         if Prone_method not in PRONE_METHODS:
             # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
             raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
@@ -535,6 +545,53 @@ class MicArray(object):
         return output_pair
 
     # ---- stage 4: global non-max suppression (sep/Mic_Array.py:399-500) -----------------
+    @staticmethod
+    def _near_matrix(centres):
+        """dis < 0.45 for every ordered pair of the (x, y) centres; entries within rounding of the threshold are settled
+        by the very call the per-pair form makes."""
+        xy = np.array([c[:2] for c in centres], dtype=np.float64)
+        d = xy[:, None, :] - xy[None, :, :]
+        dist = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1])
+        near = dist < 0.45
+        for a, b in zip(*np.nonzero(np.abs(dist - 0.45) < 1e-9)):
+            near[a, b] = np.linalg.norm(centres[a][:2] - centres[b][:2]) < 0.45
+        return near
+
+    def _candidate_rows(self, cands, scorer):
+        """The candidates' waveforms as one device tensor [n, T]: the rows the fine stage left on the GPU, or a copy."""
+        import torch
+        dev_rows = [getattr(self, "_dev_cache", {}).get(id(c[1])) for c in cands]
+        if all(r is not None and r[0] is c[1] for r, c in zip(dev_rows, cands)):
+            return torch.stack([r[1] for r in dev_rows])          # the fine stage left every row on the GPU
+        waves = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(c[1], dtype=np.float32) for c in cands])))
+        return waves.to(scorer.device if getattr(scorer, "device", None) is not None else "cuda")
+
+    def _global_clusters_device(self, cands, centres, scorer, sample_gt):
+        """``Clustering_new`` with the decisions made where the SI-SDR tensors are: four calls are enqueued, nothing of
+        theirs is read back, and the stage's one blocking copy is the [n] labels of ``global_clusters``
+        (``global_cluster.global_clusters_f64``: -1 discarded, -2 shadowed, otherwise the head's row)."""
+        n = len(cands)
+        waves = self._candidate_rows(cands, scorer)
+        near = self._near_matrix(centres).astype(np.uint8)
+        seg_tab_dev, cnt_dev = scorer.voiced_segments(waves)
+        full_dev = scorer.pair_sisdr_device(waves)
+        seg_dev = scorer.segment_sisdr_resident(waves, seg_tab_dev, cnt_dev)
+        label = scorer.global_clusters(full_dev, seg_dev, cnt_dev, near).cpu().numpy()
+        wrong = []
+        for i in range(n):
+            h = int(label[i])
+            if h == -1:
+                print("discard because no invalid split!!!")
+            elif h >= 0 and h != i and cands[i][-1] >= 0 and sample_gt is not None and cands[h][-1] == -1:
+                delta = (cands[h][-2]["audio_offset"] - sample_gt[:, cands[i][-1]]).astype(int)
+                wrong.append((cands[i][-1], cands[h][-1], delta, cands[i][2] / cands[h][2]))
+        clusters = clusters_of_labels(label)
+        print("final speaker number is ", len(clusters.keys()))
+        self.trace["final_clusters"] = [[cands[i][3] for i in clusters[h]] for h in clusters]
+        patch_final = [cands[h] for h in clusters]
+        audio_final = [p[1] for p in patch_final]
+        return audio_final, patch_final, self.big_spotforming_times + self.spotforming_times, wrong
+
     def Clustering_new(self, output_pair, simple_pos=None, sample_gt=None):
         cands = sorted(output_pair, key=lambda x: -x[2])
         # With the HIP spot model the O(n^2) waveform comparisons of this stage run on the GPU:
@@ -545,19 +602,20 @@ class MicArray(object):
         on_device = getattr(self, "segments", "host") == "device"
         if on_device and not hasattr(scorer, "voiced_segments"):
             raise RuntimeError('segments="device" needs a spot model with voiced_segments() (the HIP SpotModel)')
+        if getattr(self, "global_clustering", "host") == "device":
+            if not hasattr(scorer, "global_clusters"):
+                raise RuntimeError('global_clustering="device" needs a spot model with global_clusters() (the HIP SpotModel)')
+            centres = [c[0].center_pos() for c in cands]
+            if len(cands) > 0 and all(c is not None for c in centres):
+                return self._global_clusters_device(cands, centres, scorer, sample_gt)
+            # (a candidate without a centre: the per-pair loop below, as in host mode)
         seg_all = []
         for c in ([] if on_device else cands):
             hit = cache.get(id(c[1]))
             seg_all.append(hit[1] if hit is not None and hit[0] is c[1] else split_wav(c[1]))
         full_dev = seg_dev = None
         if scorer is not None and (len(cands) > 1 or (on_device and len(cands) > 0)):
-            import torch
-            dev_rows = [getattr(self, "_dev_cache", {}).get(id(c[1])) for c in cands]
-            if all(r is not None and r[0] is c[1] for r, c in zip(dev_rows, cands)):
-                waves = torch.stack([r[1] for r in dev_rows])         # the fine stage left every row on the GPU
-            else:
-                waves = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(c[1], dtype=np.float32) for c in cands])))
-                waves = waves.to(scorer.device if getattr(scorer, "device", None) is not None else "cuda")
+            waves = self._candidate_rows(cands, scorer)
             if on_device:
                 # one launch pair finds every head's segments; the tables stay where segment_sisdr reads them and
                 # only they (a few KB) come back, for len(segs) and the seg_tab slices below
@@ -583,14 +641,7 @@ class MicArray(object):
                 win_dev = np.any(seg_dev > -2, axis=2) & ~np.any(seg_dev < -7, axis=2)
         near = None
         if win_dev is not None and all(c is not None for c in centres):
-            # dis < 0.45 for every pair; entries within rounding of the threshold are settled by the very
-            # call the per-pair form makes
-            xy = np.array([c[:2] for c in centres], dtype=np.float64)
-            d = xy[:, None, :] - xy[None, :, :]
-            dist = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1])
-            near = dist < 0.45
-            for a, b in zip(*np.nonzero(np.abs(dist - 0.45) < 1e-9)):
-                near[a, b] = np.linalg.norm(centres[a][:2] - centres[b][:2]) < 0.45
+            near = self._near_matrix(centres)                    # dis < 0.45 for every pair
             merge = (full_dev > -1) | win_dev | near             # (:401,458) for every ordered pair
         heads = []                                               # cluster heads in creation order
         for i, cand in enumerate(cands):

@@ -286,6 +286,29 @@ class SpotModel:
         out = native.torch_ops().segment_sisdr(waves.contiguous(), seg_dev[:, :kmax].contiguous(), cnt_dev)
         return out.cpu().numpy(), cnt
 
+    def pair_sisdr_device(self, waves):
+        """``pair_sisdr`` whose result stays where it was written: the device tensor [n,n] float64.  Nothing is copied
+        and nothing waits for the device."""
+        return native.torch_ops().pair_sisdr(waves.contiguous())
+
+    def segment_sisdr_resident(self, waves, seg_tab_dev, cnt_dev):
+        """``segment_sisdr`` on the device tables of ``voiced_segments`` whose result stays on the device: the tensor
+        [n,n,kcap] float64, kcap the table's own width (NaN beyond a waveform's count), so that no count has to come
+        to the host to size it.  Nothing is copied and nothing waits for the device."""
+        return native.torch_ops().segment_sisdr(waves.contiguous(), seg_tab_dev.contiguous(), cnt_dev.contiguous())
+
+    def global_clusters(self, full_dev, seg_dev, cnt_dev, near_host_u8):
+        """The global clustering's decisions on the GPU (``global_cluster.global_clusters_f64``) over the device
+        tensors of ``pair_sisdr_device``, ``segment_sisdr_resident`` and ``voiced_segments``; ``near_host_u8`` is the
+        host's uint8 [n,n] ``dis < 0.45`` matrix and goes up through pinned memory.  Returns the device tensor label
+        [n] int32; nothing comes back and nothing waits for the device."""
+        import torch
+        near = torch.from_numpy(np.ascontiguousarray(near_host_u8, dtype=np.uint8))
+        near_d = near.pin_memory().to(full_dev.device, non_blocking=True)
+        label, _merge = native.torch_ops().global_clusters(full_dev.contiguous(), seg_dev.contiguous(),
+                                                           cnt_dev.contiguous(), near_d)
+        return label
+
     def forward(self, mix, window_embedding):
         """Network.forward: mix [B,M,t] (already normalised), window_embedding [B,2] -> [B,1,t]
         (device tensor).  Rows are grouped by identical embedding because the window gate

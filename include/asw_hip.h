@@ -574,6 +574,32 @@ int asw_fine_clusters(const float* y, int N, int T, const int32_t* bounds_host, 
                       const double* gate, const double* group_gate, double min_trigger, double ratio, void* workspace,
                       size_t workspace_bytes, int32_t* order, int32_t* label, double* gram, void* stream);
 
+/* The global clustering's decisions over n cluster heads on the device (the walk of Mic_Array.py:399-500), as
+ * global_cluster.global_clusters_f64 states them and equal to that statement on every input: there is no arithmetic,
+ * only comparisons of the float64 values below, a first-hit scan and a running maximum.  All arrays are device
+ * arrays; the rows are in visiting order (descending power).  full float64 [n][n] = SI-SDR of est i against ref j
+ * (asw_pair_sisdr); seg float64 [n][n][K], K >= 1 (asw_segment_sisdr); counts int32 [n], c_i = min(max(counts[i], 0),
+ * K): only the slots k < c_i of row i are read, the others may hold anything; near uint8 [n][n], non-zero = the two
+ * centres lie within the merge distance.
+ *   win[i][j] = (any k < c_i: seg[i][j][k] > win_hi) and not (any k < c_i: seg[i][j][k] < win_lo);
+ *   merge[i][j] = full[i][j] > sim_db or win[i][j] or near[i][j] != 0; a NaN compares false everywhere.
+ *   Walking i = 0 .. n - 1 with the heads kept in creation order: c_i == 0 -> label[i] = -1; else some head h with
+ *   merge[i][h] -> label[i] = the first such head in creation order; else, with at least one head, best[k] = the
+ *   NaN-propagating maximum over ALL heads h of seg[i][h][k], k < c_i, and (any best[k] > best_hi) and not (any
+ *   best[k] < best_lo) -> label[i] = -2; else label[i] = i and i joins the heads.  label int32 [n].
+ * merge uint8 [n][n] receives the matrix (0 or 1), or NULL: it then lives in the workspace.  workspace:
+ * asw_global_clusters_workspace_bytes(n) bytes, 8-byte aligned (one head slot per candidate and the merge matrix; 0
+ * with the error message set for n outside 0..8192; 0 for n = 0 too, without an error).  Two launches (global_merge:
+ * a wavefront per ordered pair; global_walk: one workgroup, serial in i); no atomics, no device-side assert, plain
+ * vector stores: two calls give identical bytes, every slot of label and merge is written, and the result does not
+ * depend on what the outputs or the workspace held.  Garbage in counts stays in bounds by the clamp.  Every refusal
+ * -- n < 0 or n > 8192, K < 1, a null pointer other than merge, a short or misaligned workspace -- happens on the host
+ * before the first launch; n = 0 succeeds and launches nothing, whatever the pointers are. */
+size_t asw_global_clusters_workspace_bytes(int n);
+int asw_global_clusters(const double* full, const double* seg, const int32_t* counts, const uint8_t* near, int n, int K,
+                        double sim_db, double win_hi, double win_lo, double best_hi, double best_lo, void* workspace,
+                        size_t workspace_bytes, int32_t* label, uint8_t* merge_or_null, void* stream);
+
 /* HOST function (no GPU): breadth-first subdivision of one coarse hypercube into the fine
  * candidate hypercubes -- search_area / binary_area_divide_width
  * (sep/helpers/local_utils_3d.py:212-335) with Patch.check_out / hyperbola_sample
