@@ -209,8 +209,8 @@ class CandidateBatcher(object):
 
 
 class MixtureScorer(object):
-    """The spot-model surface one search uses (coarse ``shift_and_score``, fine ``shift_and_sep_resident``,
-    the device SI-SDR helpers), bound to mixture ``k`` of a batcher.  The mixture argument of the calls is
+    """The spot-model surface one search uses (coarse ``shift_and_score`` or, with ``coarse="device"``,
+    ``score_offsets`` and ``coarse_select``; fine ``shift_and_sep_resident``; the device SI-SDR helpers), bound to mixture ``k`` of a batcher.  The mixture argument of the calls is
     ignored: the candidates are scored against ``batcher.mixes[k]``."""
 
     def __init__(self, batcher, k):
@@ -259,11 +259,26 @@ class MixtureScorer(object):
     def global_clusters(self, full_dev, seg_dev, cnt_dev, near):
         return self.inner_model.global_clusters(full_dev, seg_dev, cnt_dev, near)
 
+    host_offsets = True     # score_offsets wants the host table: the batcher concatenates the requests on the host
+
+    def score_offsets(self, input_channels, offsets, Strict=0, window=12000):
+        if hasattr(offsets, "cpu"):
+            offsets = offsets.cpu().numpy()
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        if offsets.ndim != 2 or offsets.shape[1] != self.batcher.mixes.shape[1] - 1:
+            raise RuntimeError(f"offsets of shape {offsets.shape} do not fit mixtures of {self.batcher.mixes.shape[1]} channels")
+        _w, en = self.batcher.request(self.k, offsets, Strict, window, False)
+        return en
+
+    def coarse_select(self, en_dev, dis1_dev, best_dev=None, **kw):
+        return self.inner_model.coarse_select(en_dev, dis1_dev, best_dev, **kw)
+
 
 def mixture_view(mic_array):
     """A per-search view of a MicArray: the geometry tables (tens of MB, read-only) are shared, everything a
     search writes -- the SRP map and its voxel image, counters, caches, the decision trace, the side stream --
-    is the view's own."""
+    is the view's own.  The modes (``segments``, ``clustering``, ``global_clustering``, ``coarse``) are the array's, and so
+    are the lattice tables of ``coarse="device"`` with their device copies, which no search writes."""
     v = copy.copy(mic_array)
     v.SRP_node = copy.copy(mic_array.SRP_node)
     v.SRP_node.POWER_MAP = mic_array.SRP_node.POWER_MAP.copy()

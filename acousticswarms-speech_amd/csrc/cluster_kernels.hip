@@ -1,7 +1,8 @@
 // cluster_kernels.hip -- the fine stage's per-coarse-patch clustering (MicArray._cluster_group,
 // sep/Mic_Array.py:283-383) for all coarse patches of a call, as fine_cluster.fine_clusters_f64 states it: float64, no
 // logarithm, one fixed order of additions -- every value below is the statement's value to the bit.  The second half of
-// the file is the global clustering's walk (MicArray.Clustering_new) as global_cluster.global_clusters_f64 states it.
+// the file is the global clustering's walk (MicArray.Clustering_new) as global_cluster.global_clusters_f64 states it, and the
+// last part the coarse stage's decision over a lattice as search.coarse_select_f64 states it.
 #include "asw_common.h"
 
 #include <vector>
@@ -400,6 +401,305 @@ extern "C" int asw_global_clusters(const double* full, const double* seg, const 
   }
   asw::ProfScope prof(s, "global_walk", 0.0, (double)pairs);
   hipLaunchKernelGGL(global_walk_kernel, dim3(1), dim3(256), 0, s, seg, counts, mg, n, K, best_hi, best_lo, heads, label);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+// ===========================================================================
+// The coarse stage's decision over a lattice (binary_search_baseline, sep/helpers/local_utils_3d.py:339-388, with the
+// survivors mask of Prone_method="DENSE_NMS") as search.coarse_select_f64 states it: one float64 multiply per cube and
+// comparisons of exact values, so every output byte below is the statement's.  The cubes are cut into slices of
+// COARSE_SLICE; a workgroup never waits for another one: the launches are the only hand-over.
+// ===========================================================================
+namespace {
+
+constexpr int COARSE_SLICE = 1024;                           // cubes per workgroup of coarse_slice_kernel
+constexpr int COARSE_MAX_CAP = 64;
+constexpr int COARSE_MAX_N = 1 << 24;
+constexpr int COARSE_MAX_PARTS = 256;                        // workgroups of coarse_max_kernel at most
+constexpr int COARSE_FOLD = COARSE_MAX_CAP + COARSE_SLICE;   // entries coarse_merge_kernel ranks at a time
+
+__device__ __forceinline__ double coarse_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+
+__device__ __forceinline__ bool coarse_not_finite(double v) {
+  return (__double_as_longlong(v) & 0x7ff0000000000000LL) == 0x7ff0000000000000LL;
+}
+
+// The running maximum that skips NaN (m = NaN: nothing seen yet).  Of two zeros the positive one stays, so the result
+// is a function of the set of values and not of the order they are met in.
+__device__ __forceinline__ double coarse_max2(double m, double v) {
+  if (v != v) return m;
+  if (m != m || v > m) return v;
+  if (v == m && __double_as_longlong(v) == 0LL) return v;     // +0.0 over -0.0
+  return m;
+}
+
+__device__ __forceinline__ double coarse_threshold(double max_wd, double thr1, int relative, double rel) {
+  if (!relative || max_wd != max_wd) return thr1;
+  const double t = rel * max_wd;
+  return t < thr1 ? t : thr1;
+}
+
+// cube (pa, ia) comes before cube (pb, ib): descending power, equal powers by index, every NaN last by index
+__device__ __forceinline__ bool coarse_before(double pa, int ia, double pb, int ib) {
+  const bool na = pa != pa, nb = pb != pb;
+  if (na || nb) return na == nb ? ia < ib : nb;
+  return pa > pb || (pa == pb && ia < ib);
+}
+
+// ---------------------------------------------------------------------------
+// coarse_max_kernel (relative threshold only): workgroup b strides over the cubes and stores the maximum of the wd it
+// met in part[b]; the 256 thread maxima meet in LDS and thread 0 folds them.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void coarse_max_kernel(const double* __restrict__ energies, const double* __restrict__ dis1,
+                                                         int N, double* __restrict__ part) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double m = coarse_nan();
+  for (long i = (long)blockIdx.x * 256 + tid; i < N; i += (long)gridDim.x * 256) m = coarse_max2(m, energies[2 * i + 1] * dis1[i]);
+  red[tid] = m;
+  __syncthreads();
+  if (tid == 0) {
+    for (int t = 1; t < 256; ++t) m = coarse_max2(m, red[t]);
+    part[blockIdx.x] = m;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// coarse_slice_kernel: workgroup s owns the cubes s * COARSE_SLICE ..., four per thread.  Thread 0 folds the nparts
+// maxima of coarse_max_kernel into the threshold (relative) or takes thr1.  Every thread forms wd, the pass flag and
+// its share of (cubes that pass, powers that are not finite, maximum of wd); the powers and the flags go to LDS, and
+// thread 0 stores the slice's three totals.  A cube that passes then counts the cubes of the slice that pass and come
+// before it -- every thread reads the same LDS word at a time, a broadcast -- and that count is its place: the cubes
+// with a place below cap store their index into the slice's list, every place once, and the threads from the count on
+// store -1.  So all cap slots of the list are written, by plain stores, in an order that does not matter.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void coarse_slice_kernel(const double* __restrict__ energies, const double* __restrict__ dis1,
+                                                           const int* __restrict__ best, int N, double thr1, int relative,
+                                                           double rel, int cap, const double* __restrict__ part, int nparts,
+                                                           double* __restrict__ slice_max, int* __restrict__ slice_cnt,
+                                                           int* __restrict__ slice_list) {
+  __shared__ double pw[COARSE_SLICE];
+  __shared__ unsigned char ok[COARSE_SLICE];
+  __shared__ double red[256];
+  __shared__ int cnt[256], bad[256];
+  __shared__ double thr_s;
+  __shared__ int total_s;
+  const int tid = threadIdx.x;
+  const int base = blockIdx.x * COARSE_SLICE;
+  const int len = N - base < COARSE_SLICE ? N - base : COARSE_SLICE;
+  if (tid == 0) {
+    double m = coarse_nan();
+    if (relative)
+      for (int p = 0; p < nparts; ++p) m = coarse_max2(m, part[p]);
+    thr_s = coarse_threshold(m, thr1, relative, rel);
+  }
+  __syncthreads();
+  const double thr = thr_s;
+  double m = coarse_nan();
+  int c = 0, b = 0;
+#pragma unroll
+  for (int k = 0; k < COARSE_SLICE / 256; ++k) {
+    const int l = tid + 256 * k, i = base + l;
+    double p = 0.0;
+    bool pass = false;
+    if (l < len) {
+      p = energies[2 * (long)i + 1];
+      const double wd = p * dis1[i];
+      m = coarse_max2(m, wd);
+      b += coarse_not_finite(p) ? 1 : 0;
+      pass = !(wd < thr) && (best == nullptr || best[i] == i);
+      c += pass ? 1 : 0;
+    }
+    pw[l] = p;
+    ok[l] = pass ? 1 : 0;
+  }
+  red[tid] = m;
+  cnt[tid] = c;
+  bad[tid] = b;
+  __syncthreads();
+  if (tid == 0) {
+    for (int t = 1; t < 256; ++t) {
+      m = coarse_max2(m, red[t]);
+      c += cnt[t];
+      b += bad[t];
+    }
+    slice_max[blockIdx.x] = m;
+    slice_cnt[2 * blockIdx.x] = c;
+    slice_cnt[2 * blockIdx.x + 1] = b;
+    total_s = c;
+  }
+  int* __restrict__ list = slice_list + (long)blockIdx.x * cap;
+#pragma unroll
+  for (int k = 0; k < COARSE_SLICE / 256; ++k) {
+    const int l = tid + 256 * k;
+    if (!ok[l]) continue;
+    const double p = pw[l];
+    int r = 0;
+    for (int j = 0; j < len; ++j) r += (ok[j] && coarse_before(pw[j], j, p, l)) ? 1 : 0;
+    if (r < cap) list[r] = base + l;
+  }
+  __syncthreads();                                                  // total_s is visible
+  if (tid < cap && tid >= total_s) list[tid] = -1;
+}
+
+// ---------------------------------------------------------------------------
+// coarse_merge_kernel: one workgroup.  It sums the slices' counts, folds their maxima into max_wd and the threshold and
+// stores counts[] and thr[].  The best list lives in LDS slots 0 .. 63 (index -1: empty).  The slices' lists are one
+// table of nslices * cap entries; COARSE_SLICE of them at a time join the best list in LDS with their powers, read
+// again from `energies`, every entry counts the entries that come before it, and those with a place below cap become
+// the new best list.  An index outside 0 .. N - 1 is an empty entry.  Four barriers a round: the round's entries are
+// loaded; every thread holds its entries' places in registers; the best list is cleared; the new one is written.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void coarse_merge_kernel(const double* __restrict__ energies, int N, double thr1, int relative,
+                                                           double rel, int cap, int nslices, const double* __restrict__ slice_max,
+                                                           const int* __restrict__ slice_cnt, const int* __restrict__ slice_list,
+                                                           int* __restrict__ kept, int* __restrict__ counts,
+                                                           double* __restrict__ thr) {
+  __shared__ double pw[COARSE_FOLD];
+  __shared__ int id[COARSE_FOLD];
+  __shared__ double red[256];
+  __shared__ int cnt[256], bad[256];
+  constexpr int PER = (COARSE_FOLD + 255) / 256;
+  const int tid = threadIdx.x;
+  {
+    double m = coarse_nan();
+    int c = 0, b = 0;
+    for (int s = tid; s < nslices; s += 256) {
+      m = coarse_max2(m, slice_max[s]);
+      c += slice_cnt[2 * s];
+      b += slice_cnt[2 * s + 1];
+    }
+    red[tid] = m;
+    cnt[tid] = c;
+    bad[tid] = b;
+    __syncthreads();
+    if (tid == 0) {
+      for (int t = 1; t < 256; ++t) {
+        m = coarse_max2(m, red[t]);
+        c += cnt[t];
+        b += bad[t];
+      }
+      counts[0] = c;
+      counts[1] = b;
+      thr[0] = coarse_threshold(m, thr1, relative, rel);
+      thr[1] = m;
+    }
+  }
+  if (tid < COARSE_MAX_CAP) {
+    id[tid] = -1;
+    pw[tid] = 0.0;
+  }
+  const long M = (long)nslices * cap;
+  for (long c0 = 0; c0 < M; c0 += COARSE_SLICE) {
+#pragma unroll
+    for (int k = 0; k < COARSE_SLICE / 256; ++k) {
+      const int l = tid + 256 * k;
+      int v = -1;
+      double p = 0.0;
+      if (c0 + l < M) {
+        v = slice_list[c0 + l];
+        if (v < 0 || v >= N) v = -1;
+        if (v >= 0) p = energies[2 * (long)v + 1];
+      }
+      id[COARSE_MAX_CAP + l] = v;
+      pw[COARSE_MAX_CAP + l] = p;
+    }
+    __syncthreads();
+    int my_id[PER], my_r[PER];
+    double my_p[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int e = tid + 256 * k;
+      my_id[k] = e < COARSE_FOLD ? id[e] : -1;
+      my_p[k] = e < COARSE_FOLD ? pw[e] : 0.0;
+      my_r[k] = 0;
+    }
+    for (int j = 0; j < COARSE_FOLD; ++j) {
+      const int ij = id[j];
+      if (ij < 0) continue;                                         // the same word for every thread: a uniform branch
+      const double pj = pw[j];
+#pragma unroll
+      for (int k = 0; k < PER; ++k) my_r[k] += (my_id[k] >= 0 && coarse_before(pj, ij, my_p[k], my_id[k])) ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid < COARSE_MAX_CAP) id[tid] = -1;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      if (my_id[k] >= 0 && my_r[k] < cap) {
+        id[my_r[k]] = my_id[k];
+        pw[my_r[k]] = my_p[k];
+      }
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  if (tid < cap) kept[tid] = id[tid];
+}
+
+// workspace: part [COARSE_MAX_PARTS] float64 | slice_max [ns] float64 | slice_cnt [ns][2] int32 | slice_list [ns][cap]
+// int32, ns = the number of slices; rounded up to 8 bytes
+size_t coarse_slices(int N) { return ((size_t)N + COARSE_SLICE - 1) / COARSE_SLICE; }
+size_t coarse_workspace_need(int N, int cap) {
+  const size_t ns = coarse_slices(N);
+  return (((size_t)COARSE_MAX_PARTS + ns) * sizeof(double) + ns * (2 + (size_t)cap) * sizeof(int32_t) + 7) & ~(size_t)7;
+}
+
+}  // namespace
+
+extern "C" size_t asw_coarse_select_workspace_bytes(int N, int cap) {
+  if (N < 0 || N > COARSE_MAX_N || cap < 1 || cap > COARSE_MAX_CAP) {
+    asw::set_error(ASW_ERR_ARG, "coarse_select_workspace_bytes: N = %d outside 0..%d or cap = %d outside 1..%d", N, COARSE_MAX_N,
+                   cap, COARSE_MAX_CAP);
+    return 0;
+  }
+  return coarse_workspace_need(N, cap);
+}
+
+extern "C" int asw_coarse_select(const double* energies, const double* dis1, const int32_t* best, int N, double thr1,
+                                 int relative, double rel, int cap, void* workspace, size_t workspace_bytes, int32_t* kept,
+                                 int32_t* counts, double* thr, void* stream) {
+  ASW_CHECK_ARG(N >= 0 && N <= COARSE_MAX_N, "coarse_select: N = %d outside 0..%d", N, COARSE_MAX_N);
+  ASW_CHECK_ARG(cap >= 1 && cap <= COARSE_MAX_CAP, "coarse_select: cap = %d outside 1..%d", cap, COARSE_MAX_CAP);
+  ASW_CHECK_ARG(kept && counts && thr, "coarse_select: null output");
+  hipStream_t s = asw::as_stream(stream);
+  if (N == 0) {
+    // no cube: nothing to launch; the outputs are (-1 ..), (0, 0), (thr1, NaN), written as 32-bit words
+    uint64_t bits[2] = {0, 0x7ff8000000000000ULL};
+    memcpy(&bits[0], &thr1, sizeof(double));
+    ASW_HIP(hipMemsetAsync(kept, 0xff, (size_t)cap * sizeof(int32_t), s));
+    ASW_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int32_t), s));
+    for (int w = 0; w < 4; ++w)
+      ASW_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(reinterpret_cast<uint32_t*>(thr) + w),
+                                (int)(uint32_t)(bits[w / 2] >> (32 * (w & 1))), 1, s));
+    return ASW_OK;
+  }
+  ASW_CHECK_ARG(energies && dis1 && workspace, "coarse_select: null pointer");
+  const size_t need = coarse_workspace_need(N, cap);
+  ASW_CHECK_ARG(workspace_bytes >= need, "coarse_select: workspace of %zu bytes too small, %zu needed", workspace_bytes, need);
+  ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "coarse_select: workspace not 8-byte aligned");
+
+  const int ns = (int)coarse_slices(N);
+  double* part = static_cast<double*>(workspace);
+  double* slice_max = part + COARSE_MAX_PARTS;
+  int32_t* slice_cnt = reinterpret_cast<int32_t*>(slice_max + ns);
+  int32_t* slice_list = slice_cnt + 2 * (size_t)ns;
+  const int nparts = ns < COARSE_MAX_PARTS ? ns : COARSE_MAX_PARTS;
+  if (relative) {
+    asw::ProfScope prof(s, "coarse_max", 0.0, (double)N * 24);
+    hipLaunchKernelGGL(coarse_max_kernel, dim3(nparts), dim3(256), 0, s, energies, dis1, N, part);
+    ASW_LAUNCH_CHECK();
+  }
+  {
+    asw::ProfScope prof(s, "coarse_slices", 0.0, (double)N * 28);
+    hipLaunchKernelGGL(coarse_slice_kernel, dim3(ns), dim3(256), 0, s, energies, dis1, best, N, thr1, relative ? 1 : 0, rel, cap,
+                       part, nparts, slice_max, slice_cnt, slice_list);
+    ASW_LAUNCH_CHECK();
+  }
+  asw::ProfScope prof(s, "coarse_merge", 0.0, (double)ns * (cap + 2) * 4);
+  hipLaunchKernelGGL(coarse_merge_kernel, dim3(1), dim3(256), 0, s, energies, N, thr1, relative ? 1 : 0, rel, cap, ns, slice_max,
+                     slice_cnt, slice_list, kept, counts, thr);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

@@ -294,6 +294,39 @@ std::tuple<Tensor, Tensor> global_clusters(const Tensor& full, const Tensor& seg
   return {label, merge};
 }
 
+// -> kept [cap] int32, counts [2] int32, thr [2] float64: the coarse stage's decision over the N cubes of a lattice
+// (search.coarse_select_f64).  Column 1 of `energies` is read where spot_shift_and_sep wrote it; nothing is read back.
+std::tuple<Tensor, Tensor, Tensor> coarse_select(const Tensor& energies, const Tensor& dis1, const c10::optional<Tensor>& best,
+                                                 double thr1, bool relative, double rel, int64_t cap) {
+  need(energies, "energies", at::kDouble, 2);
+  need(dis1, "dis1", at::kDouble, 1);
+  same_device(energies, dis1, "energies and dis1");
+  const int N = checked_int(energies.size(0), "N");
+  TORCH_CHECK(energies.size(1) == 2, "energies must be [N, 2]");
+  TORCH_CHECK(dis1.size(0) == N, "dis1 must be [N]");
+  TORCH_CHECK(N <= (1 << 24), "coarse_select takes at most 2^24 cubes, got ", N);
+  TORCH_CHECK(cap >= 1 && cap <= 64, "cap must lie in 1..64, got ", cap);
+  const int32_t* best_p = nullptr;
+  if (best.has_value()) {
+    need(*best, "best", at::kInt, 1);
+    same_device(energies, *best, "energies and best");
+    TORCH_CHECK(best->size(0) == N, "best must be [N]");
+    best_p = N > 0 ? best->data_ptr<int32_t>() : nullptr;
+  }
+  Tensor kept = at::empty({cap}, energies.options().dtype(at::kInt));
+  Tensor counts = at::empty({2}, energies.options().dtype(at::kInt));
+  Tensor thr = at::empty({2}, energies.options());
+  const size_t ws_bytes = asw_coarse_select_workspace_bytes(N, static_cast<int>(cap));
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_coarse_select_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>(ws_bytes / 8)}, energies.options());
+  Launch l(energies);
+  check_status(asw_coarse_select(N > 0 ? energies.data_ptr<double>() : nullptr, N > 0 ? dis1.data_ptr<double>() : nullptr, best_p,
+                                 N, thr1, relative ? 1 : 0, rel, static_cast<int>(cap), ws.data_ptr(), ws_bytes,
+                                 kept.data_ptr<int32_t>(), counts.data_ptr<int32_t>(), thr.data_ptr<double>(), l.stream),
+               "asw_coarse_select");
+  return {kept, counts, thr};
+}
+
 Tensor center_rows_(Tensor y) {
   need(y, "y", at::kFloat, 2);
   if (y.size(0) == 0) return y;
@@ -665,6 +698,8 @@ TORCH_LIBRARY(asw, m) {
         "float sim_db=-4.0, bool want_gram=False) -> (Tensor, Tensor, Tensor)");
   m.def("global_clusters(Tensor full, Tensor seg, Tensor counts, Tensor near, float sim_db=-1.0, float win_hi=-2.0, "
         "float win_lo=-7.0, float best_hi=-1.0, float best_lo=-5.0, bool want_merge=False) -> (Tensor, Tensor)");
+  m.def("coarse_select(Tensor energies, Tensor dis1, Tensor? best=None, float thr1=0.008, bool relative=False, "
+        "float rel=0.4, int cap=30) -> (Tensor, Tensor, Tensor)");
   m.def("center_rows_(Tensor(a!) y) -> Tensor(a!)");
   m.def("srp_phat_map(Tensor mix, Tensor twiddle, Tensor pair_i, Tensor pair_j, Tensor tau, Tensor omega, int window, "
         "int step, int n_windows, int nfft, int hop, float tol) -> Tensor");
@@ -698,6 +733,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("voiced_segments", &voiced_segments);
   m.impl("fine_clusters", &fine_clusters);
   m.impl("global_clusters", &global_clusters);
+  m.impl("coarse_select", &coarse_select);
   m.impl("center_rows_", &center_rows_);
   m.impl("srp_phat_map", &srp_phat_map);
   m.impl("pruner_covariance", &pruner_covariance);

@@ -132,6 +132,58 @@ def lattice_patches(node, lattice):
             for g in range(cells.shape[0])]
 
 
+def lattice_offsets_i32(lattice):
+    """int32 [N,P] = cells * width: the offsets ``spot.offsets_from_patches(lattice_patches(...))`` gives (whole
+    numbers, exact in float32), without a patch."""
+    return np.ascontiguousarray((lattice.cells.astype(np.int64) * int(lattice.width)).astype(np.int32))
+
+
+def lattice_dis1(lattice, mic_positions):
+    """float64 [N]: 1 + the distance of every cube's centre to microphone 0, formed per cube by the very expression of
+    ``search.binary_search_baseline`` (``np.linalg.norm(c - mic_positions[0])``, then ``d + 1``)."""
+    out = np.empty(lattice.n_cubes, dtype=np.float64)
+    for g in range(lattice.n_cubes):
+        out[g] = np.linalg.norm(lattice.centres[g] - mic_positions[0]) + 1
+    return out
+
+
+class LatticePatches(object):
+    """``lattice_patches(node, lattice)`` as a lazy sequence: ``len``, iteration, integer and slice indexing.  ``[g]``
+    builds a fresh ``Patch`` equal to item g of the list (``check_out`` mutates a patch, so every access returns a new
+    object); ``built`` counts them.  ``offsets_i32`` and ``dis1`` are the tables of ``lattice_offsets_i32`` and
+    ``lattice_dis1`` (``dis1`` may be None when no microphone position was given): a search that decides its coarse
+    stage on the GPU scores the first, weights by the second and builds only the patches it keeps."""
+
+    def __init__(self, node, lattice, offsets_i32=None, dis1=None):
+        self.node, self.lattice = node, lattice
+        self.offsets_i32 = lattice_offsets_i32(lattice) if offsets_i32 is None else offsets_i32
+        self.dis1 = dis1
+        self.built = 0
+
+    def __len__(self):
+        return self.lattice.n_cubes
+
+    def _patch(self, g):
+        cells, bounds, members, centres = self.lattice
+        width = self.lattice.width
+        pos = self.node.Pos_1.reshape(-1, 3)[members[bounds[g]:bounds[g + 1]]]
+        self.built += 1
+        return Patch(cells[g].astype(np.float64) * width, np.full(cells.shape[1], width), pos.T, centres[g].copy())
+
+    def __getitem__(self, g):
+        if isinstance(g, slice):
+            return [self._patch(k) for k in range(*g.indices(len(self)))]
+        k = int(g)
+        if k < 0:
+            k += len(self)
+        if not 0 <= k < len(self):
+            raise IndexError(f"cube {g} of a lattice of {len(self)}")
+        return self._patch(k)
+
+    def __iter__(self):
+        return (self._patch(g) for g in range(len(self)))
+
+
 # ---- non-maximum suppression over the lattice (Prone_method="DENSE_NMS") ---------------------------------------
 def lattice_local_maxima(cells, scores, radius=1, chunk=1 << 22):
     """(best int32 [N], degree int32 [N]) of the cubes ``cells`` int32 [N,P] (as ``coarse_lattice`` /
@@ -164,20 +216,33 @@ def lattice_local_maxima(cells, scores, radius=1, chunk=1 << 22):
     return best, degree
 
 
-def lattice_local_maxima_device(cells_dev, scores, radius=1):
+def lattice_local_maxima_device(cells_dev, scores, radius=1, sorted_checked=False):
     """``lattice_local_maxima`` by ``torch.ops.asw.lattice_nms`` on a cells tensor that lives on the GPU: only the N
     scores go up, ``best`` and ``degree`` come back.  Refuses what the statement refuses, and a table whose column 0
-    decreases somewhere -- the kernel finds the cubes near a block of rows by bisection in that column."""
+    decreases somewhere -- the kernel finds the cubes near a block of rows by bisection in that column.
+    ``scores`` may also be a float64 tensor on the cells' device: nothing goes up then, nothing waits for the device and
+    ``best`` and ``degree`` are returned as device tensors; whether every score is finite cannot be asked without a
+    read-back and is left to the caller (a score that is not finite only loses comparisons, it faults nothing), and the
+    caller vouches for the sort order with ``sorted_checked`` once it has asked."""
     import torch
     from . import native
-    scores = np.ascontiguousarray(scores, dtype=np.float64)
-    if cells_dev.dim() != 2 or scores.shape != (int(cells_dev.shape[0]),):
-        raise ValueError(f"cells must be [N, P] and scores [N], got {tuple(cells_dev.shape)} and {scores.shape}")
+    resident = isinstance(scores, torch.Tensor)
+    if resident:
+        if scores.device != cells_dev.device or scores.dtype != torch.float64:
+            raise ValueError("device scores must be float64 on the device of cells")
+        scores = scores.contiguous()
+    else:
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+    if cells_dev.dim() != 2 or tuple(scores.shape) != (int(cells_dev.shape[0]),):
+        raise ValueError(f"cells must be [N, P] and scores [N], got {tuple(cells_dev.shape)} and {tuple(scores.shape)}")
     if int(radius) != radius or radius < 1:
         raise ValueError(f"radius must be a whole number >= 1, got {radius!r}")
-    if not np.all(np.isfinite(scores)):
+    if not resident and not np.all(np.isfinite(scores)):
         raise ValueError("every score must be finite")
-    if cells_dev.shape[0] > 1 and not bool((cells_dev[1:, 0] >= cells_dev[:-1, 0]).all()):
+    if not sorted_checked and cells_dev.shape[0] > 1 and not bool((cells_dev[1:, 0] >= cells_dev[:-1, 0]).all()):
         raise ValueError("column 0 of cells must be non-decreasing (the lattice is sorted with pair 0 most significant)")
+    if resident:
+        best, degree = native.torch_ops().lattice_nms(cells_dev, scores, int(radius))
+        return best, degree
     best, degree = native.torch_ops().lattice_nms(cells_dev, torch.from_numpy(scores).to(cells_dev.device), int(radius))
     return best.cpu().numpy(), degree.cpu().numpy()

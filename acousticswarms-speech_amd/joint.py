@@ -43,10 +43,10 @@ GEOMETRY_CACHE_SIZE = 8        # arrays kept by JointModel.mic_array_for (a 7-mi
 
 
 def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host", segments="host", clustering="host",
-               global_clustering="host"):
+               global_clustering="host", coarse="host"):
     """The configuration string of the reference's ``setup`` (:125-131), extended by the pruning method, the
-    geometry mode, the segments mode, the clustering mode and the global clustering mode when they are not the
-    defaults."""
+    geometry mode, the segments mode, the clustering mode, the global clustering mode and the coarse mode when they
+    are not the defaults."""
     key = '~'.join([f"{x:.05f}" for x in np.asarray(mic_positions).flatten()]) \
         + '|' + '~'.join([f"{x:.05f}" for x in speaker_range])
     if prone_method != "SRP":
@@ -59,6 +59,8 @@ def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host"
         key += '|clustering=' + str(clustering)
     if global_clustering != "host":
         key += '|global_clustering=' + str(global_clustering)
+    if coarse != "host":
+        key += '|coarse=' + str(coarse)
     return key
 
 
@@ -72,12 +74,16 @@ class _Pending(object):
 
 class JointModel(object):
     def __init__(self, spot_model, sep_model=None, device=None, geometry="host", segments="host", clustering="host",
-                 global_clustering="host"):
+                 global_clustering="host", coarse="host"):
         """``geometry``: default of ``setup``'s argument of that name and the mode of the per-mixture arrays of
         ``mic_array_for`` -- "host" or "device" (see ``MicArray``).  ``segments``: the same for where the clustering
         finds the voiced segments of the cluster heads, and ``clustering`` for where the fine stage clusters the
         candidates of its coarse patches, and ``global_clustering`` for where the global clustering decides (``"device"``
-        needs ``segments="device"``)."""
+        needs ``segments="device"``).  ``coarse``: where the coarse stage of a lattice search decides (``"device"`` needs
+        a ``prone_method`` of ``LATTICE_METHODS`` at ``setup`` / ``mic_array_for``)."""
+        if coarse not in ("host", "device"):
+            raise ValueError(f'coarse must be "host" or "device", got {coarse!r}')
+        self.coarse = coarse
         if geometry not in ("host", "device"):
             raise ValueError(f'geometry must be "host" or "device", got {geometry!r}')
         if segments not in ("host", "device"):
@@ -104,7 +110,7 @@ class JointModel(object):
         self._mix_dev = self._mix_src = None
 
     def setup(self, mic_positions, speaker_range, cached=False, cached_folder=None, prone_method="SRP", geometry=None,
-              segments=None, clustering=None, global_clustering=None):
+              segments=None, clustering=None, global_clustering=None, coarse=None):
         """(Re)build the geometry tables unless the configuration is unchanged (:125-137).
         One-off per geometry and excluded from latency, as the reference's README notes.
         ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS"; "DENSE": no pruner, the whole
@@ -112,12 +118,15 @@ class JointModel(object):
         "device", default: the model's): where the tables are built.  ``segments`` ("host" | "device", default: the
         model's): where the voiced segments of the cluster heads are found; ``clustering`` ("host" | "device",
         default: the model's): where the fine stage clusters the candidates of its coarse patches; ``global_clustering``
-        ("host" | "device", default: the model's): where the global clustering decides."""
+        ("host" | "device", default: the model's): where the global clustering decides; ``coarse`` ("host" | "device",
+        default: the model's): where the coarse stage of a lattice search decides."""
         geometry = self.geometry if geometry is None else geometry
         segments = self.segments if segments is None else segments
         clustering = self.clustering if clustering is None else clustering
         global_clustering = self.global_clustering if global_clustering is None else global_clustering
-        key = config_key(mic_positions, speaker_range, prone_method, geometry, segments, clustering, global_clustering)
+        coarse = self.coarse if coarse is None else coarse
+        key = config_key(mic_positions, speaker_range, prone_method, geometry, segments, clustering, global_clustering,
+                         coarse)
         if key == self.previous_config:
             print("reuse the previous recycle!")
             return
@@ -125,7 +134,7 @@ class JointModel(object):
         gc.unfreeze()                       # a previous geometry may go now
         self.Mic_processor = MicArray(mic_positions, Spk_Range=speaker_range, Prone_method=prone_method,
                                       device=self.device, geometry=geometry, segments=segments,
-                                      clustering=clustering, global_clustering=global_clustering)
+                                      clustering=clustering, global_clustering=global_clustering, coarse=coarse)
         self.previous_config = key
         # The geometry tables are tens of thousands of small arrays and lists that live as long as
         # this configuration.  Left in the collector's oldest generation they make every full
@@ -147,7 +156,7 @@ class JointModel(object):
         (``batching.no_full_collections``), so no full collection lands inside a search, and an evicted array is
         released by reference counting alone -- its tables hold no reference cycle."""
         key = config_key(mic_positions, speaker_range, prone_method, self.geometry, self.segments, self.clustering,
-                         self.global_clustering)
+                         self.global_clustering, self.coarse)
         with self._geometry_lock:
             hit = self._geometry_cache.get(key)
             if hit is None:
@@ -167,7 +176,7 @@ class JointModel(object):
         try:
             mp = MicArray(np.asarray(mic_positions), Spk_Range=speaker_range, Prone_method=prone_method,
                           device=self.device, geometry=self.geometry, segments=self.segments,
-                          clustering=self.clustering, global_clustering=self.global_clustering)
+                          clustering=self.clustering, global_clustering=self.global_clustering, coarse=self.coarse)
         except BaseException as exc:
             with self._geometry_lock:
                 self._geometry_cache.pop(key, None)
@@ -190,7 +199,7 @@ class JointModel(object):
         method = self.Mic_processor.Prone_method if self.Mic_processor is not None else "SRP"
         self.Mic_processor = self.mic_array_for(mic_positions, speaker_range, method)
         self.previous_config = config_key(mic_positions, speaker_range, method, self.geometry, self.segments,
-                                          self.clustering, self.global_clustering)
+                                          self.clustering, self.global_clustering, self.coarse)
 
     def forward(self, mix_data):
         """-> (patches, audio_loc, audio, SRP_drop, stage1_drop, spot_times) (:142-149)."""

@@ -7,7 +7,7 @@ reference including its order-dependent quirks (documented inline).
 """
 import numpy as np
 
-from .dense_grid import lattice_patches
+from .dense_grid import LatticePatches, lattice_patches
 from .fine_cluster import clusters_of_group
 from .global_cluster import clusters_of_labels
 from .hostdsp import max_avg_power, si_sdr, split_wav, split_wise_sisdr
@@ -80,7 +80,7 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
 class MicArray(object):
     def __init__(self, mic_positions, demo=False, Spk_Range=None, grid_size=0.05, Prone_method="SRP",
                  MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None,
-                 geometry="host", segments="host", clustering="host", global_clustering="host"):
+                 geometry="host", segments="host", clustering="host", global_clustering="host", coarse="host"):
         """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
         (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture).
         ``Prone_method="DENSE"`` takes the pruner out: ``Apply_SRP_PHAT`` returns every width-``INIT_WIDTH`` cube of
@@ -97,7 +97,18 @@ class MicArray(object):
         ``global_clustering``: where the global clustering decides -- "host" (the SI-SDR matrix, the segment tensor and
         the segment tables are read back and walked in numpy) or "device" (the three SI-SDR ops leave their results on
         the GPU, one ``global_clusters`` call of the scorer, ``global_cluster.global_clusters_f64`` on the GPU, decides
-        there, and only the [n] labels come back; needs ``segments="device"`` and the HIP spot model)."""
+        there, and only the [n] labels come back; needs ``segments="device"`` and the HIP spot model).
+        ``coarse``: where the coarse stage of a lattice search (``Prone_method`` in ``LATTICE_METHODS``) decides --
+        "host" (a patch per cube, ``binary_search_baseline``) or "device" (``Apply_SRP_PHAT`` returns a lazy
+        ``dense_grid.LatticePatches``; the offsets and distances of the cubes stay on the GPU as tables of the array,
+        one ``score_offsets`` call, for "DENSE_NMS" one ``lattice_nms`` call on the device scores and one
+        ``coarse_select`` call of the scorer, ``search.coarse_select_f64`` on the GPU, decide there, one read-back
+        brings the decision, and only the kept patches are built; needs the HIP spot model on one GPU)."""
+        if coarse not in ("host", "device"):
+            raise ValueError(f'coarse must be "host" or "device", got {coarse!r}')
+        if coarse == "device" and Prone_method in PRONE_METHODS and Prone_method not in LATTICE_METHODS:
+            raise ValueError(f'coarse="device" needs a lattice search (Prone_method in {LATTICE_METHODS}), got {Prone_method!r}')
+        self.coarse = coarse
         if segments not in ("host", "device"):
             raise ValueError(f'segments must be "host" or "device", got {segments!r}')
         if clustering not in ("host", "device"):
@@ -127,6 +138,8 @@ class MicArray(object):
                                 geometry=geometry, lattice_width=INIT_WIDTH if Prone_method in LATTICE_METHODS else None)
         if Prone_method in LATTICE_METHODS and self.SRP_node.lattice.n_cubes == 0:
             raise RuntimeError("the keep-out region covers the whole speaker range: the TDoA lattice is empty")
+        if coarse == "device":
+            self.SRP_node.lattice_tables(mic_positions)     # once per array; the device copies follow at the first search
         self.original_times = 0
         self.spotforming_times = 0
         self.big_spotforming_times = 0
@@ -147,6 +160,10 @@ class MicArray(object):
         if self.Prone_method in LATTICE_METHODS:
             # no map, so the mixture is not read and no window length is required; fresh Patch objects per call,
             # because check_out mutates them
+            if getattr(self, "coarse", "host") == "device":
+                # nothing is built here: the cubes are rows of the array's tables until the coarse stage has decided
+                offsets, dis1 = self.SRP_node.lattice_tables()
+                return LatticePatches(self.SRP_node, self.SRP_node.lattice, offsets, dis1), np.zeros((3, 3))
             return lattice_patches(self.SRP_node, self.SRP_node.lattice), np.zeros((3, 3))
         mix_np = mix_data.numpy() if hasattr(mix_data, "numpy") else np.asarray(mix_data)
         win = 36000 if mix_np.shape[1] >= 72000 else 24000
@@ -157,6 +174,8 @@ class MicArray(object):
     # ---- stage 2: coarse Spotforming, relaxed window (sep/Mic_Array.py:196-222) ---------
     def Spotform_Big_Patch(self, mix_data, patch_list, spot_model):
         self.big_spotforming_times = len(patch_list)
+        if getattr(self, "coarse", "host") == "device":
+            return self._coarse_device(mix_data, patch_list, spot_model)
         kept, _powers_with_dis, rel_thr = binary_search_baseline(
             mix_data, spot_model, patch_list, self.mic_positions,
             survivors=self._lattice_survivors if self.Prone_method == "DENSE_NMS" else None)
@@ -164,6 +183,50 @@ class MicArray(object):
         pos = {id(p): i for i, p in enumerate(patch_list)}
         self.trace = {"coarse_kept": [pos[id(p)] for p in kept], "fine_clusters": {}, "final_clusters": []}
         return kept
+
+    def _coarse_device(self, mix_data, patch_list, spot_model):
+        """The coarse stage of a lattice search decided where the energies are: ``score_offsets`` on the array's offsets
+        table, for "DENSE_NMS" ``lattice_nms`` on the device scores, ``coarse_select`` (``search.coarse_select_f64``),
+        then the stage's one blocking copy -- kept, counts, threshold and, for the record in ``lattice_nms``, best and
+        degree -- and a ``Patch`` for each kept cube only."""
+        import torch
+        if getattr(spot_model, "world", 1) > 1:
+            raise RuntimeError('coarse="device" runs on one GPU: a sharded spot model gathers its energies as host arrays')
+        if not (hasattr(spot_model, "score_offsets") and hasattr(spot_model, "coarse_select")):
+            raise RuntimeError('coarse="device" needs a spot model with score_offsets() and coarse_select() (the HIP SpotModel)')
+        if not isinstance(patch_list, LatticePatches):
+            raise RuntimeError('coarse="device" takes the LatticePatches that Apply_SRP_PHAT returned')
+        node = self.SRP_node
+        dev = getattr(spot_model, "device", None)
+        tables = node.lattice_tables_device("cpu" if dev is None else dev)
+        offsets = patch_list.offsets_i32 if getattr(spot_model, "host_offsets", False) else tables["offsets"]
+        en_dev = spot_model.score_offsets(mix_data, offsets, Strict=0)
+        nms = self.Prone_method == "DENSE_NMS"
+        radius = search.LATTICE_NMS_RADIUS
+        best_dev = degree_dev = None
+        if nms:
+            best_dev, degree_dev = node.lattice_local_maxima_resident(en_dev[:, 1].contiguous(), radius)
+        cap = search.MAX_BIG_PATCH
+        kept_d, counts_d, thr_d = spot_model.coarse_select(en_dev, tables["dis1"], best_dev, cap=cap)
+        # int32 words throughout (the two doubles as four): one copy brings everything
+        parts = [kept_d.reshape(-1), counts_d.reshape(-1), thr_d.contiguous().view(torch.int32).reshape(-1)]
+        if nms:
+            parts += [best_dev.reshape(-1), degree_dev.reshape(-1)]
+        back = torch.cat(parts).cpu().numpy()
+        kept_idx, counts = back[:cap], back[cap:cap + 2]
+        thr = float(back[cap + 2:cap + 6].view(np.float64)[0])
+        if nms:
+            if counts[1] != 0:
+                raise ValueError("every score must be finite")
+            n = len(patch_list)
+            self.lattice_nms = {"radius": radius, "best": back[cap + 6:cap + 6 + n].copy(),
+                                "degree": back[cap + 6 + n:cap + 6 + 2 * n].copy()}
+        if counts[0] > cap:
+            print("warning too many patch remaining, only keep the best 30")
+        self.Relative_Threshold = thr * 1.2
+        kept_idx = [int(g) for g in kept_idx if g >= 0]
+        self.trace = {"coarse_kept": kept_idx, "fine_clusters": {}, "final_clusters": []}
+        return [patch_list[g] for g in kept_idx]
 
     def _lattice_survivors(self, powers_win):
         """DENSE_NMS: one flag per cube of the lattice, true for its local maxima under the windowed powers."""

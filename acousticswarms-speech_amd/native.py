@@ -232,6 +232,9 @@ SIGNATURES = {
     "asw_global_clusters_workspace_bytes": (c_size_t, [c_int]),
     "asw_global_clusters": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
                                     c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "asw_coarse_select_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "asw_coarse_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_double, c_int, c_void_p, c_size_t,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "asw_add_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "asw_search_area": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double,
                                 POINTER(c_int), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -189,3 +189,54 @@ def binary_search_baseline(mix_data, spot_model, patch_list, mic_positions, surv
             break
         kept.append(patch_list[i])
     return kept, with_dis, thr * 1.2
+
+
+def coarse_select_f64(power_win, dis1, alive=None, *, thr1=SPOT_POWER_THRESHOLD1, relative=USE_RELATIVE_SPOT_POWER, rel=0.4,
+                      cap=MAX_BIG_PATCH, stats=None):
+    """The decision of ``binary_search_baseline`` over N candidates, stated on arrays: -> (kept int32 [<= cap], n_pass,
+    thr).  csrc/cluster_kernels.hip (``asw_coarse_select``) computes the same on the GPU, byte for byte; this is its
+    statement.
+
+    ``power_win`` float64 [N]; ``dis1`` float64 [N], the loop's ``d + 1``; ``alive`` optional flags [N] (the loop's
+    ``survivors``).  ``wd[i] = power_win[i] * dis1[i]``, one IEEE multiply.  ``max_wd`` is the largest ``wd`` that is not
+    NaN -- +0.0 when that is a zero and some ``wd`` is +0.0, NaN (``np.nan``) when there is none.  ``thr = thr1``; with
+    ``relative`` and a ``max_wd`` that is not NaN, ``t = rel * max_wd`` and ``thr = t if t < thr1 else thr1``.  Candidate i
+    passes when ``not (wd[i] < thr)`` and (``alive is None`` or ``alive[i] != 0``): a NaN passes, as in the loop.  The
+    candidates that pass are ordered by descending ``power_win``, equal values (-0.0 equals 0.0) by ascending index,
+    every NaN after every number, by index.  ``kept`` is the first ``min(cap, n_pass)`` of that order and ``n_pass``
+    counts all that pass: the loop prints its warning exactly when ``n_pass > cap``.  ``thr`` is returned unscaled (the
+    loop returns ``thr * 1.2``).  ``np.argsort`` leaves the order of equal powers open, so the loop equals this
+    statement on tie-free powers.  ``stats``: a dict that receives ``max_wd`` and ``non_finite``, the number of entries
+    of ``power_win`` that are not finite."""
+    pw = np.ascontiguousarray(power_win, dtype=np.float64).reshape(-1)
+    d1 = np.ascontiguousarray(dis1, dtype=np.float64).reshape(-1)
+    if d1.shape != pw.shape:
+        raise ValueError(f"power_win and dis1 must have one shape, got {pw.shape} and {d1.shape}")
+    if alive is not None and np.shape(alive) != pw.shape:
+        raise ValueError(f"alive must hold one flag per candidate ({pw.shape[0]}), got shape {np.shape(alive)}")
+    if int(cap) != cap or cap < 1:
+        raise ValueError(f"cap must be a whole number >= 1, got {cap!r}")
+    with np.errstate(invalid="ignore", over="ignore"):
+        wd = pw * d1
+        numbers = wd[~np.isnan(wd)]
+        max_wd = np.float64(np.nan)
+        if numbers.size:
+            max_wd = np.float64(numbers.max())
+            if max_wd == 0:
+                max_wd = np.float64(0.0) if np.any((numbers == 0) & ~np.signbit(numbers)) else np.float64(-0.0)
+        thr = np.float64(thr1)
+        if relative and not np.isnan(max_wd):
+            t = np.float64(rel) * max_wd
+            thr = t if t < thr else thr
+        passing = ~(wd < thr)
+    if alive is not None:
+        passing &= np.asarray(alive).reshape(-1) != 0
+    idx = np.flatnonzero(passing)
+    p = pw[idx]
+    nan = np.isnan(p)
+    # lexsort is stable and its last key is the most significant: NaN last, then descending power, then index
+    order = np.lexsort((idx, -np.where(nan, 0.0, p), nan))
+    if stats is not None:
+        stats["max_wd"] = max_wd
+        stats["non_finite"] = int(np.count_nonzero(~np.isfinite(pw)))
+    return idx[order][:int(cap)].astype(np.int32), int(idx.shape[0]), float(thr)

@@ -309,6 +309,40 @@ class SpotModel:
                                                            cnt_dev.contiguous(), near_d)
         return label
 
+    def score_offsets(self, input_channels, offsets, Strict: int = 0, window: int = 12000):
+        """``shift_and_score`` on a table of offsets instead of a patch list, with the result left where it was written:
+        ``offsets`` int32 [N, M-1], an ndarray or a tensor on the model's device -> the device tensor [N,2] float64 =
+        (power, power2).  A host table goes up through pinned memory; nothing comes back and nothing waits for the
+        device."""
+        import torch
+        self._need()
+        mix = torch.as_tensor(input_channels)
+        mix_d = mix.to(self.device, dtype=torch.float32).contiguous()
+        if isinstance(offsets, torch.Tensor):
+            off_d = offsets.to(self.device, dtype=torch.int32).contiguous()
+        else:
+            off_d = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32)).pin_memory().to(self.device, non_blocking=True)
+        if off_d.dim() != 2 or off_d.shape[1] != mix_d.shape[0] - 1:
+            raise RuntimeError(f"offsets of shape {tuple(off_d.shape)} do not fit a mixture of {mix_d.shape[0]} channels")
+        if off_d.shape[0] == 0:
+            return torch.empty((0, 2), dtype=torch.float64, device=self.device)
+        _wave, en = self.shift_and_sep_device(mix_d, off_d, Strict, want_wave=False, want_energy=True, window=window)
+        return en
+
+    def coarse_select(self, en_dev, dis1_dev, best_dev=None, thr1=None, relative=None, rel: float = 0.4, cap=None):
+        """The coarse stage's decision on the GPU (``search.coarse_select_f64``) over the device energies [N,2] of
+        ``score_offsets``, the device table ``dis1_dev`` [N] and, for the lattice's local maxima, ``best_dev`` int32 [N]
+        of ``lattice_nms``.  The thresholds default to ``search``'s constants, read per call.  Returns the device
+        tensors (kept [cap] int32 with -1 in the unused slots, counts [2] int32 = (cubes that pass, powers that are not
+        finite), thr [2] float64 = (threshold, largest weighted power)); nothing comes back and nothing waits for the
+        device."""
+        from . import search
+        return native.torch_ops().coarse_select(
+            en_dev.contiguous(), dis1_dev.contiguous(), None if best_dev is None else best_dev.contiguous(),
+            float(search.SPOT_POWER_THRESHOLD1 if thr1 is None else thr1),
+            bool(search.USE_RELATIVE_SPOT_POWER if relative is None else relative), float(rel),
+            int(search.MAX_BIG_PATCH if cap is None else cap))
+
     def forward(self, mix, window_embedding):
         """Network.forward: mix [B,M,t] (already normalised), window_embedding [B,2] -> [B,1,t]
         (device tensor).  Rows are grouped by identical embedding because the window gate

@@ -112,6 +112,7 @@ class LookupPositions(object):
         return a if dtype is None else a.astype(dtype)
 
 
+_TABLES_LOCK = threading.RLock()        # guards the lazily built lattice tables of every node (SRPPhat.lattice_tables)
 _TWIDDLES = {}
 _TWIDDLES_LOCK = threading.Lock()
 
@@ -326,6 +327,60 @@ class SRPPhat(object):
         if self.geometry != "device":
             return lattice_local_maxima(self.lattice.cells, scores, radius)
         return lattice_local_maxima_device(self._geom_dev["cells"], scores, radius)
+
+    def lattice_tables(self, mic_positions=None):
+        """(offsets_i32 [N,P], dis1 [N]) of this node's lattice (``dense_grid.lattice_offsets_i32`` / ``lattice_dis1``
+        against ``mic_positions[0]``, default the node's own microphone 0), built at the first call and kept: the
+        tables of a search that decides its coarse stage on the GPU."""
+        from .dense_grid import lattice_dis1, lattice_offsets_i32
+        if self.lattice is None:
+            raise RuntimeError("this node has no lattice: make it with lattice_width=")
+        with _TABLES_LOCK:
+            if getattr(self, "_lattice_tables", None) is None:
+                mic = self.mic_pos if mic_positions is None else mic_positions
+                self._lattice_tables = (lattice_offsets_i32(self.lattice), lattice_dis1(self.lattice, mic))
+                self._lattice_dev = {}
+            return self._lattice_tables
+
+    def lattice_tables_device(self, device):
+        """{"offsets": int32 [N,P], "dis1": float64 [N], "cells": int32 [N,P]} of ``lattice_tables`` as tensors on
+        ``device``, made once per device and kept.  On a device-built node whose cells live on that device the
+        offsets derive from that tensor and the cells are it; everything else goes up once.  The sort order the
+        ``lattice_nms`` kernel needs is asked here, once."""
+        import torch
+        offsets, dis1 = self.lattice_tables()
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        with _TABLES_LOCK:
+            hit = self._lattice_dev.get(device)
+            if hit is None:
+                g = self._geom_dev
+                cells = g.get("cells") if g is not None else None
+                if cells is not None and cells.device == device:
+                    off_d = (cells * int(self.lattice.width)).contiguous()
+                else:
+                    cells = torch.from_numpy(np.ascontiguousarray(self.lattice.cells, dtype=np.int32)).to(device)
+                    off_d = torch.from_numpy(offsets).to(device)
+                if cells.shape[0] > 1 and not bool((cells[1:, 0] >= cells[:-1, 0]).all()):
+                    raise ValueError("column 0 of cells must be non-decreasing (the lattice is sorted with pair 0 most significant)")
+                hit = self._lattice_dev[device] = {"offsets": off_d, "dis1": torch.from_numpy(dis1).to(device), "cells": cells}
+            return hit
+
+    def lattice_local_maxima_resident(self, scores_dev, radius=1):
+        """``lattice_local_maxima`` under scores that are a float64 tensor [n_cubes]: -> (best, degree) as int32 tensors
+        on the scores' device.  On the GPU ``torch.ops.asw.lattice_nms`` runs on the cells of ``lattice_tables_device``
+        with no upload, no read-back and no check that the scores are finite (the caller learns that from
+        ``coarse_select``'s count); CPU tensors (a stand-in scorer) go through the numpy statement."""
+        import torch
+        from .dense_grid import lattice_local_maxima, lattice_local_maxima_device
+        if tuple(scores_dev.shape) != (self.lattice.n_cubes,):
+            raise ValueError(f"scores must hold one value per cube ({self.lattice.n_cubes}), got shape {tuple(scores_dev.shape)}")
+        if not scores_dev.is_cuda:
+            best, degree = lattice_local_maxima(self.lattice.cells, scores_dev.numpy(), radius)
+            return torch.from_numpy(best), torch.from_numpy(degree)
+        cells = self.lattice_tables_device(scores_dev.device)["cells"]
+        return lattice_local_maxima_device(cells, scores_dev, radius, sorted_checked=True)
 
     def _lookup_grid(self, step):
         r = self.Range_spk

@@ -600,6 +600,35 @@ int asw_global_clusters(const double* full, const double* seg, const int32_t* co
                         double sim_db, double win_hi, double win_lo, double best_hi, double best_lo, void* workspace,
                         size_t workspace_bytes, int32_t* label, uint8_t* merge_or_null, void* stream);
 
+/* The coarse stage's decision over the N cubes of a lattice on the device (binary_search_baseline,
+ * local_utils_3d.py:339-388, with the survivors mask of Prone_method="DENSE_NMS"), as search.coarse_select_f64 states
+ * it and equal to that statement in every output byte.  All arrays are device arrays.  energies float64 [N][2] as
+ * asw_spot_shift_and_sep writes it: only column 1, power_win, is read, in place; dis1 float64 [N] = 1 + the distance
+ * of the cube's centre to microphone 0; best int32 [N] from asw_lattice_nms, or NULL: cube i is alive when best[i] ==
+ * i (NULL: every cube is).
+ *   wd[i] = power_win[i] * dis1[i], one IEEE multiply.  max_wd = the largest wd that is not NaN (+0.0 when the largest
+ *   is a zero and some wd is +0.0; the quiet NaN 0x7ff8000000000000 when there is none).  thr = thr1; with relative != 0
+ *   and a max_wd that is not NaN, t = rel * max_wd and thr = t < thr1 ? t : thr1.
+ *   Cube i passes when not (wd[i] < thr) and it is alive -- a NaN passes.  The cubes that pass are ordered by descending
+ *   power_win, equal values (-0.0 equals 0.0) by ascending index, every NaN after every number, by index.
+ * kept int32 [cap]: the first min(cap, n_pass) of that order, the other slots -1.  counts int32 [2] = (n_pass, the number
+ * of cubes, alive or not, whose power_win is not finite).  thr float64 [2] = (thr, max_wd).
+ * workspace: asw_coarse_select_workspace_bytes(N, cap) bytes, 8-byte aligned (0 with the error message set for N outside
+ * 0..2^24 or cap outside 1..64).  The cubes are cut into slices of 1024.  Launches: coarse_max (only with relative != 0;
+ * at most 256 workgroups, each writes the maximum of its share of the cubes), coarse_slices (a workgroup per slice: its counts, its
+ * maximum and its ordered best cap cubes, found by counting each cube's predecessors in LDS) and coarse_merge (one
+ * workgroup folds the slices' lists, 1024 entries at a time, into the best cap and sums the counts).  Workgroups hand
+ * nothing to each other inside a launch; no atomics, no device-side assert, plain vector stores: two calls give
+ * identical bytes, every output slot is written, every workspace slot that is read is written first, and the result does
+ * not depend on what the outputs or the workspace held.  A value of best outside 0..N-1 only makes its cube not alive.
+ * Every refusal -- N < 0 or N > 2^24, cap outside 1..64, a null pointer other than best, a short or misaligned
+ * workspace -- happens on the host before the first launch; N = 0 succeeds, launches no kernel and fills the outputs
+ * (-1, (0, 0), (thr1, NaN)) by memsets on the stream. */
+size_t asw_coarse_select_workspace_bytes(int N, int cap);
+int asw_coarse_select(const double* energies, const double* dis1, const int32_t* best_or_null, int N, double thr1,
+                      int relative, double rel, int cap, void* workspace, size_t workspace_bytes, int32_t* kept,
+                      int32_t* counts, double* thr, void* stream);
+
 /* HOST function (no GPU): breadth-first subdivision of one coarse hypercube into the fine
  * candidate hypercubes -- search_area / binary_area_divide_width
  * (sep/helpers/local_utils_3d.py:212-335) with Patch.check_out / hyperbola_sample
