@@ -209,15 +209,27 @@ class CandidateBatcher(object):
 
 
 class MixtureScorer(object):
-    """The spot-model surface one search uses (coarse ``shift_and_score`` or, with ``coarse="device"``,
-    ``score_offsets`` and ``coarse_select``; fine ``shift_and_sep_resident``; the device SI-SDR helpers), bound to mixture ``k`` of a batcher.  The mixture argument of the calls is
-    ignored: the candidates are scored against ``batcher.mixes[k]``."""
+    """The spot-model surface one search uses, bound to mixture ``k`` of a batcher: the scoring calls (coarse
+    ``shift_and_score`` or, with ``coarse="device"``, ``score_offsets``; fine ``shift_and_sep_resident``) go through
+    the batcher -- their mixture argument is ignored, the candidates are scored against ``batcher.mixes[k]`` -- and
+    the device helpers of ``FORWARDED`` are the wrapped model's."""
+
+    # the device helpers that do not touch the mixture: passed to the wrapped model unchanged
+    FORWARDED = ("pair_sisdr", "segment_sisdr", "voiced_segments", "segment_sisdr_device", "fine_clusters",
+                 "pair_sisdr_device", "segment_sisdr_resident", "global_clusters", "coarse_select")
 
     def __init__(self, batcher, k):
         self.batcher, self.k = batcher, k
         self.inner_model = batcher.model
         self.device = batcher.model.device
         self.batch_size = batcher.model.batch_size
+
+    def __getattr__(self, name):
+        """The device helpers are the wrapped model's own: ``hasattr`` answers as the model does, which is what the
+        capability checks of the modes (``modes.need_methods``) ask."""
+        if name in self.FORWARDED:
+            return getattr(self.inner_model, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def _offsets(self, patch_list):
         return offsets_from_patches(patch_list, self.batcher.mixes.shape[1] - 1)
@@ -235,30 +247,6 @@ class MixtureScorer(object):
     def shift_and_sep(self, input_channels, patch_list, Strict=0, save_input=False):
         raise RuntimeError("a batched search scores through shift_and_score / shift_and_sep_resident only")
 
-    def pair_sisdr(self, waves):
-        return self.inner_model.pair_sisdr(waves)
-
-    def segment_sisdr(self, waves, segments):
-        return self.inner_model.segment_sisdr(waves, segments)
-
-    def voiced_segments(self, waves):
-        return self.inner_model.voiced_segments(waves)
-
-    def segment_sisdr_device(self, waves, seg_dev, cnt_dev):
-        return self.inner_model.segment_sisdr_device(waves, seg_dev, cnt_dev)
-
-    def fine_clusters(self, waves, bounds, en_dev, gate, group_gate, min_trigger):
-        return self.inner_model.fine_clusters(waves, bounds, en_dev, gate, group_gate, min_trigger)
-
-    def pair_sisdr_device(self, waves):
-        return self.inner_model.pair_sisdr_device(waves)
-
-    def segment_sisdr_resident(self, waves, seg_dev, cnt_dev):
-        return self.inner_model.segment_sisdr_resident(waves, seg_dev, cnt_dev)
-
-    def global_clusters(self, full_dev, seg_dev, cnt_dev, near):
-        return self.inner_model.global_clusters(full_dev, seg_dev, cnt_dev, near)
-
     host_offsets = True     # score_offsets wants the host table: the batcher concatenates the requests on the host
 
     def score_offsets(self, input_channels, offsets, Strict=0, window=12000):
@@ -270,14 +258,11 @@ class MixtureScorer(object):
         _w, en = self.batcher.request(self.k, offsets, Strict, window, False)
         return en
 
-    def coarse_select(self, en_dev, dis1_dev, best_dev=None, **kw):
-        return self.inner_model.coarse_select(en_dev, dis1_dev, best_dev, **kw)
-
 
 def mixture_view(mic_array):
     """A per-search view of a MicArray: the geometry tables (tens of MB, read-only) are shared, everything a
     search writes -- the SRP map and its voxel image, counters, caches, the decision trace, the side stream --
-    is the view's own.  The modes (``segments``, ``clustering``, ``global_clustering``, ``coarse``) are the array's, and so
+    is the view's own.  The modes (``modes.MODE_NAMES``) are the array's, and so
     are the lattice tables of ``coarse="device"`` with their device copies, which no search writes."""
     v = copy.copy(mic_array)
     v.SRP_node = copy.copy(mic_array.SRP_node)

@@ -17,6 +17,7 @@ import time
 import numpy as np
 
 from .mic_array import MicArray
+from .modes import MODE_NAMES, check_modes
 
 
 def _sync():
@@ -44,23 +45,15 @@ GEOMETRY_CACHE_SIZE = 8        # arrays kept by JointModel.mic_array_for (a 7-mi
 
 def config_key(mic_positions, speaker_range, prone_method="SRP", geometry="host", segments="host", clustering="host",
                global_clustering="host", coarse="host"):
-    """The configuration string of the reference's ``setup`` (:125-131), extended by the pruning method, the
-    geometry mode, the segments mode, the clustering mode, the global clustering mode and the coarse mode when they
-    are not the defaults."""
+    """The configuration string of the reference's ``setup`` (:125-131), extended by the pruning method and by every
+    mode (``modes.MODE_NAMES``, in that order) that is not at its default."""
     key = '~'.join([f"{x:.05f}" for x in np.asarray(mic_positions).flatten()]) \
         + '|' + '~'.join([f"{x:.05f}" for x in speaker_range])
     if prone_method != "SRP":
         key += '|' + str(prone_method)
-    if geometry != "host":
-        key += '|geometry=' + str(geometry)
-    if segments != "host":
-        key += '|segments=' + str(segments)
-    if clustering != "host":
-        key += '|clustering=' + str(clustering)
-    if global_clustering != "host":
-        key += '|global_clustering=' + str(global_clustering)
-    if coarse != "host":
-        key += '|coarse=' + str(coarse)
+    for name, value in zip(MODE_NAMES, (geometry, segments, clustering, global_clustering, coarse)):
+        if value != "host":
+            key += '|' + name + '=' + str(value)
     return key
 
 
@@ -75,32 +68,14 @@ class _Pending(object):
 class JointModel(object):
     def __init__(self, spot_model, sep_model=None, device=None, geometry="host", segments="host", clustering="host",
                  global_clustering="host", coarse="host"):
-        """``geometry``: default of ``setup``'s argument of that name and the mode of the per-mixture arrays of
-        ``mic_array_for`` -- "host" or "device" (see ``MicArray``).  ``segments``: the same for where the clustering
-        finds the voiced segments of the cluster heads, and ``clustering`` for where the fine stage clusters the
-        candidates of its coarse patches, and ``global_clustering`` for where the global clustering decides (``"device"``
-        needs ``segments="device"``).  ``coarse``: where the coarse stage of a lattice search decides (``"device"`` needs
-        a ``prone_method`` of ``LATTICE_METHODS`` at ``setup`` / ``mic_array_for``)."""
-        if coarse not in ("host", "device"):
-            raise ValueError(f'coarse must be "host" or "device", got {coarse!r}')
-        self.coarse = coarse
-        if geometry not in ("host", "device"):
-            raise ValueError(f'geometry must be "host" or "device", got {geometry!r}')
-        if segments not in ("host", "device"):
-            raise ValueError(f'segments must be "host" or "device", got {segments!r}')
-        if clustering not in ("host", "device"):
-            raise ValueError(f'clustering must be "host" or "device", got {clustering!r}')
-        if global_clustering not in ("host", "device"):
-            raise ValueError(f'global_clustering must be "host" or "device", got {global_clustering!r}')
-        if global_clustering == "device" and segments != "device":
-            raise ValueError('global_clustering="device" needs segments="device"')
-        self.segments = segments
-        self.clustering = clustering
-        self.global_clustering = global_clustering
+        """The five modes (``modes.MODE_NAMES``; ``MicArray.__init__`` describes them) are the defaults of ``setup``'s
+        arguments of these names and the modes of the per-mixture arrays of ``mic_array_for``.  The rule that needs a
+        ``prone_method`` (``coarse="device"``) is checked at ``setup`` / ``mic_array_for``, where one is known."""
+        for name, value in zip(MODE_NAMES, check_modes(geometry, segments, clustering, global_clustering, coarse)):
+            setattr(self, name, value)
         self.spot_model = spot_model
         self.sep_model = sep_model
         self.device = device
-        self.geometry = geometry
         self._geometry_cache = collections.OrderedDict()      # config key -> MicArray | _Pending, least recent first
         self._geometry_lock = threading.Lock()
         self.geometry_stats = {"builds": 0, "hits": 0}
@@ -114,27 +89,17 @@ class JointModel(object):
         """(Re)build the geometry tables unless the configuration is unchanged (:125-137).
         One-off per geometry and excluded from latency, as the reference's README notes.
         ``prone_method`` picks the stage-1 pruning map ("SRP", "MUSIC" or "TOPS"; "DENSE": no pruner, the whole
-        coarse TDoA lattice of the array) and is part of the configuration, and so is ``geometry`` ("host" |
-        "device", default: the model's): where the tables are built.  ``segments`` ("host" | "device", default: the
-        model's): where the voiced segments of the cluster heads are found; ``clustering`` ("host" | "device",
-        default: the model's): where the fine stage clusters the candidates of its coarse patches; ``global_clustering``
-        ("host" | "device", default: the model's): where the global clustering decides; ``coarse`` ("host" | "device",
-        default: the model's): where the coarse stage of a lattice search decides."""
-        geometry = self.geometry if geometry is None else geometry
-        segments = self.segments if segments is None else segments
-        clustering = self.clustering if clustering is None else clustering
-        global_clustering = self.global_clustering if global_clustering is None else global_clustering
-        coarse = self.coarse if coarse is None else coarse
-        key = config_key(mic_positions, speaker_range, prone_method, geometry, segments, clustering, global_clustering,
-                         coarse)
+        coarse TDoA lattice of the array) and is part of the configuration, and so is each of the five modes
+        ("host" | "device", default: the model's; ``MicArray.__init__`` describes them)."""
+        modes = self._modes(geometry, segments, clustering, global_clustering, coarse)
+        key = config_key(mic_positions, speaker_range, prone_method, **modes)
         if key == self.previous_config:
             print("reuse the previous recycle!")
             return
         import gc
         gc.unfreeze()                       # a previous geometry may go now
         self.Mic_processor = MicArray(mic_positions, Spk_Range=speaker_range, Prone_method=prone_method,
-                                      device=self.device, geometry=geometry, segments=segments,
-                                      clustering=clustering, global_clustering=global_clustering, coarse=coarse)
+                                      device=self.device, **modes)
         self.previous_config = key
         # The geometry tables are tens of thousands of small arrays and lists that live as long as
         # this configuration.  Left in the collector's oldest generation they make every full
@@ -143,6 +108,13 @@ class JointModel(object):
         # generation: later collections only look at what a forward() itself allocates.
         gc.collect()
         gc.freeze()
+
+    def _modes(self, *given):
+        """The five modes as the keywords of ``config_key`` / ``MicArray``: the model's, or ``given`` (in the order of
+        ``MODE_NAMES``) where that is not None."""
+        values = [getattr(self, name) if value is None else value
+                  for name, value in zip(MODE_NAMES, given or [None] * len(MODE_NAMES))]
+        return dict(zip(MODE_NAMES, check_modes(*values)))
 
     def mic_array_for(self, mic_positions, speaker_range, prone_method="SRP"):
         """The ``MicArray`` of one mixture's own geometry (batch path, ``geometries=``), built in the model's
@@ -155,8 +127,8 @@ class JointModel(object):
         generation.  Instead the batch raises the collector's oldest-generation threshold while it runs
         (``batching.no_full_collections``), so no full collection lands inside a search, and an evicted array is
         released by reference counting alone -- its tables hold no reference cycle."""
-        key = config_key(mic_positions, speaker_range, prone_method, self.geometry, self.segments, self.clustering,
-                         self.global_clustering, self.coarse)
+        modes = self._modes()
+        key = config_key(mic_positions, speaker_range, prone_method, **modes)
         with self._geometry_lock:
             hit = self._geometry_cache.get(key)
             if hit is None:
@@ -175,8 +147,7 @@ class JointModel(object):
             return hit
         try:
             mp = MicArray(np.asarray(mic_positions), Spk_Range=speaker_range, Prone_method=prone_method,
-                          device=self.device, geometry=self.geometry, segments=self.segments,
-                          clustering=self.clustering, global_clustering=self.global_clustering, coarse=self.coarse)
+                          device=self.device, **modes)
         except BaseException as exc:
             with self._geometry_lock:
                 self._geometry_cache.pop(key, None)
@@ -198,8 +169,7 @@ class JointModel(object):
         per-mixture loop of ``shard.localize_batch(..., geometries=...)``."""
         method = self.Mic_processor.Prone_method if self.Mic_processor is not None else "SRP"
         self.Mic_processor = self.mic_array_for(mic_positions, speaker_range, method)
-        self.previous_config = config_key(mic_positions, speaker_range, method, self.geometry, self.segments,
-                                          self.clustering, self.global_clustering, self.coarse)
+        self.previous_config = config_key(mic_positions, speaker_range, method, **self._modes())
 
     def forward(self, mix_data):
         """-> (patches, audio_loc, audio, SRP_drop, stage1_drop, spot_times) (:142-149)."""

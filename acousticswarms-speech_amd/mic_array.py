@@ -11,6 +11,8 @@ from .dense_grid import LatticePatches, lattice_patches
 from .fine_cluster import clusters_of_group
 from .global_cluster import clusters_of_labels
 from .hostdsp import max_avg_power, si_sdr, split_wav, split_wise_sisdr
+from .modes import LATTICE_METHODS, MODE_NAMES, check_modes, need_methods
+from .native import read_back
 from .patch import FS, SPEED_OF_SOUND, Patch, pair_offsets
 from . import search
 from .search import (INIT_WIDTH, SPOT_POWER_THRESHOLD2, USE_RELATIVE_SPOT_POWER, binary_search_baseline,
@@ -28,7 +30,6 @@ FREQ_BINS = np.arange(BIN0, BIN1)
 # with a coarse stage that keeps only the lattice's local maxima (dense_grid.lattice_local_maxima)
 PRONE_METHODS = {"SRP": "SRP_Map_WINDOW_new", "MUSIC": "MUSIC_Map_WINDOW", "TOPS": "TOPS_Map_WINDOW", "DENSE": None,
                  "DENSE_NMS": None}
-LATTICE_METHODS = ("DENSE", "DENSE_NMS")
 
 
 def check_sisnr_win(sisnr_list, SISNR_THRESHOLD=-2, SISNR_THRESHOLD2=-7):
@@ -78,10 +79,14 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
 
 
 class MicArray(object):
+    # the modes (modes.MODE_NAMES; ``geometry`` is the SRP node's) of an array whose __init__ did not run
+    segments = clustering = global_clustering = coarse = "host"
+
     def __init__(self, mic_positions, demo=False, Spk_Range=None, grid_size=0.05, Prone_method="SRP",
                  MIN_TRIGGER_POWER=0.5, SRP_fast=False, cached=False, cached_folder=None, device=None,
                  geometry="host", segments="host", clustering="host", global_clustering="host", coarse="host"):
-        """``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
+        """The five modes (``modes.MODE_NAMES``), each "host" or "device", are described here and nowhere else.
+        ``geometry``: where the SRP stage's geometry tables are built -- "host" (numpy) or "device"
         (csrc/geometry_kernels.hip; same tables, for arrays that change from mixture to mixture).
         ``Prone_method="DENSE"`` takes the pruner out: ``Apply_SRP_PHAT`` returns every width-``INIT_WIDTH`` cube of
         the array's TDoA lattice, and the later stages run on that list unchanged.  ``"DENSE_NMS"`` has the same
@@ -104,22 +109,11 @@ class MicArray(object):
         one ``score_offsets`` call, for "DENSE_NMS" one ``lattice_nms`` call on the device scores and one
         ``coarse_select`` call of the scorer, ``search.coarse_select_f64`` on the GPU, decide there, one read-back
         brings the decision, and only the kept patches are built; needs the HIP spot model on one GPU)."""
-        if coarse not in ("host", "device"):
-            raise ValueError(f'coarse must be "host" or "device", got {coarse!r}')
-        if coarse == "device" and Prone_method in PRONE_METHODS and Prone_method not in LATTICE_METHODS:
-            raise ValueError(f'coarse="device" needs a lattice search (Prone_method in {LATTICE_METHODS}), got {Prone_method!r}')
-        self.coarse = coarse
-        if segments not in ("host", "device"):
-            raise ValueError(f'segments must be "host" or "device", got {segments!r}')
-        if clustering not in ("host", "device"):
-            raise ValueError(f'clustering must be "host" or "device", got {clustering!r}')
-        if global_clustering not in ("host", "device"):
-            raise ValueError(f'global_clustering must be "host" or "device", got {global_clustering!r}')
-        if global_clustering == "device" and segments != "device":
-            raise ValueError('global_clustering="device" needs segments="device"')
-        self.segments = segments
-        self.clustering = clustering
-        self.global_clustering = global_clustering
+        # (an unknown Prone_method is refused below, whatever the modes are)
+        modes = check_modes(geometry, segments, clustering, global_clustering, coarse,
+                            Prone_method=Prone_method if Prone_method in PRONE_METHODS else None)
+        for name, value in zip(MODE_NAMES[1:], modes[1:]):              # (``geometry`` goes to the SRP node below)
+            setattr(self, name, value)
         if Prone_method not in PRONE_METHODS:
             # the reference silently keeps an all-zero map for an unknown name (sep/Mic_Array.py:165-170)
             raise ValueError(f"Prone_method must be one of {sorted(PRONE_METHODS)}, got {Prone_method!r}")
@@ -160,7 +154,7 @@ class MicArray(object):
         if self.Prone_method in LATTICE_METHODS:
             # no map, so the mixture is not read and no window length is required; fresh Patch objects per call,
             # because check_out mutates them
-            if getattr(self, "coarse", "host") == "device":
+            if self.coarse == "device":
                 # nothing is built here: the cubes are rows of the array's tables until the coarse stage has decided
                 offsets, dis1 = self.SRP_node.lattice_tables()
                 return LatticePatches(self.SRP_node, self.SRP_node.lattice, offsets, dis1), np.zeros((3, 3))
@@ -174,7 +168,7 @@ class MicArray(object):
     # ---- stage 2: coarse Spotforming, relaxed window (sep/Mic_Array.py:196-222) ---------
     def Spotform_Big_Patch(self, mix_data, patch_list, spot_model):
         self.big_spotforming_times = len(patch_list)
-        if getattr(self, "coarse", "host") == "device":
+        if self.coarse == "device":
             return self._coarse_device(mix_data, patch_list, spot_model)
         kept, _powers_with_dis, rel_thr = binary_search_baseline(
             mix_data, spot_model, patch_list, self.mic_positions,
@@ -189,11 +183,9 @@ class MicArray(object):
         table, for "DENSE_NMS" ``lattice_nms`` on the device scores, ``coarse_select`` (``search.coarse_select_f64``),
         then the stage's one blocking copy -- kept, counts, threshold and, for the record in ``lattice_nms``, best and
         degree -- and a ``Patch`` for each kept cube only."""
-        import torch
         if getattr(spot_model, "world", 1) > 1:
             raise RuntimeError('coarse="device" runs on one GPU: a sharded spot model gathers its energies as host arrays')
-        if not (hasattr(spot_model, "score_offsets") and hasattr(spot_model, "coarse_select")):
-            raise RuntimeError('coarse="device" needs a spot model with score_offsets() and coarse_select() (the HIP SpotModel)')
+        need_methods(spot_model, 'coarse="device"', "score_offsets", "coarse_select")
         if not isinstance(patch_list, LatticePatches):
             raise RuntimeError('coarse="device" takes the LatticePatches that Apply_SRP_PHAT returned')
         node = self.SRP_node
@@ -208,22 +200,14 @@ class MicArray(object):
             best_dev, degree_dev = node.lattice_local_maxima_resident(en_dev[:, 1].contiguous(), radius)
         cap = search.MAX_BIG_PATCH
         kept_d, counts_d, thr_d = spot_model.coarse_select(en_dev, tables["dis1"], best_dev, cap=cap)
-        # int32 words throughout (the two doubles as four): one copy brings everything
-        parts = [kept_d.reshape(-1), counts_d.reshape(-1), thr_d.contiguous().view(torch.int32).reshape(-1)]
-        if nms:
-            parts += [best_dev.reshape(-1), degree_dev.reshape(-1)]
-        back = torch.cat(parts).cpu().numpy()
-        kept_idx, counts = back[:cap], back[cap:cap + 2]
-        thr = float(back[cap + 2:cap + 6].view(np.float64)[0])
+        kept_idx, counts, thr, *maxima = read_back(kept_d, counts_d, thr_d, *([best_dev, degree_dev] if nms else []))
         if nms:
             if counts[1] != 0:
                 raise ValueError("every score must be finite")
-            n = len(patch_list)
-            self.lattice_nms = {"radius": radius, "best": back[cap + 6:cap + 6 + n].copy(),
-                                "degree": back[cap + 6 + n:cap + 6 + 2 * n].copy()}
+            self.lattice_nms = {"radius": radius, "best": maxima[0], "degree": maxima[1]}
         if counts[0] > cap:
             print("warning too many patch remaining, only keep the best 30")
-        self.Relative_Threshold = thr * 1.2
+        self.Relative_Threshold = float(thr[0]) * 1.2
         kept_idx = [int(g) for g in kept_idx if g >= 0]
         self.trace = {"coarse_kept": kept_idx, "fine_clusters": {}, "final_clusters": []}
         return [patch_list[g] for g in kept_idx]
@@ -331,11 +315,18 @@ class MicArray(object):
             return kept["rows"].cpu().numpy()
         out = self._cluster_group(g, big, patches, list(energies_g[:, 0]), list(energies_g[:, 1]), area, centre,
                                   T_len, thr_new, sample_gt, sim_of, audio_of)
-        for n, pair in enumerate(out):     # the global clustering needs these; here they hide behind the GPU
-            if self.segments != "device":  # (device mode: the clustering finds all heads' segments in one launch)
-                self._seg_cache[id(pair[1])] = (pair[1], split_wav(pair[1]))
-            self._dev_cache[id(pair[1])] = (pair[1], kept["rows"][n])      # the same waveform, still on the GPU
+        self._register_heads(out, kept.get("rows", ()))
         return out
+
+    def _register_heads(self, pairs, rows_dev):
+        """What the global clustering needs of the heads the fine stage just copied to the host: their voiced
+        segments, found here while they hide behind the GPU (``segments="device"``: not here, the clustering finds all
+        heads' segments in one launch), and ``rows_dev``, the same waveforms still on the GPU."""
+        assert len(pairs) == len(rows_dev)
+        for pair, row in zip(pairs, rows_dev):
+            if self.segments != "device":
+                self._seg_cache[id(pair[1])] = (pair[1], split_wav(pair[1]))
+            self._dev_cache[id(pair[1])] = (pair[1], row)
 
     def _fine_gates(self, bigs, fines, thr_new):
         """(bounds [G+1], gate [N], group_gate [G]) of a chunk of coarse patches for ``fine_clusters``: the very
@@ -358,14 +349,10 @@ class MicArray(object):
         then the bookkeeping of ``_cluster_group`` per patch.  -> (output tuples, host energies [N, 2])."""
         import torch
         bounds, gate, group_gate = gates
-        N = int(bounds[-1])
         # the reference scales the trigger by the length of the LAST candidate row (:343)
         min_trigger = self.MIN_TRIGGER_POWER / (3 * 48000) * T_len
         order_d, label_d = scorer.fine_clusters(waves, bounds, en_dev, gate, group_gate, min_trigger)
-        # int32 is exact in float64: the three tables come back in one copy
-        back = torch.cat([en_dev.reshape(-1), order_d.to(torch.float64), label_d.to(torch.float64)]).cpu().numpy()
-        energies = back[:2 * N].reshape(N, 2)
-        order, label = back[2 * N:3 * N].astype(np.int64), back[3 * N:].astype(np.int64)
+        energies, order, label = read_back(en_dev, order_d, label_d)
         opened = []                                        # (position in the chunk, clusters) of the open patches
         head_rows = []
         for i in range(len(groups)):
@@ -375,6 +362,7 @@ class MicArray(object):
             clusters = clusters_of_group(order, label, b0, n)
             opened.append((i, clusters))
             head_rows.extend(b0 + h for h in clusters)
+        rows_dev = rows = ()                               # (a chunk whose open patches have no head copies nothing)
         if head_rows:
             idx = torch.from_numpy(np.asarray(head_rows, dtype=np.int64))
             if waves.is_cuda:
@@ -389,12 +377,40 @@ class MicArray(object):
             pairs = self._cluster_outputs(groups[i], fines[i], list(energies[b0:b0 + n, 0]), clusters,
                                           bigs[i].area_points, centres[i], self._big_label(bigs[i], sample_gt),
                                           lambda heads, first=first: rows[first:first + len(heads)])
-            for m, pair in enumerate(pairs):
-                if self.segments != "device":
-                    self._seg_cache[id(pair[1])] = (pair[1], split_wav(pair[1]))
-                self._dev_cache[id(pair[1])] = (pair[1], rows_dev[first + m])
+            self._register_heads(pairs, rows_dev[first:pos])
             out.extend(pairs)
         return out, energies
+
+    def _cluster_chunk(self, groups, bigs, fines, centres, waves, en_dev, gates, T_len, thr_new, sample_gt, spot_model):
+        """The clustering of one chunk of coarse patches ``groups`` (``bigs``, their subdivisions ``fines`` and
+        ``centres``) whose candidates' waveforms ``waves`` [N, T] and energies ``en_dev`` [N, 2] are on the GPU.
+        ``gates`` (``_fine_gates``) says the clustering is on the device: one ``_device_groups`` call; with None the
+        energies are read back and the patches go through ``_resident_group`` one by one.
+        -> (output tuples, host energies [N, 2])."""
+        if gates is not None:
+            return self._device_groups(groups, bigs, fines, centres, waves, en_dev, gates, T_len, sample_gt,
+                                       getattr(spot_model, "inner", spot_model))
+        energies = en_dev.cpu().numpy()
+        out, pos = [], 0
+        for g, big, fine, centre in zip(groups, bigs, fines, centres):
+            n = len(fine)
+            out.extend(self._resident_group(g, big, fine, waves[pos:pos + n], energies[pos:pos + n], big.area_points,
+                                            centre, T_len, thr_new, sample_gt, spot_model))
+            pos += n
+        return out, energies
+
+    def _gather_pairs(self, output_pair, spot_model):
+        """The sharded fine stage's last exchange: every rank's output tuples, in one order on all of them.  The voiced
+        segments of every head travel with its tuple: the global clustering of every rank then finds them cached for
+        the remote heads too, as it does for its own (segments="device": the cache is empty, None travels in their
+        place and every rank finds them on its GPU)."""
+        tagged = [p + (self._seg_cache.get(id(p[1]), (None, None))[1],) for p in output_pair]
+        merged = spot_model.gather_pairs(tagged)
+        output_pair = [t[:-1] for t in merged]
+        for t, p in zip(merged, output_pair):
+            if t[-1] is not None:
+                self._seg_cache[id(p[1])] = (p[1], t[-1])
+        return output_pair
 
     def Spotform_Small_Patch_Parallel(self, mix_data, candidate_finished, spot_model, sample_gt=None,
                                       run_demo_folder=None):
@@ -403,11 +419,11 @@ class MicArray(object):
         resident = hasattr(spot_model, "shift_and_sep_resident")
         inner = getattr(spot_model, "inner", spot_model)                 # ShardedSpotModel wraps the scorer
         self._device_scorer = inner if (resident and hasattr(inner, "segment_sisdr")) else None
-        if self.segments == "device" and not hasattr(self._device_scorer, "voiced_segments"):
-            raise RuntimeError('segments="device" needs a spot model with voiced_segments() (the HIP SpotModel)')
+        if self.segments == "device":
+            need_methods(self._device_scorer, 'segments="device"', "voiced_segments")
         on_device = self.clustering == "device"
-        if on_device and not (resident and hasattr(inner, "fine_clusters")):
-            raise RuntimeError('clustering="device" needs a spot model with fine_clusters() (the HIP SpotModel)')
+        if on_device:                                      # (the reference's host loops below cannot serve it either)
+            need_methods(inner if resident else None, 'clustering="device"', "fine_clusters")
         sharded = getattr(spot_model, "world", 1) > 1
         n_groups = len(candidate_finished)
         self.spotforming_times = 0
@@ -418,82 +434,53 @@ class MicArray(object):
         if resident and sharded and getattr(inner, "device", None) is not None:
             return self._fine_stage_sharded(mix_data, candidate_finished, spot_model, sample_gt, thr_new)
 
-        total_patch, bounds, areas, centers = [], [0], [], []
+        subdivided, centers, bounds = [], [], [0]
         for big in candidate_finished:
             fine, c = self._subdivide(big)
-            areas.append(big.area_points)
+            subdivided.append(fine)
             centers.append(c)
             self.spotforming_times += len(fine)
-            total_patch.extend(fine)
             bounds.append(self.spotforming_times)
 
         # one rank per GPU (shard.ShardedSpotModel): whole coarse patches are dealt to ranks so
         # the per-patch clustering below stays local; energies are all-gathered (the stage's one
         # collective) and only the finished output tuples travel.
-        mine = spot_model.my_groups([bounds[i + 1] - bounds[i] for i in range(n_groups)]) if sharded \
-            else list(range(n_groups))
-        if sharded:
-            gbounds = bounds
-            total_patch_all = total_patch
-            total_patch, bounds = [], [0]
-            for i in mine:
-                total_patch.extend(total_patch_all[gbounds[i]:gbounds[i + 1]])
-                bounds.append(len(total_patch))
-        slot = {g: n for n, g in enumerate(mine)}              # coarse patch -> local group slot
+        mine = spot_model.my_groups([len(fine) for fine in subdivided]) if sharded else list(range(n_groups))
+        bigs, fines, centres = ([seq[g] for g in mine] for seq in (candidate_finished, subdivided, centers))
+        flat = [p for fine in fines for p in fine]             # this rank's candidates
 
         # the hot call.  With the HIP spot model the N x T outputs stay on the GPU: energies come
         # from the device reduction, SI-SDR similarities from the device Gram kernel, and only
-        # the cluster heads' waveforms are copied to the host.  Any other
-        # duck-typed model goes through the reference's host loops.
-        if len(total_patch) == 0:                          # a rank that was dealt no coarse patch
-            waves_dev, energies, sep_all = None, np.zeros((0, 2)), None
-            T_len = int(mix_data.shape[1])
-        elif resident:
-            waves_dev, energies = spot_model.shift_and_sep_resident(mix_data, total_patch, Strict=1,
-                                                                    device_energies=on_device)
-            T_len = int(waves_dev.shape[1])
-        else:
-            sep_all = spot_model.shift_and_sep(mix_data, total_patch, Strict=1)
-            T_len = int(sep_all.shape[1])
+        # the cluster heads' waveforms are copied to the host: this rank's patches
+        # are one chunk of ``_cluster_chunk``.  Any other duck-typed model goes through the
+        # reference's host loops.
         output_pair = []
-        if on_device and len(total_patch) > 0:
-            bigs = [candidate_finished[g] for g in mine]
-            fines = [total_patch[bounds[slot[g]]:bounds[slot[g] + 1]] for g in mine]
-            output_pair, energies = self._device_groups(
-                list(mine), bigs, fines, [centers[g] for g in mine], waves_dev, energies,
-                self._fine_gates(bigs, fines, thr_new), T_len, sample_gt, inner)
-        if sharded and resident:
-            self.fine_energies = spot_model.all_gather_groups(energies, mine, gbounds)
-
-        for g in ([] if on_device and len(total_patch) > 0 else mine):
-            i = slot[g]                                                     # local slot of coarse patch g
-            big = candidate_finished[g]
-            patches = total_patch[bounds[i]:bounds[i + 1]]
-            if resident:
-                output_pair.extend(self._resident_group(g, big, patches, waves_dev[bounds[i]:bounds[i + 1]],
-                                                        energies[bounds[i]:bounds[i + 1]], areas[g], centers[g],
-                                                        T_len, thr_new, sample_gt, spot_model))
-                continue
-            sep = sep_all[bounds[i]:bounds[i + 1]]
-            powers, powers2 = [], []
-            for j in range(len(patches)):
-                sep[j, :] = sep[j, :] - np.mean(sep[j, :])                 # in place, as :291
-                powers.append(np.sum(sep[j, :] ** 2))
-                powers2.append(max_avg_power(sep[j, :]))
-            output_pair.extend(self._cluster_group(
-                g, big, patches, powers, powers2, areas[g], centers[g], T_len, thr_new, sample_gt,
-                lambda k, h, sep=sep: si_sdr(sep[k, :], sep[h]), lambda heads, sep=sep: [sep[h, :] for h in heads]))
-        if sharded:
-            # the voiced segments of every head travel with its tuple: the global clustering of every rank
-            # then finds them cached for the remote heads too, as it does for its own (segments="device": the cache
-            # is empty, None travels in their place and every rank finds them on its GPU)
-            tagged = [p + (self._seg_cache.get(id(p[1]), (None, None))[1],) for p in output_pair]
-            merged = spot_model.gather_pairs(tagged)
-            output_pair = [t[:-1] for t in merged]
-            for t, p in zip(merged, output_pair):
-                if t[-1] is not None:
-                    self._seg_cache[id(p[1])] = (p[1], t[-1])
-        return output_pair
+        if resident:
+            if flat:
+                waves, en_dev = spot_model.shift_and_sep_resident(mix_data, flat, Strict=1, device_energies=True)
+                gates = self._fine_gates(bigs, fines, thr_new) if on_device else None
+                output_pair, energies = self._cluster_chunk(list(mine), bigs, fines, centres, waves, en_dev, gates,
+                                                            int(waves.shape[1]), thr_new, sample_gt, spot_model)
+            else:                                              # a rank that was dealt no coarse patch asks nothing
+                output_pair, energies = [], np.zeros((0, 2))
+            if sharded:
+                self.fine_energies = spot_model.all_gather_groups(energies, mine, bounds)
+        elif flat:
+            sep_all = spot_model.shift_and_sep(mix_data, flat, Strict=1)
+            T_len = int(sep_all.shape[1])
+            pos = 0
+            for g, big, patches, centre in zip(mine, bigs, fines, centres):
+                sep = sep_all[pos:pos + len(patches)]
+                pos += len(patches)
+                powers, powers2 = [], []
+                for j in range(len(patches)):
+                    sep[j, :] = sep[j, :] - np.mean(sep[j, :])             # in place, as :291
+                    powers.append(np.sum(sep[j, :] ** 2))
+                    powers2.append(max_avg_power(sep[j, :]))
+                output_pair.extend(self._cluster_group(
+                    g, big, patches, powers, powers2, big.area_points, centre, T_len, thr_new, sample_gt,
+                    lambda k, h, sep=sep: si_sdr(sep[k, :], sep[h]), lambda heads, sep=sep: [sep[h, :] for h in heads]))
+        return self._gather_pairs(output_pair, spot_model) if sharded else output_pair
 
     def _fine_stage_sharded(self, mix_data, candidate_finished, spot_model, sample_gt, thr_new):
         """One rank per GPU with the HIP model (shard.ShardedSpotModel).  Whole coarse patches are dealt to
@@ -514,16 +501,7 @@ class MicArray(object):
         for n in sizes:
             gbounds.append(gbounds[-1] + n)
         self.fine_energies = spot_model.all_gather_groups(energies, mine, gbounds, owners=owners)
-        # the voiced segments of every head travel with its tuple: the global clustering of every rank
-        # then finds them cached for the remote heads too, as it does for its own (segments="device": the cache
-        # is empty, None travels in their place and every rank finds them on its GPU)
-        tagged = [p + (self._seg_cache.get(id(p[1]), (None, None))[1],) for p in output_pair]
-        merged = spot_model.gather_pairs(tagged)
-        output_pair = [t[:-1] for t in merged]
-        for t, p in zip(merged, output_pair):
-            if t[-1] is not None:
-                self._seg_cache[id(p[1])] = (p[1], t[-1])
-        return output_pair
+        return self._gather_pairs(output_pair, spot_model)
 
     def _fine_stage_pipelined(self, mix_data, candidate_finished, spot_model, sample_gt, thr_new, owned=None, sizes_out=None):
         """Single-GPU fine stage with the host work hidden behind the GPU: the coarse patches are
@@ -536,7 +514,7 @@ class MicArray(object):
         energies of these groups in that order) and reports their subdivision sizes in ``sizes_out``."""
         import torch
         dev = getattr(spot_model, "inner", spot_model).device
-        scorer = getattr(spot_model, "inner", spot_model) if self.clustering == "device" else None
+        on_device = self.clustering == "device"
         mix_dev = torch.as_tensor(mix_data).to(dev, dtype=torch.float32).contiguous()
         T_len = int(mix_dev.shape[1])
         order = list(range(len(candidate_finished))) if owned is None else [int(g) for g in owned]
@@ -564,21 +542,10 @@ class MicArray(object):
                 side.wait_event(ev)
                 waves.record_stream(side)
                 en_dev.record_stream(side)
-                if gates is not None:                          # clustering="device": the whole chunk in one call
-                    pairs, energies = self._device_groups(groups, [candidate_finished[g] for g in groups], fines, centres,
-                                                          waves, en_dev, gates, T_len, sample_gt, scorer)
-                    local_energies.append(energies)
-                    output_pair.extend(pairs)
-                    return
-                energies = en_dev.cpu().numpy()
-                local_energies.append(energies)
-                pos = 0
-                for g, fine, centre in zip(groups, fines, centres):
-                    n = len(fine)
-                    output_pair.extend(self._resident_group(
-                        g, candidate_finished[g], fine, waves[pos:pos + n], energies[pos:pos + n],
-                        candidate_finished[g].area_points, centre, T_len, thr_new, sample_gt, spot_model))
-                    pos += n
+                pairs, energies = self._cluster_chunk(groups, [candidate_finished[g] for g in groups], fines, centres,
+                                                      waves, en_dev, gates, T_len, thr_new, sample_gt, spot_model)
+            output_pair.extend(pairs)
+            local_energies.append(energies)
 
         for k in range(n_chunks):
             groups = order[edges[k]:edges[k + 1]]
@@ -597,7 +564,7 @@ class MicArray(object):
             ev = torch.cuda.Event()
             ev.record(main)
             # (device clustering: the thresholds are geometry alone, formed while the GPU runs this chunk)
-            gates = self._fine_gates([candidate_finished[g] for g in groups], fines, thr_new) if scorer is not None else None
+            gates = self._fine_gates([candidate_finished[g] for g in groups], fines, thr_new) if on_device else None
             if inflight is not None:
                 finish(inflight)                               # host clustering of the previous chunk
             inflight = (groups, fines, centres, waves, en_dev, ev, gates)
@@ -648,10 +615,14 @@ class MicArray(object):
             elif h >= 0 and h != i and cands[i][-1] >= 0 and sample_gt is not None and cands[h][-1] == -1:
                 delta = (cands[h][-2]["audio_offset"] - sample_gt[:, cands[i][-1]]).astype(int)
                 wrong.append((cands[i][-1], cands[h][-1], delta, cands[i][2] / cands[h][2]))
-        clusters = clusters_of_labels(label)
+        return self._final_clusters(cands, clusters_of_labels(label), wrong)
+
+    def _final_clusters(self, cands, clusters, wrong):
+        """What ``Clustering_new`` returns for ``clusters`` = {head: members, the head first} over the sorted candidates,
+        heads in creation order; records them in the trace."""
         print("final speaker number is ", len(clusters.keys()))
         self.trace["final_clusters"] = [[cands[i][3] for i in clusters[h]] for h in clusters]
-        patch_final = [cands[h] for h in clusters]
+        patch_final = [cands[clusters[h][0]] for h in clusters]
         audio_final = [p[1] for p in patch_final]
         return audio_final, patch_final, self.big_spotforming_times + self.spotforming_times, wrong
 
@@ -662,12 +633,11 @@ class MicArray(object):
         # (SURVEY.md §8f-2).  Any other model keeps the reference's host loops.
         scorer = getattr(self, "_device_scorer", None)
         cache = getattr(self, "_seg_cache", {})
-        on_device = getattr(self, "segments", "host") == "device"
-        if on_device and not hasattr(scorer, "voiced_segments"):
-            raise RuntimeError('segments="device" needs a spot model with voiced_segments() (the HIP SpotModel)')
-        if getattr(self, "global_clustering", "host") == "device":
-            if not hasattr(scorer, "global_clusters"):
-                raise RuntimeError('global_clustering="device" needs a spot model with global_clusters() (the HIP SpotModel)')
+        on_device = self.segments == "device"
+        if on_device:
+            need_methods(scorer, 'segments="device"', "voiced_segments")
+        if self.global_clustering == "device":
+            need_methods(scorer, 'global_clustering="device"', "global_clusters")
             centres = [c[0].center_pos() for c in cands]
             if len(cands) > 0 and all(c is not None for c in centres):
                 return self._global_clusters_device(cands, centres, scorer, sample_gt)
@@ -750,8 +720,4 @@ class MicArray(object):
                 if cands[h][-1] == -1:
                     delta = (cands[h][-2]["audio_offset"] - sample_gt[:, big_label]).astype(int)
                     wrong.append((big_label, cands[h][-1], delta, power1 / cands[h][2]))
-        print("final speaker number is ", len(clusters.keys()))
-        self.trace["final_clusters"] = [[cands[i][3] for i in clusters[h]] for h in clusters]
-        patch_final = [cands[clusters[h][0]] for h in clusters]
-        audio_final = [p[1] for p in patch_final]
-        return audio_final, patch_final, self.big_spotforming_times + self.spotforming_times, wrong
+        return self._final_clusters(cands, clusters, wrong)

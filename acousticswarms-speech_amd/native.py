@@ -349,3 +349,21 @@ def to_host(t):
     host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
     host.copy_(t)
     return host.numpy()
+
+
+def read_back(*tensors):
+    """Tensors of any dtypes and shapes -> their numpy arrays, through ONE blocking copy: the bytes of all of them
+    are concatenated where they live, come over together, and each piece is copied out of the byte buffer (so that it
+    is aligned and owns its memory) and viewed as its own dtype and shape.  Same bytes as ``t.cpu().numpy()`` of each.
+    CPU tensors (the stand-in scorers of the host tests) take the same path."""
+    import torch
+    if not tensors:
+        return []
+    flat = [t.contiguous().reshape(-1).view(torch.uint8) for t in tensors]
+    back = torch.cat(flat).cpu()
+    out, pos = [], 0
+    for t, f in zip(tensors, flat):
+        piece = back[pos:pos + f.numel()].clone()
+        out.append(piece.view(t.dtype).reshape(t.shape).numpy())
+        pos += f.numel()
+    return out

@@ -147,7 +147,7 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 
     def emit(rec):
-        rec = dict(rec, device=torch.cuda.get_device_name(0))
+        rec = dict(rec, gpu=torch.cuda.get_device_name(0))      # ("device" is a mode's record)
         line = json.dumps(rec)
         print(line, flush=True)
         with open(args.out, "a") as f:

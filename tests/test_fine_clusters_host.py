@@ -305,6 +305,42 @@ def test_fine_stage_with_device_clustering_equals_host_clustering(monkeypatch):
         assert ma._dev_cache[id(p[1])][0] is p[1] and np.array_equal(ma._dev_cache[id(p[1])][1].numpy(), p[1])
 
 
+def test_chunk_whose_only_open_patch_has_no_head():
+    """One coarse patch, far from the array, whose two candidates sit at the reference microphone: the best candidate
+    passes the patch's gate (thr / 10) and none passes its own (thr), so the patch is open and has no cluster head.
+    Both clustering modes return no output tuple and the energies, record the empty trace entry, copy no row and
+    register nothing -- device mode from one ``fine_clusters`` call, host mode without a ``pair_sisdr`` call."""
+    import torch
+    from acousticswarms_speech_amd.mic_array import MicArray
+
+    class Array(MicArray):
+        def __init__(self, mode):                            # no geometry tables: the clustering needs none
+            self.MIN_TRIGGER_POWER = 0.5
+            self.mic_positions = np.zeros((7, 3))
+            self.segments, self.clustering = "host", mode
+            self.trace = {"fine_clusters": {}}
+            self._seg_cache, self._dev_cache = {}, {}
+
+    T, thr_new, g = 4000, 1.0, 5
+    big = _Patch([9.0, 0.0, 0.0])
+    big.area_points = None
+    fine = [_Patch([0.0, 0.0, 0.0]), _Patch([0.0, 0.0, 0.0])]
+    waves = torch.from_numpy(make_group(np.random.default_rng(3), 2, T))
+    energies = np.array([[40.0, 0.5], [30.0, 0.25]])                         # (power, windowed power) per candidate
+    for mode in ("host", "device"):
+        ma = Array(mode)
+        spot = _CpuSpot({}, mode == "device")
+        gates = ma._fine_gates([big], [fine], thr_new) if mode == "device" else None
+        if gates is not None:
+            assert gates[1].tolist() == [1.0, 1.0] and gates[2].tolist() == [0.1]
+        out, back = ma._cluster_chunk([g], [big], [fine], [None], waves, torch.from_numpy(energies), gates, T, thr_new,
+                                      None, spot)
+        assert out == [] and back.dtype == np.float64 and back.tobytes() == energies.tobytes() and back.shape == (2, 2)
+        assert ma.trace["fine_clusters"] == {g: {}}
+        assert ma._seg_cache == {} and ma._dev_cache == {}
+        assert spot.calls == {"pair_sisdr": 0, "fine_clusters": int(mode == "device")}
+
+
 # ---------------------------------------------------------------- the C entry points
 def test_entry_points_reject_bad_arguments_without_a_gpu():
     from ctypes import c_void_p

@@ -127,6 +127,56 @@ def test_fine_stage_device_resident_equals_host_path(mic_array, golden):
         np.testing.assert_allclose(pa[1], pb[1], rtol=0, atol=5e-6 * max(1.0, np.abs(pb[1]).max()))
 
 
+def test_fine_stage_plain_resident_driver_equals_host_path(mic_array, golden):
+    """Two coarse patches: fewer than the three the pipelined driver starts at, so ``Spotform_Small_Patch_Parallel``
+    takes the resident branch of its plain driver -- all patches as one chunk.  With the HIP model in both clustering
+    modes it must equal the reference-style host loops (the neighbouring test's tolerances), and the two modes must
+    agree exactly on names and fine-stage clusters."""
+    import copy
+    from acousticswarms_speech_amd.config import FULL
+    from acousticswarms_speech_amd.spot import SpotModel
+    from acousticswarms_speech_amd.weights import make_spot_state_dict
+    ma, mics, spk, mix = mic_array
+    g7 = golden("g7_srp_map")
+    spot = SpotModel(FULL, make_spot_state_dict(FULL, 5), batch_size=32, precision="f16x3").to("cuda")
+
+    class HostOnly:                       # hides the resident entry point -> reference host loops
+        def __init__(self, m):
+            self.m = m
+
+        def shift_and_sep(self, *a, **k):
+            return self.m.shift_and_sep(*a, **k)
+
+    mix_t = torch.from_numpy(mix[:, :24000 * 2])
+    node = ma.SRP_node
+    got, traces = {}, {}
+    before = ma.clustering
+    try:
+        with redirect_stdout(io.StringIO()):
+            node.set_map(g7["srp_map"])
+            coarse = node.local_source_adaptive()[:2]
+            ma.Relative_Threshold = 0.0
+            for mode in ("host", "device"):
+                ma.clustering = mode
+                ma.trace["fine_clusters"] = {}            # (the coarse stage resets it in a whole search)
+                got[mode] = ma.Spotform_Small_Patch_Parallel(mix_t, copy.deepcopy(coarse), spot)
+                traces[mode] = copy.deepcopy(ma.trace["fine_clusters"])
+            ma.clustering = "host"
+            ref = ma.Spotform_Small_Patch_Parallel(mix_t, copy.deepcopy(coarse), HostOnly(spot))
+    finally:
+        ma.clustering = before
+    _log(f"fine stage, plain driver: resident {len(got['host'])} / {len(got['device'])} pairs, host {len(ref)} pairs")
+    assert len(coarse) == 2 and len(ref) > 0
+    assert [p[3] for p in got["host"]] == [p[3] for p in got["device"]] and traces["host"] == traces["device"]
+    for a in got.values():
+        assert [p[3] for p in a] == [p[3] for p in ref]
+        np.testing.assert_allclose([p[2] for p in a], [p[2] for p in ref], rtol=1e-5)
+        for pa, pb in zip(a, ref):
+            np.testing.assert_array_equal(pa[4]["audio_offset"], pb[4]["audio_offset"])
+            np.testing.assert_allclose(pa[4]["localization_offset"], pb[4]["localization_offset"], rtol=1e-5, atol=1e-6)
+            np.testing.assert_allclose(pa[1], pb[1], rtol=0, atol=5e-6 * max(1.0, np.abs(pb[1]).max()))
+
+
 def test_search_hip_vs_oracle_north_star_tolerance(mic_array):
     """The north-star tolerance, end to end: the complete search (SRP-PHAT -> coarse -> fine ->
     clustering) run twice on the same mixture with the same seeded FULL weights -- once with the
