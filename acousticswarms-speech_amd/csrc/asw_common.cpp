@@ -1,5 +1,7 @@
 #include "asw_common.h"
 
+#include <cmath>
+
 namespace asw {
 char* err_buf() {
   static thread_local char buf[512] = {0};
@@ -25,6 +27,59 @@ int SmemAttr::ensure(const void* kern, size_t want) {
 
 extern "C" const char* asw_last_error(void) { return asw::err_buf(); }
 extern "C" int asw_abi_version(void) { return 3; }   // 2: + joint separation network (asw_sep_*); 3: + asw_resstack64_f16x3
+
+// ---- host-side weight preparation of the f16x3 kernels (layout: f16x3_tile.h) ------------
+extern "C" int asw_split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo, int32_t* w_shift) {
+  ASW_CHECK_ARG(w && hi && lo && w_shift, "split_weights: null pointer");
+  float mx = 0.f;
+  // (a NaN compares false with everything: it has to be carried into mx by hand to reach the check below)
+  for (size_t i = 0; i < n; ++i) { const float a = w[i] < 0 ? -w[i] : w[i]; if (a > mx || a != a) mx = a; }
+  ASW_CHECK_ARG(mx == mx && mx < 3.0e38f, "split_weights: non-finite weight");
+  // largest power of two with max|w| * 2^shift < 2048 (fp16 keeps 11 significant bits there and
+  // typical weights, 10-100x below the maximum, still have normal lo parts); bounded to +-24.
+  int shift = 0;
+  if (mx > 0.f) {
+    int e;
+    (void)frexpf(mx, &e);                  // mx = f * 2^e, f in [0.5,1)
+    shift = 11 - e;
+    if (shift > 24) shift = 24;
+    if (shift < -24) shift = -24;
+  }
+  const float sc = ldexpf(1.0f, shift);
+  for (size_t i = 0; i < n; ++i) {
+    float c = w[i] * sc;
+    if (c > 65504.f) c = 65504.f;
+    if (c < -65504.f) c = -65504.f;
+    const _Float16 h = (_Float16)c;
+    const _Float16 l = (_Float16)(c - (float)h);
+    memcpy(hi + i, &h, 2);
+    memcpy(lo + i, &l, 2);
+  }
+  *w_shift = shift;
+  return ASW_OK;
+}
+
+extern "C" int asw_pack_fragments_f16(const float* Wt, int N, int K, uint16_t* hi, uint16_t* lo, int32_t* w_shift) {
+  ASW_CHECK_ARG(Wt && hi && lo && w_shift, "pack_fragments: null pointer");
+  ASW_CHECK_ARG(N > 0 && K > 0 && N % 32 == 0 && K % 16 == 0, "pack_fragments: N %% 32, K %% 16 required (N=%d K=%d)", N, K);
+  const size_t n = (size_t)N * K;
+  uint16_t* th = new uint16_t[2 * n];
+  uint16_t* tl = th + n;
+  int rc = asw_split_weights_f16(Wt, n, th, tl, w_shift);
+  if (rc == ASW_OK) {
+    const int NT = N / 32;
+    for (int ks = 0; ks < K / 16; ++ks)
+      for (int nt = 0; nt < NT; ++nt)
+        for (int l = 0; l < 64; ++l) {
+          const size_t src = (size_t)(nt * 32 + (l & 31)) * K + ks * 16 + 8 * (l >> 5);
+          const size_t dst = (((size_t)ks * NT + nt) * 64 + l) * 8;
+          memcpy(hi + dst, th + src, 16);
+          memcpy(lo + dst, tl + src, 16);
+        }
+  }
+  delete[] th;
+  return rc;
+}
 
 // ---- launch profiler -----------------------------------------------------------------
 #include <map>

@@ -1,5 +1,5 @@
-// f16x3_tile.h -- the building blocks the split-fp16 ("f16x3") matrix kernels share (convgemm.hip, resstack.hip,
-// downconv.hip): the three-term product, the fragment-order weight load, the halo-image row layout with its staging
+// f16x3_tile.h -- the building blocks the split-fp16 ("f16x3") matrix kernels share (convgemm.hip, pipegemm.hip,
+// resconv.hip, resstack.hip, downconv.hip): the three-term product, the fragment-order weight load, the halo-image row layout with its staging
 // loop, the pinned transposed k-loop, the chunked A operand of the row-major GEMMs and the XCD-aware tile orders.
 // Everything is inlined into its caller; a kernel experiment changes one of these instead of a copy per kernel.
 #pragma once

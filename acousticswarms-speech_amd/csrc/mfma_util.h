@@ -1,4 +1,4 @@
-// mfma_util.h -- device helpers shared by the MFMA kernels (convgemm.hip, resstack.hip, downconv.hip): vector types,
+// mfma_util.h -- device helpers shared by the MFMA kernels (convgemm.hip, pipegemm.hip, resconv.hip, resstack.hip, downconv.hip): vector types,
 // the buffer-descriptor activation load and the fp32 -> fp16 hi / lo operand split of the f16x3 mode.
 #pragma once
 #include "asw_common.h"

@@ -164,7 +164,7 @@ inline bool glu_on_load_ok(const std::vector<ResLayer>& res, int prec, int ch) {
 // 64-channel stacks in f16x3 arithmetic run through asw_resstack64_f16x3 (resstack.hip): consecutive layers whose
 // later dilations leave most of a 256-row tile (summed halo <= 64 rows per side) share ONE launch, the rest
 // (dilation 49) run as single layers of the same kernel.  ASW_NO_RESSTACK=1 keeps the per-layer kernels
-// of convgemm.hip (A/B measurements).
+// of resconv.hip (A/B measurements).
 inline bool resstack_ok(const std::vector<ResLayer>& res, int prec, int ch, int K) {
   static const bool off = getenv("ASW_NO_RESSTACK") != nullptr;
   if (off || prec < 1 || ch != 64 || K % 2 == 0 || K < 3 || K > 15) return false;

@@ -1,0 +1,322 @@
+// pipegemm.hip -- the pipelined 256-column f16x3 GEMM (convgemm16p) and the mask path built on its main loop, reached
+// from the dispatcher of convgemm.hip through asw::pipe_gemm and from asw_mask_path_f16x3.  Layout and arithmetic
+// are described at the head of convgemm.hip, the epilogue in gemm_epilogue.h.
+#include <type_traits>
+
+#include "gemm_epilogue.h"
+
+namespace {
+using namespace asw_mfma;
+
+// ------------------------------------------------------------------ pipelined wide-tile GEMM
+// The 8-wave 256-column tiles (mask encoder, strided / transposed convolutions, big linears) as a
+// software pipeline with ONE barrier per 32-wide chunk instead of two (cycle counters on the
+// two-barrier kernel above, mask-encoder shape: per chunk wave 0 spent 1150 cycles depositing the
+// next chunk with every MFMA pipe of the workgroup idle, tests/micro/phase_timing.py):
+//  * B never touches LDS: the weights are pre-packed in MFMA-fragment order (asw_pack_fragments_f16,
+//    the layout of the residual kernel), each wave pulls its two column fragments per k-step with
+//    coalesced 1 KiB loads, QDB k-steps ahead of their use (L2-resident: one column tile of the
+//    largest matrix is 2.1 MB);
+//  * A (fp32 activations) is split to fp16 hi / lo while it is deposited, into a two-stage LDS ring:
+//    the rows of chunk k+1 are fetched before, and deposited after, the MFMAs of chunk k, so the
+//    deposit of one wave overlaps the MFMAs of the others and only the ring hand-over needs a barrier.
+// Same tiling (wave tile BM/2 x 64), same epilogue, same XCD-aware tile order as the kernel above.
+// Measured (T = 48 000, batch 64): mask encoder 312 -> 332 TFLOP/s, strided / transposed convolutions
+// +3-6 %.  64-wide chunks (half the barriers, 147 KB ring) spill and lose: 304.
+// Main loop of one 256-column tile: picks the tile of this workgroup (false: none, the whole workgroup
+// leaves), runs the K loop and returns the accumulators (wave (wm, wn) of WM x 4 holds rows
+// wm*BM/WM + 32*i.., columns wn*64 + 32*j..).  Ends on a barrier: the ring is free for the epilogue.
+// WM = 2: eight waves on a 256-row tile, one workgroup per CU.  WM = 1: four waves on a 128-row tile with the
+// SAME wave tile (128 x 64), two independent workgroups per CU -- one's epilogue under the other's main loop.
+template <int BM, bool A2F, int BK, int NTERM = 3, int WM = 2>
+__device__ __forceinline__ bool pipe_mainloop(const asw_convgemm_args& p, float* smem, floatx16 (&acc)[BM / WM / 32][2],
+                                              dim3& tile_out, int& ncol_out) {
+  constexpr int BN = 256, WN = 4, NT = 64 * WM * WN;
+  constexpr int QDB = 2;                           // B fragments in flight, in k-steps
+  constexpr int LDH = BK + 8;
+  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
+  constexpr int STAGE = 2 * BM * LDH;              // halves per ring stage (hi image + lo image)
+
+  _Float16* ring = reinterpret_cast<_Float16*>(smem);
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / WN, wn = wid % WN;
+  const int ncol = p.N / BN, nrt = (p.M_out + BM - 1) / BM;
+  uint3 tl;
+  if (!xcd_tile_groups(p.B, nrt, ncol, tl)) return false;     // XCD-aware order, groups of 8
+  const dim3 tile(tl.x, tl.y, tl.z);
+  tile_out = tile;
+  ncol_out = ncol;
+  const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
+  const int nk = p.taps * (p.Cin / BK);
+  const half8* __restrict__ Wh = reinterpret_cast<const half8*>(p.Wf_hi);
+  const half8* __restrict__ Wl = reinterpret_cast<const half8*>(p.Wf_lo);
+  const int NTF = p.N / 32;                        // column fragments across N
+  const int nt0 = n0 / 32 + wn * TN;
+
+  ChunkedA<BM, BK, NT, A2F> A(p, b, m0, tid);
+  auto deposit = [&](int stage) {
+    _Float16* Ah = ring + stage * STAGE;
+    A.template deposit<NTERM>(Ah, Ah + BM * LDH);
+  };
+  auto bload = [&](int kg, half8 (&bh)[TN], half8 (&bl)[TN]) {          // kg = global k-step (16 K each)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) frag_load<NTERM>(Wh, Wl, (long)kg * NTF + nt0 + j, lane, bh[j], bl[j]);
+  };
+
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  const int a_off = (wm * (BM / WM) + (lane & 31)) * LDH + (lane >> 5) * 8;
+  half8 qh[QDB][TN], ql[QDB][TN];                  // B fragments of the next QDB k-steps
+  const int nks = nk * (BK / 16);                  // k-steps in all
+#pragma unroll
+  for (int q = 0; q < QDB; ++q) bload(q, qh[q], ql[q]);
+  A.load(0);
+  deposit(0);
+  __syncthreads();
+  constexpr int KS = BK / 16;
+  static_assert(KS % QDB == 0, "the B ring is one chunk deep");
+  // One chunk; PAR = chunk parity, compile-time so that ring stage and B buffer indices are static
+  // (the loop below is unrolled by two).
+  auto chunk = [&](int kc, auto par) {
+    constexpr int PAR = decltype(par)::value;
+    if (kc + 1 < nk) A.load(kc + 1);               // in flight under the MFMAs of this chunk
+    const _Float16* Ah = ring + PAR * STAGE;
+    const _Float16* Al = Ah + BM * LDH;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      half8 ah[TM], al[TM];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        ah[i] = *reinterpret_cast<const half8*>(Ah + a_off + i * 32 * LDH + ks * 16);
+        if (NTERM == 3) al[i] = *reinterpret_cast<const half8*>(Al + a_off + i * 32 * LDH + ks * 16);
+      }
+      const int q = (PAR * KS + ks) % QDB;         // B register buffer of this k-step
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) mma3<NTERM>(acc[i][j], ah[i], al[i], qh[q][j], ql[q][j]);
+      const int kg = kc * KS + ks + QDB;           // same slot, QDB k-steps ahead
+      if (kg < nks) bload(kg, qh[q], ql[q]);
+      // deposit of the next chunk between the k-steps: its conversions and LDS writes issue in the
+      // shadow of this wave's own MFMAs (the other stage was last read one chunk ago, before the
+      // previous barrier)
+      if (ks == KS / 2 - 1 && kc + 1 < nk) deposit(PAR ^ 1);
+    }
+    __syncthreads();
+  };
+  for (int kc = 0; kc < nk; kc += 2) {
+    chunk(kc, std::integral_constant<int, 0>{});
+    if (kc + 1 < nk) chunk(kc + 1, std::integral_constant<int, 1>{});
+  }
+  return true;
+}
+
+template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int NTERM = 3, int WM = 2>
+__global__ __launch_bounds__(256 * WM) __attribute__((amdgpu_waves_per_eu(2)))
+void convgemm16p_kernel(const asw_convgemm_args p) {
+  constexpr int BN = 256, WN = 4;
+  extern __shared__ __align__(16) float smem[];
+  floatx16 acc[BM / WM / 32][2];
+  dim3 tile;
+  int ncol;
+  if (!pipe_mainloop<BM, A2F, BK, NTERM, WM>(p, smem, acc, tile, ncol)) return;
+  epilogue<BM, BN, WM, WN, false, STATS, false, MUL>(acc, p, smem, __builtin_ldexpf(1.0f, -p.w_shift),
+                                                     RowsContig{(int)tile.x * BM, p.M_out}, tile, ncol);
+}
+
+// ------------------------------------------------------------------ mask path in one kernel
+// reference_bypass, mask_encoder and the output_decoder taps (network.py:327-349,397-405) without the
+// 2048-channel latents ever reaching memory:
+//   taps[f][j] = sum_e relu(mask_enc(x)[f][e] + b_e) * relu(bypass(ref)[f][e] + c_e) * D[e][j]
+// The main loop is the pipelined GEMM above (mask encoder, K = taps*Cin).  Epilogue, per 256 x 256 tile:
+//  A. each wave computes the bypass tile of its own 32 x 32 accumulator blocks with nine more MFMAs
+//     (K = 33 padded to 48; the frames of the reference channel are read straight from global memory
+//     in A-fragment order) and gates the accumulators in registers;
+//  B. the gated latent goes through an LDS slab, 128 rows at a time, and comes back in A-fragment
+//     order for the decoder contraction over the tile's 256 latent channels: eight waves = four
+//     32-row blocks x two 32-tap blocks, 48 MFMAs each.  The result is a PARTIAL tap product (this
+//     column tile's share of the sum over e); the overlap-add kernel adds the N/256 partials.
+// Per candidate (T = 48 000) this writes 8 x 3008 x 33 floats instead of writing the bypass latent,
+// reading it, writing the gated latent and reading that again (4 x 24.6 MB).
+template <int BM, int KSB, int NTERM = 3>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
+void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
+  constexpr int BN = 256, WN = 4, TM = BM / 64, TN = 2, LDC = BN + 4, BK = 32;
+  static_assert(BM == 256, "slab passes are written for 2 x 128 rows");
+  extern __shared__ __align__(16) float smem[];
+  floatx16 acc[TM][TN];
+  dim3 tile;
+  int ncol;
+  if (!pipe_mainloop<BM, false, BK, NTERM>(p, smem, acc, tile, ncol)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / WN, wn = wid % WN;
+  const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
+  const float acc_scale = __builtin_ldexpf(1.0f, -p.w_shift);
+  const float byp_scale = __builtin_ldexpf(1.0f, -mf.byp_shift), dec_scale = __builtin_ldexpf(1.0f, -mf.dec_shift);
+  // ---- A: bypass tile + gating, in registers
+  const __amdgpu_buffer_rsrc_t rR = act_rsrc(mf.ref + (long)b * mf.ref_batch_stride, mf.ref_len);
+  const half8* __restrict__ Bh = reinterpret_cast<const half8*>(mf.byp_hi);
+  const half8* __restrict__ Bl = reinterpret_cast<const half8*>(mf.byp_lo);
+  const int NTF = p.N / 32;
+  float amax = 0.f;
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) {
+    const int nt = n0 / 32 + wn * TN + tn;
+    const int col = nt * 32 + (lane & 31);
+    const float bm = p.bias ? p.bias[col] : 0.f, bb = mf.byp_bias ? mf.byp_bias[col] : 0.f;
+    half8 wh[KSB], wl[KSB];
+#pragma unroll
+    for (int ks = 0; ks < KSB; ++ks) frag_load<NTERM>(Bh, Bl, (long)ks * NTF + nt, lane, wh[ks], wl[ks]);
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+      const int f = m0 + wm * (BM / 2) + tm * 32 + (lane & 31);
+      const bool ok = f < p.M_out;
+      floatx16 bp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bp[r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < KSB; ++ks) {
+        const long e = (long)f * mf.ref_hop + ks * 16 + (lane >> 5) * 8;
+        const float4 x0 = act_load4(rR, e, ok), x1 = act_load4(rR, e + 4, ok);
+        half4 h0, l0, h1, l1;
+        split4t<NTERM>(x0, h0, l0);
+        split4t<NTERM>(x1, h1, l1);
+        const half8 ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+        const half8 al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+        mma3<NTERM>(bp, ah, al, wh[ks], wl[ks]);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = fmaxf(acc[tm][tn][r] * acc_scale + bm, 0.f) * fmaxf(bp[r] * byp_scale + bb, 0.f);
+        amax = fmaxf(amax, v);
+        acc[tm][tn][r] = v;
+      }
+    }
+  }
+  // the latent is split to fp16 halves below: same range guard as a latent written for a later GEMM
+  if (!(amax <= 65504.f)) atomicAdd(&g_f16x3_overflow, 1u);
+  // ---- B: decoder contraction through the slab, rows [pass*128, pass*128 + 128) of the tile per pass
+  float* Ct = smem;
+  const half8* __restrict__ Dh = reinterpret_cast<const half8*>(mf.dec_hi);
+  const half8* __restrict__ Dl = reinterpret_cast<const half8*>(mf.dec_lo);
+  const int ft = wid & 3, tt = wid >> 2;                       // 32-row block, 32-tap block of this wave
+  float* __restrict__ outp = mf.taps + ((long)tile.y * p.B + b) * p.M_out * 64;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass) __syncthreads();                                 // (pass 0: the main loop ended on a barrier)
+    if (wm == pass) {
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+          const int col = wn * 64 + tn * 32 + (lane & 31);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int row = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            Ct[row * LDC + col] = acc[tm][tn][r];
+          }
+        }
+    }
+    __syncthreads();
+    floatx16 tp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tp[r] = 0.f;
+    const float* src = Ct + (ft * 32 + (lane & 31)) * LDC + (lane >> 5) * 8;
+#pragma unroll 4
+    for (int ks = 0; ks < BN / 16; ++ks) {
+      const float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
+      const float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
+      half8 dh, dl;
+      frag_load<NTERM>(Dh, Dl, (long)(n0 / 16 + ks) * 2 + tt, lane, dh, dl);
+      half4 h0, l0, h1, l1;
+      split4t<NTERM>(x0, h0, l0);
+      split4t<NTERM>(x1, h1, l1);
+      const half8 ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+      const half8 al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+      mma3<NTERM>(tp, ah, al, dh, dl);
+    }
+    const int j = tt * 32 + (lane & 31);
+    if (j < mf.dec_taps) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int f = m0 + pass * 128 + ft * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (f < p.M_out) outp[(long)f * 64 + j] = tp[r] * dec_scale;
+      }
+    }
+  }
+}
+
+int launch_mask_path(const asw_maskpath_args* args, void* stream) {
+  ASW_CHECK_ARG(args, "mask_path: null argument block");
+  const asw_maskpath_args& m = *args;
+  asw_convgemm_args a = m.enc;
+  hipStream_t s = asw::as_stream(stream);
+  constexpr int BM = 256, BN = 256, BK = 32, KSB = 3;
+  ASW_CHECK_ARG(a.A && a.Wf_hi && a.Wf_lo && m.ref && m.byp_hi && m.byp_lo && m.dec_hi && m.dec_lo && m.taps,
+                "mask_path: null pointer (fragment-order weights are required)");
+  ASW_CHECK_ARG(a.B > 0 && a.M_out > 0 && a.N % BN == 0 && a.Cin % BK == 0 && a.taps > 0 && a.stride > 0,
+                "mask_path: shape (N %% 256 == 0, Cin %% 32 == 0)");
+  ASW_CHECK_ARG(a.A2 == nullptr && a.mul == nullptr && a.resid == nullptr && a.ln_gamma == nullptr && a.stats == nullptr,
+                "mask_path: the encoder block takes A, weights and bias only");
+  ASW_CHECK_ARG(m.byp_k == 16 * KSB, "mask_path: bypass kernel padded to %d taps, %d given", 16 * KSB, m.byp_k);
+  ASW_CHECK_ARG(m.dec_taps > 0 && m.dec_taps <= 64 && m.ref_hop > 0 && m.ref_hop % 4 == 0 && m.ref_len > 0,
+                "mask_path: decoder taps 1..64, reference hop a multiple of 4 samples");
+  ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(m.ref) & 15) == 0 && m.ref_batch_stride % 4 == 0,
+                "mask_path: reference rows must be 16-byte aligned");
+  ASW_CHECK_ARG(a.precision == 1 || a.precision == 2, "mask_path: precision 1 (f16x3) or 2 (single-pass f16)");
+  a.relu = 1;
+  constexpr size_t ring = (size_t)2 * 2 * BM * (BK + 8) * sizeof(_Float16);
+  constexpr size_t slab = (size_t)128 * (BN + 4) * sizeof(float);
+  constexpr size_t smem = ring > slab ? ring : slab;
+  static_assert(smem <= 160 * 1024, "LDS budget");
+  // mask encoder + bypass + decoder taps
+  return asw::launch_pair<maskpath16p_kernel<BM, KSB, 1>, maskpath16p_kernel<BM, KSB, 3>>(
+      a.precision, dim3(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN)), dim3(512), smem, smem,
+      "maskpath16p<256,256,32>", asw::ShapeTag(a, 's', a.stride).s,
+      2.0 * a.B * (double)a.M_out * a.N * ((double)a.taps * a.Cin + m.byp_taps + m.dec_taps), 0.0, s, a, m);
+}
+
+template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int WM = 2>
+int launch_pipe(const asw_convgemm_args& a, hipStream_t s) {
+  constexpr int BN = 256;
+  constexpr size_t ring = (size_t)2 * 2 * BM * (BK + 8) * sizeof(_Float16);
+  constexpr size_t slab = (size_t)(WM * 32) * (BN + 4) * sizeof(float);
+  constexpr size_t smem = ring > slab ? ring : slab;
+  static_assert(smem <= 160 * 1024, "LDS budget");
+  static_assert(BM == 128 * WM, "wave tile 128 x 64");
+  ASW_CHECK_ARG(A2F == (a.A2 != nullptr), "convgemm: skip operand variant mismatch");
+  ASW_CHECK_ARG(a.Cin % BK == 0 && a.N % BN == 0, "convgemm: pipelined tile needs Cin %% BK == 0 and N %% 256 == 0");
+  return asw::launch_pair<convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 1, WM>, convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 3, WM>>(
+      a.precision, dim3(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN)), dim3(256 * WM), smem, smem,
+      asw::prof_name(MUL ? "convgemm16pm" : "convgemm16p", BM, BN, BK, false, STATS), asw::ShapeTag(a, 's', a.stride).s,
+      2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin, 0.0, s, a);
+}
+
+template <int BM, int WM>
+struct PipeTile {                        // pipelined 256-column kernel: convgemm16p
+  template <bool STATS, bool MUL, bool A2F>
+  static int run(const asw_convgemm_args& a, hipStream_t s) { return launch_pipe<BM, STATS, MUL, A2F, 32, WM>(a, s); }
+};
+
+}  // namespace
+
+namespace asw {
+int pipegemm_f16x3_overflow(int reset, unsigned int* count) { return f16x3_overflow_read(reset, count); }
+
+// The wide f16x3 tile with fragment-order weights (the caller has checked both).
+int pipe_gemm(const asw_convgemm_args& a, hipStream_t s) {
+  // Short K (the decoder's transposed convolutions): two independent 4-wave workgroups of 128 rows per CU, same
+  // wave tile -- one drains its tile while the other computes (K = 512: 234 -> 260 TFLOP/s, K = 256: 186 -> 193;
+  // at K >= 896 and in the mask path the 8-wave tile is 2-4 % ahead).
+  if (a.taps * a.Cin <= 512 && !a.mul) return launch_variant<PipeTile<128, 1>, false>(a, s);
+  return launch_variant<PipeTile<256, 2>>(a, s);
+}
+}  // namespace asw
+
+extern "C" int asw_mask_path_f16x3(const asw_maskpath_args* args, void* stream) { return launch_mask_path(args, stream); }

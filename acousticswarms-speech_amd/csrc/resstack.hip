@@ -5,7 +5,7 @@
 // (sep/training/SpeakerLocalization/network.py:50-82, sep/training/SpeakerSeparation/network.py, same
 // classes): out_i = LayerNorm(ReLU(conv_{d_i}(x_i) + b_i) + x_i), x_{i+1} = out_i.
 //
-// Why a second residual kernel.  At C = 64 the halo-staged layer of convgemm.hip (resconv16_kernel)
+// Why a second residual kernel.  At C = 64 the halo-staged layer of resconv.hip (resconv16_kernel)
 // moves 112 FLOP per byte of HBM traffic -- exactly the ridge of this chip -- and spends 44 % of a
 // workgroup's time in its epilogue (accumulators -> LDS slab -> row-wise LayerNorm -> store).  Two changes:
 //

@@ -5,6 +5,7 @@ PyTorch fallback.  ``lib()`` raises if the shared object is missing, and every
 wrapper raises ``RuntimeError`` with ``asw_last_error()`` on a non-zero status.
 """
 import ctypes
+import glob
 import os
 import subprocess
 import sys
@@ -14,10 +15,10 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ASW_LIB_PATH") or os.path.join(_HERE, "libasw_hip.so")   # env: A/B builds only
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["asw_common.cpp", "convgemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip", "misc_kernels.hip", "attention_mfma.hip", "srp_kernels.hip",
+SOURCES = ["asw_common.cpp", "convgemm.hip", "resconv.hip", "pipegemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip",
+           "misc_kernels.hip", "attention_mfma.hip", "srp_kernels.hip",
            "pruner_kernels.hip", "geometry_kernels.hip", "cluster_kernels.hip",
            "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip"]
-HEADERS = ["asw_common.h", "model_common.h", "mfma_util.h", "f16x3_tile.h"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
 # (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out)
 EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"], "cluster_kernels.hip": ["-ffp-contract=off"]}
@@ -29,7 +30,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into libasw_hip.so (in-tree): one object per source
     under build/ (only the stale ones, in parallel), then one link."""
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(os.path.dirname(_HERE), "include", "asw_hip.h")]
+    # every header of csrc/ invalidates every object (no per-source dependencies): none can be forgotten in a list
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(os.path.dirname(_HERE), "include", "asw_hip.h")]
     hdr_time = max(os.path.getmtime(h) for h in hdrs)
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)

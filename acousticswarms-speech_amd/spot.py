@@ -35,7 +35,7 @@ class SpotModel:
     def __init__(self, cfg: SpotConfig = FULL, state_dict=None, batch_size: int = 32, precision: str = "f32",
                  lanes: int = 1):
         """precision: "f32" = exact fp32 MFMA; "f16x3" = split-operand half MFMA with fp32
-        accumulation (~21-bit operands, 5.3x the f32 matrix rate), see csrc/convgemm.hip."""
+        accumulation (~21-bit operands, 5.3x the f32 matrix rate), see csrc/convgemm.hip (and pipegemm.hip, resconv.hip)."""
         if precision not in self.PRECISIONS:
             raise RuntimeError(f"precision must be one of {list(self.PRECISIONS)}")
         self.cfg = cfg

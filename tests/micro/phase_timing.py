@@ -3,8 +3,11 @@ ASW_LIB_PATH (the .so is not kept in the tree):
 
     cd acousticswarms-speech_amd && python -c "import native; native.build()" &&
     hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -DASW_PHASE_TIMING -c csrc/convgemm.hip -o /tmp/convgemm_dbg.o &&
-    hipcc --offload-arch=gfx950 -fPIC -shared -o ../tests/micro/libasw_hip_phase.so /tmp/convgemm_dbg.o \
-        $(ls build/*.o | grep -v convgemm.o)
+    hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -DASW_PHASE_TIMING -c csrc/resconv.hip -o /tmp/resconv_dbg.o &&
+    hipcc --offload-arch=gfx950 -fPIC -shared -o ../tests/micro/libasw_hip_phase.so /tmp/convgemm_dbg.o /tmp/resconv_dbg.o \
+        $(ls build/*.o | grep -v -e convgemm.o -e resconv.o)
+
+(asw_debug_phase_cycles: the residual layer, csrc/resconv.hip; asw_debug_gemm_cycles: the 256x256 two-barrier GEMM, csrc/convgemm.hip)
 
 Round-2 result (T = 48 128, batch 32, before the k-loop was software-pipelined): C = 64: staging 16 %,
 k-loop 40 %, epilogue 44 % of a workgroup's cycles; C = 128: 12 / 51 / 37; C = 256: 8 / 66 / 26;

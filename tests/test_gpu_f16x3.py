@@ -1,4 +1,4 @@
-"""Parity of the "f16x3" split-operand MFMA mode (csrc/convgemm.hip, precision 1) -- the
+"""Parity of the "f16x3" split-operand MFMA mode (csrc/convgemm.hip, pipegemm.hip, resconv.hip; precision 1) -- the
 fast arithmetic of the GEMM-class layers.  Same references and same end-to-end bar as the
 exact-f32 mode (>= 80 dB SNR against the reference's own outputs; north-star tolerance:
 SI-SDR within 0.1 dB); per-kernel tolerance 2e-5 relative L2 (operands carry ~21 bits).
@@ -455,3 +455,45 @@ def test_f16x3_range_guard_counts_saturating_activations():
     assert ops.f16x3_overflow_count(reset=True) == 0          # the exact mode has no such limit
     SpotModel(SMALL, big, batch_size=4, precision="f16x3").to("cuda").shift_and_sep(mix, offs, Strict=1)
     assert ops.f16x3_overflow_count(reset=True) > 0
+
+
+def test_f16x3_range_guard_counts_in_both_translation_units():
+    """The counter behind asw_f16x3_overflow_count exists once per translation unit that writes it: pipegemm.hip
+    (convgemm16p, the mask path) and convgemm.hip (the two-barrier kernels).  One shape of the dispatch table reaches
+    either file with and without fragment-order weights: each file counts, each is cleared by a reset, and the
+    call returns the sum of the two."""
+    import ctypes
+    import json
+    from acousticswarms_speech_amd import native, ops
+    B, M, N, K = 256, 500, 256, 256
+    unit = _gemm_case(B, M, N, K)
+    # output standard deviation near 1e6, far beyond 65504, from inputs that fp16 still holds (|x|, |w| < 1e4)
+    big_x, big_w = _grand(B, M, K, seed=46, scale=1e3), _grand(N, K, seed=47, scale=1e3 / math.sqrt(K))
+    names = {True: "convgemm16p<128,256,32,plain>[B256 M500 N256 K256 s1]",        # pipegemm.hip
+             False: "convgemm16<256,256,32,plain>[B256 M500 N256 K256 s1]"}        # convgemm.hip
+    L = native.lib()
+
+    def run(x, w, bias, frag):
+        L.asw_profile_enable(2)
+        ops.convgemm(x, w, M, N, K, bias=bias, precision="f16x3", use_fragments=frag)
+        torch.cuda.synchronize()
+        buf = ctypes.create_string_buffer(1 << 16)
+        native.check(L.asw_profile_report(buf, len(buf)))
+        L.asw_profile_enable(0)
+        assert list(json.loads(buf.value.decode())) == [names[frag]]
+
+    ops.f16x3_overflow_count(reset=True)
+    single = {}
+    for frag in (True, False):
+        run(unit["x"], unit["w"], unit["bias"], frag)
+        assert ops.f16x3_overflow_count(reset=False) == 0
+        run(big_x, big_w, None, frag)
+        single[frag] = ops.f16x3_overflow_count(reset=True)
+        _log(f"range guard frag={frag}: {single[frag]} threads")
+        assert single[frag] > 0
+        assert ops.f16x3_overflow_count(reset=True) == 0
+    run(big_x, big_w, None, True)
+    run(big_x, big_w, None, False)
+    assert ops.f16x3_overflow_count(reset=False) == single[True] + single[False]
+    assert ops.f16x3_overflow_count(reset=True) == single[True] + single[False]          # (this call clears both)
+    assert ops.f16x3_overflow_count(reset=True) == 0

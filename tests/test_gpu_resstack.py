@@ -1,7 +1,7 @@
 """Parity of the fused 64-channel residual stacks (csrc/resstack.hip, asw_resstack64_f16x3): the layers'
 intermediate tensors stay in LDS, accumulators are transposed (a lane owns one time row), LayerNorm runs in
 registers.  References: the torch fp32 statement of DilatedResidualLayer / DilatedResidualSequence
-(sep/training/SpeakerLocalization/network.py:50-82) and the per-layer HIP kernels (asw_convgemm_f32).
+(sep/training/SpeakerLocalization/network.py:50-82) and the per-layer HIP kernels (asw_convgemm_f32 -> csrc/resconv.hip).
 Bar: relative L2 <= 2e-5 against torch fp32 (the f16x3 bar of tests/test_gpu_f16x3.py), <= 3e-6 against the
 per-layer HIP path (same arithmetic; only summation order and the residual's hi + lo read differ).
 Needs an MI355X."""
