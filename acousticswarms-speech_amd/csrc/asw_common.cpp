@@ -1,6 +1,7 @@
 #include "asw_common.h"
 
 #include <cmath>
+#include <cstdlib>
 
 namespace asw {
 char* err_buf() {
@@ -27,6 +28,7 @@ int SmemAttr::ensure(const void* kern, size_t want) {
 
 extern "C" const char* asw_last_error(void) { return asw::err_buf(); }
 extern "C" int asw_abi_version(void) { return 3; }   // 2: + joint separation network (asw_sep_*); 3: + asw_resstack64_f16x3
+                                                     // (asw_residue_schedule is an addition: no bump)
 
 // ---- host-side weight preparation of the f16x3 kernels (layout: f16x3_tile.h) ------------
 extern "C" int asw_split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo, int32_t* w_shift) {
@@ -79,6 +81,43 @@ extern "C" int asw_pack_fragments_f16(const float* Wt, int N, int K, uint16_t* h
   }
   delete[] th;
   return rc;
+}
+
+// ---- residue-image A feed: the schedule of pipe_mainloop_res, enumerated on the host ----
+namespace asw {
+bool residue_feed_on() {                  // like ASW_NO_RESSTACK: set to anything, "0" included, means off
+  static const bool off = getenv("ASW_NO_RESIDUE_FEED") != nullptr;
+  return !off;
+}
+}  // namespace asw
+
+extern "C" int asw_residue_schedule(int taps, int stride, int dil, int pad, int Cin, int BK, int BM, int m0, int has_skip,
+                                    asw_residue_stage* out, int cap, int* n_stages, int* max_shift) {
+  ASW_CHECK_ARG(n_stages != nullptr && cap >= 0 && (out != nullptr || cap == 0), "residue_schedule: null pointer");
+  ASW_CHECK_ARG(taps > 0 && stride > 0 && dil > 0 && Cin > 0 && BK > 0 && BM > 0, "residue_schedule: bad dims");
+  *n_stages = 0;
+  if (max_shift) *max_shift = 0;
+  if (!asw::residue_feed_applies(taps, stride, dil, Cin, BK, has_skip != 0)) return ASW_OK;
+  const asw::ResidueFeed rf{taps, stride, Cin / BK};
+  ASW_CHECK_ARG(rf.ntaps(0) <= ASW_RESIDUE_MAX_TAPS, "residue_schedule: %d taps on one image, at most %d", rf.ntaps(0),
+                ASW_RESIDUE_MAX_TAPS);
+  *n_stages = rf.stages();
+  if (max_shift) *max_shift = rf.shifts(0);
+  for (int s = 0; s < rf.stages() && s < cap; ++s) {
+    asw_residue_stage& d = out[s];
+    memset(&d, 0, sizeof d);
+    d.residue = s / rf.cpb;
+    d.chunk = s - d.residue * rf.cpb;
+    d.rows = BM + rf.shifts(d.residue);
+    d.first_row = m0 * stride - pad + d.residue;
+    d.ntaps = rf.ntaps(d.residue);
+    for (int q = 0; q < d.ntaps; ++q) {
+      d.tap[q] = rf.tap(d.residue, q);
+      d.shift[q] = q;
+      d.kstep[q] = rf.kstep(d.tap[q], d.chunk, BK / 16);
+    }
+  }
+  return ASW_OK;
 }
 
 // ---- launch profiler -----------------------------------------------------------------

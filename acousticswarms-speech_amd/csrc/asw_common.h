@@ -47,6 +47,34 @@ struct SmemAttr {
 };
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ---- residue-image A feed (include/asw_hip.h: asw_residue_schedule).  The formulae of the schedule, written once:
+// the host enumeration (asw_common.cpp) and the device loop (pipe_mainloop_res, pipegemm.hip) both go through them.
+#ifdef __HIPCC__
+#define ASW_HOST_DEVICE __host__ __device__
+#else
+#define ASW_HOST_DEVICE
+#endif
+struct ResidueFeed {
+  int taps, stride, cpb;                                   // cpb = Cin / BK chunks per tap
+  ASW_HOST_DEVICE int stages() const { return stride * cpb; }                           // stage = r * cpb + c
+  ASW_HOST_DEVICE int shifts(int r) const { return (taps - 1 - r) / stride; }           // rows of image r beyond BM
+  ASW_HOST_DEVICE int ntaps(int r) const { return shifts(r) + 1; }                      // taps r, r + stride, ...
+  ASW_HOST_DEVICE int tap(int r, int q) const { return r + q * stride; }
+  // first k-step (16 K each, KS = BK / 16 per chunk) of (tap, chunk c) in the packed fragment-order weights
+  ASW_HOST_DEVICE int kstep(int tap, int c, int KS) const { return (tap * cpb + c) * KS; }
+};
+inline bool residue_feed_applies(int taps, int stride, int dil, int Cin, int BK, bool skip) {
+  return dil == 1 && stride >= 2 && taps > stride && BK > 0 && BK % 16 == 0 && Cin > 0 && Cin % BK == 0 && !skip;
+}
+bool residue_feed_on();                                    // false when ASW_NO_RESIDUE_FEED is set, to any value (read once)
+// what the pipelined tiles ask before they take the feed: their ring has ASW_RESIDUE_MAX_SHIFT rows beyond BM per image,
+// and their element offsets are 32-bit (a tile reaches at most BM + 64 rows past a_len)
+inline bool residue_feed_ok(const asw_convgemm_args& a, int BK) {
+  return residue_feed_on() && residue_feed_applies(a.taps, a.stride, a.dil, a.Cin, BK, a.A2 != nullptr) &&
+         (a.taps - 1) / a.stride <= ASW_RESIDUE_MAX_SHIFT && a.a_len < ((int64_t)1 << 29) &&
+         (int64_t)a.stride * a.a_row_stride < (1 << 20) && (int64_t)a.pad * a.a_row_stride < (1 << 20);
+}
+
 #ifdef __HIPCC__
 // GroupNorm(2) + GLU of one (value, gate) pair: (a - m0) r0 ga + ba, gated by the sigmoid of the normalised
 // gate.  One definition with every rounding spelled out, because two kernels apply it (gn_glu_kernel and the
@@ -82,11 +110,13 @@ struct ProfScope {
   hipStream_t stream;
 };
 
-// "[B.. M.. N.. K.. <key><val>]": the shape suffix of a GEMM launch name in the detailed profile (empty otherwise)
+// "[B.. M.. N.. K.. <key><val>]": the shape suffix of a GEMM launch name in the detailed profile (empty otherwise);
+// `feed` (" res": the residue-image A feed) goes in front of the closing bracket
 struct ShapeTag {
   char s[64] = "";
-  ShapeTag(const asw_convgemm_args& a, char key, int val) {
-    if (prof_detail()) snprintf(s, sizeof s, "[B%d M%d N%d K%d %c%d]", a.B, a.M_out, a.N, a.taps * a.Cin, key, val);
+  ShapeTag(const asw_convgemm_args& a, char key, int val, const char* feed = "") {
+    if (prof_detail())
+      snprintf(s, sizeof s, "[B%d M%d N%d K%d %c%d%s]", a.B, a.M_out, a.N, a.taps * a.Cin, key, val, feed);
   }
 };
 

@@ -1,6 +1,7 @@
 // f16x3_tile.h -- the building blocks the split-fp16 ("f16x3") matrix kernels share (convgemm.hip, pipegemm.hip,
 // resconv.hip, resstack.hip, downconv.hip): the three-term product, the fragment-order weight load, the halo-image row layout with its staging
-// loop, the pinned transposed k-loop, the chunked A operand of the row-major GEMMs and the XCD-aware tile orders.
+// loop, the pinned transposed k-loop, the chunked and the residue-image A operand of the row-major GEMMs and the XCD-aware
+// tile orders.
 // Everything is inlined into its caller; a kernel experiment changes one of these instead of a copy per kernel.
 #pragma once
 #include "mfma_util.h"
@@ -229,6 +230,71 @@ struct ChunkedA {
       const int idx = tid + v * NT;
       const int row = idx / KV, cv = idx - row * KV;
       if (idx < BM * KV) {
+        half4 hi, lo;
+        split4t<NTERM>(ra[v], hi, lo);
+        *reinterpret_cast<half4*>(Ah + row * LDH + cv * 4) = hi;
+        if (NTERM == 3) *reinterpret_cast<half4*>(Al + row * LDH + cv * 4) = lo;
+      }
+    }
+  }
+};
+
+// ------------------------------------------------------------------ residue-image A operand (strided convolutions)
+// ChunkedA fetches, splits and deposits the BM rows of every (tap, chunk).  With taps > stride, tap j of frame f and
+// tap j + stride of frame f - 1 are the same input row: a 33-tap stride-16 tile handles every row 2.05 times.  Here a
+// stage is the image of ONE residue r = tap mod stride and one BK-channel chunk c: image row i is input row
+// (m0 + i) * stride - pad + r, and tap r + q * stride of tile row i reads image row i + q (asw::ResidueFeed,
+// include/asw_hip.h: asw_residue_schedule).  An image has BM + (taps - 1 - r) / stride rows; the ring stage is sized
+// for ROWS = BM + ASW_RESIDUE_MAX_SHIFT.  The BM rows every image has are FULL float4 per thread, as in ChunkedA; the
+// rows beyond them are one more float4 in the first threads only (the other lanes' loads are disabled: no traffic).
+// Loads stay on the buffer descriptor: padding, rows past a_len and disabled lanes read as zeros and no index can fault.
+// No skip operand (A2F only occurs with one tap), dil == 1.
+// Unlike ChunkedA, rows of frames past M_out ARE fetched where a valid frame reads them through a shift (only rows
+// from M_out + ASW_RESIDUE_MAX_SHIFT on are left zero), so the phantom frames of a ragged tile accumulate real data:
+// the caller clears their accumulators after the K loop.
+template <int BM, int BK, int NT>
+struct ResidueA {
+  static constexpr int KV = BK / 4;                // float4 per row
+  static constexpr int LDH = BK + 8;               // halves per staged row
+  static constexpr int ROWS = BM + ASW_RESIDUE_MAX_SHIFT;
+  static constexpr int FULL = BM * KV / NT;
+  static constexpr int A_VEC = (ROWS * KV + NT - 1) / NT;
+  static_assert(BM * KV % NT == 0 && A_VEC == FULL + 1, "BM rows split evenly; the shifted rows fit one more float4");
+  float4 ra[A_VEC];
+  // The staging addresses are ONE per-thread element offset plus uniform terms (float4 v of a thread is NT / KV rows
+  // below float4 v - 1): an offset and a flag per float4, as ChunkedA keeps them, cost the three-term mask path its
+  // last VGPRs and eight bytes of scratch.  32-bit: offsets stay below a_len + (BM + shift) rows, a_len < 2^29.
+  int a_base;                                      // element offset of (image row tid / KV, residue 0, c 0) + column
+  int blk_step;                                    // NT / KV rows
+  int row_lim;                                     // image rows from here on serve phantom frames only: left zero
+  int row_step;
+  __amdgpu_buffer_rsrc_t rA;
+  const int& tid;                                  // (by reference: see ChunkedA)
+
+  __device__ __forceinline__ ResidueA(const asw_convgemm_args& p, int b, int m0, const int& tid) : tid(tid) {
+    const int row = tid / KV, cv = tid - row * KV;
+    a_base = (int)(((long)(m0 + row) * p.stride - p.pad) * p.a_row_stride) + cv * 4;
+    blk_step = (NT / KV) * p.stride * (int)p.a_row_stride;
+    row_lim = p.M_out + ASW_RESIDUE_MAX_SHIFT - m0;
+    row_step = (int)p.a_row_stride;
+    rA = act_rsrc(p.A + (long)b * p.a_batch_stride, p.a_len);
+  }
+  // image of residue r, chunk c; `shifts` = its rows beyond BM
+  __device__ __forceinline__ void load(int r, int c, int shifts) {
+    const int koff = r * row_step + c * BK;
+    const int rows = min(BM + shifts, row_lim);
+#pragma unroll
+    for (int v = 0; v < A_VEC; ++v)                     // padding / past-the-end offsets read as zeros
+      ra[v] = act_load4(rA, a_base + v * blk_step + koff, tid / KV + v * (NT / KV) < rows);
+  }
+  // (rows an image does not have are deposited as the zeros their disabled loads returned: no tap reads them)
+  template <int NTERM>
+  __device__ __forceinline__ void deposit(_Float16* Ah, _Float16* Al) const {
+#pragma unroll
+    for (int v = 0; v < A_VEC; ++v) {
+      const int idx = tid + v * NT;
+      const int row = idx / KV, cv = idx - row * KV;
+      if (v < FULL || idx < ROWS * KV) {
         half4 hi, lo;
         split4t<NTERM>(ra[v], hi, lo);
         *reinterpret_cast<half4*>(Ah + row * LDH + cv * 4) = hi;

@@ -117,15 +117,146 @@ __device__ __forceinline__ bool pipe_mainloop(const asw_convgemm_args& p, float*
   return true;
 }
 
-template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int NTERM = 3, int WM = 2>
+// The same main loop over the stages of the residue-image feed (ResidueA, f16x3_tile.h; asw::residue_feed_ok decides
+// at the launch sites): strided convolutions with taps > stride deposit every input row once per tile instead of
+// once per tap.  A stage is the image of one (residue, chunk); ONE barrier per stage; the next image is fetched at
+// the top of the stage and deposited after the first tap's k-steps; the image's other taps (row shift q) follow
+// before the barrier.  Mask encoder (33 taps, stride 16): 32 deposits and barriers per tile instead of 66, 4 k-steps
+// (6 for residue 0) between barriers instead of 2.  The fragment index of a k-step is what it is in pipe_mainloop,
+// only the order of the visit differs; every tap contributes KS == QDB k-steps, so the B slot of a k-step is static.
+// Frames past M_out: an image row serves up to three frames, so the phantom frames of a ragged tile have
+// accumulated real rows.  That is undone HERE, by clearing their accumulators after the loop -- the state ChunkedA's
+// a_ok leaves -- and not in the epilogues: outputs, GroupNorm partial sums, the mask path's bypass gating, decoder
+// contraction and range guard all see zeros as they did.
+template <int BM, int BK, int NTERM = 3, int WM = 2>
+__device__ __forceinline__ bool pipe_mainloop_res(const asw_convgemm_args& p, float* smem, floatx16 (&acc)[BM / WM / 32][2],
+                                                  dim3& tile_out, int& ncol_out) {
+  constexpr int BN = 256, WN = 4, NT = 64 * WM * WN;
+  constexpr int QDB = 2, KS = BK / 16;
+  static_assert(KS == QDB, "a tap is QDB k-steps: the B buffer of a k-step is its index within the tap");
+  using Feed = ResidueA<BM, BK, NT>;
+  constexpr int LDH = Feed::LDH, ROWS = Feed::ROWS;
+  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
+  constexpr int STAGE = 2 * ROWS * LDH;            // halves per ring stage (hi image + lo image)
+
+  _Float16* ring = reinterpret_cast<_Float16*>(smem);
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / WN, wn = wid % WN;
+  const int ncol = p.N / BN, nrt = (p.M_out + BM - 1) / BM;
+  uint3 tl;
+  if (!xcd_tile_groups(p.B, nrt, ncol, tl)) return false;     // XCD-aware order, groups of 8
+  const dim3 tile(tl.x, tl.y, tl.z);
+  tile_out = tile;
+  ncol_out = ncol;
+  const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
+  const asw::ResidueFeed rf{p.taps, p.stride, p.Cin / BK};
+  const int nst = rf.stages();
+  const int tap_ks = p.stride * rf.cpb * KS;       // k-steps from a tap to the next tap of the same image
+  const half8* __restrict__ Wh = reinterpret_cast<const half8*>(p.Wf_hi);
+  const half8* __restrict__ Wl = reinterpret_cast<const half8*>(p.Wf_lo);
+  const int NTF = p.N / 32;                        // column fragments across N
+  const int nt0 = n0 / 32 + wn * TN;
+
+  Feed A(p, b, m0, tid);
+  auto deposit = [&](int stage) {
+    _Float16* Ah = ring + stage * STAGE;
+    A.template deposit<NTERM>(Ah, Ah + ROWS * LDH);
+  };
+  auto bload = [&](int kg, half8 (&bh)[TN], half8 (&bl)[TN]) {          // kg = global k-step (16 K each)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) frag_load<NTERM>(Wh, Wl, (long)kg * NTF + nt0 + j, lane, bh[j], bl[j]);
+  };
+
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  const int a_off = (wm * (BM / WM) + (lane & 31)) * LDH + (lane >> 5) * 8;
+  half8 qh[QDB][TN], ql[QDB][TN];                  // B fragments of the next tap's k-steps
+  int r = 0, c = 0, sh = rf.shifts(0);             // the stage being multiplied: residue, chunk, largest row shift
+#pragma unroll
+  for (int q = 0; q < QDB; ++q) bload(rf.kstep(rf.tap(0, 0), 0, KS) + q, qh[q], ql[q]);
+  A.load(r, c, sh);
+  deposit(0);
+  __syncthreads();
+  // One stage; PAR = stage parity, compile-time so that the ring stage index is static (the loop below is
+  // unrolled by two).
+  auto stage = [&](int s, auto par) {
+    constexpr int PAR = decltype(par)::value;
+    const bool more = s + 1 < nst;
+    int rn = r, cn = c + 1, shn = sh;              // residue-major, chunk inner
+    if (cn == rf.cpb) { cn = 0; rn = r + 1; shn = rf.shifts(rn); }
+    // Every load of the loop is UNCONDITIONAL (f16x3_tile.h, kloop): after the last stage the A lanes are all disabled
+    // (no traffic) and the B index is the fragment already held -- a load under an `if` costs a vmcnt(0) at the join
+    A.load(rn, cn, more ? shn : -BM);              // in flight under the MFMAs of this stage
+    const _Float16* Ah = ring + PAR * STAGE;
+    const _Float16* Al = Ah + ROWS * LDH;
+#pragma unroll
+    for (int q = 0; q <= ASW_RESIDUE_MAX_SHIFT; ++q) {
+      if (q == 0 || q <= sh) {                     // tap r + q * stride: tile row i reads image row i + q
+        const bool last = q == sh;
+        // the fragments QDB k-steps ahead: the same k-steps of the image's next tap, or of the next image's first
+        const int kb = rf.kstep(rf.tap(r, q), c, KS);
+        const int kn = !last ? kb + tap_ks : more ? rf.kstep(rf.tap(rn, 0), cn, KS) : kb;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          half8 ah[TM], al[TM];
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            ah[i] = *reinterpret_cast<const half8*>(Ah + a_off + (i * 32 + q) * LDH + ks * 16);
+            if (NTERM == 3) al[i] = *reinterpret_cast<const half8*>(Al + a_off + (i * 32 + q) * LDH + ks * 16);
+          }
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) mma3<NTERM>(acc[i][j], ah[i], al[i], qh[ks][j], ql[ks][j]);
+          bload(kn + ks, qh[ks], ql[ks]);
+        }
+        // deposit of the next image after the first tap: its conversions and LDS writes issue in the shadow of
+        // this wave's own MFMAs (the other stage was last read one stage ago, before the previous barrier)
+        if (q == 0 && more) deposit(PAR ^ 1);
+      }
+    }
+    __syncthreads();
+    r = rn; c = cn; sh = shn;
+  };
+  for (int s = 0; s < nst; s += 2) {
+    stage(s, std::integral_constant<int, 0>{});
+    if (s + 1 < nst) stage(s + 1, std::integral_constant<int, 1>{});
+  }
+  if (m0 + BM > p.M_out) {                         // ragged tile: frames past M_out contribute nothing (see above)
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = wm * (BM / WM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+        if (m0 + row >= p.M_out) {
+#pragma unroll
+          for (int j = 0; j < TN; ++j) acc[i][j][e] = 0.f;
+        }
+      }
+  }
+  return true;
+}
+
+template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int NTERM = 3, int WM = 2, bool RES = false>
 __global__ __launch_bounds__(256 * WM) __attribute__((amdgpu_waves_per_eu(2)))
 void convgemm16p_kernel(const asw_convgemm_args p) {
   constexpr int BN = 256, WN = 4;
+  static_assert(!(RES && A2F), "the residue-image feed has no skip operand");
   extern __shared__ __align__(16) float smem[];
   floatx16 acc[BM / WM / 32][2];
   dim3 tile;
   int ncol;
-  if (!pipe_mainloop<BM, A2F, BK, NTERM, WM>(p, smem, acc, tile, ncol)) return;
+  if constexpr (RES) {
+    if (!pipe_mainloop_res<BM, BK, NTERM, WM>(p, smem, acc, tile, ncol)) return;
+  } else {
+    if (!pipe_mainloop<BM, A2F, BK, NTERM, WM>(p, smem, acc, tile, ncol)) return;
+  }
   epilogue<BM, BN, WM, WN, false, STATS, false, MUL>(acc, p, smem, __builtin_ldexpf(1.0f, -p.w_shift),
                                                      RowsContig{(int)tile.x * BM, p.M_out}, tile, ncol);
 }
@@ -144,7 +275,7 @@ void convgemm16p_kernel(const asw_convgemm_args p) {
 //     column tile's share of the sum over e); the overlap-add kernel adds the N/256 partials.
 // Per candidate (T = 48 000) this writes 8 x 3008 x 33 floats instead of writing the bypass latent,
 // reading it, writing the gated latent and reading that again (4 x 24.6 MB).
-template <int BM, int KSB, int NTERM = 3>
+template <int BM, int KSB, int NTERM = 3, bool RES = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
 void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
   constexpr int BN = 256, WN = 4, TM = BM / 64, TN = 2, LDC = BN + 4, BK = 32;
@@ -153,7 +284,11 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
   floatx16 acc[TM][TN];
   dim3 tile;
   int ncol;
-  if (!pipe_mainloop<BM, false, BK, NTERM>(p, smem, acc, tile, ncol)) return;
+  if constexpr (RES) {
+    if (!pipe_mainloop_res<BM, BK, NTERM>(p, smem, acc, tile, ncol)) return;
+  } else {
+    if (!pipe_mainloop<BM, false, BK, NTERM>(p, smem, acc, tile, ncol)) return;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
@@ -252,6 +387,12 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
   }
 }
 
+// bytes of the two-stage A ring: hi + lo image of BM rows per stage, or of ResidueA's BM + ASW_RESIDUE_MAX_SHIFT
+template <int BM, int BK, bool RES>
+constexpr size_t pipe_ring_bytes() {
+  return (size_t)2 * 2 * (BM + (RES ? ASW_RESIDUE_MAX_SHIFT : 0)) * (BK + 8) * sizeof(_Float16);
+}
+
 int launch_mask_path(const asw_maskpath_args* args, void* stream) {
   ASW_CHECK_ARG(args, "mask_path: null argument block");
   const asw_maskpath_args& m = *args;
@@ -271,37 +412,48 @@ int launch_mask_path(const asw_maskpath_args* args, void* stream) {
                 "mask_path: reference rows must be 16-byte aligned");
   ASW_CHECK_ARG(a.precision == 1 || a.precision == 2, "mask_path: precision 1 (f16x3) or 2 (single-pass f16)");
   a.relu = 1;
-  constexpr size_t ring = (size_t)2 * 2 * BM * (BK + 8) * sizeof(_Float16);
+  constexpr size_t ring = pipe_ring_bytes<BM, BK, true>();     // (the larger of the two feeds' rings)
   constexpr size_t slab = (size_t)128 * (BN + 4) * sizeof(float);
   constexpr size_t smem = ring > slab ? ring : slab;
-  static_assert(smem <= 160 * 1024, "LDS budget");
-  // mask encoder + bypass + decoder taps
+  static_assert(pipe_ring_bytes<BM, BK, false>() <= ring && smem <= 160 * 1024, "LDS budget");
+  const dim3 grid(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN));
+  const double flops = 2.0 * a.B * (double)a.M_out * a.N * ((double)a.taps * a.Cin + m.byp_taps + m.dec_taps);
+  const bool res = asw::residue_feed_ok(a, BK);
+  const asw::ShapeTag tag(a, 's', a.stride, res ? " res" : "");     // the detailed profile says which feed ran
+  // mask encoder + bypass + decoder taps; the encoder's rows through the residue-image feed where it applies
+  if (res)
+    return asw::launch_pair<maskpath16p_kernel<BM, KSB, 1, true>, maskpath16p_kernel<BM, KSB, 3, true>>(
+        a.precision, grid, dim3(512), smem, smem, "maskpath16p<256,256,32>", tag.s, flops, 0.0, s, a, m);
   return asw::launch_pair<maskpath16p_kernel<BM, KSB, 1>, maskpath16p_kernel<BM, KSB, 3>>(
-      a.precision, dim3(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN)), dim3(512), smem, smem,
-      "maskpath16p<256,256,32>", asw::ShapeTag(a, 's', a.stride).s,
-      2.0 * a.B * (double)a.M_out * a.N * ((double)a.taps * a.Cin + m.byp_taps + m.dec_taps), 0.0, s, a, m);
+      a.precision, grid, dim3(512), smem, smem, "maskpath16p<256,256,32>", tag.s, flops, 0.0, s, a, m);
 }
 
-template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int WM = 2>
+template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int WM = 2, bool RES = false>
 int launch_pipe(const asw_convgemm_args& a, hipStream_t s) {
   constexpr int BN = 256;
-  constexpr size_t ring = (size_t)2 * 2 * BM * (BK + 8) * sizeof(_Float16);
+  constexpr size_t ring = pipe_ring_bytes<BM, BK, RES>();
   constexpr size_t slab = (size_t)(WM * 32) * (BN + 4) * sizeof(float);
   constexpr size_t smem = ring > slab ? ring : slab;
   static_assert(smem <= 160 * 1024, "LDS budget");
   static_assert(BM == 128 * WM, "wave tile 128 x 64");
   ASW_CHECK_ARG(A2F == (a.A2 != nullptr), "convgemm: skip operand variant mismatch");
   ASW_CHECK_ARG(a.Cin % BK == 0 && a.N % BN == 0, "convgemm: pipelined tile needs Cin %% BK == 0 and N %% 256 == 0");
-  return asw::launch_pair<convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 1, WM>, convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 3, WM>>(
+  return asw::launch_pair<convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 1, WM, RES>, convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 3, WM, RES>>(
       a.precision, dim3(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN)), dim3(256 * WM), smem, smem,
-      asw::prof_name(MUL ? "convgemm16pm" : "convgemm16p", BM, BN, BK, false, STATS), asw::ShapeTag(a, 's', a.stride).s,
+      asw::prof_name(MUL ? "convgemm16pm" : "convgemm16p", BM, BN, BK, false, STATS),
+      asw::ShapeTag(a, 's', a.stride, RES ? " res" : "").s,
       2.0 * a.B * (double)a.M_out * a.N * (double)a.taps * a.Cin, 0.0, s, a);
 }
 
 template <int BM, int WM>
 struct PipeTile {                        // pipelined 256-column kernel: convgemm16p
   template <bool STATS, bool MUL, bool A2F>
-  static int run(const asw_convgemm_args& a, hipStream_t s) { return launch_pipe<BM, STATS, MUL, A2F, 32, WM>(a, s); }
+  static int run(const asw_convgemm_args& a, hipStream_t s) {
+    // strided convolutions with taps > stride: every input row deposited once per tile (plain and statistics forms)
+    if constexpr (!MUL && !A2F)
+      if (asw::residue_feed_ok(a, 32)) return launch_pipe<BM, STATS, MUL, A2F, 32, WM, true>(a, s);
+    return launch_pipe<BM, STATS, MUL, A2F, 32, WM>(a, s);
+  }
 };
 
 }  // namespace

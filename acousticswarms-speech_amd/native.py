@@ -154,6 +154,15 @@ class ResStackArgs(Structure):
 
 
 # name -> (restype, argtypes); must list every symbol declared in include/asw_hip.h
+RESIDUE_MAX_TAPS = 8            # ASW_RESIDUE_MAX_TAPS
+
+
+class ResidueStage(Structure):  # asw_residue_stage
+    _fields_ = [("residue", c_int32), ("chunk", c_int32), ("rows", c_int32), ("first_row", c_int32), ("ntaps", c_int32),
+                ("tap", c_int32 * RESIDUE_MAX_TAPS), ("shift", c_int32 * RESIDUE_MAX_TAPS),
+                ("kstep", c_int32 * RESIDUE_MAX_TAPS)]
+
+
 SIGNATURES = {
     "asw_last_error": (c_char_p, []),
     "asw_abi_version": (c_int, []),
@@ -212,6 +221,8 @@ SIGNATURES = {
     "asw_compose_source_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "asw_convgemm_stats_tiles": (c_int, [c_int, c_int]),
     "asw_f16x3_overflow_count": (c_int, [c_int, POINTER(c_int32)]),
+    "asw_residue_schedule": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     POINTER(ResidueStage), c_int, POINTER(c_int), POINTER(c_int)]),
     "asw_gn_glu": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
                            c_void_p]),
     "asw_gn_finalize": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
@@ -314,6 +325,24 @@ def torch_ops():
         torch.ops.load_library(OPS_PATH)
         _ops = torch.ops.asw
     return _ops
+
+
+def residue_schedule(taps, stride, Cin, BK=32, BM=256, m0=0, dil=1, pad=0, has_skip=False):
+    """The residue-image A feed of the pipelined f16x3 tiles as the library enumerates it (asw_residue_schedule):
+    None when the feed does not apply to the shape, else (stages, max_shift) with one dict per stage -- residue, chunk,
+    rows, first_row and taps = [(tap, row shift, first k-step index)].  Host code only: needs no GPU."""
+    n, mx = c_int(), c_int()
+    L = lib()
+    check(L.asw_residue_schedule(taps, stride, dil, pad, Cin, BK, BM, m0, int(has_skip), None, 0, ctypes.byref(n),
+                                 ctypes.byref(mx)))
+    if n.value == 0:
+        return None
+    buf = (ResidueStage * n.value)()
+    check(L.asw_residue_schedule(taps, stride, dil, pad, Cin, BK, BM, m0, int(has_skip), buf, n.value, ctypes.byref(n),
+                                 ctypes.byref(mx)))
+    stages = [{"residue": d.residue, "chunk": d.chunk, "rows": d.rows, "first_row": d.first_row,
+               "taps": [(d.tap[q], d.shift[q], d.kstep[q]) for q in range(d.ntaps)]} for d in buf]
+    return stages, mx.value
 
 
 def check(status: int):

@@ -249,10 +249,11 @@ def overlap_add_parts(Dp, taps, hop, t, trim_left, trim_right, bias, mean=None, 
     return out
 
 
-def mask_path(x, ref, ref_hop, enc_w, enc_b, byp_w, byp_b, dec_w, frames, stride, pad):
+def mask_path(x, ref, ref_hop, enc_w, enc_b, byp_w, byp_b, dec_w, frames, stride, pad, precision="f16x3"):
     """Fused mask path (asw_mask_path_f16x3).  x [B][Tp][C] channels-last activations, ref [B][RL] padded
     reference rows (frame f reads ref[b][f*ref_hop + k]), enc_w [E][C][EK], byp_w [E][1][EKb], dec_w
-    [E][1][EKd] torch-layout weights.  Returns the partial tap products [E/256][B][frames][64]."""
+    [E][1][EKd] torch-layout weights.  Returns the partial tap products [E/256][B][frames][64].
+    precision: "f16x3" or the single-pass "f16"."""
     B, Tp, C = x.shape
     E, _, EK = enc_w.shape
     dev = x.device
@@ -270,7 +271,7 @@ def mask_path(x, ref, ref_hop, enc_w, enc_b, byp_w, byp_b, dec_w, frames, stride
     a.A, a.bias = _f32(x).data_ptr(), (_f32(enc_b).data_ptr() if enc_b is not None else None)
     a.B, a.M_out, a.N, a.Cin, a.taps, a.stride, a.dil, a.pad = B, frames, E, C, EK, stride, 1, pad
     a.a_row_stride, a.a_batch_stride, a.a_len = C, Tp * C, Tp * C
-    a.precision, a.w_shift, a.Wf_hi, a.Wf_lo = 1, sh, fh.data_ptr(), fl.data_ptr()
+    a.precision, a.w_shift, a.Wf_hi, a.Wf_lo = {"f16x3": 1, "f16": 2}[precision], sh, fh.data_ptr(), fl.data_ptr()
     m.ref, m.ref_batch_stride, m.ref_len, m.ref_hop = _f32(ref).data_ptr(), ref.shape[1], ref.shape[1], ref_hop
     m.byp_k, m.byp_taps, m.byp_shift = 48, byp_w.shape[-1], bsh
     m.byp_hi, m.byp_lo = bh.data_ptr(), bl.data_ptr()

@@ -459,6 +459,33 @@ int asw_split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo, 
 int asw_f16x3_overflow_count(int reset, uint32_t* count);
 /* Number of stats partials per batch item the call above will write. */
 int asw_convgemm_stats_tiles(int M_out, int N);
+/* The residue-image A feed of the pipelined f16x3 tiles (convgemm16p, the mask path).  In a strided convolution
+ * with taps > stride, tap j of frame f and tap j + stride of frame f - 1 are the same input row.  The rows
+ * {(m0 + i) * stride - pad + r}, r = tap mod stride, of one BK-channel chunk c form ONE LDS image; it serves tap
+ * r + q * stride of frame m0 + i at image row i + q.  The image is fetched, split and deposited once and all of its
+ * taps' k-steps run before the next barrier.  Stage order: residue-major, channel chunk inner (stage = r * Cin/BK + c).
+ * The weight packing is untouched: the first k-step of (tap, chunk c) is index (tap * Cin/BK + c) * (BK/16) of
+ * asw_pack_fragments_f16, whatever the order of the visit.
+ * asw_residue_schedule enumerates that schedule for a tile whose first frame is m0: *n_stages = stride * Cin/BK and up
+ * to `cap` entries of `out` (may be NULL with cap 0), or *n_stages = 0 when the feed does not apply: it needs dil == 1,
+ * stride >= 2, taps > stride, Cin % BK == 0, BK % 16 == 0 and no skip operand.  *max_shift (optional) receives
+ * (taps - 1) / stride, the largest row shift; the kernels take the feed up to ASW_RESIDUE_MAX_SHIFT (their ring has
+ * that many rows beyond BM per image) and ASW_NO_RESIDUE_FEED=1 in the environment keeps them on the chunk-per-tap
+ * feed (A/B measurements). */
+#define ASW_RESIDUE_MAX_TAPS 8
+#define ASW_RESIDUE_MAX_SHIFT 2
+typedef struct asw_residue_stage {
+  int32_t residue;                        /* r: tap mod stride of every tap of this stage */
+  int32_t chunk;                          /* c: channels [c * BK, (c + 1) * BK) */
+  int32_t rows;                           /* image rows: BM + (taps - 1 - r) / stride */
+  int32_t first_row;                      /* input row of image row 0: m0 * stride - pad + r (image row i: + i * stride) */
+  int32_t ntaps;                          /* taps served by the image, in the order of the visit */
+  int32_t tap[ASW_RESIDUE_MAX_TAPS];      /* r + q * stride */
+  int32_t shift[ASW_RESIDUE_MAX_TAPS];    /* q: frame m0 + i reads image row i + q */
+  int32_t kstep[ASW_RESIDUE_MAX_TAPS];    /* first of the tap's BK/16 consecutive k-step indices */
+} asw_residue_stage;
+int asw_residue_schedule(int taps, int stride, int dil, int pad, int Cin, int BK, int BM, int m0, int has_skip,
+                         asw_residue_stage* out, int cap, int* n_stages, int* max_shift);
 
 /* GroupNorm(2 groups) + GLU over channels-last raw [B][T][2C] using the partial
  * statistics written by asw_convgemm_f32 (network.py:107-113,194-197). */
