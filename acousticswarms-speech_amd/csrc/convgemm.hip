@@ -412,7 +412,7 @@ extern "C" int asw_convgemm_f32(const asw_convgemm_args* args, void* stream) {
     ASW_HIP(hipMemsetAsync(a.stats, 0, (size_t)a.B * a.stats_stride * 4 * sizeof(float), s));
   }
   ASW_CHECK_ARG(a.A && a.out, "convgemm: null tensor");
-  ASW_CHECK_ARG(a.precision >= 0 && a.precision <= 2, "convgemm: precision %d", a.precision);
+  ASW_CHECK_ARG(a.precision >= 0 && a.precision <= 3, "convgemm: precision %d", a.precision);
   if (a.precision >= 1) ASW_CHECK_ARG(a.Wt_hi && a.Wt_lo, "convgemm: the f16 modes need Wt_hi/Wt_lo");
   else ASW_CHECK_ARG(a.Wt != nullptr, "convgemm: null weights");
   ASW_CHECK_ARG(a.B > 0 && a.M_out > 0 && a.N > 0 && a.Cin > 0 && a.taps > 0, "convgemm: bad dims");

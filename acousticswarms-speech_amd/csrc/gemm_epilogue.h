@@ -16,7 +16,9 @@ namespace asw_mfma {
 // of a plain epilogue (the masked latent, the feed-forward intermediate).  The plain epilogue
 // therefore counts, in f16x3 mode, the threads that wrote a value beyond the fp16 range;
 // asw_f16x3_overflow_count() reads the counter.  Zero on every test and bench run with seeded
-// weights; a non-zero count means the next GEMM clipped its input and the f32 mode must be used.
+// weights; a non-zero count means the next GEMM clipped its input and the f32 or the f16x3_safe mode must be used.
+// In the f16x3_safe mode (model_common.h, Trunk::site) the un-normalised tensors are read by exact f32 kernels only;
+// its split GEMMs run under per-call precision 3, where the guard counts non-finite values alone.
 //
 // There is no relocatable device code, so every translation unit that includes this header has a counter of its
 // own.  convgemm.hip and pipegemm.hip write theirs and export an accessor over f16x3_overflow_read();
@@ -184,7 +186,8 @@ floatx16 (&acc)[BM / WM / 32][BN / WN / 32], const asw_convgemm_args& p,
       }
     }
   }
-  if (guard && !(amax <= 65504.f)) atomicAdd(&g_f16x3_overflow, 1u);      // also catches NaN
+  // (precision 3: no split GEMM reads this output, only a non-finite value is an error)
+  if (guard && !(amax <= (p.precision == 3 ? 3.402823466e38f : 65504.f))) atomicAdd(&g_f16x3_overflow, 1u);      // also catches NaN
   if (STATS) {
     __syncthreads();
     st0 = wave_sum(st0); sq0 = wave_sum(sq0); st1 = wave_sum(st1); sq1 = wave_sum(sq1);

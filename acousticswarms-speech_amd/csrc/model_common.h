@@ -345,6 +345,7 @@ struct Trunk {
   bool finalized = false;
   int device = 0;                          // HIP device the weights and the workspace live on
   int precision = 0;                       // 0 = exact f32 MFMA, 1 = f16x3 split MFMA, 2 = single-pass f16
+  bool exact_raw = false;                  // "f16x3_safe" (ABI value 3 = precision 1 + this flag), see site()
   bool fuse_mask = true;                   // f16x3: GroupNorm + GLU on load; bypass + mask encoder + decoder taps in one launch
   bool want_src = false;                   // the network has a source-fed front end (the spot network's candidate loop)
   bool src_stack = true;                   // ... and uses it (asw_spot_set_source_stack)
@@ -364,6 +365,18 @@ struct Trunk {
   int byp_k = 0;                           // padded K of the bypass GEMM
 
   const std::vector<float>& P(const std::string& k) const { return raw.at(k); }
+
+  // The per-call precision of a GEMM-class site, decided by what its A operand is.  Normed: the output of a LayerNorm,
+  // of GroupNorm + GLU or of the input normalisation, that output through a bounded pointwise step (Swish), or the
+  // skip-add of two such tensors -- bounded by the affine parameters whatever the weights do.  Raw: anything else (the
+  // attention context, a feed-forward hidden layer, the masked latent).  The residual stacks and the strided /
+  // transposed convolutions of the trunk all read Normed operands and pass `precision` itself.
+  //  * f32 / f16x3 / f16: every site runs in the model's precision.
+  //  * f16x3_safe: a Raw site runs on the exact f32 MFMA (the fp32 weights sit beside the split ones, WBuf::bind); a
+  //    Normed site runs the f16x3 kernels under per-call precision 3, which differs from 1 only in the range guard of
+  //    the plain epilogue: no split GEMM reads that output, so a finite value of any size is no error.
+  enum class Src { Normed, Raw };
+  int site(Src a) const { return !exact_raw ? precision : a == Src::Raw ? 0 : 3; }
 
   // ---- create: the device, the derived shape and its checks
   int init_shape(const TrunkCfg& c, const char* who) {
@@ -681,7 +694,7 @@ struct Trunk {
     const int B = pl.B, C = tc.channels, E = tc.encoder_channels, EK = tc.encoder_kernel_size, ES = tc.encoder_stride;
     int rc;
     asw_convgemm_args me = {};    // mask_encoder
-    me.A = x; mask_wt.bind(me, precision); me.bias = mask_b.p;
+    me.A = x; mask_wt.bind(me, site(Src::Normed)); me.bias = mask_b.p;
     me.B = B; me.M_out = pl.F; me.N = E; me.Cin = C; me.taps = EK; me.stride = ES; me.dil = 1; me.pad = EK / 2;
     me.a_row_stride = C; me.a_batch_stride = (int64_t)pl.Tp * C; me.a_len = me.a_batch_stride;
     if (fused_mask_path()) {
@@ -692,12 +705,14 @@ struct Trunk {
       f.byp_bias = byp_b.p;
       f.dec_hi = dec_wt.fhi; f.dec_lo = dec_wt.flo; f.dec_shift = dec_wt.shift; f.dec_taps = EK;
       f.taps = pl.D;
-      if ((rc = asw_mask_path_f16x3(&f, s))) return rc;
+      // the gated latent is split inside the kernel: the safe mode takes the variant that scales every frame first
+      f.enc.precision = precision;
+      if ((rc = exact_raw ? asw_mask_path_f16x3_scaled(&f, s) : asw_mask_path_f16x3(&f, s))) return rc;
       return asw_overlap_add_parts(pl.D, E / 256, B, pl.F, 64, EK, EK / 2, pl.T, 9, 8, out_bias, mean, stdv, out_wave, s);
     }
     {
       asw_convgemm_args a = {};   // reference_bypass: rows of the padded reference channel, hop ES
-      a.A = pl.refn; byp_wt.bind(a, precision); a.bias = byp_b.p; a.out = pl.Y;
+      a.A = pl.refn; byp_wt.bind(a, site(Src::Normed)); a.bias = byp_b.p; a.out = pl.Y;
       a.B = B; a.M_out = pl.F; a.N = E; a.Cin = byp_k; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
       a.a_row_stride = ES; a.a_batch_stride = pl.RL; a.a_len = pl.RL; a.relu = 1;
       if ((rc = asw_convgemm_f32(&a, s))) return rc;
@@ -707,7 +722,7 @@ struct Trunk {
     taps["latent"] = {pl.Y, (size_t)B * pl.F * E};
     {
       asw_convgemm_args a = {};   // output_decoder taps: D[f][j] = sum_e latent[f][e] * w[e][j]
-      a.A = pl.Y; dec_wt.bind(a, precision); a.out = pl.D;
+      a.A = pl.Y; dec_wt.bind(a, site(Src::Raw)); a.out = pl.D;
       a.B = B; a.M_out = pl.F; a.N = 64; a.Cin = E; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
       a.a_row_stride = E; a.a_batch_stride = (int64_t)pl.F * E; a.a_len = a.a_batch_stride;
       if ((rc = asw_convgemm_f32(&a, s))) return rc;
@@ -728,8 +743,10 @@ inline int check_ready(const Trunk* m, const char* fin) {
 }
 
 inline int set_precision(Trunk* m, const char* who, int precision) {
-  ASW_CHECK_ARG(m && (precision >= 0 && precision <= 2), "%s: 0 (f32), 1 (f16x3) or 2 (single-pass f16)", who);
-  m->precision = precision;
+  ASW_CHECK_ARG(m && (precision >= 0 && precision <= 3), "%s: 0 (f32), 1 (f16x3), 2 (single-pass f16) or 3 (f16x3_safe)", who);
+  // 3 is the three-term split (every `precision == 1` choice of kernels holds) plus exact arithmetic at the Raw sites
+  m->exact_raw = precision == 3;
+  m->precision = m->exact_raw ? 1 : precision;
   return ASW_OK;
 }
 

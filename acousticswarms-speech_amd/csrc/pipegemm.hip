@@ -275,7 +275,19 @@ void convgemm16p_kernel(const asw_convgemm_args p) {
 //     column tile's share of the sum over e); the overlap-add kernel adds the N/256 partials.
 // Per candidate (T = 48 000) this writes 8 x 3008 x 33 floats instead of writing the bypass latent,
 // reading it, writing the gated latent and reading that again (4 x 24.6 MB).
-template <int BM, int KSB, int NTERM = 3, bool RES = false>
+//
+// SCALED (asw_mask_path_f16x3_scaled, the f16x3_safe mode): the gated latent is the one un-normalised tensor that is
+// split to fp16 inside a kernel, and split4 saturates at 65504.  This variant gives every latent row of a pass (one
+// frame, the tile's 256 channels) a power-of-two scale of its own: with 2^e <= max|row| < 2^(e+1) the row is
+// multiplied by 2^(MASK_BINADE - e) before the split, which puts its largest magnitude into [2^12, 2^13) whatever it
+// was -- up as well as down, so small rows keep their lo halves out of the fp16 subnormals too -- and the frame's taps
+// by 2^(e - MASK_BINADE) after the contraction.  Both steps are exact (v_ldexp_f32), so the kernel is exactly
+// homogeneous per frame: scaling a frame's latent by 2^k scales its taps by 2^k, bit for bit.  A lane owns one slab
+// row in A-fragment order: the row maximum is a pre-pass over its own 128 values and one exchange with lane ^ 32; an
+// output register belongs to another row than the lane's A row, so the exponents come back through a bpermute.  A
+// row of zeros (or of fp32 subnormals) keeps scale 1.  The range guard counts non-finite latents only.
+constexpr int MASK_BINADE = 12;
+template <int BM, int KSB, int NTERM = 3, bool RES = false, bool SCALED = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
 void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
   constexpr int BN = 256, WN = 4, TM = BM / 64, TN = 2, LDC = BN + 4, BK = 32;
@@ -289,7 +301,9 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
   } else {
     if (!pipe_mainloop<BM, false, BK, NTERM>(p, smem, acc, tile, ncol)) return;
   }
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // (SCALED: the wave index as a scalar, which frees the vector registers the extra pass needs -- no scratch)
+  const int wid = SCALED ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
   const float acc_scale = __builtin_ldexpf(1.0f, -p.w_shift);
@@ -329,13 +343,14 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = fmaxf(acc[tm][tn][r] * acc_scale + bm, 0.f) * fmaxf(bp[r] * byp_scale + bb, 0.f);
-        amax = fmaxf(amax, v);
+        if constexpr (!SCALED) amax = fmaxf(amax, v);
         acc[tm][tn][r] = v;
       }
     }
   }
   // the latent is split to fp16 halves below: same range guard as a latent written for a later GEMM
-  if (!(amax <= 65504.f)) atomicAdd(&g_f16x3_overflow, 1u);
+  // (SCALED: every row is brought into range first, a finite magnitude is no error; the row maxima below find the rest)
+  if (!SCALED && !(amax <= 65504.f)) atomicAdd(&g_f16x3_overflow, 1u);
   // ---- B: decoder contraction through the slab, rows [pass*128, pass*128 + 128) of the tile per pass
   float* Ct = smem;
   const half8* __restrict__ Dh = reinterpret_cast<const half8*>(mf.dec_hi);
@@ -363,10 +378,31 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) tp[r] = 0.f;
     const float* src = Ct + (ft * 32 + (lane & 31)) * LDC + (lane >> 5) * 8;
+    int rsh = 0;                                               // SCALED: this lane's row is split as row * 2^rsh
+    if constexpr (SCALED) {
+      // magnitudes order like their bit patterns, and a NaN (which fmaxf would drop) sorts above every number
+      unsigned mb = 0;
+      auto mag = [](float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; };
+#pragma unroll 4
+      for (int ks = 0; ks < BN / 16; ++ks) {
+        const float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
+        const float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
+        mb = max(max(max(mb, mag(x0.x)), max(mag(x0.y), mag(x0.z))), max(max(mag(x0.w), mag(x1.x)), mag(x1.y)));
+        mb = max(mb, max(mag(x1.z), mag(x1.w)));
+      }
+      const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);   // the other half of the row: lane ^ 32
+      const int ef = (int)(max(sw[0], sw[1]) >> 23);                            // biased exponent of the row maximum
+      rsh = (ef == 0 || ef == 255) ? 0 : MASK_BINADE + 127 - ef;
+      if (ef == 255) atomicAdd(&g_f16x3_overflow, 1u);                          // range guard: inf or NaN in the latent
+    }
 #pragma unroll 4
     for (int ks = 0; ks < BN / 16; ++ks) {
-      const float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
-      const float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
+      float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
+      float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
+      if constexpr (SCALED) {
+        x0 = make_float4(__builtin_ldexpf(x0.x, rsh), __builtin_ldexpf(x0.y, rsh), __builtin_ldexpf(x0.z, rsh), __builtin_ldexpf(x0.w, rsh));
+        x1 = make_float4(__builtin_ldexpf(x1.x, rsh), __builtin_ldexpf(x1.y, rsh), __builtin_ldexpf(x1.z, rsh), __builtin_ldexpf(x1.w, rsh));
+      }
       half8 dh, dl;
       frag_load<NTERM>(Dh, Dl, (long)(n0 / 16 + ks) * 2 + tt, lane, dh, dl);
       half4 h0, l0, h1, l1;
@@ -375,6 +411,13 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
       const half8 ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
       const half8 al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
       mma3<NTERM>(tp, ah, al, dh, dl);
+    }
+    if constexpr (SCALED) {
+      // register r holds row (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of the block: undo that row's scale (every lane
+      // takes part in the exchange, whatever it stores below)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        tp[r] = __builtin_ldexpf(tp[r], -__shfl(rsh, (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), 64));
     }
     const int j = tt * 32 + (lane & 31);
     if (j < mf.dec_taps) {
@@ -393,7 +436,7 @@ constexpr size_t pipe_ring_bytes() {
   return (size_t)2 * 2 * (BM + (RES ? ASW_RESIDUE_MAX_SHIFT : 0)) * (BK + 8) * sizeof(_Float16);
 }
 
-int launch_mask_path(const asw_maskpath_args* args, void* stream) {
+int launch_mask_path(const asw_maskpath_args* args, void* stream, bool scaled = false) {
   ASW_CHECK_ARG(args, "mask_path: null argument block");
   const asw_maskpath_args& m = *args;
   asw_convgemm_args a = m.enc;
@@ -411,6 +454,7 @@ int launch_mask_path(const asw_maskpath_args* args, void* stream) {
   ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(m.ref) & 15) == 0 && m.ref_batch_stride % 4 == 0,
                 "mask_path: reference rows must be 16-byte aligned");
   ASW_CHECK_ARG(a.precision == 1 || a.precision == 2, "mask_path: precision 1 (f16x3) or 2 (single-pass f16)");
+  ASW_CHECK_ARG(!scaled || a.precision == 1, "mask_path: the per-frame scale exists for precision 1 (f16x3) only");
   a.relu = 1;
   constexpr size_t ring = pipe_ring_bytes<BM, BK, true>();     // (the larger of the two feeds' rings)
   constexpr size_t slab = (size_t)128 * (BN + 4) * sizeof(float);
@@ -421,6 +465,14 @@ int launch_mask_path(const asw_maskpath_args* args, void* stream) {
   const bool res = asw::residue_feed_ok(a, BK);
   const asw::ShapeTag tag(a, 's', a.stride, res ? " res" : "");     // the detailed profile says which feed ran
   // mask encoder + bypass + decoder taps; the encoder's rows through the residue-image feed where it applies
+  if (scaled) {
+    constexpr const char* name = "maskpath16ps<256,256,32>";
+    if (res)
+      return asw::launch_pair<maskpath16p_kernel<BM, KSB, 3, true, true>, maskpath16p_kernel<BM, KSB, 3, true, true>>(
+          a.precision, grid, dim3(512), smem, smem, name, tag.s, flops, 0.0, s, a, m);
+    return asw::launch_pair<maskpath16p_kernel<BM, KSB, 3, false, true>, maskpath16p_kernel<BM, KSB, 3, false, true>>(
+        a.precision, grid, dim3(512), smem, smem, name, tag.s, flops, 0.0, s, a, m);
+  }
   if (res)
     return asw::launch_pair<maskpath16p_kernel<BM, KSB, 1, true>, maskpath16p_kernel<BM, KSB, 3, true>>(
         a.precision, grid, dim3(512), smem, smem, "maskpath16p<256,256,32>", tag.s, flops, 0.0, s, a, m);
@@ -472,3 +524,6 @@ int pipe_gemm(const asw_convgemm_args& a, hipStream_t s) {
 }  // namespace asw
 
 extern "C" int asw_mask_path_f16x3(const asw_maskpath_args* args, void* stream) { return launch_mask_path(args, stream); }
+extern "C" int asw_mask_path_f16x3_scaled(const asw_maskpath_args* args, void* stream) {
+  return launch_mask_path(args, stream, true);
+}

@@ -204,19 +204,22 @@ int ffn_first(const Ffn& f, int prec, const float* hin, int rows, int d, int ffw
 // one Conformer layer along time for the BS sequences: x -> out (both [BS*L][d])
 int run_conformer(asw_sep* m, Plan& pl, ConfLayer& c, const float* x, float* out, hipStream_t s) {
   const asw_sep_config& cfg = m->cfg;
-  const int rows = pl.B * pl.L, d = pl.d, ffw = cfg.ffw_dim, prec = m->precision;
+  const int rows = pl.B * pl.L, d = pl.d, ffw = cfg.ffw_dim;
+  // prec: A is a LayerNorm output, the sinusoid table, or Swish of a LayerNorm output; rawp: the Swish'd hidden layer
+  // of a feed-forward module and the attention context (Trunk::site)
+  const int prec = m->site(Trunk::Src::Normed), rawp = m->site(Trunk::Src::Raw);
   int rc;
   // x1 = x + FFN1(x)/2
   if ((rc = asw_add_layernorm2(x, nullptr, 0.f, c.f1.lng.p, c.f1.lnb.p, rows, d, 1e-5f, 0, nullptr, pl.h, s))) return rc;
   if ((rc = ffn_first(c.f1, prec, pl.h, rows, d, ffw, pl.f, s))) return rc;
-  if ((rc = linear(pl.f, c.f1.w2, prec, c.f1.b2.p, rows, d, ffw, 0, nullptr, nullptr, nullptr, pl.g, s))) return rc;
+  if ((rc = linear(pl.f, c.f1.w2, rawp, c.f1.b2.p, rows, d, ffw, 0, nullptr, nullptr, nullptr, pl.g, s))) return rc;
   if ((rc = asw_add_layernorm2(x, pl.g, 1.f, c.n1g.p, c.n1b.p, rows, d, 1e-5f, 0, pl.x1, pl.h, s))) return rc;   // h = norm1(x1)
   // x2 = x1 + MHA(norm1(x1))
   if ((rc = linear(pl.h, c.w_in, prec, nullptr, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
   if ((rc = linear(m->pe.p, c.w_pos, prec, nullptr, 2 * pl.L - 1, d, d, 0, nullptr, nullptr, nullptr, pl.pos, s))) return rc;
   if ((rc = asw_relpos_attention(pl.qkv, pl.pos, c.bu.p, c.bv.p, pl.B, pl.L, d, cfg.num_head, 1.0f / sqrtf((float)d), pl.ctx, s)))
     return rc;
-  if ((rc = linear(pl.ctx, c.w_out, prec, c.b_out.p, rows, d, d, 0, nullptr, nullptr, nullptr, pl.g, s))) return rc;
+  if ((rc = linear(pl.ctx, c.w_out, rawp, c.b_out.p, rows, d, d, 0, nullptr, nullptr, nullptr, pl.g, s))) return rc;
   if ((rc = asw_add_layernorm2(pl.x1, pl.g, 1.f, c.cm_lng.p, c.cm_lnb.p, rows, d, 1e-5f, 0, pl.x2, pl.h, s))) return rc;
   // x3 = x2 + ConvolutionModule(x2)
   if ((rc = linear(pl.h, c.cm_pw, prec, c.cm_pwb.p, rows, 2 * d, d, 0, nullptr, nullptr, nullptr, pl.raw2, s))) return rc;
@@ -228,19 +231,20 @@ int run_conformer(asw_sep* m, Plan& pl, ConfLayer& c, const float* x, float* out
   if ((rc = asw_add_layernorm2(pl.x2, pl.g, 1.f, c.f2.lng.p, c.f2.lnb.p, rows, d, 1e-5f, 0, pl.x3, pl.h, s))) return rc;
   // y = norm2(x3 + FFN2(x3)/2); out = final norm (eps 1e-6)
   if ((rc = ffn_first(c.f2, prec, pl.h, rows, d, ffw, pl.f, s))) return rc;
-  if ((rc = linear(pl.f, c.f2.w2, prec, c.f2.b2.p, rows, d, ffw, 0, pl.x3, c.n2g.p, c.n2b.p, pl.y, s))) return rc;
+  if ((rc = linear(pl.f, c.f2.w2, rawp, c.f2.b2.p, rows, d, ffw, 0, pl.x3, c.n2g.p, c.n2b.p, pl.y, s))) return rc;
   return asw_add_layernorm2(pl.y, nullptr, 0.f, c.fng.p, c.fnb.p, rows, d, 1e-6f, 0, nullptr, out, s);
 }
 
 // post-norm transformer layer across the S speakers of every time step: x -> out
 int run_inter(asw_sep* m, Plan& pl, InterLayer& t, const float* x, float* out, hipStream_t s) {
-  const int rows = pl.B * pl.L, d = pl.d, ffw = m->cfg.ffw_dim, prec = m->precision;
+  const int rows = pl.B * pl.L, d = pl.d, ffw = m->cfg.ffw_dim;
+  const int prec = m->site(Trunk::Src::Normed), rawp = m->site(Trunk::Src::Raw);   // x, x1: LayerNorm outputs; ctx, f: not
   int rc;
   if ((rc = linear(x, t.w_in, prec, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
   if ((rc = asw_inter_attention(pl.qkv, pl.NB, pl.S, pl.L, d, m->cfg.num_head, pl.ctx, s))) return rc;
-  if ((rc = linear(pl.ctx, t.w_out, prec, t.b_out.p, rows, d, d, 0, x, t.n1g.p, t.n1b.p, pl.x1, s))) return rc;
+  if ((rc = linear(pl.ctx, t.w_out, rawp, t.b_out.p, rows, d, d, 0, x, t.n1g.p, t.n1b.p, pl.x1, s))) return rc;
   if ((rc = linear(pl.x1, t.w1, prec, t.b1.p, rows, ffw, d, 1, nullptr, nullptr, nullptr, pl.f, s))) return rc;
-  return linear(pl.f, t.w2, prec, t.b2.p, rows, d, ffw, 0, pl.x1, t.n2g.p, t.n2b.p, out, s);
+  return linear(pl.f, t.w2, rawp, t.b2.p, rows, d, ffw, 0, pl.x1, t.n2g.p, t.n2b.p, out, s);
 }
 
 // everything after the preproc stage; pl.X[0] / pl.refn are filled

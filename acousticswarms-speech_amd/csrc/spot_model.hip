@@ -175,14 +175,16 @@ int run_network(asw_spot* m, Plan& pl, GateSet* gs, const float* mean, const flo
   // ---- bottleneck (network.py:240-265): post-norm transformer layers, batch-first rows
   const int L = pl.Tl[c.depth], d = m->enc_cout.back(), rows = pl.B * L;
   const float* h = pl.X[c.depth];
+  // h and x1 are GroupNorm + GLU / LayerNorm outputs; qkv -> ctx and the ReLU'd hidden layer ff are not (Trunk::site)
+  const int normed = m->site(Trunk::Src::Normed), rawp = m->site(Trunk::Src::Raw);
   for (int l = 0; l < c.num_transformer_layers; ++l) {
     TfLayer& t = m->tf[l];
     float* hout = (l % 2 == 0) ? pl.ha : pl.hb;
-    if ((rc = linear(h, t.w_in, m->precision, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
-    if ((rc = asw_attention_prec(pl.qkv, pl.B, L, d, c.num_head, m->precision, pl.ctx, s))) return rc;
-    if ((rc = linear(pl.ctx, t.w_out, m->precision, t.b_out.p, rows, d, d, 0, h, t.n1g.p, t.n1b.p, pl.x1, s))) return rc;
-    if ((rc = linear(pl.x1, t.w1, m->precision, t.b1.p, rows, c.ffw_dim, d, 1, nullptr, nullptr, nullptr, pl.ff, s))) return rc;
-    if ((rc = linear(pl.ff, t.w2, m->precision, t.b2.p, rows, d, c.ffw_dim, 0, pl.x1, t.n2g.p, t.n2b.p, hout, s))) return rc;
+    if ((rc = linear(h, t.w_in, normed, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
+    if ((rc = asw_attention_prec(pl.qkv, pl.B, L, d, c.num_head, rawp, pl.ctx, s))) return rc;
+    if ((rc = linear(pl.ctx, t.w_out, rawp, t.b_out.p, rows, d, d, 0, h, t.n1g.p, t.n1b.p, pl.x1, s))) return rc;
+    if ((rc = linear(pl.x1, t.w1, normed, t.b1.p, rows, c.ffw_dim, d, 1, nullptr, nullptr, nullptr, pl.ff, s))) return rc;
+    if ((rc = linear(pl.ff, t.w2, rawp, t.b2.p, rows, d, c.ffw_dim, 0, pl.x1, t.n2g.p, t.n2b.p, hout, s))) return rc;
     h = hout;
   }
   m->taps["bottleneck"] = {h, (size_t)rows * d};

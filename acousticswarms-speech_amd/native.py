@@ -217,6 +217,7 @@ SIGNATURES = {
                                 c_void_p, c_long, c_void_p]),
     "asw_convgemm_f32": (c_int, [POINTER(ConvGemmArgs), c_void_p]),
     "asw_mask_path_f16x3": (c_int, [POINTER(MaskPathArgs), c_void_p]),
+    "asw_mask_path_f16x3_scaled": (c_int, [POINTER(MaskPathArgs), c_void_p]),
     "asw_resstack64_f16x3": (c_int, [POINTER(ResStackArgs), c_void_p]),
     "asw_compose_source_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "asw_convgemm_stats_tiles": (c_int, [c_int, c_int]),

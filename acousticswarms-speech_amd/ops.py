@@ -249,8 +249,9 @@ def overlap_add_parts(Dp, taps, hop, t, trim_left, trim_right, bias, mean=None, 
     return out
 
 
-def mask_path(x, ref, ref_hop, enc_w, enc_b, byp_w, byp_b, dec_w, frames, stride, pad, precision="f16x3"):
-    """Fused mask path (asw_mask_path_f16x3).  x [B][Tp][C] channels-last activations, ref [B][RL] padded
+def mask_path(x, ref, ref_hop, enc_w, enc_b, byp_w, byp_b, dec_w, frames, stride, pad, precision="f16x3", scaled=False):
+    """Fused mask path (asw_mask_path_f16x3; scaled=True: asw_mask_path_f16x3_scaled, every latent row brought into
+    one fp16 binade before the split, "f16x3" only).  x [B][Tp][C] channels-last activations, ref [B][RL] padded
     reference rows (frame f reads ref[b][f*ref_hop + k]), enc_w [E][C][EK], byp_w [E][1][EKb], dec_w
     [E][1][EKd] torch-layout weights.  Returns the partial tap products [E/256][B][frames][64].
     precision: "f16x3" or the single-pass "f16"."""
@@ -278,7 +279,7 @@ def mask_path(x, ref, ref_hop, enc_w, enc_b, byp_w, byp_b, dec_w, frames, stride
     m.byp_bias = _f32(byp_b).data_ptr() if byp_b is not None else None
     m.dec_hi, m.dec_lo, m.dec_shift, m.dec_taps = dh.data_ptr(), dl.data_ptr(), dsh, dec_w.shape[-1]
     m.taps = parts.data_ptr()
-    check(lib().asw_mask_path_f16x3(byref(m), current_stream()))
+    check((lib().asw_mask_path_f16x3_scaled if scaled else lib().asw_mask_path_f16x3)(byref(m), current_stream()))
     torch.cuda.current_stream().synchronize()
     return parts
 

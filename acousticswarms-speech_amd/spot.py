@@ -30,12 +30,15 @@ def offsets_from_patches(patch_list, n_pairs: int) -> np.ndarray:
 
 
 class SpotModel:
-    PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2}
+    PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2, "f16x3_safe": 3}
 
     def __init__(self, cfg: SpotConfig = FULL, state_dict=None, batch_size: int = 32, precision: str = "f32",
                  lanes: int = 1):
         """precision: "f32" = exact fp32 MFMA; "f16x3" = split-operand half MFMA with fp32
-        accumulation (~21-bit operands, 5.3x the f32 matrix rate), see csrc/convgemm.hip (and pipegemm.hip, resconv.hip)."""
+        accumulation (~21-bit operands, 5.3x the f32 matrix rate), see csrc/convgemm.hip (and pipegemm.hip, resconv.hip);
+        "f16x3_safe" = f16x3 wherever a GEMM reads a normalised tensor, exact f32 (and a per-frame scale in the
+        one-launch mask path) where it reads an un-normalised one, so that no magnitude can saturate the fp16 split
+        (csrc/model_common.h, Trunk::site)."""
         if precision not in self.PRECISIONS:
             raise RuntimeError(f"precision must be one of {list(self.PRECISIONS)}")
         self.cfg = cfg

@@ -90,7 +90,16 @@ int asw_spot_set_lanes(asw_spot* m, int lanes);
 
 /* Arithmetic of the GEMM-class layers: 0 = exact fp32 MFMA (default), 1 = "f16x3"
  * split-operand half MFMA with fp32 accumulation, 2 = optional single-pass f16 (reduced
- * precision; see asw_convgemm_args.precision). */
+ * precision; see asw_convgemm_args.precision), 3 = "f16x3_safe": f16x3 without its fp16 range limit.
+ * In mode 3 a GEMM runs the f16x3 kernels exactly as in mode 1 if and only if its A operand is bounded by
+ * construction -- the output of a LayerNorm, of GroupNorm + GLU or of the input normalisation, Swish of such an
+ * output, or the skip-add of two of them: the whole U-Net trunk, in_proj, the first feed-forward linears, the
+ * Conformer's pointwise convolutions, the mask encoder and the bypass.  The sites that read an un-normalised tensor
+ * run on the exact f32 MFMA: the attention core, out_proj (reads the context), the second feed-forward linears (read
+ * the hidden layer), and the output_decoder tap GEMM of the three-GEMM mask path (reads the masked latent); the
+ * one-launch mask path becomes asw_mask_path_f16x3_scaled.  asw_f16x3_overflow_count then reads 0 for any finite
+ * weights.  What remains assumed: a normalised tensor is bounded by its affine parameters, roughly
+ * sqrt(n) * max|gamma| + max|beta| for n channels, and that bound is below 65504. */
 int asw_spot_set_precision(asw_spot* m, int precision);
 
 /* The hot loop: replaces DataParallelSpotModel.shift_and_sep
@@ -184,7 +193,7 @@ int asw_sep_create(const asw_sep_config* cfg, asw_sep** out);
 void asw_sep_destroy(asw_sep* m);
 int asw_sep_set_param(asw_sep* m, const char* key, const float* host_data, size_t numel);
 int asw_sep_finalize(asw_sep* m);
-int asw_sep_set_precision(asw_sep* m, int precision);
+int asw_sep_set_precision(asw_sep* m, int precision);   /* 0..3, as asw_spot_set_precision */
 
 /* Network.infer_sample (SpeakerSeparation/network.py:496-548): for each of the S speakers
  * advance channel m>=1 of `mix` by offsets[s][m-1] samples with ZERO fill (:510-522), stack to
@@ -325,7 +334,10 @@ typedef struct asw_convgemm_args {
    *   activations are split on the fly (saturated at +-65504).
    * precision 2 ("f16", optional, reduced precision): the same kernels with ONE MFMA per product, hi * hi on
    *   round-to-nearest halves (same weight arrays; the lo halves are ignored): ~2e-4 per layer, 47-48 dB
-   *   end to end against the reference, 1.5x the f16x3 throughput.  Never the default. */
+   *   end to end against the reference, 1.5x the f16x3 throughput.  Never the default.
+   * precision 3: the kernels and the arithmetic of precision 1, for a GEMM whose output no split GEMM reads (every
+   *   f16x3 site of the "f16x3_safe" model precision): the range guard of the plain epilogue counts non-finite
+   *   outputs only (asw_f16x3_overflow_count).  asw_convgemm_f32 only. */
   int32_t precision;
   int32_t w_shift;
   const void* Wt_hi;
@@ -392,6 +404,16 @@ typedef struct asw_maskpath_args {
   float* taps;            /* [N/256][B][M_out][64] */
 } asw_maskpath_args;
 int asw_mask_path_f16x3(const asw_maskpath_args* args, void* stream);
+/* The same launch without the fp16 range limit (the mask path of the "f16x3_safe" model precision; enc.precision 1
+ * only).  asw_mask_path_f16x3 splits the gated latent relu(..) * relu(..) to fp16 halves for the decoder
+ * contraction, which saturates at +-65504.  Here every latent row (one frame, the 256 channels of a column tile)
+ * is first multiplied by the power of two that brings its largest magnitude into [2^12, 2^13) -- up as well as
+ * down -- and the frame's partial taps by the inverse afterwards; both steps are exact.  The result is what
+ * asw_mask_path_f16x3 gives wherever that is in range (up to the rounding of the lo halves, which small rows no
+ * longer lose to fp16 subnormals), the kernel is exactly homogeneous per frame (latent row * 2^k -> taps * 2^k, bit
+ * for bit, short of fp32 overflow / underflow), and asw_f16x3_overflow_count counts non-finite latents only.  A row
+ * whose largest magnitude is zero or an fp32 subnormal keeps scale 1.  Profile name "maskpath16ps<256,256,32>". */
+int asw_mask_path_f16x3_scaled(const asw_maskpath_args* args, void* stream);
 /* A stack of 1..3 consecutive 64-channel DilatedResidualLayers (DilatedResidualSequence,
  * sep/training/SpeakerLocalization/network.py:50-82; the separation network uses the same classes) in
  * ONE launch, f16x3 arithmetic: out_i = LayerNorm(ReLU(conv_{dil_i}(x_i) + bias_i) + x_i), x_{i+1} = out_i.
@@ -455,7 +477,8 @@ int asw_split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo, 
  * projections) are checked where they are produced.  Returns through *count how many threads
  * of f16x3 launches on the current device wrote a value beyond the fp16 range (or a NaN) since
  * the last reset; waits for the device.  Non-zero means a later GEMM clipped its input: rerun in
- * precision 0.  The device must be the one the launches ran on. */
+ * precision 0 or 3.  (In model precision 3 nothing un-normalised is split unscaled, and only non-finite values
+ * count.)  The device must be the one the launches ran on. */
 int asw_f16x3_overflow_count(int reset, uint32_t* count);
 /* Number of stats partials per batch item the call above will write. */
 int asw_convgemm_stats_tiles(int M_out, int N);
