@@ -312,7 +312,18 @@ def no_full_collections():
         gc.set_threshold(*thr)
 
 
-def search_batched(joint_model, mixes, concurrent=2, geometries=None):
+def separate_stack(sep_model, stack, patch_lists):
+    """The separation stage of a finished batch from the mixtures already on the device: stack [K,M,T] cuda,
+    ``patch_lists[k]`` the final patches of mixture k.  The talkers of all mixtures are packed, whole mixtures in order,
+    into as few device calls as the sequence limit allows (``SepModel.infer_packed``).
+    -> list of float32 ndarrays [S_k, T]."""
+    from .sep import rounded_offsets
+    P = int(stack.shape[1]) - 1
+    return sep_model.infer_packed(stack, [rounded_offsets([p[0].sample_offset for p in patches], P)
+                                          for patches in patch_lists])
+
+
+def search_batched(joint_model, mixes, concurrent=2, geometries=None, separate=False):
     """The complete localization search (SRP-PHAT -> coarse -> fine -> clustering) of every mixture in
     ``mixes`` on this rank's GPU: ``concurrent`` worker threads pull mixtures from a queue -- a finished
     search is replaced at once, so the GPU never waits for a group to drain -- and score through one
@@ -321,8 +332,14 @@ def search_batched(joint_model, mixes, concurrent=2, geometries=None):
     ``geometries``: one ``(mic_positions, speaker_range)`` per mixture (``check_geometries``).  Search k then runs on
     a view of the ``MicArray`` of its own geometry, taken from ``joint_model.mic_array_for`` -- built by the
     searching thread in the model's ``geometry`` mode, once per distinct array while it stays in the LRU.  With
-    ``None`` every search uses the array of ``joint_model.setup()``, as before."""
+    ``None`` every search uses the array of ``joint_model.setup()``, as before.
+
+    ``separate=True``: every result dict also holds ``"audio"``, the joint separation of the mixture's talkers
+    (float32 [K_i, T], (0, T) without talkers).  The searches run as without it; after the last one the separation of all
+    mixtures runs from the device stack (``separate_stack``).  Needs ``joint_model.sep_model``."""
     check_geometries(mixes, geometries)
+    if separate and joint_model.sep_model is None:
+        raise RuntimeError("separate=True needs a separation model (JointModel(sep_model=None))")
     import torch
     spot = joint_model.spot_model
     mp = joint_model.Mic_processor
@@ -330,7 +347,7 @@ def search_batched(joint_model, mixes, concurrent=2, geometries=None):
     method = mp.Prone_method if mp is not None else "SRP"
     dev = spot.device
     n = len(mixes)
-    results = [None] * n
+    results, finals = [None] * n, [None] * n
     hosts = [torch.as_tensor(m).to(dtype=torch.float32).cpu() for m in mixes]
     stack = torch.stack(hosts).to(dev).contiguous()          # [K,M,T]: 1.3 MB per 7-mic, 48 000-sample mixture
     torch.cuda.synchronize(dev)                              # the launch stream reads it
@@ -360,6 +377,7 @@ def search_batched(joint_model, mixes, concurrent=2, geometries=None):
                     times[3] = time.time() - t0
         if len(patches) == 0:
             patches, spot_times = [], 0                    # the reference's empty-result early returns (:151-199)
+        finals[k] = patches
         results[k] = {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
                       "powers": np.array([p[2] for p in patches]), "names": [p[3] for p in patches],
                       "spot_times": spot_times, "times": times}
@@ -399,6 +417,9 @@ def search_batched(joint_model, mixes, concurrent=2, geometries=None):
         sys.setswitchinterval(switch)
     if errors:
         raise errors[0]
+    if separate:
+        for r, audio in zip(results, separate_stack(joint_model.sep_model, stack, finals)):
+            r["audio"] = audio
     torch.cuda.synchronize(dev)
     stats = {"launches": batcher.launches, "requests": batcher.requests, "launch_rule": dict(batcher.reasons), "candidates": batcher.candidates, "launch_sizes": list(batcher.sizes),
              "spot_gpu_s": sum(a.elapsed_time(b) for a, b in batcher.events) * 1e-3, "enqueue_host_s": batcher.host_s,

@@ -44,9 +44,14 @@ __device__ __forceinline__ float swishf(float v) { return v / (1.0f + expf(-v));
 constexpr int JS_MAXCH = 2048;
 constexpr int JS_BLOCKS = 128;
 
-__global__ __launch_bounds__(256) void joint_stats_partial_kernel(const float* __restrict__ mix, int M, int T,
-                                                                  const int32_t* __restrict__ offsets, int S,
-                                                                  double* __restrict__ part) {
+// Sequence groups of a ragged call, passed to the kernels by value (a few hundred bytes of kernel arguments: no device
+// buffer, no copy): group g is the sequences bounds[g] .. bounds[g+1]-1 and, for the statistics, reads mixture item[g].
+constexpr int RG_MAXG = 64;
+struct GroupTable { int32_t bounds[RG_MAXG + 1]; int32_t item[RG_MAXG]; };
+
+// blocks blockIdx.x of gridDim.x over the T samples of one item
+__device__ __forceinline__ void joint_stats_partial(const float* __restrict__ mix, int M, int T,
+                                                    const int32_t* __restrict__ offsets, int S, double* __restrict__ part) {
   __shared__ int off[JS_MAXCH];
   __shared__ double red[4][2];
   const int SM = S * M;
@@ -78,8 +83,8 @@ __global__ __launch_bounds__(256) void joint_stats_partial_kernel(const float* _
   }
 }
 
-__global__ __launch_bounds__(64) void joint_stats_final_kernel(const double* __restrict__ part, int nblocks, int T, int S,
-                                                               float* __restrict__ mean_out, float* __restrict__ std_out) {
+__device__ __forceinline__ void joint_stats_final(const double* __restrict__ part, int nblocks, int T, int S,
+                                                  float* __restrict__ mean_out, float* __restrict__ std_out) {
   double a0 = 0.0, a1 = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += 64) { a0 += part[i * 2]; a1 += part[i * 2 + 1]; }
   a0 = wsum_d(a0); a1 = wsum_d(a1);
@@ -88,6 +93,34 @@ __global__ __launch_bounds__(64) void joint_stats_final_kernel(const double* __r
   if (var < 0) var = 0;
   const float mu = (float)mean, sg = (float)sqrt(var);
   for (int s = threadIdx.x; s < S; s += 64) { mean_out[s] = mu; std_out[s] = sg; }
+}
+
+__global__ __launch_bounds__(256) void joint_stats_partial_kernel(const float* __restrict__ mix, int M, int T,
+                                                                  const int32_t* __restrict__ offsets, int S,
+                                                                  double* __restrict__ part) {
+  joint_stats_partial(mix, M, T, offsets, S, part);
+}
+
+__global__ __launch_bounds__(64) void joint_stats_final_kernel(const double* __restrict__ part, int nblocks, int T, int S,
+                                                               float* __restrict__ mean_out, float* __restrict__ std_out) {
+  joint_stats_final(part, nblocks, T, S, mean_out, std_out);
+}
+
+// The same two passes for the G items of a ragged call, item g = blockIdx.y: its own mixture, offsets, S_g, partials
+// (2 * JS_BLOCKS doubles each) and rows of mean / std.  mix [K][M][T], offsets / mean / std over all N sequences.
+__global__ __launch_bounds__(256) void joint_stats_partial_groups_kernel(const float* __restrict__ mix, int M, int T,
+                                                                         const int32_t* __restrict__ offsets, GroupTable tab,
+                                                                         double* __restrict__ part) {
+  const int g = blockIdx.y, n0 = tab.bounds[g];
+  joint_stats_partial(mix + (long)tab.item[g] * M * T, M, T, offsets + (long)n0 * (M - 1), tab.bounds[g + 1] - n0,
+                      part + (long)g * 2 * JS_BLOCKS);
+}
+
+__global__ __launch_bounds__(64) void joint_stats_final_groups_kernel(const double* __restrict__ part, int nblocks, int T,
+                                                                      GroupTable tab, float* __restrict__ mean_out,
+                                                                      float* __restrict__ std_out) {
+  const int g = blockIdx.x, n0 = tab.bounds[g];
+  joint_stats_final(part + (long)g * 2 * JS_BLOCKS, nblocks, T, tab.bounds[g + 1] - n0, mean_out + n0, std_out + n0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -500,28 +533,21 @@ __global__ __launch_bounds__(256) void relpos_attention_mfma_kernel(const float*
 // to hd+1 floats so the per-lane row walks are conflict free); lane s2 computes the scores
 // (s1, s2) for every s1 with an in-lane dot product, the softmax runs across lanes, and for the
 // output lane = head dimension.  S <= 64, hd <= 64.  IA_WAVES waves (units) per workgroup: 4 while their
-// regions fit the CU's LDS (S <= 38 at hd = 64), else 2 (any S <= 64: 2 x 66 KB at S = 64, hd = 64) or 1.
+// regions fit the CU's LDS (S <= 39 at hd = 64), else 2 (any S <= 64: 2 x 66 KB at S = 64, hd = 64) or 1.
 // ---------------------------------------------------------------------------------------
-template <int IA_WAVES>
-__global__ __launch_bounds__(64 * IA_WAVES) void inter_attention_kernel(const float* __restrict__ qkv, int NB, int S, int L,
-                                                                        int d, int nhead, float* __restrict__ ctx) {
-  extern __shared__ __align__(16) float smem[];
-  const int hd = d / nhead, ldk = hd + 1;
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float* Qs = smem + (size_t)wid * (3 * S * ldk + S * 64);     // per-wave region: Q, K, V [S][hd+1], P [S][64]
-  float* Ks = Qs + S * ldk;
+// One unit on one wave: the S sequences n0 .. n0+S-1 at time step t, head h, in the wave's LDS region
+// (3 * S * (hd+1) + S * 64 floats).  Every wave of the workgroup reaches both barriers; an inactive one does nothing else.
+__device__ __forceinline__ void inter_attention_unit(const float* __restrict__ qkv, int n0, int S, int t, int h, int L, int d,
+                                                     int hd, bool active, float* __restrict__ Qs, int lane,
+                                                     float* __restrict__ ctx) {
+  const int ldk = hd + 1;
+  float* Ks = Qs + S * ldk;                                       // per-wave region: Q, K, V [S][hd+1], P [S][64]
   float* Vs = Ks + S * ldk;
   float* Ps = Vs + S * ldk;
-  long unit = (long)blockIdx.x * IA_WAVES + wid;                  // (n, t, h)
-  const bool active = unit < (long)NB * L * nhead;                // wave-uniform
-  if (!active) unit = 0;
-  const int h = (int)(unit % nhead);
-  const long nt = unit / nhead;
-  const int n = (int)(nt / L), t = (int)(nt - (long)n * L);
   const float scale = 1.0f / sqrtf((float)hd);
   for (int i = lane; active && i < S * hd; i += 64) {
     const int s = i / hd, c = i - s * hd;
-    const float* row = qkv + ((long)(n * S + s) * L + t) * 3 * d + h * hd + c;
+    const float* row = qkv + ((long)(n0 + s) * L + t) * 3 * d + h * hd + c;
     Qs[s * ldk + c] = row[0] * scale;
     Ks[s * ldk + c] = row[d];
     Vs[s * ldk + c] = row[2 * d];
@@ -546,9 +572,71 @@ __global__ __launch_bounds__(64 * IA_WAVES) void inter_attention_kernel(const fl
     for (int s1 = 0; s1 < S; ++s1) {
       float acc = 0.f;
       for (int s2 = 0; s2 < S; ++s2) acc = fmaf(Ps[s1 * 64 + s2], Vs[s2 * ldk + lane], acc);
-      ctx[((long)(n * S + s1) * L + t) * d + h * hd + lane] = acc;
+      ctx[((long)(n0 + s1) * L + t) * d + h * hd + lane] = acc;
     }
   }
+}
+
+template <int IA_WAVES>
+__global__ __launch_bounds__(64 * IA_WAVES) void inter_attention_kernel(const float* __restrict__ qkv, int NB, int S, int L,
+                                                                        int d, int nhead, float* __restrict__ ctx) {
+  extern __shared__ __align__(16) float smem[];
+  const int hd = d / nhead;
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  long unit = (long)blockIdx.x * IA_WAVES + wid;                  // (n, t, h)
+  const bool active = unit < (long)NB * L * nhead;                // wave-uniform
+  if (!active) unit = 0;
+  const int h = (int)(unit % nhead);
+  const long nt = unit / nhead;
+  const int n = (int)(nt / L), t = (int)(nt - (long)n * L);
+  inter_attention_unit(qkv, n * S, S, t, h, L, d, hd, active, smem + (size_t)wid * (3 * S * (hd + 1) + S * 64), lane, ctx);
+}
+
+// The same units over G groups of DIFFERENT sizes: unit (g, t, h) attends over the S_g sequences of group g only.
+// qkv [N][L][3d], ctx [N][L][d] with N = tab.bounds[G]; the LDS regions are S_max = max S_g wide.
+template <int IA_WAVES>
+__global__ __launch_bounds__(64 * IA_WAVES) void inter_attention_groups_kernel(const float* __restrict__ qkv, GroupTable tab,
+                                                                               int G, int S_max, int L, int d, int nhead,
+                                                                               float* __restrict__ ctx) {
+  extern __shared__ __align__(16) float smem[];
+  const int hd = d / nhead;
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  long unit = (long)blockIdx.x * IA_WAVES + wid;                  // (g, t, h)
+  const bool active = unit < (long)G * L * nhead;                 // wave-uniform
+  if (!active) unit = 0;
+  const int h = (int)(unit % nhead);
+  const long gt = unit / nhead;
+  const int g = (int)(gt / L), t = (int)(gt - (long)g * L);
+  const int n0 = tab.bounds[g];
+  inter_attention_unit(qkv, n0, tab.bounds[g + 1] - n0, t, h, L, d, hd, active,
+                       smem + (size_t)wid * (3 * S_max * (hd + 1) + S_max * 64), lane, ctx);
+}
+
+// host: the groups of a ragged call.  bounds [G+1] non-decreasing from 0, every group 1..64 sequences.
+int fill_group_table(const char* who, const int32_t* bounds, int G, GroupTable& tab, int* s_max) {
+  if (G < 1 || G > RG_MAXG) return asw::set_error(ASW_ERR_ARG, "%s: G=%d groups (1..%d per call)", who, G, RG_MAXG);
+  if (bounds[0] != 0) return asw::set_error(ASW_ERR_ARG, "%s: bounds[0]=%d, must be 0", who, bounds[0]);
+  *s_max = 0;
+  for (int g = 0; g < G; ++g) {
+    const long sg = (long)bounds[g + 1] - bounds[g];
+    if (sg < 1 || sg > 64)
+      return asw::set_error(ASW_ERR_ARG, "%s: group %d holds %ld sequences (1..64; empty groups are left out)", who, g, sg);
+    *s_max = (int)sg > *s_max ? (int)sg : *s_max;
+  }
+  for (int g = 0; g <= RG_MAXG; ++g) tab.bounds[g] = bounds[g <= G ? g : G];
+  for (int g = 0; g < RG_MAXG; ++g) tab.item[g] = 0;
+  return ASW_OK;
+}
+
+// waves (units) per workgroup of the inter-speaker attention and the LDS bytes of one: 4 regions while they fit, else 2, 1
+int inter_attention_waves(const char* who, int S, int hd, size_t* per_wave) {
+  *per_wave = sizeof(float) * (3 * (size_t)S * (hd + 1) + (size_t)S * 64);
+  const size_t lds_max = 160 * 1024;
+  if (*per_wave > lds_max) {
+    asw::set_error(ASW_ERR_ARG, "%s: S=%d x head_dim %d needs %zu bytes of LDS per wave", who, S, hd, *per_wave);
+    return 0;
+  }
+  return 4 * *per_wave <= lds_max ? 4 : 2 * *per_wave <= lds_max ? 2 : 1;
 }
 
 }  // namespace
@@ -568,6 +656,31 @@ extern "C" int asw_joint_shift_stats(const float* mix, int M, int T, const int32
 }
 
 extern "C" int asw_joint_shift_stats_scratch_doubles(void) { return 2 * JS_BLOCKS; }
+
+extern "C" int asw_joint_shift_stats_groups(const float* mix, int M, int T, const int32_t* offsets, const int32_t* bounds,
+                                            int G, const int32_t* item_of_group, double* scratch, float* mean, float* std,
+                                            void* stream) {
+  ASW_CHECK_ARG(G >= 0, "joint_shift_stats_groups: G=%d", G);
+  if (G == 0) return ASW_OK;
+  ASW_CHECK_ARG(mix && offsets && bounds && item_of_group && scratch && mean && std, "joint_shift_stats_groups: null pointer");
+  ASW_CHECK_ARG(M >= 1 && T >= 2, "joint_shift_stats_groups: M=%d T=%d unsupported", M, T);
+  GroupTable tab;
+  int s_max;
+  if (int rc = fill_group_table("joint_shift_stats_groups", bounds, G, tab, &s_max)) return rc;
+  ASW_CHECK_ARG((long)s_max * M <= JS_MAXCH, "joint_shift_stats_groups: an item of %d sequences x %d channels (S*M <= %d)", s_max,
+                M, JS_MAXCH);
+  for (int g = 0; g < G; ++g) {
+    ASW_CHECK_ARG(item_of_group[g] >= 0, "joint_shift_stats_groups: group %d reads mixture %d", g, item_of_group[g]);
+    tab.item[g] = item_of_group[g];
+  }
+  hipStream_t s = asw::as_stream(stream);
+  const int nb = asw::cdiv(T, 256) < JS_BLOCKS ? asw::cdiv(T, 256) : JS_BLOCKS;
+  hipLaunchKernelGGL(joint_stats_partial_groups_kernel, dim3(nb, G), dim3(256), 0, s, mix, M, T, offsets, tab, scratch);
+  ASW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(joint_stats_final_groups_kernel, dim3(G), dim3(64), 0, s, scratch, nb, T, tab, mean, std);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
 
 extern "C" int asw_add_layernorm2(const float* x, const float* y, float alpha, const float* gamma, const float* beta,
                                   int rows, int N, float eps, int act, float* sum_out, float* ln_out, void* stream) {
@@ -658,11 +771,9 @@ extern "C" int asw_inter_attention(const float* qkv, int NB, int S, int L, int d
   ASW_CHECK_ARG(qkv && ctx, "inter_attention: null pointer");
   ASW_CHECK_ARG(NB > 0 && S > 0 && S <= 64 && L > 0 && nhead > 0 && d % nhead == 0 && d / nhead <= 64,
                 "inter_attention: bad shape (S <= 64, head_dim <= 64)");
-  const int hd = d / nhead;
-  const size_t per_wave = sizeof(float) * (3 * (size_t)S * (hd + 1) + (size_t)S * 64);
-  const size_t lds_max = 160 * 1024;
-  const int waves = 4 * per_wave <= lds_max ? 4 : 2 * per_wave <= lds_max ? 2 : 1;
-  ASW_CHECK_ARG(per_wave <= lds_max, "inter_attention: S=%d x head_dim %d needs %zu bytes of LDS per wave", S, hd, per_wave);
+  size_t per_wave;
+  const int waves = inter_attention_waves("inter_attention", S, d / nhead, &per_wave);
+  if (!waves) return ASW_ERR_ARG;
   const size_t smem = per_wave * waves;
   const void* kern = waves == 4 ? reinterpret_cast<const void*>(inter_attention_kernel<4>)
                    : waves == 2 ? reinterpret_cast<const void*>(inter_attention_kernel<2>)
@@ -674,6 +785,37 @@ extern "C" int asw_inter_attention(const float* qkv, int NB, int S, int L, int d
   if (waves == 4) hipLaunchKernelGGL(inter_attention_kernel<4>, grid, dim3(256), smem, st, qkv, NB, S, L, d, nhead, ctx);
   else if (waves == 2) hipLaunchKernelGGL(inter_attention_kernel<2>, grid, dim3(128), smem, st, qkv, NB, S, L, d, nhead, ctx);
   else hipLaunchKernelGGL(inter_attention_kernel<1>, grid, dim3(64), smem, st, qkv, NB, S, L, d, nhead, ctx);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
+extern "C" int asw_inter_attention_groups(const float* qkv, const int32_t* bounds, int G, int L, int d, int nhead, float* ctx,
+                                          void* stream) {
+  ASW_CHECK_ARG(G >= 0, "inter_attention_groups: G=%d", G);
+  if (G == 0) return ASW_OK;
+  ASW_CHECK_ARG(qkv && bounds && ctx, "inter_attention_groups: null pointer");
+  ASW_CHECK_ARG(L > 0 && nhead > 0 && d > 0 && d % nhead == 0 && d / nhead <= 64,
+                "inter_attention_groups: bad shape (head_dim <= 64)");
+  GroupTable tab;
+  int s_max;
+  if (int rc = fill_group_table("inter_attention_groups", bounds, G, tab, &s_max)) return rc;
+  size_t per_wave;
+  const int waves = inter_attention_waves("inter_attention_groups", s_max, d / nhead, &per_wave);
+  if (!waves) return ASW_ERR_ARG;
+  const size_t smem = per_wave * waves;
+  const void* kern = waves == 4 ? reinterpret_cast<const void*>(inter_attention_groups_kernel<4>)
+                   : waves == 2 ? reinterpret_cast<const void*>(inter_attention_groups_kernel<2>)
+                                : reinterpret_cast<const void*>(inter_attention_groups_kernel<1>);
+  static asw::SmemAttr attr[3];                                // per device and instantiation
+  if (int rc = attr[waves == 4 ? 0 : waves == 2 ? 1 : 2].ensure(kern, smem)) return rc;
+  dim3 grid(asw::cdiv((long)G * L * nhead, waves));
+  hipStream_t st = asw::as_stream(stream);
+  if (waves == 4)
+    hipLaunchKernelGGL(inter_attention_groups_kernel<4>, grid, dim3(256), smem, st, qkv, tab, G, s_max, L, d, nhead, ctx);
+  else if (waves == 2)
+    hipLaunchKernelGGL(inter_attention_groups_kernel<2>, grid, dim3(128), smem, st, qkv, tab, G, s_max, L, d, nhead, ctx);
+  else
+    hipLaunchKernelGGL(inter_attention_groups_kernel<1>, grid, dim3(64), smem, st, qkv, tab, G, s_max, L, d, nhead, ctx);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

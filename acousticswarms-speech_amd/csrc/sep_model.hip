@@ -132,9 +132,13 @@ struct Plan : TrunkPlan {
   std::vector<float*> intra_out, inter_out;   // per bottleneck layer (kept apart so every tap stays readable)
   float *h, *g, *x1, *x2, *x3, *qkv, *ctx, *raw2, *u, *v2, *y, *f, *pos;
   const int32_t* counts = nullptr;            // host [NB]: speakers present per item (NULL: S everywhere), forward() only
+  // infer_batch() only: the B sequences are G groups (host [G+1] bounds) that attend and are normalised apart
+  const int32_t* group_bounds = nullptr;
+  int G = 0;
+  int32_t* mix_index;                         // device [B]
 };
 
-void layout(const asw_sep* m, int NB, int S, int T, Arena& a, Plan& pl) {
+void layout(const asw_sep* m, int NB, int S, int T, int groups, Arena& a, Plan& pl) {
   const asw_sep_config& c = m->cfg;
   pl.NB = NB; pl.S = S;
   m->layout_levels(NB * S, T, a, pl);
@@ -149,12 +153,13 @@ void layout(const asw_sep* m, int NB, int S, int T, Arena& a, Plan& pl) {
   pl.f = a.take<float>(rows * c.ffw_dim);
   pl.pos = a.take<float>((2 * L - 1) * d);
   m->layout_mask(a, pl);
-  pl.jscr = a.take<double>(asw_joint_shift_stats_scratch_doubles());
+  pl.jscr = a.take<double>((size_t)asw_joint_shift_stats_scratch_doubles() * groups);
+  pl.mix_index = a.take<int32_t>(pl.B);
 }
 
-int ensure_ws(asw_sep* m, int NB, int S, int T, Plan& pl) {
+int ensure_ws(asw_sep* m, int NB, int S, int T, Plan& pl, int groups = 1) {
   Arena dry(nullptr, 0, true);
-  layout(m, NB, S, T, dry, pl);
+  layout(m, NB, S, T, groups, dry, pl);
   const size_t need = dry.off + 4096;
   if (need > m->ws_bytes) {
     // the number of talkers changes from mixture to mixture: grow by half again, not to the exact size, so that a
@@ -171,7 +176,7 @@ int ensure_ws(asw_sep* m, int NB, int S, int T, Plan& pl) {
     m->ws_bytes = want;
   }
   Arena real(m->ws, m->ws_bytes, false);
-  layout(m, NB, S, T, real, pl);
+  layout(m, NB, S, T, groups, real, pl);
   return ASW_OK;
 }
 
@@ -241,7 +246,9 @@ int run_inter(asw_sep* m, Plan& pl, InterLayer& t, const float* x, float* out, h
   const int prec = m->site(Trunk::Src::Normed), rawp = m->site(Trunk::Src::Raw);   // x, x1: LayerNorm outputs; ctx, f: not
   int rc;
   if ((rc = linear(x, t.w_in, prec, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
-  if ((rc = asw_inter_attention(pl.qkv, pl.NB, pl.S, pl.L, d, m->cfg.num_head, pl.ctx, s))) return rc;
+  if (pl.group_bounds) rc = asw_inter_attention_groups(pl.qkv, pl.group_bounds, pl.G, pl.L, d, m->cfg.num_head, pl.ctx, s);
+  else rc = asw_inter_attention(pl.qkv, pl.NB, pl.S, pl.L, d, m->cfg.num_head, pl.ctx, s);
+  if (rc) return rc;
   if ((rc = linear(pl.ctx, t.w_out, rawp, t.b_out.p, rows, d, d, 0, x, t.n1g.p, t.n1b.p, pl.x1, s))) return rc;
   if ((rc = linear(pl.x1, t.w1, prec, t.b1.p, rows, ffw, d, 1, nullptr, nullptr, nullptr, pl.f, s))) return rc;
   return linear(pl.f, t.w2, rawp, t.b2.p, rows, d, ffw, 0, pl.x1, t.n2g.p, t.n2b.p, out, s);
@@ -396,6 +403,47 @@ extern "C" int asw_sep_infer(asw_sep* m, const float* mix, int M, int T, const i
   if ((rc = asw_shift_norm_preproc(mix, M, T, pl.Tp, offsets, S, /*circular*/ 0, pl.mean, pl.stdv, m->pre_w.p, m->pre_b.p, C,
                                    pl.X[0], pl.refn + pad_l, pl.RL, s)))
     return rc;
+  return run_network(m, pl, pl.mean, pl.stdv, out, s);
+}
+
+extern "C" int asw_sep_infer_batch(asw_sep* m, const float* mix, int K, int M, int T, const int32_t* offsets,
+                                   const int32_t* counts, float* out, void* stream) {
+  int rc = check_ready(m, "asw_sep_finalize");
+  if (rc) return rc;
+  ASW_CHECK_ARG(K >= 0, "sep_infer_batch: K=%d mixtures", K);
+  if (K == 0) return ASW_OK;
+  ASW_CHECK_ARG(counts, "sep_infer_batch: null pointer (counts)");
+  // the groups: one per item that holds a talker, in order; sequence n reads mixture mix_index[n]
+  std::vector<int32_t> bounds(1, 0), item, mix_index;
+  long N = 0;
+  for (int k = 0; k < K; ++k) {
+    ASW_CHECK_ARG(counts[k] >= 0 && counts[k] <= 64, "sep_infer_batch: item %d holds %d speakers (0..64)", k, counts[k]);
+    N += counts[k];
+    if (counts[k] == 0) continue;
+    bounds.push_back((int32_t)N);
+    item.push_back(k);
+    mix_index.insert(mix_index.end(), counts[k], k);
+  }
+  ASW_CHECK_ARG(N <= 64, "sep_infer_batch: %ld sequences (at most 64 per call)", N);
+  if (N == 0) return ASW_OK;
+  ASW_CHECK_ARG(mix && offsets && out, "sep_infer_batch: null pointer");
+  ASW_CHECK_ARG(M == m->cfg.n_mics, "sep_infer_batch: mixtures have %d channels, model expects %d", M, m->cfg.n_mics);
+  ASW_CHECK_ARG(T >= 2, "sep_infer_batch: T=%d", T);
+  hipStream_t s = asw::as_stream(stream);
+  const int B = (int)N, G = (int)item.size();
+  Plan pl;
+  if ((rc = ensure_ws(m, 1, B, T, pl, G))) return rc;
+  const int C = m->cfg.channels, pad_l = m->cfg.encoder_kernel_size / 2;
+  ASW_HIP(hipMemsetAsync(pl.refn, 0, (size_t)B * pl.RL * sizeof(float), s));
+  if ((rc = asw_joint_shift_stats_groups(mix, M, T, offsets, bounds.data(), G, item.data(), pl.jscr, pl.mean, pl.stdv, s)))
+    return rc;
+  // pageable source: the runtime has taken the table before the call returns
+  ASW_HIP(hipMemcpyAsync(pl.mix_index, mix_index.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if ((rc = asw_shift_norm_preproc_multi(mix, M, T, pl.Tp, offsets, pl.mix_index, B, /*circular*/ 0, pl.mean, pl.stdv,
+                                         m->pre_w.p, m->pre_b.p, C, pl.X[0], pl.refn + pad_l, pl.RL, s)))
+    return rc;
+  pl.group_bounds = bounds.data();
+  pl.G = G;
   return run_network(m, pl, pl.mean, pl.stdv, out, s);
 }
 

@@ -632,6 +632,31 @@ Tensor sep_infer(int64_t model, const Tensor& mix, const Tensor& offsets) {
   return out;
 }
 
+// infer_sample for K mixtures in one call: mix [K, M, T], offsets [N, M-1] item after item, counts[k] talkers in item k
+Tensor sep_infer_batch(int64_t model, const Tensor& mix, const Tensor& offsets, at::IntArrayRef counts) {
+  TORCH_CHECK(model != 0, "sep_infer_batch: null model handle");
+  need(mix, "mix", at::kFloat, 3);
+  need(offsets, "offsets", at::kInt, 2);
+  same_device(mix, offsets, "mix and offsets");
+  const int K = checked_int(mix.size(0), "K"), M = checked_int(mix.size(1), "M"), T = checked_int(mix.size(2), "T");
+  const int N = checked_int(offsets.size(0), "N");
+  TORCH_CHECK((int64_t)counts.size() == K, "counts must hold one entry per mixture: ", counts.size(), " for ", K);
+  std::vector<int32_t> c(K);
+  int64_t total = 0;
+  for (int k = 0; k < K; ++k) {
+    c[k] = checked_int(counts[k], "count");
+    total += c[k];
+  }
+  TORCH_CHECK(total == N && offsets.size(1) == M - 1, "offsets must be [sum(counts), M-1] = [", total, ", ", M - 1, "], got [", N,
+              ", ", offsets.size(1), "]");
+  Tensor out = at::empty({N, T}, mix.options());
+  Launch l(mix);
+  check_status(asw_sep_infer_batch(reinterpret_cast<asw_sep*>(model), mix.data_ptr<float>(), K, M, T,
+                                   offsets.data_ptr<int32_t>(), c.data(), out.data_ptr<float>(), l.stream),
+               "asw_sep_infer_batch");
+  return out;
+}
+
 Tensor sep_forward(int64_t model, const Tensor& mix_norm, int64_t n_speakers, int64_t n_mics, int64_t max_speakers) {
   TORCH_CHECK(model != 0, "sep_forward: null model handle");
   need(mix_norm, "mix", at::kFloat, 3);
@@ -718,6 +743,7 @@ TORCH_LIBRARY(asw, m) {
   m.def("geom_lattice(Tensor planes, Tensor xs, Tensor ys, Tensor zs, float[] border, float width) -> Tensor[]");
   m.def("lattice_nms(Tensor cells, Tensor scores, int radius) -> Tensor[]");
   m.def("sep_infer(int model, Tensor mix, Tensor offsets) -> Tensor");
+  m.def("sep_infer_batch(int model, Tensor mix, Tensor offsets, int[] counts) -> Tensor");
   m.def("sep_forward(int model, Tensor mix, int n_speakers, int n_mics, int max_speakers) -> Tensor");
   m.def("sep_forward_counts(int model, Tensor mix, int[] counts, int n_mics, int max_speakers) -> Tensor");
 }
@@ -747,6 +773,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("geom_lattice", &geom_lattice);
   m.impl("lattice_nms", &lattice_nms);
   m.impl("sep_infer", &sep_infer);
+  m.impl("sep_infer_batch", &sep_infer_batch);
   m.impl("sep_forward", &sep_forward);
   m.impl("sep_forward_counts", &sep_forward_counts);
 }

@@ -252,6 +252,20 @@ class JointModel(object):
             mix_data = cached
         return self.sep_model.infer(mix_data, [p[0] for p in target_patches])
 
+    def separate_by_localization_by_sample(self, mix_data, sample_lists):
+        """:206-209: the separation stage from sample offsets instead of patches."""
+        if len(sample_lists) == 0:
+            return None
+        return self.sep_model.infer_sample(mix_data, sample_lists)
+
+    def separate_batch(self, mixes, patch_lists):
+        """The separation stage of a batch: ``patch_lists[k]`` are the final patches of mixture k as ``forward`` returns
+        them (tuples whose first entry is the patch).  -> list of float32 ndarrays [S_k, T], (0, T) for a mixture with
+        no talker (``SepModel.infer_batch``: the mixtures of one shape, packed into as few device calls as fit)."""
+        if self.sep_model is None:
+            raise RuntimeError("separate_batch needs a separation model (sep_model=None)")
+        return self.sep_model.infer_batch(mixes, [[p[0].sample_offset for p in patches] for patches in patch_lists])
+
     def to(self, device=None):
         if device is not None:
             self.device = device

@@ -347,6 +347,34 @@ def joint_shift_stats(mix, offsets):
     return mean, std
 
 
+def _group_tables(counts):
+    """host tables of a ragged call: bounds [G+1] and the item of each group, over the items that hold a sequence"""
+    import ctypes
+    bounds, items = [0], []
+    for k, c in enumerate(counts):
+        if int(c) > 0:
+            bounds.append(bounds[-1] + int(c))
+            items.append(k)
+    return (ctypes.c_int32 * len(bounds))(*bounds), (ctypes.c_int32 * max(1, len(items)))(*items), len(items)
+
+
+def joint_shift_stats_groups(mix_stack, offsets, counts):
+    """``joint_shift_stats`` per item of a ragged call: mix_stack [K,M,T], offsets [N,M-1] item after item, counts [K]
+    -> mean, std [N] (one value per item, on each of its sequences)."""
+    K, M, T = mix_stack.shape
+    N = offsets.shape[0]
+    assert len(counts) == K and sum(int(c) for c in counts) == N and all(int(c) >= 0 for c in counts)
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.shape[1] == M - 1
+    bounds, items, G = _group_tables(counts)
+    scratch = torch.empty((max(1, G) * lib().asw_joint_shift_stats_scratch_doubles(),), dtype=torch.float64,
+                          device=mix_stack.device)
+    mean = torch.empty((N,), dtype=torch.float32, device=mix_stack.device)
+    std = torch.empty((N,), dtype=torch.float32, device=mix_stack.device)
+    check(lib().asw_joint_shift_stats_groups(ptr(_f32(mix_stack)), M, T, ptr(offsets), bounds, G, items, ptr(scratch),
+                                             ptr(mean), ptr(std), current_stream()))
+    return mean, std
+
+
 def add_layernorm2(x, y=None, alpha=1.0, gamma=None, beta=None, eps=1e-5, act=0, want_sum=False, want_ln=True):
     rows, N = x.shape
     s = torch.empty_like(x) if want_sum else None
@@ -388,6 +416,19 @@ def inter_attention(qkv, nhead):
     d = d3 // 3
     ctx = torch.empty((NB, S, L, d), dtype=torch.float32, device=qkv.device)
     check(lib().asw_inter_attention(ptr(_f32(qkv)), NB, S, L, d, nhead, ptr(ctx), current_stream()))
+    return ctx
+
+
+def inter_attention_groups(qkv, counts, nhead, out=None):
+    """``inter_attention`` over groups of different sizes: qkv [N,L,3d] with counts[g] consecutive sequences in group g
+    (zeros are left out) -> ctx [N,L,d].  ``out``: write into this tensor (tests)."""
+    N, L, d3 = qkv.shape
+    d = d3 // 3
+    assert sum(int(c) for c in counts) == N and all(int(c) >= 0 for c in counts)
+    bounds, _items, G = _group_tables(counts)
+    ctx = torch.empty((N, L, d), dtype=torch.float32, device=qkv.device) if out is None else out
+    assert ctx.shape == (N, L, d)
+    check(lib().asw_inter_attention_groups(ptr(_f32(qkv)), bounds, G, L, d, nhead, ptr(_f32(ctx)), current_stream()))
     return ctx
 
 

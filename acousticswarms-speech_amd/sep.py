@@ -4,7 +4,8 @@
 (sep/training/SpeakerSeparation/network.py:323-548): ``infer(input_channels, patch_list)``,
 ``infer_sample(input_channels, sample_list)`` -> ndarray [S, T], and ``forward(mix,
 num_speakers)`` on already normalised input.  It is what ``JointModel.sep_model`` holds
-(sep/training/JointModel/network.py:122,201-209).  All arithmetic runs in the HIP library,
+(sep/training/JointModel/network.py:122,201-209).  ``infer_batch(mixes, sample_lists)`` is ``infer_sample`` over a batch
+of mixtures in packed device calls (no counterpart in the reference).  All arithmetic runs in the HIP library,
 reached through ``torch.ops.asw.sep_infer`` / ``sep_forward``; PyTorch is used for device
 memory and streams only.  There is no CPU path.
 """
@@ -27,6 +28,39 @@ def rounded_offsets(sample_list, n_pairs: int) -> np.ndarray:
     if offs.ndim != 2 or offs.shape[1] != n_pairs:
         raise RuntimeError(f"speaker has {offs.shape[-1]} offsets, mixture has {n_pairs + 1} channels")
     return np.round(offs).astype(np.int32)
+
+
+def pack_items(counts, cap: int = MAX_SEQUENCES):
+    """The device calls of a batch: items stay whole and in order, and every call takes as many as fit ``cap``
+    sequences.  -> list of (first, last) item ranges, ``last`` exclusive, covering every item once (an item with no
+    sequence rides along with its neighbours).  An item wider than ``cap`` raises ``RuntimeError``."""
+    calls, first, total = [], 0, 0
+    for k, c in enumerate(counts):
+        c = int(c)
+        if c < 0:
+            raise ValueError(f"item {k} holds {c} sequences")
+        if c > cap:
+            raise RuntimeError(f"{c} speakers in one item; the library takes at most {cap} sequences per call")
+        if total + c > cap:
+            calls.append((first, k))
+            first, total = k, 0
+        total += c
+    if first < len(counts):
+        calls.append((first, len(counts)))
+    return calls
+
+
+def check_batch(mixes, sample_lists):
+    """Shapes of an ``infer_batch`` call, looked at before any device work: one sample list per mixture, every mixture
+    [M, T] of one shape.  ``ValueError`` otherwise.  -> (M, T), (0, 0) for an empty batch."""
+    if len(mixes) != len(sample_lists):
+        raise ValueError(f"{len(sample_lists)} sample lists for {len(mixes)} mixtures")
+    shapes = [tuple(int(v) for v in np.shape(m)) for m in mixes]
+    if any(len(sh) != 2 for sh in shapes):
+        raise ValueError("every mixture must be [M, T]")
+    if len(set(shapes)) > 1:
+        raise ValueError(f"the mixtures of one batch must share M and T, got the shapes {sorted(set(shapes))}")
+    return shapes[0] if shapes else (0, 0)
 
 
 class SepModel:
@@ -134,6 +168,51 @@ class SepModel:
         assert mix_dev.dtype == torch.float32 and mix_dev.is_contiguous() and mix_dev.is_cuda
         assert offsets_dev.dtype == torch.int32 and offsets_dev.is_contiguous() and offsets_dev.is_cuda
         return native.torch_ops().sep_infer(self._h.value, mix_dev, offsets_dev)
+
+    def infer_batch_device(self, mix_stack, offsets_dev, counts):
+        """``infer_device`` for K mixtures in one library call: mix_stack [K,M,T] float32 cuda, offsets_dev [N,M-1] int32
+        cuda (rounded, item after item), counts [K] talkers per item (0 allowed) with N = sum(counts) <= MAX_SEQUENCES
+        -> [N,T] float32 cuda.  Each item's talkers are normalised with that item's statistics and attend only to each
+        other: the rows are those of ``infer_device`` item by item."""
+        self._need()
+        counts = [int(c) for c in counts]
+        if len(counts) != mix_stack.shape[0]:
+            raise RuntimeError(f"{len(counts)} counts for {mix_stack.shape[0]} mixtures")
+        return native.torch_ops().sep_infer_batch(self._h.value, mix_stack, offsets_dev, counts)
+
+    def infer_batch(self, mixes, sample_lists):
+        """``infer_sample`` over a batch: mixes K x (M x T) of one shape, sample_lists K x (S_k x (M-1)) -> list of K
+        float32 ndarrays [S_k, T] ((0, T) for an item with no talker).  The items go to the device whole and in order,
+        in as few ``infer_batch_device`` calls as MAX_SEQUENCES allows (``pack_items``)."""
+        import torch
+        M, T = check_batch(mixes, sample_lists)
+        offs = [rounded_offsets(sl, M - 1) for sl in sample_lists]
+        counts = [o.shape[0] for o in offs]
+        pack_items(counts)                                    # an item beyond the limit raises before the upload
+        if sum(counts) == 0:
+            return [np.empty((0, T), dtype=np.float32) for _ in mixes]
+        self._need()
+        stack = torch.stack([torch.as_tensor(m).to(dtype=torch.float32) for m in mixes]).to(self.device).contiguous()
+        return self.infer_packed(stack, offs)
+
+    def infer_packed(self, mix_stack, offsets):
+        """mix_stack [K,M,T] float32 cuda, offsets: K rounded int32 arrays [S_k, M-1] -> K float32 ndarrays [S_k, T],
+        through one ``infer_batch_device`` call per range of ``pack_items``."""
+        counts = [int(o.shape[0]) for o in offsets]
+        T = int(mix_stack.shape[2])
+        out = []
+        for first, last in pack_items(counts):
+            if sum(counts[first:last]) == 0:
+                out.extend(np.empty((0, T), dtype=np.float32) for _ in range(first, last))
+                continue
+            rows = native.to_host(self.infer_batch_device(
+                mix_stack[first:last], native.to_device(np.concatenate(offsets[first:last], axis=0), mix_stack.device),
+                counts[first:last]))
+            pos = 0
+            for c in counts[first:last]:
+                out.append(rows[pos:pos + c])
+                pos += c
+        return out
 
     # ---- reference call surface ---------------------------------------------------
     def infer(self, input_channels, patch_list) -> np.ndarray:

@@ -213,7 +213,7 @@ class ShardedSpotModel:
         return sorted(merged, key=key)
 
 
-def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None):
+def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None, separate=False):
     """A batch of mixtures over the ranks of one node (BASELINE config "batch of 64 mixtures"):
     with at least as many mixtures as ranks the cheapest partition is by whole mixture --
     contiguous balanced blocks, each rank runs the complete search of its mixtures on its own
@@ -232,15 +232,24 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
     from ``JointModel.mic_array_for`` (built in the model's ``geometry`` mode, repeated arrays once), in the batched
     form and in the plain loop alike.  ``None``: every mixture on the array of ``joint_model.setup()``.
 
+    ``separate=True``: every dict also holds ``"audio"``, the separated talkers of the mixture (float32 [K, T]; (0, T)
+    when none was found) -- in the batched form from ONE packed separation of all mixtures after the searches
+    (batching.separate_stack), in the plain loop the ``audio`` of ``forward``.  Needs ``joint_model.sep_model`` and a
+    single rank (``RuntimeError`` otherwise: audio does not travel over the object all-gather).
+
     ``joint_model.spot_model`` must be the plain per-rank model here.  Returns, on every rank and
     in mixture order, a list of dicts {centres [K,3], powers [K], names, spot_times, times[5]}."""
     from .batching import check_geometries, no_full_collections
     check_geometries(mixes, geometries)
+    if separate and getattr(joint_model, "sep_model", None) is None:
+        raise RuntimeError("separate=True needs a separation model (JointModel(sep_model=None))")
     import contextlib
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
     world = dist.get_world_size(group) if on else 1
+    if separate and world > 1:
+        raise RuntimeError("separate=True runs on one rank only: the audio is not gathered across ranks")
     if getattr(joint_model.spot_model, "world", 1) > 1:
         raise RuntimeError("localize_batch shards by mixture: pass the un-sharded per-rank spot model")
     b = shard_bounds(len(mixes), world)
@@ -252,7 +261,8 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
     if batched:
         from .batching import search_batched
         res, stats = search_batched(joint_model, [mixes[k] for k in mine], concurrent=concurrent,
-                                    geometries=None if geometries is None else [geometries[k] for k in mine])
+                                    geometries=None if geometries is None else [geometries[k] for k in mine],
+                                    separate=separate)
         localize_batch.last_stats = stats                    # diagnostic: launches, candidates, GPU seconds inside them
         local = list(zip(mine, res))
     else:
@@ -265,11 +275,14 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
                 for k in mine:
                     if own:
                         joint_model.use_geometry(geometries[k][0], geometries[k][1])
-                    patches, _audio_loc, _audio, _d0, _d1, spot_times = joint_model.forward(mixes[k])
+                    patches, _audio_loc, audio, _d0, _d1, spot_times = joint_model.forward(mixes[k])
                     local.append((k, {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
                                       "powers": np.array([p[2] for p in patches]),
                                       "names": [p[3] for p in patches],
                                       "spot_times": spot_times, "times": list(joint_model.times)}))
+                    if separate:
+                        local[-1][1]["audio"] = np.empty((0, np.shape(mixes[k])[-1]), dtype=np.float32) if audio is None \
+                            else np.asarray(audio, dtype=np.float32)
         finally:
             if own:                                           # the array of setup() is the model's again
                 joint_model.Mic_processor, joint_model.previous_config = before

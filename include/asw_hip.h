@@ -204,6 +204,17 @@ int asw_sep_set_precision(asw_sep* m, int precision);   /* 0..3, as asw_spot_set
 int asw_sep_infer(asw_sep* m, const float* mix, int M, int T, const int32_t* offsets, int S, float* out,
                   void* stream);
 
+/* asw_sep_infer for K mixtures of one shape in ONE call, each with its own number of talkers: sequence n of item k is
+ * exactly what asw_sep_infer(mix[k], the offsets of item k) computes for it.  The talkers of an item are normalised with
+ * that item's joint statistics and attend only to each other in the inter-speaker layers; the N = sum counts sequences
+ * are packed item after item with no padding, so the rest of the network runs once with batch N.
+ *   mix [K][M][T] float32 device; offsets [N][M-1] int32 device, item after item, already rounded;
+ *   counts host int32 [K], each 0..64 (an item with none contributes no rows); out [N][T] float32 device.  N <= 64.
+ * K = 0 or N = 0 succeeds and launches nothing.  Refused on the host, before any launch: a null pointer, M other than
+ * the model's, T < 2, K < 0, a count outside 0..64, N > 64. */
+int asw_sep_infer_batch(asw_sep* m, const float* mix, int K, int M, int T, const int32_t* offsets,
+                        const int32_t* counts, float* out, void* stream);
+
 /* Network.forward (:418-490) on already normalised input, every item with the same number of
  * speakers: mix_norm [B][S*M][t] -> out [B][max(S, max_speakers)][t] (rows beyond S are zeros,
  * :486-488).  B*S <= 64. */
@@ -229,6 +240,14 @@ int asw_sep_get_tap(asw_sep* m, const char* name, float* dst, size_t capacity, s
 int asw_joint_shift_stats(const float* mix, int M, int T, const int32_t* offsets, int S, double* scratch,
                           float* mean, float* std, void* stream);
 int asw_joint_shift_stats_scratch_doubles(void);
+/* The same statistics for the G items of a ragged call (asw_sep_infer_batch), each over its own S_g*M channels:
+ * mix [K][M][T]; offsets [N][M-1], mean / std [N] over all sequences; bounds host int32 [G+1], non-decreasing from 0
+ * with bounds[G] = N: item g is the sequences bounds[g] .. bounds[g+1]-1 (1..64 of them, S_g*M <= 2048) and reads
+ * mixture item_of_group[g] (host int32 [G], values in [0, K): not range-checked).  G <= 64; the two tables travel as
+ * kernel arguments.  Same partition of the samples and same order of the sums as asw_joint_shift_stats: a one-item
+ * call writes the same bytes.  scratch: G * asw_joint_shift_stats_scratch_doubles() doubles (device). */
+int asw_joint_shift_stats_groups(const float* mix, int M, int T, const int32_t* offsets, const int32_t* bounds, int G,
+                                 const int32_t* item_of_group, double* scratch, float* mean, float* std, void* stream);
 
 /* Row kernel of the Conformer layer: s = x + alpha*y (y may be NULL); sum_out = s (may be NULL);
  * ln_out = act(LayerNorm(s)*gamma + beta) (may be NULL; act 0 none, 2 Swish).  rows x N floats,
@@ -256,6 +275,12 @@ int asw_relpos_attention(const float* qkv, const float* P, const float* bias_u, 
  * S speakers (nn.TransformerEncoderLayer on x.reshape(N*T, S, F), :311-316).
  * qkv [NB][S][L][3d] (in_proj bias included) -> ctx [NB][S][L][d].  S <= 64, head_dim <= 64. */
 int asw_inter_attention(const float* qkv, int NB, int S, int L, int d, int nhead, float* ctx, void* stream);
+/* The same core over G groups of DIFFERENT sizes: qkv [N][L][3d] -> ctx [N][L][d]; bounds host int32 [G+1],
+ * non-decreasing from 0 with bounds[G] = N; group g is the sequences bounds[g] .. bounds[g+1]-1 (1..64 of them) and its
+ * members attend only to each other.  G <= 64 (the table travels as a kernel argument); G = 0 launches nothing.  The
+ * arithmetic of a unit is that of asw_inter_attention: groups of one size give the same bytes. */
+int asw_inter_attention_groups(const float* qkv, const int32_t* bounds, int G, int L, int d, int nhead, float* ctx,
+                               void* stream);
 
 /* ------------------------------------------------------------------------
  * Individual kernels (unit-testable; the model above is built from these).
