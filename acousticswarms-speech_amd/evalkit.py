@@ -168,24 +168,152 @@ def bss_eval_sdr(reference_sources, estimated_sources, flen: int = 512):
     return out
 
 
-def compute_metrics(input_signal, est_signal, gt):
+# ---- BSS-eval SDR on the device (csrc/bss_kernels.hip: asw_bss_eval_sdr) -------------------------
+METRICS = ("host", "device")
+BSS_WORKSPACE_BUDGET = 1 << 30          # bytes of device workspace one call may ask for (G at 5 talkers is 52 MB)
+BSS_MAX_TALKERS, BSS_MAX_FLEN, BSS_MAX_ORDER = 16, 1024, 8192          # the library's limits (include/asw_hip.h)
+_BSS_TILE, _BSS_CHUNK, _BSS_SPLIT = 64, 1024, 8
+
+
+def check_metrics(metrics):
+    if metrics not in METRICS:
+        raise ValueError(f"metrics must be one of {METRICS}, got {metrics!r}")
+
+
+def bss_workspace_bytes(counts, R: int, T: int, flen: int) -> int:
+    """What ``asw_bss_eval_sdr_workspace_bytes`` answers for one call, restated so that the packing rule below is a pure
+    function (tests/test_bss_eval_host.py holds the two equal): the lists, the correlations and their partial sums,
+    the dense systems, the solutions and the energy partials."""
+    counts = [int(c) for c in counts]
+    N = sum(counts)
+    P = sum((R + 1) * S * S for S in counts)
+    nsys = sum(S + 1 if S > 1 else S for S in counts)
+    nsolve = sum(R * S * (2 if S > 1 else 1) for S in counts)
+    E = R * N
+    nchunk = -(-T // _BSS_CHUNK)
+    cps = -(-nchunk // min(nchunk, _BSS_SPLIT))
+    nsplit = -(-nchunk // cps)
+    nchunk_p = -(-(T + flen - 1) // _BSS_CHUNK)
+    gram = sum(S * flen * flen + ((S * flen) ** 2 if S > 1 else 0) for S in counts)
+    x = sum(R * S * (flen + (S * flen if S > 1 else 0)) for S in counts)
+    tables = 32 * len(counts) + 24 * nsys + 16 * P + 24 * nsolve + 8 * E
+    return tables + 8 * (P * nsplit * flen + P * flen + gram + x + 2 * E * nchunk_p)
+
+
+def pack_bss_items(counts, lengths, R: int, flen: int = 512, budget: int = BSS_WORKSPACE_BUDGET):
+    """The device calls of a batch: items stay whole and in order, a call holds items of one length only and takes as
+    many as its workspace (``bss_workspace_bytes``) fits into ``budget``.  -> list of (first, last) item ranges,
+    ``last`` exclusive, covering every item once.  ``ValueError`` for an item the library refuses (talkers outside
+    0..16, talkers * flen > 8192, T < flen), ``RuntimeError`` for one whose workspace alone exceeds the budget."""
+    if R < 1 or not 1 <= flen <= BSS_MAX_FLEN:
+        raise ValueError(f"R = {R} < 1 or flen = {flen} outside 1..{BSS_MAX_FLEN}")
+    if len(counts) != len(lengths):
+        raise ValueError(f"{len(lengths)} lengths for {len(counts)} items")
+    calls, first = [], 0
+    for k, (S, T) in enumerate(zip(counts, lengths)):
+        S, T = int(S), int(T)
+        if not 0 <= S <= BSS_MAX_TALKERS or S * flen > BSS_MAX_ORDER:
+            raise ValueError(f"item {k}: {S} talkers of {flen} taps (at most {BSS_MAX_TALKERS} and {BSS_MAX_ORDER} in all)")
+        if T < flen:
+            raise ValueError(f"item {k}: {T} samples are fewer than flen = {flen}")
+        if bss_workspace_bytes([S], R, T, flen) > budget:
+            raise RuntimeError(f"item {k} alone needs {bss_workspace_bytes([S], R, T, flen)} bytes of workspace, budget {budget}")
+        if k > first and (T != int(lengths[first]) or bss_workspace_bytes(counts[first:k + 1], R, T, flen) > budget):
+            calls.append((first, k))
+            first = k
+    if first < len(counts):
+        calls.append((first, len(counts)))
+    return calls
+
+
+def _bss_device_op(device):
+    """(``torch.ops.asw.bss_eval_sdr``, device) or ``RuntimeError``: there is no quiet fall-back to the host metric."""
+    import torch
+    from . import native
+    op = native.torch_ops().bss_eval_sdr                   # RuntimeError when the library has not been built
+    if not torch.cuda.is_available():
+        raise RuntimeError('metrics="device" needs a GPU: none is visible to torch')
+    return op, torch.device("cuda:0" if device is None else device)
+
+
+def bss_eval_sdr_batch(refs, est_sets, flen: int = 512, device=None, op=None, budget: int = BSS_WORKSPACE_BUDGET):
+    """``bss_eval_sdr`` of many samples on the device.  ``refs[k]`` is [S_k, T_k], ``est_sets[k]`` is [R, S_k, T_k] (R
+    estimate sets of the same references, one R for the batch); talker counts and lengths may differ from sample to
+    sample.  The samples are rounded to float32 (exact for wav and network output) and packed into as few
+    ``torch.ops.asw.bss_eval_sdr`` calls as ``pack_bss_items`` allows.  -> (list of [R, S_k] float64 arrays, sorted list
+    of the items that were recomputed on the host).  An item is recomputed with ``bss_eval_sdr`` when the device
+    reports status 1 for it -- silent or duplicated references, where the Gram matrix has no Cholesky factor and the
+    host statement itself leaves ``solve`` for ``lstsq`` -- so its values are exactly the host result.
+    ``op`` replaces the device op (a stand-in on CPU tensors in the host tests); without it a missing library or GPU
+    is a ``RuntimeError``."""
+    import torch
+    if len(refs) != len(est_sets):
+        raise ValueError(f"{len(est_sets)} estimate sets for {len(refs)} samples")
+    if not refs:
+        return [], []
+    refs = [np.ascontiguousarray(np.atleast_2d(r), dtype=np.float32) for r in refs]
+    ests = [np.ascontiguousarray(e, dtype=np.float32) for e in est_sets]
+    R = ests[0].shape[0] if ests[0].ndim == 3 else -1
+    for k, (r, e) in enumerate(zip(refs, ests)):
+        if e.ndim != 3 or e.shape[0] != R or e.shape[1:] != r.shape:
+            raise ValueError(f"sample {k}: estimates {e.shape} do not go with references {r.shape} as [R = {R}, S, T]")
+    if op is None:
+        op, dev = _bss_device_op(device)
+    else:
+        dev = torch.device("cpu" if device is None else device)
+    counts, lengths = [r.shape[0] for r in refs], [r.shape[1] for r in refs]
+    calls = pack_bss_items(counts, lengths, R, flen, budget)
+    out, recomputed = [None] * len(refs), []
+    for first, last in calls:
+        ref = torch.from_numpy(np.concatenate(refs[first:last], axis=0)).to(dev)
+        est = torch.from_numpy(np.concatenate(ests[first:last], axis=1)).to(dev)
+        sdr, status = op(ref, est, counts[first:last], int(flen))
+        sdr, status = sdr.cpu().numpy(), status.cpu().numpy()
+        n0 = 0
+        for k in range(first, last):
+            S = counts[k]
+            if status[k - first] != 0:
+                recomputed.append(k)
+                out[k] = np.stack([bss_eval_sdr(refs[k], ests[k][r], flen) for r in range(R)])
+            else:
+                out[k] = np.array(sdr[:, n0:n0 + S], dtype=np.float64)
+            n0 += S
+    return out, recomputed
+
+
+def bss_eval_sdr_device(reference_sources, estimated_sets, flen: int = 512, device=None, op=None):
+    """[R, S] float64: ``bss_eval_sdr(reference_sources, estimated_sets[r], flen)`` for every set r, on the device
+    (one ``bss_eval_sdr_batch`` call of one sample)."""
+    out, _ = bss_eval_sdr_batch([reference_sources], [estimated_sets], flen, device, op)
+    return out[0]
+
+
+def compute_metrics(input_signal, est_signal, gt, metrics="host"):
     """(input_sdr, output_sdr, input_sisdr, output_sisdr) per matched talker, as
     sep/eval/get_items.py:46-70 with permute=False: BSS-eval SDR and SI-SDR of the unprocessed
-    reference-microphone signal and of the separated output against the ground truth."""
+    reference-microphone signal and of the separated output against the ground truth.
+    ``metrics="device"`` takes the two BSS-eval SDRs from one ``bss_eval_sdr_device`` call (R = 2: the
+    unprocessed set and the separated set); the signals are read as float32 there."""
+    check_metrics(metrics)
     gt = np.asarray(gt, dtype=np.float64)
     inp = np.asarray(input_signal, dtype=np.float64)
     est = np.asarray(est_signal, dtype=np.float64)
-    input_sdr, output_sdr = bss_eval_sdr(gt, inp), bss_eval_sdr(gt, est)
+    if metrics == "device":
+        input_sdr, output_sdr = bss_eval_sdr_device(gt, np.stack([inp, est]))
+    else:
+        input_sdr, output_sdr = bss_eval_sdr(gt, inp), bss_eval_sdr(gt, est)
     input_sisdr = [si_sdr(inp[i], gt[i]) for i in range(gt.shape[0])]
     output_sisdr = [si_sdr(est[i], gt[i]) for i in range(gt.shape[0])]
     return input_sdr, output_sdr, input_sisdr, output_sisdr
 
 
 # ---- one sample --------------------------------------------------------------------------------
-def evaluate_sample(model, metadata, mix, gt):
+def evaluate_sample(model, metadata, mix, gt, metrics="host"):
     """Run ``model`` (a ``JointModel``) on one sample and build the reference's result record
-    (sep/eval/eval_model.py:129-236).  Returns (record, tp, fp, fn)."""
+    (sep/eval/eval_model.py:129-236).  Returns (record, tp, fp, fn).  ``metrics``: "host" or "device", where the
+    record's two BSS-eval SDR fields come from (``compute_metrics``)."""
     import torch
+    check_metrics(metrics)
     _mics, mic_positions, _voices, gt_pos, offsets_gt, roi = preprocess_metadata(metadata)
     model.setup(mic_positions=mic_positions, speaker_range=roi)
     patches, audio_loc, audio, _, _, _ = model(torch.from_numpy(np.ascontiguousarray(mix, dtype=np.float32)))
@@ -206,7 +334,7 @@ def evaluate_sample(model, metadata, mix, gt):
         # decoder when attached), localisation-stage output, ground truth, unprocessed mic 0
         pa = np.array(perm)
         ref_sig = np.repeat(mix[0:1].astype(np.float64), len(perm), axis=0)
-        in_sdr, out_sdr, in_sisdr_l, out_sisdr_l = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]])
+        in_sdr, out_sdr, in_sisdr_l, out_sisdr_l = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics)
     for i, (out_id, s) in enumerate(perm):
         unmatched.remove(out_id)
         in_sisdr = in_sisdr_l[i]
@@ -225,13 +353,14 @@ def evaluate_sample(model, metadata, mix, gt):
     return rec, tp, fp, fn
 
 
-def evaluate_dataset(model, dataset_dir, results_folder=None):
+def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host"):
     """Every sample directory of ``dataset_dir``; writes ``result_<sample>.json`` like the
-    reference and returns overall (tp, fp, fn, precision, recall)."""
+    reference and returns overall (tp, fp, fn, precision, recall).  ``metrics`` as in ``evaluate_sample``."""
+    check_metrics(metrics)
     tot = np.zeros(3, dtype=np.int64)
     for name in sorted(d for d in os.listdir(dataset_dir) if os.path.isdir(os.path.join(dataset_dir, d))):
         metadata, mix, gt = get_items(os.path.join(dataset_dir, name))
-        rec, tp, fp, fn = evaluate_sample(model, metadata, mix, gt)
+        rec, tp, fp, fn = evaluate_sample(model, metadata, mix, gt, metrics)
         tot += (tp, fp, fn)
         if results_folder is not None:
             os.makedirs(results_folder, exist_ok=True)

@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["asw_common.cpp", "convgemm.hip", "resconv.hip", "pipegemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip",
            "misc_kernels.hip", "attention_mfma.hip", "srp_kernels.hip",
            "pruner_kernels.hip", "geometry_kernels.hip", "cluster_kernels.hip",
-           "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip"]
+           "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip", "bss_kernels.hip"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
 # (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out)
 EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"], "cluster_kernels.hip": ["-ffp-contract=off"]}
@@ -253,6 +253,9 @@ SIGNATURES = {
     "asw_coarse_select_workspace_bytes": (c_size_t, [c_int, c_int]),
     "asw_coarse_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_double, c_int, c_void_p, c_size_t,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "asw_bss_eval_sdr_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "asw_bss_eval_sdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
     "asw_add_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "asw_search_area": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double,
                                 POINTER(c_int), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -704,6 +704,45 @@ int asw_coarse_select(const double* energies, const double* dis1, const int32_t*
                       int relative, double rel, int cap, void* workspace, size_t workspace_bytes, int32_t* kept,
                       int32_t* counts, double* thr, void* stream);
 
+/* BSS-eval SDR of a ragged batch of K samples on the device, as evalkit.bss_eval_sdr states it (the BSS-eval v3
+ * "mtifilt" decomposition of evalkit._project; a restatement of the published algorithm, so parity with mir_eval stays
+ * unpinned: what is pinned is this entry point against the repository's own float64 statement).  ref float32 [N][T]
+ * (device), N = sum counts, the references of item after item with no padding; est float32 [R][N][T] (device), R
+ * estimate sets, est[r][n] goes with ref[n]; counts_host int32 [K] is a HOST array read before the call returns.  For
+ * item k with S = counts[k] references at rows n0 .. n0 + S, sdr[r][n0 + j] is what
+ * evalkit.bss_eval_sdr(ref_k, est_k[r], flen)[j] returns.  The float32 inputs are widened exactly; everything after
+ * is float64.  sdr float64 [R][N], status int32 [K] (device).
+ *   Correlations, directly and in a fixed order: c(i, b, p) = sum_t ref_i[t - p] b[t], p = 0 .. flen - 1, for every
+ *   reference i and every row b (reference or estimate) of the item; T is cut into chunks of 1024, a workgroup sums a
+ *   run of whole chunks in order (at most 8 runs), a second launch folds the runs left to right.
+ *   Systems: per item the (S flen)^2 block-Toeplitz Gram matrix G[(i,a)][(j,b)] = sum_u ref_i[u-a] ref_j[u-b] (only when
+ *   S > 1) and the S single-reference flen^2 Toeplitz matrices, dense, lower triangle in use; all systems of the call
+ *   form one ragged list that one blocked Cholesky walks in 64-wide steps (diagonal tile in LDS, panel solve, trailing
+ *   update: three launches per step over the whole list; a system that has run out of tiles exits at the top).
+ *   A pivot that is not > 2^-40 times the row's original diagonal entry (NaN included) sets status[k] = 1 and is
+ *   replaced by 1.0: nothing loops on data.  status[k] = 0 otherwise, also for an item with no reference.  The sdr
+ *   rows of an item with status 1 are written but meaningless: the caller recomputes them (evalkit does, with the
+ *   host statement, which itself leaves its LU route for lstsq on such input -- silent or duplicated references).
+ *   Right-hand sides: R S for the full system, R for each single one; forward and backward substitution, a workgroup
+ *   per right-hand side.  An item with S = 1 has no full system: its full projection IS the single one, so e_interf is
+ *   exactly 0, as in the statement.
+ *   Projections as direct flen-tap FIRs over T + flen - 1 samples, then s_true, e_spat, e_interf, e_artif and the two
+ *   sums of squares exactly as the statement forms them, per chunk of 1024 samples with a fixed tree, the chunks folded
+ *   left to right; sdr = 10 log10(num / den), +inf when den == 0.
+ * workspace: asw_bss_eval_sdr_workspace_bytes(counts_host, K, R, T, flen) bytes, 8-byte aligned (the lists, the
+ * correlations and their partial sums, the systems, the solutions, the energy partials; the systems dominate: 52 MB
+ * for S = 5, flen = 512; 0 with the error message set for arguments this call would refuse).  One small
+ * host-to-device copy of the lists and one memset of status on the stream.  No atomics, no cross-lane operations, no
+ * device-side assert, plain vector stores; workgroups hand nothing to each other inside a launch: two calls give
+ * identical bytes, every output slot is written, every workspace word that is read is written first, and the result
+ * does not depend on what the outputs or the workspace held.  Every refusal -- a null pointer, K < 0, R < 1, flen
+ * outside 1..1024, T < flen (or T > 2^25), a count outside 0..16, an item with S flen > 8192, a short or misaligned
+ * workspace -- happens on the host before the copy and the first launch; K = 0 succeeds and touches nothing, N = 0
+ * only clears status. */
+size_t asw_bss_eval_sdr_workspace_bytes(const int32_t* counts_host, int K, int R, int T, int flen);
+int asw_bss_eval_sdr(const float* ref, const float* est, const int32_t* counts_host, int K, int R, int T, int flen,
+                     double* sdr, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* HOST function (no GPU): breadth-first subdivision of one coarse hypercube into the fine
  * candidate hypercubes -- search_area / binary_area_divide_width
  * (sep/helpers/local_utils_3d.py:212-335) with Patch.check_out / hyperbola_sample
