@@ -12,26 +12,15 @@
 #include <cstdlib>
 
 #include "asw_common.h"
+#include "mfma_util.h"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+using asw_mfma::floatx16;
+using asw_mfma::mma_row;
 
 constexpr int AD = 128;           // head_dim
 constexpr int LDQ = AD + 4;       // Q / K row stride (floats)
-
-__device__ __forceinline__ floatx16 mma_row(const float* a_row, const float* b_row, int ksteps, floatx16 acc) {
-  // a_row / b_row already include this lane's (row, 4*(lane>>5)) offset; 8 k per iteration
-  for (int kk = 0; kk < ksteps; ++kk) {
-    const float4 a = *reinterpret_cast<const float4*>(a_row + kk * 8);
-    const float4 b = *reinterpret_cast<const float4*>(b_row + kk * 8);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-  }
-  return acc;
-}
 
 // ---- short sequences (L <= 352: T = 48 000 gives L = 188): whole score row in LDS ----------
 // 64 queries per workgroup; the 64 x 64 score tile of a key block is four MFMA tiles (one per
@@ -39,13 +28,13 @@ __device__ __forceinline__ floatx16 mma_row(const float* a_row, const float* b_r
 // ds_read_b32 per four MFMAs (no transposition through scalar LDS stores).
 constexpr int BQ = 64;            // queries per workgroup
 constexpr int BK = 64;            // keys per staged tile
-typedef int intx4a __attribute__((ext_vector_type(4)));
-typedef float floatx4a __attribute__((ext_vector_type(4)));
 
+// asw_mfma::act_load4 without its `elem >= 0` test (no offset here is negative).  Kept apart from it: with the test the
+// three kernels below take more registers (attention_mfma16_kernel 208 -> 220 VGPRs, 4 to 8 SGPRs in the other two).
 __device__ __forceinline__ float4 row_load4(__amdgpu_buffer_rsrc_t r, long elem, bool ok) {
   // rows past the sequence end read as zeros through the descriptor's range check (no branch)
-  const intx4a v = __builtin_amdgcn_raw_buffer_load_b128(r, ok ? (int)(elem * 4) : (int)0x80000000, 0, 0);
-  const floatx4a f = __builtin_bit_cast(floatx4a, v);
+  const asw_mfma::intx4 v = __builtin_amdgcn_raw_buffer_load_b128(r, ok ? (int)(elem * 4) : (int)0x80000000, 0, 0);
+  const asw_mfma::floatx4v f = __builtin_bit_cast(asw_mfma::floatx4v, v);
   return make_float4(f[0], f[1], f[2], f[3]);
 }
 
@@ -82,7 +71,7 @@ __global__ __launch_bounds__(256) void attention_mfma64_kernel(const float* __re
     floatx16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    acc = mma_row(Qs + (qi * 32 + lr) * LDQ + lh * 4, KV + (kj * 32 + lr) * LDQ + lh * 4, AD / 8, acc);
+    acc = mma_row<AD / 8>(Qs + (qi * 32 + lr) * LDQ + lh * 4, KV + (kj * 32 + lr) * LDQ + lh * 4, acc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = qi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -409,7 +398,7 @@ __global__ __launch_bounds__(256) void attention_mfma_flash_kernel(const float* 
     floatx16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    acc = mma_row(Qs + (qi * 32 + lr) * LDQ + lh * 4, KV + (kj * 32 + lr) * LDQ + lh * 4, AD / 8, acc);
+    acc = mma_row<AD / 8>(Qs + (qi * 32 + lr) * LDQ + lh * 4, KV + (kj * 32 + lr) * LDQ + lh * 4, acc);
     const bool valid = k0 + kj * 32 + lr < L;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {

@@ -1,7 +1,9 @@
-// mfma_util.h -- device helpers shared by the MFMA kernels (convgemm.hip, pipegemm.hip, resconv.hip, resstack.hip, downconv.hip): vector types,
-// the buffer-descriptor activation load and the fp32 -> fp16 hi / lo operand split of the f16x3 mode.
+// mfma_util.h -- device helpers shared by the MFMA kernels (convgemm.hip, pipegemm.hip, resconv.hip, resstack.hip, downconv.hip,
+// attention_mfma.hip, sep_kernels.hip): vector types, the buffer-descriptor activation load, the f32 row product of the
+// attention kernels and the fp32 -> fp16 hi / lo operand split of the f16x3 mode.
 #pragma once
 #include "asw_common.h"
+#include "wave_util.h"
 
 namespace asw_mfma {
 
@@ -9,10 +11,22 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float wave_sum(float v) {
+using asw::wave_sum;
+
+// acc += A B^T of two row-major fp32 operands on v_mfma_f32_32x32x2_f32 (an fmaf chain: exact fp32): a_row / b_row
+// already include this lane's (row, 4 * (lane >> 5)) offset; 8 k per step, KSTEPS = K / 8
+template <int KSTEPS>
+__device__ __forceinline__ floatx16 mma_row(const float* a_row, const float* b_row, floatx16 acc) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  for (int kk = 0; kk < KSTEPS; ++kk) {
+    const float4 a = *reinterpret_cast<const float4*>(a_row + kk * 8);
+    const float4 b = *reinterpret_cast<const float4*>(b_row + kk * 8);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+  }
+  return acc;
 }
 
 // Activation loads go through a raw buffer descriptor: an offset outside [0, bytes) -- the

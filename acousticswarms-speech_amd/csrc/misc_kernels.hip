@@ -1,23 +1,11 @@
 // misc_kernels.hip -- the memory-bound / small kernels around the MFMA GEMMs.
 #include "asw_common.h"
+#include "wave_util.h"
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+using asw::block_sum;
+using asw::wave_sum;
 
 // ---------------------------------------------------------------------------
 // GroupNorm(2) + GLU.  EncoderBlock / DecoderBlock tail
@@ -38,7 +26,7 @@ __device__ __forceinline__ void gn_group_stats(const float* __restrict__ stats, 
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    s[k] = wave_sum_d(s[k]);
+    s[k] = wave_sum(s[k]);
     if (lane == 0) red[wid][k] = s[k];
   }
   __syncthreads();
@@ -276,12 +264,7 @@ __global__ __launch_bounds__(1024) void energy_kernel(const float* __restrict__ 
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc += (double)v[e];
   }
-  acc = wave_sum_d(acc);
-  if (lane == 0) red[wid] = acc;
-  __syncthreads();
-  double tot = 0.0;
-  for (int i = 0; i < 16; ++i) tot += red[i];
-  const float mu = (float)(tot / (double)T);     // np.mean of a float32 row is float32
+  const float mu = (float)(block_sum(acc, red) / (double)T);     // np.mean of a float32 row is float32
   // squared, mean-removed samples of the lane (0 past the end)
   auto squares = [&](long i0, float (&q)[VEC]) {
     float v[VEC];
@@ -296,7 +279,7 @@ __global__ __launch_bounds__(1024) void energy_kernel(const float* __restrict__ 
     double s = 0.0;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) s += (double)q[e];
-    s = wave_sum_d(s);
+    s = wave_sum(s);
     if (lane == 0) P[j + 1] = s;
   }
   __syncthreads();
@@ -330,7 +313,7 @@ __global__ __launch_bounds__(1024) void energy_kernel(const float* __restrict__ 
         double part = 0.0;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) part += ((long)js * BLK + lane * VEC + e < s) ? (double)q[e] : 0.0;
-        carryB = P[js] + wave_sum_d(part);
+        carryB = P[js] + wave_sum(part);
       }
     }
     for (int j = jb; j < je; ++j) {
@@ -447,7 +430,7 @@ __global__ __launch_bounds__(256) void pair_sisdr_small_kernel(const float* __re
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    a[k] = wave_sum_d(a[k]);
+    a[k] = wave_sum(a[k]);
     if (lane == 0) red[wid][k] = a[k];
   }
   __syncthreads();
@@ -673,12 +656,7 @@ __global__ __launch_bounds__(1024) void center_rows_kernel(float* __restrict__ y
   float* yb = y + (long)blockIdx.x * T;
   double acc = 0.0;
   for (int i = threadIdx.x; i < T; i += 1024) acc += (double)yb[i];
-  acc = wave_sum_d(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  double tot = 0.0;
-  for (int i = 0; i < 16; ++i) tot += red[i];
-  const float mu = (float)(tot / (double)T);
+  const float mu = (float)(block_sum(acc, red) / (double)T);
   for (int i = threadIdx.x; i < T; i += 1024) yb[i] -= mu;
 }
 
@@ -688,6 +666,11 @@ __global__ __launch_bounds__(1024) void center_rows_kernel(float* __restrict__ y
 // shuffles -- the same arithmetic as the GEMM epilogue's fused LayerNorm.  Used for rows too
 // wide (d = 1024) for a LayerNorm-fused GEMM tile of useful height: the GEMM then runs on the
 // wide 256x256 tile and this pass costs one read + one write of the activations.
+// In place (x == out, as `linear` calls it) is legal: every lane holds its part of the row in registers before it writes.
+// Not a view of add_ln2_kernel (sep_kernels.hip) although the arithmetic reads the same: with N fixed at compile time
+// and no optional operand all 2 * NV loads of a row are in flight at once, where the general kernel waits for each pair
+// behind its bounds and null tests -- 0.111 against 0.102 ms per launch at 48 k rows of 1024, measured -- and at
+// N = 256 the compiler fuses dx * dx + dy * dy here and not there, so the two differ in the last bit.
 template <int NV>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ resid,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -705,18 +688,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const float* __restr
     v[i] = make_float4(a.x + r.x, a.y + r.y, a.z + r.z, a.w + r.w);
     sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  const float mu = sum / (float)N;
+  const float mu = wave_sum(sum) / (float)N;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const float dx = v[i].x - mu, dy = v[i].y - mu, dz = v[i].z - mu, dw = v[i].w - mu;
     sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-  const float rstd = 1.0f / sqrtf(sq / (float)N + eps);
+  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)N + eps);
   const float4* g4 = reinterpret_cast<const float4*>(gamma);
   const float4* b4 = reinterpret_cast<const float4*>(beta);
   float4* orow = reinterpret_cast<float4*>(out + (long)row * N);
@@ -835,7 +814,7 @@ extern "C" int asw_energies(const float* y, int B, int T, int window, double* sc
   ASW_CHECK_ARG(y && out, "energies: null pointer");
   ASW_CHECK_ARG(T > 0 && window > 0, "energies: bad shape");
   if (B == 0) return ASW_OK;
-  (void)scratch;                                       // kept in the ABI; the prefix sums no longer go through memory
+  (void)scratch;                                       // ignored, may be NULL: the prefix sums no longer go through memory
   hipStream_t s = asw::as_stream(stream);
   asw::ProfScope prof(s, "energy", 0.0, (double)B * T * 4);
   // four samples per lane when every row is 16-byte aligned, one otherwise

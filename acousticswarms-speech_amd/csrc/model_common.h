@@ -731,6 +731,27 @@ struct Trunk {
   }
 };
 
+// ---- the post-norm transformer layer of both bottlenecks (nn.TransformerEncoderLayer, norm_first = False): the spot
+// network's layers along time and the separation network's layers across speakers.  The uploads stay with the networks
+// and differ on purpose: the spot layer packs MFMA fragments (WBuf::upload_gemm), the separation layer does not (UP) --
+// `linear` picks its kernel by what the weight carries, so uploading alike would change the kernels a network runs.
+struct PostNormLayer { WBuf w_in, w_out, w1, w2; DevBuf b_in, b_out, b1, b2, n1g, n1b, n2g, n2b; };
+struct PostNormBufs { float *qkv, *ctx, *x1, *ff; };      // [rows][3d], [rows][d], [rows][d], [rows][ffw] of the caller's plan
+
+// x -> out, both [rows][d]: in-proj, attention(qkv, ctx), out-proj + residual + LayerNorm, linear1 + ReLU,
+// linear2 + residual + LayerNorm.  x and x1 are normalised tensors, ctx and the hidden layer are not (Trunk::site).
+template <class Attention>
+int run_post_norm(const Trunk& m, const PostNormLayer& t, const PostNormBufs& b, const float* x, float* out, int rows, int d,
+                  int ffw, Attention&& attention, hipStream_t s) {
+  const int normed = m.site(Trunk::Src::Normed), rawp = m.site(Trunk::Src::Raw);
+  int rc;
+  if ((rc = linear(x, t.w_in, normed, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, b.qkv, s))) return rc;
+  if ((rc = attention(b.qkv, b.ctx))) return rc;
+  if ((rc = linear(b.ctx, t.w_out, rawp, t.b_out.p, rows, d, d, 0, x, t.n1g.p, t.n1b.p, b.x1, s))) return rc;
+  if ((rc = linear(b.x1, t.w1, normed, t.b1.p, rows, ffw, d, 1, nullptr, nullptr, nullptr, b.ff, s))) return rc;
+  return linear(b.ff, t.w2, rawp, t.b2.p, rows, d, ffw, 0, b.x1, t.n2g.p, t.n2b.p, out, s);
+}
+
 // ---- the handle calls both networks share; `who` / `fin` name the entry point in the messages
 inline int check_ready(const Trunk* m, const char* fin) {
   if (!m) return asw::set_error(ASW_ERR_ARG, "null model handle");

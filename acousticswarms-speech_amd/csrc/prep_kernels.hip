@@ -15,22 +15,8 @@ namespace {
 
 constexpr int MAX_MICS = 32;
 
-__device__ __forceinline__ float quant16(float x) {
-  // (x * 2**15).round() / 2**15, round-half-even like torch.round (network.py:34)
-  return rintf(x * 32768.0f) * (1.0f / 32768.0f);
-}
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wid] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < nw; ++i) s += red[i];
-  return s;
-}
+using asw::block_sum;
+using asw::quant16;
 
 // One workgroup per candidate: two passes over T (sum, then centred sum of squares),
 // double accumulation; the mixture stays in L2 across candidates.

@@ -13,25 +13,16 @@
 #include <cstdlib>
 
 #include "asw_common.h"
+#include "mfma_util.h"
 
 namespace {
 
-__device__ __forceinline__ float quant16(float x) { return rintf(x * 32768.0f) * (1.0f / 32768.0f); }
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wsum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using asw::quant16;
+using asw::wave_max;
+using asw::wave_sum;
+using asw_mfma::floatx16;
+using asw_mfma::mma_row;
+
 __device__ __forceinline__ float swishf(float v) { return v / (1.0f + expf(-v)); }
 
 // ---------------------------------------------------------------------------------------
@@ -73,7 +64,7 @@ __device__ __forceinline__ void joint_stats_partial(const float* __restrict__ mi
     a0 += (double)r;
     a1 += (double)r * (double)r;
   }
-  a0 = wsum_d(a0); a1 = wsum_d(a1);
+  a0 = wave_sum(a0); a1 = wave_sum(a1);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   if (lane == 0) { red[wid][0] = a0; red[wid][1] = a1; }
   __syncthreads();
@@ -87,7 +78,7 @@ __device__ __forceinline__ void joint_stats_final(const double* __restrict__ par
                                                   float* __restrict__ mean_out, float* __restrict__ std_out) {
   double a0 = 0.0, a1 = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += 64) { a0 += part[i * 2]; a1 += part[i * 2 + 1]; }
-  a0 = wsum_d(a0); a1 = wsum_d(a1);
+  a0 = wave_sum(a0); a1 = wave_sum(a1);
   const double mean = a0 / (double)T;
   double var = (a1 - a0 * a0 / (double)T) / (double)(T - 1);      // Bessel, torch.std default
   if (var < 0) var = 0;
@@ -95,19 +86,9 @@ __device__ __forceinline__ void joint_stats_final(const double* __restrict__ par
   for (int s = threadIdx.x; s < S; s += 64) { mean_out[s] = mu; std_out[s] = sg; }
 }
 
-__global__ __launch_bounds__(256) void joint_stats_partial_kernel(const float* __restrict__ mix, int M, int T,
-                                                                  const int32_t* __restrict__ offsets, int S,
-                                                                  double* __restrict__ part) {
-  joint_stats_partial(mix, M, T, offsets, S, part);
-}
-
-__global__ __launch_bounds__(64) void joint_stats_final_kernel(const double* __restrict__ part, int nblocks, int T, int S,
-                                                               float* __restrict__ mean_out, float* __restrict__ std_out) {
-  joint_stats_final(part, nblocks, T, S, mean_out, std_out);
-}
-
-// The same two passes for the G items of a ragged call, item g = blockIdx.y: its own mixture, offsets, S_g, partials
+// The two passes for the G items of a call, item g = blockIdx.y: its own mixture, offsets, S_g, partials
 // (2 * JS_BLOCKS doubles each) and rows of mean / std.  mix [K][M][T], offsets / mean / std over all N sequences.
+// asw_joint_shift_stats is the call with one group.
 __global__ __launch_bounds__(256) void joint_stats_partial_groups_kernel(const float* __restrict__ mix, int M, int T,
                                                                          const int32_t* __restrict__ offsets, GroupTable tab,
                                                                          double* __restrict__ part) {
@@ -154,7 +135,7 @@ __global__ __launch_bounds__(256) void add_ln2_kernel(const float* __restrict__ 
     sum += (a.x + a.y) + (a.z + a.w);
   }
   if (!ln_out) return;
-  const float mu = wsum(sum) / (float)N;
+  const float mu = wave_sum(sum) / (float)N;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -163,7 +144,7 @@ __global__ __launch_bounds__(256) void add_ln2_kernel(const float* __restrict__ 
       sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
   }
-  const float rstd = 1.0f / sqrtf(wsum(sq) / (float)N + eps);
+  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)N + eps);
   const float4* g4 = reinterpret_cast<const float4*>(gamma);
   const float4* b4 = reinterpret_cast<const float4*>(beta);
   float4* orow = reinterpret_cast<float4*>(ln_out + (long)row * N);
@@ -234,7 +215,7 @@ __global__ __launch_bounds__(256) void dwconv_ln_swish_kernel(const float* __res
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) sum += (acc[i].x + acc[i].y) + (acc[i].z + acc[i].w);     // lanes past the row hold zeros
-  const float mu = wsum(sum) / (float)d;
+  const float mu = wave_sum(sum) / (float)d;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
@@ -242,7 +223,7 @@ __global__ __launch_bounds__(256) void dwconv_ln_swish_kernel(const float* __res
       const float dx = acc[i].x - mu, dy = acc[i].y - mu, dz = acc[i].z - mu, dw = acc[i].w - mu;
       sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
-  const float rstd = 1.0f / sqrtf(wsum(sq) / (float)d + eps);
+  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)d + eps);
   float4* orow = reinterpret_cast<float4*>(out + row * d);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -373,22 +354,7 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const float* __re
 //       and reads it back skewed: bd[i][j] = G[i][(j - i) + 31].
 //   O   = O * alpha + P V      wave (qi, dj) owns a 32 x 32 block of the 64 x 64 output tile.
 // ---------------------------------------------------------------------------------------
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 constexpr int RM_BQ = 64, RM_BK = 64, RM_HD = 64, RM_LD = RM_HD + 4;     // row stride 68 floats: conflict-free b128 reads
-
-__device__ __forceinline__ floatx16 rm_mma(const float* a_row, const float* b_row, floatx16 acc) {
-  // a_row / b_row include this lane's (row, 4*(lane>>5)) offset; 8 k per iteration, hd = 64
-#pragma unroll
-  for (int kk = 0; kk < RM_HD / 8; ++kk) {
-    const float4 a = *reinterpret_cast<const float4*>(a_row + kk * 8);
-    const float4 b = *reinterpret_cast<const float4*>(b_row + kk * 8);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-  }
-  return acc;
-}
 
 __global__ __launch_bounds__(256) void relpos_attention_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ P,
                                                                     const float* __restrict__ bu, const float* __restrict__ bv,
@@ -446,9 +412,9 @@ __global__ __launch_bounds__(256) void relpos_attention_mfma_kernel(const float*
     for (int r = 0; r < 16; ++r) { ac[r] = 0.f; g0[r] = 0.f; g1[r] = 0.f; }
     const float* qa = Qu + (qi * 32 + lr) * RM_LD + lh * 4;
     const float* qb = Qv + (qi * 32 + lr) * RM_LD + lh * 4;
-    ac = rm_mma(qa, KV + (kj * 32 + lr) * RM_LD + lh * 4, ac);
-    g0 = rm_mma(qb, Pw + (rt0 * 32 + lr) * RM_LD + lh * 4, g0);
-    g1 = rm_mma(qb, Pw + ((rt0 + 1) * 32 + lr) * RM_LD + lh * 4, g1);
+    ac = mma_row<RM_HD / 8>(qa, KV + (kj * 32 + lr) * RM_LD + lh * 4, ac);
+    g0 = mma_row<RM_HD / 8>(qb, Pw + (rt0 * 32 + lr) * RM_LD + lh * 4, g0);
+    g1 = mma_row<RM_HD / 8>(qb, Pw + ((rt0 + 1) * 32 + lr) * RM_LD + lh * 4, g1);
     __syncthreads();                         // every wave is done with the P window and the K tile
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -562,9 +528,9 @@ __device__ __forceinline__ void inter_attention_unit(const float* __restrict__ q
       for (int c = 0; c < hd; ++c) acc = fmaf(qr[c], kr[c], acc);
       sc = acc;
     }
-    const float mx = wmax(sc);
+    const float mx = wave_max(sc);
     const float e = lane < S ? expf(sc - mx) : 0.f;
-    const float p = e / wsum(e);
+    const float p = e / wave_sum(e);
     Ps[s1 * 64 + lane] = p;
   }
   __syncthreads();
@@ -577,27 +543,14 @@ __device__ __forceinline__ void inter_attention_unit(const float* __restrict__ q
   }
 }
 
-template <int IA_WAVES>
-__global__ __launch_bounds__(64 * IA_WAVES) void inter_attention_kernel(const float* __restrict__ qkv, int NB, int S, int L,
-                                                                        int d, int nhead, float* __restrict__ ctx) {
-  extern __shared__ __align__(16) float smem[];
-  const int hd = d / nhead;
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  long unit = (long)blockIdx.x * IA_WAVES + wid;                  // (n, t, h)
-  const bool active = unit < (long)NB * L * nhead;                // wave-uniform
-  if (!active) unit = 0;
-  const int h = (int)(unit % nhead);
-  const long nt = unit / nhead;
-  const int n = (int)(nt / L), t = (int)(nt - (long)n * L);
-  inter_attention_unit(qkv, n * S, S, t, h, L, d, hd, active, smem + (size_t)wid * (3 * S * (hd + 1) + S * 64), lane, ctx);
-}
-
-// The same units over G groups of DIFFERENT sizes: unit (g, t, h) attends over the S_g sequences of group g only.
-// qkv [N][L][3d], ctx [N][L][d] with N = tab.bounds[G]; the LDS regions are S_max = max S_g wide.
+// The units of one call: unit (g, t, h) attends over the sequences of group g only.  qkv [N][L][3d], ctx [N][L][d].
+// The groups are either all S_uniform > 0 sequences wide -- group g is the sequences g * S_uniform ..., any number of
+// groups, the table is not read -- or, with S_uniform == 0, the G <= RG_MAXG groups of `tab`, of different sizes
+// (N = tab.bounds[G]).  The LDS regions are S_max = max S_g wide.
 template <int IA_WAVES>
 __global__ __launch_bounds__(64 * IA_WAVES) void inter_attention_groups_kernel(const float* __restrict__ qkv, GroupTable tab,
-                                                                               int G, int S_max, int L, int d, int nhead,
-                                                                               float* __restrict__ ctx) {
+                                                                               int G, int S_uniform, int S_max, int L, int d,
+                                                                               int nhead, float* __restrict__ ctx) {
   extern __shared__ __align__(16) float smem[];
   const int hd = d / nhead;
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -607,9 +560,9 @@ __global__ __launch_bounds__(64 * IA_WAVES) void inter_attention_groups_kernel(c
   const int h = (int)(unit % nhead);
   const long gt = unit / nhead;
   const int g = (int)(gt / L), t = (int)(gt - (long)g * L);
-  const int n0 = tab.bounds[g];
-  inter_attention_unit(qkv, n0, tab.bounds[g + 1] - n0, t, h, L, d, hd, active,
-                       smem + (size_t)wid * (3 * S_max * (hd + 1) + S_max * 64), lane, ctx);
+  const int n0 = S_uniform ? g * S_uniform : tab.bounds[g];
+  const int S = S_uniform ? S_uniform : tab.bounds[g + 1] - n0;
+  inter_attention_unit(qkv, n0, S, t, h, L, d, hd, active, smem + (size_t)wid * (3 * S_max * (hd + 1) + S_max * 64), lane, ctx);
 }
 
 // host: the groups of a ragged call.  bounds [G+1] non-decreasing from 0, every group 1..64 sequences.
@@ -639,20 +592,54 @@ int inter_attention_waves(const char* who, int S, int hd, size_t* per_wave) {
   return 4 * *per_wave <= lds_max ? 4 : 2 * *per_wave <= lds_max ? 2 : 1;
 }
 
+// the two passes of the joint statistics over the G groups of `tab`; scratch holds 2 * JS_BLOCKS doubles per group
+int launch_joint_stats(const float* mix, int M, int T, const int32_t* offsets, const GroupTable& tab, int G, double* scratch,
+                       float* mean, float* std, hipStream_t s) {
+  const int nb = asw::cdiv(T, 256) < JS_BLOCKS ? asw::cdiv(T, 256) : JS_BLOCKS;
+  hipLaunchKernelGGL(joint_stats_partial_groups_kernel, dim3(nb, G), dim3(256), 0, s, mix, M, T, offsets, tab, scratch);
+  ASW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(joint_stats_final_groups_kernel, dim3(G), dim3(64), 0, s, scratch, nb, T, tab, mean, std);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+
 }  // namespace
+
+// The one launcher of the inter-speaker attention (internal; sep_model.hip calls it for every kind of call): G groups,
+// either all S_uniform > 0 wide (bounds unused, any G) or the host bounds [G+1] of a ragged call (S_uniform == 0).
+// The shape (L, d, nhead, head_dim <= 64, S_uniform <= 64) is the caller's to check.
+namespace asw {
+int inter_attention_launch(const char* who, const float* qkv, const int32_t* bounds, int G, int S_uniform, int L, int d,
+                           int nhead, float* ctx, hipStream_t st) {
+  GroupTable tab = {};
+  int s_max = S_uniform;
+  if (!S_uniform)
+    if (int rc = fill_group_table(who, bounds, G, tab, &s_max)) return rc;
+  size_t per_wave;
+  const int waves = inter_attention_waves(who, s_max, d / nhead, &per_wave);
+  if (!waves) return ASW_ERR_ARG;
+  const size_t smem = per_wave * waves;
+  const int v = waves == 4 ? 0 : waves == 2 ? 1 : 2;
+  using Kern = void (*)(const float*, GroupTable, int, int, int, int, int, int, float*);
+  static const Kern kern[3] = {inter_attention_groups_kernel<4>, inter_attention_groups_kernel<2>, inter_attention_groups_kernel<1>};
+  static SmemAttr attr[3];                                     // per device and instantiation
+  if (int rc = attr[v].ensure(reinterpret_cast<const void*>(kern[v]), smem)) return rc;
+  hipLaunchKernelGGL(kern[v], dim3(cdiv((long)G * L * nhead, waves)), dim3(64 * waves), smem, st, qkv, tab, G, S_uniform, s_max,
+                     L, d, nhead, ctx);
+  ASW_LAUNCH_CHECK();
+  return ASW_OK;
+}
+}  // namespace asw
 
 extern "C" int asw_joint_shift_stats(const float* mix, int M, int T, const int32_t* offsets, int S, double* scratch,
                                      float* mean, float* std, void* stream) {
   ASW_CHECK_ARG(mix && offsets && scratch && mean && std, "joint_shift_stats: null pointer");
   ASW_CHECK_ARG(M >= 1 && S >= 1 && S * M <= JS_MAXCH && T >= 2, "joint_shift_stats: S=%d M=%d T=%d unsupported (S*M <= %d)", S,
                 M, T, JS_MAXCH);
-  hipStream_t s = asw::as_stream(stream);
-  const int nb = asw::cdiv(T, 256) < JS_BLOCKS ? asw::cdiv(T, 256) : JS_BLOCKS;
-  hipLaunchKernelGGL(joint_stats_partial_kernel, dim3(nb), dim3(256), 0, s, mix, M, T, offsets, S, scratch);
-  ASW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(joint_stats_final_kernel, dim3(1), dim3(64), 0, s, scratch, nb, T, S, mean, std);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  // one group: every sequence, mixture 0.  Built here, not by fill_group_table: S is bounded by S * M alone
+  GroupTable tab = {};
+  for (int g = 1; g <= RG_MAXG; ++g) tab.bounds[g] = S;
+  return launch_joint_stats(mix, M, T, offsets, tab, 1, scratch, mean, std, asw::as_stream(stream));
 }
 
 extern "C" int asw_joint_shift_stats_scratch_doubles(void) { return 2 * JS_BLOCKS; }
@@ -673,13 +660,7 @@ extern "C" int asw_joint_shift_stats_groups(const float* mix, int M, int T, cons
     ASW_CHECK_ARG(item_of_group[g] >= 0, "joint_shift_stats_groups: group %d reads mixture %d", g, item_of_group[g]);
     tab.item[g] = item_of_group[g];
   }
-  hipStream_t s = asw::as_stream(stream);
-  const int nb = asw::cdiv(T, 256) < JS_BLOCKS ? asw::cdiv(T, 256) : JS_BLOCKS;
-  hipLaunchKernelGGL(joint_stats_partial_groups_kernel, dim3(nb, G), dim3(256), 0, s, mix, M, T, offsets, tab, scratch);
-  ASW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(joint_stats_final_groups_kernel, dim3(G), dim3(64), 0, s, scratch, nb, T, tab, mean, std);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  return launch_joint_stats(mix, M, T, offsets, tab, G, scratch, mean, std, asw::as_stream(stream));
 }
 
 extern "C" int asw_add_layernorm2(const float* x, const float* y, float alpha, const float* gamma, const float* beta,
@@ -771,22 +752,7 @@ extern "C" int asw_inter_attention(const float* qkv, int NB, int S, int L, int d
   ASW_CHECK_ARG(qkv && ctx, "inter_attention: null pointer");
   ASW_CHECK_ARG(NB > 0 && S > 0 && S <= 64 && L > 0 && nhead > 0 && d % nhead == 0 && d / nhead <= 64,
                 "inter_attention: bad shape (S <= 64, head_dim <= 64)");
-  size_t per_wave;
-  const int waves = inter_attention_waves("inter_attention", S, d / nhead, &per_wave);
-  if (!waves) return ASW_ERR_ARG;
-  const size_t smem = per_wave * waves;
-  const void* kern = waves == 4 ? reinterpret_cast<const void*>(inter_attention_kernel<4>)
-                   : waves == 2 ? reinterpret_cast<const void*>(inter_attention_kernel<2>)
-                                : reinterpret_cast<const void*>(inter_attention_kernel<1>);
-  static asw::SmemAttr attr[3];                                // per device and instantiation
-  if (int rc = attr[waves == 4 ? 0 : waves == 2 ? 1 : 2].ensure(kern, smem)) return rc;
-  dim3 grid(asw::cdiv((long)NB * L * nhead, waves));
-  hipStream_t st = asw::as_stream(stream);
-  if (waves == 4) hipLaunchKernelGGL(inter_attention_kernel<4>, grid, dim3(256), smem, st, qkv, NB, S, L, d, nhead, ctx);
-  else if (waves == 2) hipLaunchKernelGGL(inter_attention_kernel<2>, grid, dim3(128), smem, st, qkv, NB, S, L, d, nhead, ctx);
-  else hipLaunchKernelGGL(inter_attention_kernel<1>, grid, dim3(64), smem, st, qkv, NB, S, L, d, nhead, ctx);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  return asw::inter_attention_launch("inter_attention", qkv, nullptr, NB, S, L, d, nhead, ctx, asw::as_stream(stream));
 }
 
 extern "C" int asw_inter_attention_groups(const float* qkv, const int32_t* bounds, int G, int L, int d, int nhead, float* ctx,
@@ -796,26 +762,5 @@ extern "C" int asw_inter_attention_groups(const float* qkv, const int32_t* bound
   ASW_CHECK_ARG(qkv && bounds && ctx, "inter_attention_groups: null pointer");
   ASW_CHECK_ARG(L > 0 && nhead > 0 && d > 0 && d % nhead == 0 && d / nhead <= 64,
                 "inter_attention_groups: bad shape (head_dim <= 64)");
-  GroupTable tab;
-  int s_max;
-  if (int rc = fill_group_table("inter_attention_groups", bounds, G, tab, &s_max)) return rc;
-  size_t per_wave;
-  const int waves = inter_attention_waves("inter_attention_groups", s_max, d / nhead, &per_wave);
-  if (!waves) return ASW_ERR_ARG;
-  const size_t smem = per_wave * waves;
-  const void* kern = waves == 4 ? reinterpret_cast<const void*>(inter_attention_groups_kernel<4>)
-                   : waves == 2 ? reinterpret_cast<const void*>(inter_attention_groups_kernel<2>)
-                                : reinterpret_cast<const void*>(inter_attention_groups_kernel<1>);
-  static asw::SmemAttr attr[3];                                // per device and instantiation
-  if (int rc = attr[waves == 4 ? 0 : waves == 2 ? 1 : 2].ensure(kern, smem)) return rc;
-  dim3 grid(asw::cdiv((long)G * L * nhead, waves));
-  hipStream_t st = asw::as_stream(stream);
-  if (waves == 4)
-    hipLaunchKernelGGL(inter_attention_groups_kernel<4>, grid, dim3(256), smem, st, qkv, tab, G, s_max, L, d, nhead, ctx);
-  else if (waves == 2)
-    hipLaunchKernelGGL(inter_attention_groups_kernel<2>, grid, dim3(128), smem, st, qkv, tab, G, s_max, L, d, nhead, ctx);
-  else
-    hipLaunchKernelGGL(inter_attention_groups_kernel<1>, grid, dim3(64), smem, st, qkv, tab, G, s_max, L, d, nhead, ctx);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
+  return asw::inter_attention_launch("inter_attention_groups", qkv, bounds, G, 0, L, d, nhead, ctx, asw::as_stream(stream));
 }

@@ -30,6 +30,10 @@
 using namespace asw_model;
 
 extern "C" int asw_joint_shift_stats_scratch_doubles(void);
+namespace asw {   // sep_kernels.hip: the launcher behind asw_inter_attention / asw_inter_attention_groups
+int inter_attention_launch(const char* who, const float* qkv, const int32_t* bounds, int G, int S_uniform, int L, int d,
+                           int nhead, float* ctx, hipStream_t st);
+}
 
 namespace {
 
@@ -42,7 +46,6 @@ struct ConfLayer {
   DevBuf cm_lng, cm_lnb, cm_pwb, dw_wT, dw_b, ac_lng, ac_lnb, ac_b;
   WBuf cm_pw, ac_w;
 };
-struct InterLayer { WBuf w_in, w_out, w1, w2; DevBuf b_in, b_out, b1, b2, n1g, n1b, n2g, n2b; };
 
 }  // namespace
 
@@ -50,7 +53,7 @@ struct asw_sep : Trunk {
   asw_sep_config cfg;
   GatedConvs convs;                         // down / up convolutions (no window gate in this network)
   std::vector<ConfLayer> conf;
-  std::vector<InterLayer> inter;
+  std::vector<PostNormLayer> inter;           // across the speakers of a time step
   std::vector<float> inv_freq;
   DevBuf pe;                                // sinusoid table [2L-1][d] of the last sequence length
   int pe_L = 0;
@@ -127,21 +130,21 @@ std::vector<float> scaled(const std::vector<float>& w, float a) {
 
 // ---- workspace ---------------------------------------------------------------------------
 struct Plan : TrunkPlan {
-  int NB, S, L, d;                            // B = NB * S sequences
+  int L, d;
+  // The B sequences are G groups that attend -- and, in infer / infer_batch, are normalised -- apart: all S > 0 wide
+  // (forward: B = G * S), or with S == 0 the groups of the host bounds [G+1] (infer: one group; infer_batch: ragged).
+  int G = 0, S = 0;
+  const int32_t* bounds = nullptr;
   double* jscr;
   std::vector<float*> intra_out, inter_out;   // per bottleneck layer (kept apart so every tap stays readable)
   float *h, *g, *x1, *x2, *x3, *qkv, *ctx, *raw2, *u, *v2, *y, *f, *pos;
-  const int32_t* counts = nullptr;            // host [NB]: speakers present per item (NULL: S everywhere), forward() only
-  // infer_batch() only: the B sequences are G groups (host [G+1] bounds) that attend and are normalised apart
-  const int32_t* group_bounds = nullptr;
-  int G = 0;
+  const int32_t* counts = nullptr;            // forward_counts() only, host [G]: speakers present per item, the rest are zero rows
   int32_t* mix_index;                         // device [B]
 };
 
-void layout(const asw_sep* m, int NB, int S, int T, int groups, Arena& a, Plan& pl) {
+void layout(const asw_sep* m, int B, int T, int groups, Arena& a, Plan& pl) {
   const asw_sep_config& c = m->cfg;
-  pl.NB = NB; pl.S = S;
-  m->layout_levels(NB * S, T, a, pl);
+  m->layout_levels(B, T, a, pl);
   const size_t L = pl.Tl[c.depth], d = m->enc_cout.back(), rows = (size_t)pl.B * L;
   pl.L = (int)L; pl.d = (int)d;
   pl.intra_out.resize(c.bottleneck_layers); pl.inter_out.resize(c.bottleneck_layers);
@@ -157,9 +160,9 @@ void layout(const asw_sep* m, int NB, int S, int T, int groups, Arena& a, Plan& 
   pl.mix_index = a.take<int32_t>(pl.B);
 }
 
-int ensure_ws(asw_sep* m, int NB, int S, int T, Plan& pl, int groups = 1) {
+int ensure_ws(asw_sep* m, int B, int T, Plan& pl, int groups = 1) {
   Arena dry(nullptr, 0, true);
-  layout(m, NB, S, T, groups, dry, pl);
+  layout(m, B, T, groups, dry, pl);
   const size_t need = dry.off + 4096;
   if (need > m->ws_bytes) {
     // the number of talkers changes from mixture to mixture: grow by half again, not to the exact size, so that a
@@ -171,12 +174,12 @@ int ensure_ws(asw_sep* m, int NB, int S, int T, Plan& pl, int groups = 1) {
       (void)hipGetLastError();
       want = need;
       if (hipMalloc(&m->ws, want) != hipSuccess)
-        return asw::set_error(ASW_ERR_NOMEM, "workspace of %.1f MiB for %d sequences, T=%d", need / 1048576.0, NB * S, T);
+        return asw::set_error(ASW_ERR_NOMEM, "workspace of %.1f MiB for %d sequences, T=%d", need / 1048576.0, B, T);
     }
     m->ws_bytes = want;
   }
   Arena real(m->ws, m->ws_bytes, false);
-  layout(m, NB, S, T, groups, real, pl);
+  layout(m, B, T, groups, real, pl);
   return ASW_OK;
 }
 
@@ -240,18 +243,12 @@ int run_conformer(asw_sep* m, Plan& pl, ConfLayer& c, const float* x, float* out
   return asw_add_layernorm2(pl.y, nullptr, 0.f, c.fng.p, c.fnb.p, rows, d, 1e-6f, 0, nullptr, out, s);
 }
 
-// post-norm transformer layer across the S speakers of every time step: x -> out
-int run_inter(asw_sep* m, Plan& pl, InterLayer& t, const float* x, float* out, hipStream_t s) {
-  const int rows = pl.B * pl.L, d = pl.d, ffw = m->cfg.ffw_dim;
-  const int prec = m->site(Trunk::Src::Normed), rawp = m->site(Trunk::Src::Raw);   // x, x1: LayerNorm outputs; ctx, f: not
-  int rc;
-  if ((rc = linear(x, t.w_in, prec, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
-  if (pl.group_bounds) rc = asw_inter_attention_groups(pl.qkv, pl.group_bounds, pl.G, pl.L, d, m->cfg.num_head, pl.ctx, s);
-  else rc = asw_inter_attention(pl.qkv, pl.NB, pl.S, pl.L, d, m->cfg.num_head, pl.ctx, s);
-  if (rc) return rc;
-  if ((rc = linear(pl.ctx, t.w_out, rawp, t.b_out.p, rows, d, d, 0, x, t.n1g.p, t.n1b.p, pl.x1, s))) return rc;
-  if ((rc = linear(pl.x1, t.w1, prec, t.b1.p, rows, ffw, d, 1, nullptr, nullptr, nullptr, pl.f, s))) return rc;
-  return linear(pl.f, t.w2, rawp, t.b2.p, rows, d, ffw, 0, pl.x1, t.n2g.p, t.n2b.p, out, s);
+// post-norm transformer layer across the speakers of every time step, group by group: x -> out
+int run_inter(asw_sep* m, Plan& pl, PostNormLayer& t, const float* x, float* out, hipStream_t s) {
+  auto attention = [&](const float* qkv, float* ctx) {
+    return asw::inter_attention_launch("inter_attention", qkv, pl.bounds, pl.G, pl.S, pl.L, pl.d, m->cfg.num_head, ctx, s);
+  };
+  return run_post_norm(*m, t, {pl.qkv, pl.ctx, pl.x1, pl.f}, x, out, pl.B * pl.L, pl.d, m->cfg.ffw_dim, attention, s);
 }
 
 // everything after the preproc stage; pl.X[0] / pl.refn are filled
@@ -270,7 +267,7 @@ int run_network(asw_sep* m, Plan& pl, const float* mean, const float* stdv, floa
     if (pl.counts) {
       // items with fewer speakers: batches_to_speakers (:250-268) re-inserts the missing ones as ZERO sequences, which
       // take part in the inter-speaker attention below; whatever the Conformer made of those rows is discarded
-      for (int n = 0; n < pl.NB; ++n)
+      for (int n = 0; n < pl.G; ++n)
         if (pl.counts[n] < pl.S)
           ASW_HIP(hipMemsetAsync(pl.intra_out[l] + ((size_t)n * pl.S + pl.counts[n]) * pl.L * pl.d, 0,
                                  (size_t)(pl.S - pl.counts[n]) * pl.L * pl.d * sizeof(float), s));
@@ -373,7 +370,7 @@ extern "C" int asw_sep_finalize(asw_sep* m) {
     UP(q.ac_w, m->P(cl + ".convolution_module.after_conv.2.weight"));
     UP(q.ac_b, m->P(cl + ".convolution_module.after_conv.2.bias"));
     const std::string t = "bottleneck.module_list." + std::to_string(l) + ".inter.layers.0";
-    InterLayer& il = m->inter[l];
+    PostNormLayer& il = m->inter[l];
     UP(il.w_in, m->P(t + ".self_attn.in_proj_weight")); UP(il.b_in, m->P(t + ".self_attn.in_proj_bias"));
     UP(il.w_out, m->P(t + ".self_attn.out_proj.weight")); UP(il.b_out, m->P(t + ".self_attn.out_proj.bias"));
     UP(il.w1, m->P(t + ".linear1.weight")); UP(il.b1, m->P(t + ".linear1.bias"));
@@ -385,6 +382,38 @@ extern "C" int asw_sep_finalize(asw_sep* m) {
   return ASW_OK;
 }
 
+namespace {
+// The one inference body.  The B = bounds[G] sequences are the G groups of `bounds`, group g the talkers of mixture
+// item[g] of mix [K][M][T] (items ascending): joint statistics and inter-speaker attention per group, everything else
+// over all B sequences at once.  The callers have checked the arguments.
+int infer_groups(asw_sep* m, const float* mix, int M, int T, const int32_t* offsets, const std::vector<int32_t>& bounds,
+                 const std::vector<int32_t>& item, float* out, hipStream_t s) {
+  const int B = bounds.back(), G = (int)item.size();
+  int rc;
+  Plan pl;
+  if ((rc = ensure_ws(m, B, T, pl, G))) return rc;
+  const int C = m->cfg.channels, pad_l = m->cfg.encoder_kernel_size / 2;
+  ASW_HIP(hipMemsetAsync(pl.refn, 0, (size_t)B * pl.RL * sizeof(float), s));
+  if ((rc = asw_joint_shift_stats_groups(mix, M, T, offsets, bounds.data(), G, item.data(), pl.jscr, pl.mean, pl.stdv, s)))
+    return rc;
+  // sequence n reads mixture mix_index[n]; when every one reads mixture 0 no table is needed (and none is copied)
+  const int32_t* mix_index = nullptr;
+  if (item.back() != 0) {
+    std::vector<int32_t> mi;
+    for (int g = 0; g < G; ++g) mi.insert(mi.end(), bounds[g + 1] - bounds[g], item[g]);
+    // pageable source: the runtime has taken the table before the call returns
+    ASW_HIP(hipMemcpyAsync(pl.mix_index, mi.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    mix_index = pl.mix_index;
+  }
+  if ((rc = asw_shift_norm_preproc_multi(mix, M, T, pl.Tp, offsets, mix_index, B, /*circular*/ 0, pl.mean, pl.stdv, m->pre_w.p,
+                                         m->pre_b.p, C, pl.X[0], pl.refn + pad_l, pl.RL, s)))
+    return rc;
+  pl.G = G;
+  pl.bounds = bounds.data();
+  return run_network(m, pl, pl.mean, pl.stdv, out, s);
+}
+}  // namespace
+
 extern "C" int asw_sep_infer(asw_sep* m, const float* mix, int M, int T, const int32_t* offsets, int S, float* out,
                              void* stream) {
   int rc = check_ready(m, "asw_sep_finalize");
@@ -394,16 +423,7 @@ extern "C" int asw_sep_infer(asw_sep* m, const float* mix, int M, int T, const i
   ASW_CHECK_ARG(mix && offsets && out, "sep_infer: null pointer");
   ASW_CHECK_ARG(M == m->cfg.n_mics, "sep_infer: mixture has %d channels, model expects %d", M, m->cfg.n_mics);
   ASW_CHECK_ARG(T >= 2, "sep_infer: T=%d", T);
-  hipStream_t s = asw::as_stream(stream);
-  Plan pl;
-  if ((rc = ensure_ws(m, 1, S, T, pl))) return rc;
-  const int C = m->cfg.channels, pad_l = m->cfg.encoder_kernel_size / 2;
-  ASW_HIP(hipMemsetAsync(pl.refn, 0, (size_t)S * pl.RL * sizeof(float), s));
-  if ((rc = asw_joint_shift_stats(mix, M, T, offsets, S, pl.jscr, pl.mean, pl.stdv, s))) return rc;
-  if ((rc = asw_shift_norm_preproc(mix, M, T, pl.Tp, offsets, S, /*circular*/ 0, pl.mean, pl.stdv, m->pre_w.p, m->pre_b.p, C,
-                                   pl.X[0], pl.refn + pad_l, pl.RL, s)))
-    return rc;
-  return run_network(m, pl, pl.mean, pl.stdv, out, s);
+  return infer_groups(m, mix, M, T, offsets, {0, S}, {0}, out, asw::as_stream(stream));   // one mixture, one group
 }
 
 extern "C" int asw_sep_infer_batch(asw_sep* m, const float* mix, int K, int M, int T, const int32_t* offsets,
@@ -413,8 +433,8 @@ extern "C" int asw_sep_infer_batch(asw_sep* m, const float* mix, int K, int M, i
   ASW_CHECK_ARG(K >= 0, "sep_infer_batch: K=%d mixtures", K);
   if (K == 0) return ASW_OK;
   ASW_CHECK_ARG(counts, "sep_infer_batch: null pointer (counts)");
-  // the groups: one per item that holds a talker, in order; sequence n reads mixture mix_index[n]
-  std::vector<int32_t> bounds(1, 0), item, mix_index;
+  // the groups: one per item that holds a talker, in order
+  std::vector<int32_t> bounds(1, 0), item;
   long N = 0;
   for (int k = 0; k < K; ++k) {
     ASW_CHECK_ARG(counts[k] >= 0 && counts[k] <= 64, "sep_infer_batch: item %d holds %d speakers (0..64)", k, counts[k]);
@@ -422,29 +442,13 @@ extern "C" int asw_sep_infer_batch(asw_sep* m, const float* mix, int K, int M, i
     if (counts[k] == 0) continue;
     bounds.push_back((int32_t)N);
     item.push_back(k);
-    mix_index.insert(mix_index.end(), counts[k], k);
   }
   ASW_CHECK_ARG(N <= 64, "sep_infer_batch: %ld sequences (at most 64 per call)", N);
   if (N == 0) return ASW_OK;
   ASW_CHECK_ARG(mix && offsets && out, "sep_infer_batch: null pointer");
   ASW_CHECK_ARG(M == m->cfg.n_mics, "sep_infer_batch: mixtures have %d channels, model expects %d", M, m->cfg.n_mics);
   ASW_CHECK_ARG(T >= 2, "sep_infer_batch: T=%d", T);
-  hipStream_t s = asw::as_stream(stream);
-  const int B = (int)N, G = (int)item.size();
-  Plan pl;
-  if ((rc = ensure_ws(m, 1, B, T, pl, G))) return rc;
-  const int C = m->cfg.channels, pad_l = m->cfg.encoder_kernel_size / 2;
-  ASW_HIP(hipMemsetAsync(pl.refn, 0, (size_t)B * pl.RL * sizeof(float), s));
-  if ((rc = asw_joint_shift_stats_groups(mix, M, T, offsets, bounds.data(), G, item.data(), pl.jscr, pl.mean, pl.stdv, s)))
-    return rc;
-  // pageable source: the runtime has taken the table before the call returns
-  ASW_HIP(hipMemcpyAsync(pl.mix_index, mix_index.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  if ((rc = asw_shift_norm_preproc_multi(mix, M, T, pl.Tp, offsets, pl.mix_index, B, /*circular*/ 0, pl.mean, pl.stdv,
-                                         m->pre_w.p, m->pre_b.p, C, pl.X[0], pl.refn + pad_l, pl.RL, s)))
-    return rc;
-  pl.group_bounds = bounds.data();
-  pl.G = G;
-  return run_network(m, pl, pl.mean, pl.stdv, out, s);
+  return infer_groups(m, mix, M, T, offsets, bounds, item, out, asw::as_stream(stream));
 }
 
 extern "C" int asw_sep_forward(asw_sep* m, const float* mix_norm, int B, int S, int M, int t, float* out, void* stream) {
@@ -470,8 +474,9 @@ extern "C" int asw_sep_forward_counts(asw_sep* m, const float* mix_norm, int B, 
   ASW_CHECK_ARG(M == m->cfg.n_mics && t >= 1, "sep_forward: bad shape");
   hipStream_t s = asw::as_stream(stream);
   Plan pl;
-  if ((rc = ensure_ws(m, B, S, t, pl))) return rc;
-  const int BS = B * S, C = m->cfg.channels, pad_l = m->cfg.encoder_kernel_size / 2;
+  const int BS = B * S;
+  if ((rc = ensure_ws(m, BS, t, pl))) return rc;
+  const int C = m->cfg.channels, pad_l = m->cfg.encoder_kernel_size / 2;
   ASW_HIP(hipMemsetAsync(pl.refn, 0, (size_t)BS * pl.RL * sizeof(float), s));
   // [B][S*M][t] is [B*S][M][t]: every speaker block of M channels is one sequence (:436-437)
   if ((rc = asw_pad_preproc(mix_norm, BS, M, t, pl.Tp, m->pre_w.p, m->pre_b.p, C, pl.X[0], pl.refn + pad_l, pl.RL, s))) return rc;
@@ -480,6 +485,7 @@ extern "C" int asw_sep_forward_counts(asw_sep* m, const float* mix_norm, int B, 
   for (int sp = 1; sp < S; ++sp)
     ASW_HIP(hipMemcpy2DAsync(pl.refn + (size_t)sp * pl.RL, (size_t)S * pl.RL * sizeof(float), pl.refn,
                              (size_t)S * pl.RL * sizeof(float), (size_t)pl.RL * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+  pl.G = B; pl.S = S;                       // every item is one group, as wide as the stack
   pl.counts = counts;
   if ((rc = run_network(m, pl, nullptr, nullptr, pl.ywave, s))) return rc;
   if (counts) {

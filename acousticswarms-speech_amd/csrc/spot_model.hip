@@ -23,7 +23,6 @@ using namespace asw_model;
 
 namespace {
 
-struct TfLayer { WBuf w_in, w_out, w1, w2; DevBuf b_in, b_out, b1, b2, n1g, n1b, n2g, n2b; };
 // the gated convolutions of one window embedding
 struct GateSet : GatedConvs { uint64_t stamp = 0; };   // stamp: last use (LRU eviction)
 
@@ -33,7 +32,7 @@ struct asw_spot : Trunk {
   asw_spot_config cfg;
   int batch = 32;
   uint64_t clock = 0;
-  std::vector<TfLayer> tf;
+  std::vector<PostNormLayer> tf;
   std::map<std::pair<float, float>, std::unique_ptr<GateSet>> gates;
 
   // workspace: one arena per lane.  With two lanes consecutive internal batches run on two HIP
@@ -121,7 +120,6 @@ int get_gates(asw_spot* m, float w0, float w1, GateSet** out) {
 
 struct Plan : TrunkPlan {
   float *qkv, *ctx, *x1, *ff, *ha, *hb;
-  double* escr;
 };
 
 void layout(const asw_spot* m, int B, int T, Arena& a, Plan& pl) {
@@ -134,7 +132,6 @@ void layout(const asw_spot* m, int B, int T, Arena& a, Plan& pl) {
   pl.ha = a.take<float>(rows * d);
   pl.hb = a.take<float>(rows * d);
   m->layout_mask(a, pl);
-  pl.escr = a.take<double>((size_t)B * (T + 1));
 }
 
 int ensure_ws(asw_spot* m, int B, int T, Plan& pl, int lane = 0) {
@@ -175,16 +172,12 @@ int run_network(asw_spot* m, Plan& pl, GateSet* gs, const float* mean, const flo
   // ---- bottleneck (network.py:240-265): post-norm transformer layers, batch-first rows
   const int L = pl.Tl[c.depth], d = m->enc_cout.back(), rows = pl.B * L;
   const float* h = pl.X[c.depth];
-  // h and x1 are GroupNorm + GLU / LayerNorm outputs; qkv -> ctx and the ReLU'd hidden layer ff are not (Trunk::site)
-  const int normed = m->site(Trunk::Src::Normed), rawp = m->site(Trunk::Src::Raw);
+  // h is a GroupNorm + GLU / LayerNorm output; the attention reads qkv, a Raw operand (Trunk::site)
+  const int rawp = m->site(Trunk::Src::Raw);
+  auto attention = [&](const float* qkv, float* ctx) { return asw_attention_prec(qkv, pl.B, L, d, c.num_head, rawp, ctx, s); };
   for (int l = 0; l < c.num_transformer_layers; ++l) {
-    TfLayer& t = m->tf[l];
     float* hout = (l % 2 == 0) ? pl.ha : pl.hb;
-    if ((rc = linear(h, t.w_in, normed, t.b_in.p, rows, 3 * d, d, 0, nullptr, nullptr, nullptr, pl.qkv, s))) return rc;
-    if ((rc = asw_attention_prec(pl.qkv, pl.B, L, d, c.num_head, rawp, pl.ctx, s))) return rc;
-    if ((rc = linear(pl.ctx, t.w_out, rawp, t.b_out.p, rows, d, d, 0, h, t.n1g.p, t.n1b.p, pl.x1, s))) return rc;
-    if ((rc = linear(pl.x1, t.w1, normed, t.b1.p, rows, c.ffw_dim, d, 1, nullptr, nullptr, nullptr, pl.ff, s))) return rc;
-    if ((rc = linear(pl.ff, t.w2, rawp, t.b2.p, rows, d, c.ffw_dim, 0, pl.x1, t.n2g.p, t.n2b.p, hout, s))) return rc;
+    if ((rc = run_post_norm(*m, m->tf[l], {pl.qkv, pl.ctx, pl.x1, pl.ff}, h, hout, rows, d, c.ffw_dim, attention, s))) return rc;
     h = hout;
   }
   m->taps["bottleneck"] = {h, (size_t)rows * d};
@@ -235,7 +228,7 @@ extern "C" int asw_spot_finalize(asw_spot* m) {
   m->tf.clear(); m->tf.resize(c.num_transformer_layers);
   for (int l = 0; l < c.num_transformer_layers; ++l) {
     const std::string p = "bottleneck.transf.layers." + std::to_string(l);
-    TfLayer& t = m->tf[l];
+    PostNormLayer& t = m->tf[l];
     {
       const int dm = m->enc_cout.back(), ff = c.ffw_dim;
       if ((rc = t.w_in.upload_gemm(m->P(p + ".self_attn.in_proj_weight"), 3 * dm, dm))) return rc;
@@ -322,7 +315,7 @@ extern "C" int asw_spot_shift_and_sep_multi(asw_spot* m, const float* mix, int K
       }
       float* y = out_wave ? out_wave + (size_t)i0 * T : p.ywave;
       if ((r = run_network(m, p, gs, p.mean, p.stdv, y, q, src0))) return r;
-      if (out_energy && (r = asw_energies(y, B, T, energy_window, p.escr, out_energy + (size_t)i0 * 2, q))) return r;
+      if (out_energy && (r = asw_energies(y, B, T, energy_window, nullptr, out_energy + (size_t)i0 * 2, q))) return r;
     }
     return ASW_OK;
   };

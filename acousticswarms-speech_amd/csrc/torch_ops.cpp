@@ -159,9 +159,8 @@ Tensor energies(const Tensor& y, int64_t window) {
   const int B = checked_int(y.size(0), "B"), T = checked_int(y.size(1), "T");
   Tensor out = at::empty({B, 2}, y.options().dtype(at::kDouble));
   if (B == 0) return out;
-  Tensor scratch = at::empty({B, T + 1}, y.options().dtype(at::kDouble));
   Launch l(y);
-  check_status(asw_energies(y.data_ptr<float>(), B, T, checked_int(window, "window"), scratch.data_ptr<double>(),
+  check_status(asw_energies(y.data_ptr<float>(), B, T, checked_int(window, "window"), /*scratch: ignored*/ nullptr,
                             out.data_ptr<double>(), l.stream),
                "asw_energies");
   return out;

@@ -286,9 +286,8 @@ def mask_path(x, ref, ref_hop, enc_w, enc_b, byp_w, byp_b, dec_w, frames, stride
 
 def energies(y, window=12000):
     B, T = y.shape
-    scratch = torch.empty((B, T + 1), dtype=torch.float64, device=y.device)
     out = torch.empty((B, 2), dtype=torch.float64, device=y.device)
-    check(lib().asw_energies(ptr(_f32(y)), B, T, window, ptr(scratch), ptr(out), current_stream()))
+    check(lib().asw_energies(ptr(_f32(y)), B, T, window, None, ptr(out), current_stream()))   # scratch: ignored
     return out
 
 

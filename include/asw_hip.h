@@ -568,8 +568,9 @@ int asw_overlap_add_parts(const float* D, int nparts, int B, int F, int ldd, int
                           const float* std, float* out, void* stream);
 
 /* Per-candidate energies: mean removal, power = sum x^2, power2 = max windowed RMS
- * (local_utils_3d.py:13-17,349-354).  out [B][2] float64.  scratch is unused since ABI 3 (the prefix
- * sums stay in registers / LDS) and may be NULL. */
+ * (local_utils_3d.py:13-17,349-354).  out [B][2] float64.  T <= 4096 * 256 samples when T and window are
+ * multiples of 4 and y is 16-byte aligned, T <= 4096 * 64 otherwise.  scratch is ignored (the prefix sums stay in
+ * registers / LDS; the argument is kept for the ABI): pass NULL, nothing needs to be allocated for it. */
 int asw_energies(const float* y, int B, int T, int window, double* scratch, double* out,
                  void* stream);
 

@@ -122,3 +122,36 @@ def test_sep_argument_errors_do_not_need_a_gpu():
     assert L.asw_relpos_attention(None, None, None, None, 1, 10, 128, 8, 0.1, None, None) == -1
     assert L.asw_add_layernorm2(None, None, 1.0, None, None, 4, 512, 1e-5, 0, None, None, None) == -1
     assert L.asw_joint_shift_stats_scratch_doubles() > 0
+
+
+def test_single_shape_entry_points_keep_their_refusals():
+    """The single-shape entry points are views of the general ones and check their own arguments first: every call
+    below is refused on the host, with the entry point's own message."""
+    import ctypes
+    import numpy as np
+    L = native.lib()
+    buf = np.zeros(64)
+    p = ctypes.c_void_p(buf.ctypes.data)                               # never dereferenced: every call below is refused
+    # asw_energies ignores `scratch` (NULL is the documented value); the pointers it uses are still checked
+    assert L.asw_energies(None, 2, 100, 10, None, p, None) == -1
+    assert b"energies: null pointer" in L.asw_last_error()
+    assert L.asw_energies(p, 2, 100, 10, None, None, None) == -1
+    assert b"energies: null pointer" in L.asw_last_error()
+    assert L.asw_energies(p, 2, 100, 0, None, p, None) == -1           # scratch = NULL passes the pointer check: window 0
+    assert b"energies: bad shape" in L.asw_last_error()
+    # the uniform attention call: S <= 64 whatever the number of items
+    assert L.asw_inter_attention(p, 1, 65, 5, 128, 8, p, None) == -1
+    assert b"inter_attention: bad shape (S <= 64" in L.asw_last_error()
+    assert L.asw_inter_attention(p, 70, 65, 5, 128, 8, p, None) == -1
+    assert L.asw_inter_attention(None, 2, 3, 5, 128, 8, p, None) == -1
+    assert b"inter_attention: null pointer" in L.asw_last_error()
+    assert L.asw_inter_attention(p, 2, 3, 5, 1024, 8, p, None) == -1   # head_dim 128
+    # the one-group statistics call: S bounded by S * M <= 2048 alone (292 * 7 = 2044 channels would pass)
+    assert L.asw_joint_shift_stats(p, 7, 4000, p, 293, p, p, p, None) == -1
+    assert b"joint_shift_stats: S=293 M=7 T=4000 unsupported (S*M <= 2048)" in L.asw_last_error()
+    assert L.asw_joint_shift_stats(p, 32, 4000, p, 65, p, p, p, None) == -1
+    assert b"joint_shift_stats: S=65" in L.asw_last_error()
+    assert L.asw_joint_shift_stats(p, 7, 4000, p, 2, None, p, p, None) == -1
+    assert b"joint_shift_stats: null pointer" in L.asw_last_error()
+    assert L.asw_add_layernorm(p, p, p, p, 4, 100, 1e-5, p, None) == -1
+    assert b"add_layernorm: N=100 must be a multiple of 256" in L.asw_last_error()

@@ -195,6 +195,23 @@ def test_add_layernorm(ops, rows, N):
         ops.add_layernorm(x[:, :100].contiguous().cuda(), r[:, :100].contiguous().cuda(), g[:100].cuda(), b[:100].cuda())
 
 
+@pytest.mark.parametrize("rows,N", [(5, 256), (7, 1024)])
+def test_add_layernorm_in_place_and_its_width_rule(ops, rows, N):
+    """The wide linear layers call asw_add_layernorm in place (x == out): same bytes as out of place.  It takes only
+    N % 256 == 0; N = 100 is the general row kernel's (asw_add_layernorm2)."""
+    from acousticswarms_speech_amd.native import check, current_stream, lib, ptr
+    x, r = (_rand(rows, N, seed=44, scale=2.0) + 0.3).cuda(), _rand(rows, N, seed=45).cuda()
+    g, b = (_rand(N, seed=46) * 0.2 + 1.0).cuda(), _rand(N, seed=47, scale=0.1).cuda()
+    want = ops.add_layernorm(x, r, g, b)
+    xin = x.clone()
+    check(lib().asw_add_layernorm(ptr(xin), ptr(r), ptr(g), ptr(b), rows, N, 1e-5, ptr(xin), current_stream()))
+    np.testing.assert_array_equal(xin.cpu().numpy(), want.cpu().numpy())
+    with pytest.raises(RuntimeError, match="multiple of 256"):
+        ops.add_layernorm(x[:, :100].contiguous(), r[:, :100].contiguous(), g[:100], b[:100])
+    _s, o100 = ops.add_layernorm2(x[:, :100].contiguous(), r[:, :100].contiguous(), 1.0, g[:100], b[:100])
+    assert o100.shape == (rows, 100)
+
+
 def test_mask_path(ops):
     """reference_bypass * mask_encoder -> output_decoder -> trim (network.py:397-405)."""
     B, C, E, EK, ES, Tp, t = 2, 64, 256, 33, 16, 2048, 1900

@@ -120,6 +120,18 @@ def test_inter_attention(ops, S):
     assert _relerr(got.cpu(), want) < 2e-6
 
 
+def test_inter_attention_takes_more_items_than_the_group_table_holds(ops):
+    """The uniform call reads no group table: NB = 70 items is beyond the 64 groups a ragged call may name."""
+    NB, S, L, d, H = 70, 2, 1, 128, 8
+    hd = d // H
+    qkv = _rand(NB, S, L, 3 * d, seed=19, scale=0.7)
+    q, k, v = [t.permute(0, 2, 1, 3).reshape(NB * L, S, H, hd).transpose(1, 2) for t in qkv.split(d, dim=-1)]
+    att = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(hd), dim=-1)
+    want = (att @ v).transpose(1, 2).reshape(NB, L, S, d).permute(0, 2, 1, 3)
+    got = ops.inter_attention(qkv.cuda(), H)
+    assert _relerr(got.cpu(), want) < 2e-6
+
+
 def test_swish_epilogue(ops):
     x = _rand(1, 200, 128, seed=16)
     w, b = _rand(256, 128, seed=17, scale=0.1), _rand(256, seed=18, scale=0.1)
@@ -206,6 +218,23 @@ def test_infer_sample_small_vs_reference_golden(golden, precision):
             self.sample_offset = o
     y2 = model.infer(mix, [P(o) for o in g["samples1"]])
     np.testing.assert_array_equal(y2, model.infer_sample(mix, list(g["samples1"])))
+
+
+def test_infer_is_infer_batch_with_one_item(golden):
+    """asw_sep_infer is asw_sep_infer_batch with K = 1: the same bytes."""
+    from acousticswarms_speech_amd import native
+    from acousticswarms_speech_amd.config import SEP_SMALL
+    from acousticswarms_speech_amd.scenes import make_scene
+    from acousticswarms_speech_amd.sep import rounded_offsets
+    model, _sd = _model(SEP_SMALL, 31, "f32")
+    mix = torch.from_numpy(make_scene(4, 3, 7, 4000).mix).cuda()
+    offs = native.to_device(rounded_offsets(list(golden("g11b_sep_infer_small")["samples2"]), 6), mix.device)
+    S = offs.shape[0]
+    assert S >= 2
+    one = model.infer_device(mix, offs)
+    batch = model.infer_batch_device(mix.unsqueeze(0).contiguous(), offs, [S])
+    assert one.shape == batch.shape == (S, 4000)
+    np.testing.assert_array_equal(one.cpu().numpy(), batch.cpu().numpy())
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
