@@ -24,6 +24,9 @@ import time
 
 import numpy as np
 
+from .mic_array import run_search
+from .scorer import DeviceScorer
+from .sep import one_mixture_shape
 from .spot import offsets_from_patches
 
 
@@ -215,8 +218,7 @@ class MixtureScorer(object):
     the device helpers of ``FORWARDED`` are the wrapped model's."""
 
     # the device helpers that do not touch the mixture: passed to the wrapped model unchanged
-    FORWARDED = ("pair_sisdr", "segment_sisdr", "voiced_segments", "segment_sisdr_device", "fine_clusters",
-                 "pair_sisdr_device", "segment_sisdr_resident", "global_clusters", "coarse_select")
+    FORWARDED = DeviceScorer.HELPERS
 
     def __init__(self, batcher, k):
         self.batcher, self.k = batcher, k
@@ -282,18 +284,14 @@ def check_geometries(mixes, geometries):
         return
     if len(geometries) != len(mixes):
         raise ValueError(f"geometries holds {len(geometries)} entries for {len(mixes)} mixtures")
-    shapes = [tuple(int(v) for v in np.shape(m)) for m in mixes]
-    if any(len(sh) != 2 for sh in shapes):
-        raise ValueError("every mixture must be [M, T]")
-    if len(set(shapes)) > 1:
-        raise ValueError(f"the mixtures of one batch must share M and T, got the shapes {sorted(set(shapes))}")
+    shape = one_mixture_shape(mixes)
     for k, g in enumerate(geometries):
         if len(g) != 2:
             raise ValueError(f"geometries[{k}] must be (mic_positions, speaker_range)")
         mic_shape = tuple(np.shape(g[0]))
-        if len(mic_shape) != 2 or mic_shape[1] != 3 or (shapes and mic_shape[0] != shapes[0][0]):
+        if len(mic_shape) != 2 or mic_shape[1] != 3 or (shape and mic_shape[0] != shape[0]):
             raise ValueError(f"geometries[{k}]: mic_positions {mic_shape} do not fit mixtures of "
-                             f"{shapes[0][0] if shapes else '?'} channels")
+                             f"{shape[0] if shape else '?'} channels")
         if len(g[1]) != 6:
             raise ValueError(f"geometries[{k}]: speaker_range must hold 6 values")
 
@@ -321,6 +319,29 @@ def separate_stack(sep_model, stack, patch_lists):
     P = int(stack.shape[1]) - 1
     return sep_model.infer_packed(stack, [rounded_offsets([p[0].sample_offset for p in patches], P)
                                           for patches in patch_lists])
+
+
+def result_record(patches, spot_times, times):
+    """The per-mixture result dict of ``shard.localize_batch`` from the final patches of a search (tuples (patch, audio,
+    power, name)): centres [K,3] ((0, 3) without talkers), powers [K], names, and ``spot_times`` / ``times`` as given."""
+    return {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
+            "powers": np.array([p[2] for p in patches]), "names": [p[3] for p in patches],
+            "spot_times": spot_times, "times": times}
+
+
+def search_one(view, scorer, host_mix, dev_mix):
+    """One search of a batch: ``mic_array.run_search`` on the mixture's own view and scorer, timed by the wall clock
+    without touching the device and without a word printed -- SRP-PHAT reads the host copy of the mixture, the scoring
+    stages its row of the device stack.  -> (final patches, ``result_record``)."""
+    times = [0.0] * 5
+
+    def timed(slot, fn, *args):
+        t0 = time.time()
+        out = fn(*args)
+        times[slot] = time.time() - t0
+        return out
+    patches, _audio, spot_times, _empty = run_search(view, scorer, timed, host_mix, lambda: dev_mix)
+    return patches, result_record(patches, spot_times, times)
 
 
 def search_batched(joint_model, mixes, concurrent=2, geometries=None, separate=False):
@@ -357,30 +378,7 @@ def search_batched(joint_model, mixes, concurrent=2, geometries=None, separate=F
 
     def search(k):
         own = mp if geometries is None else joint_model.mic_array_for(geometries[k][0], geometries[k][1], method)
-        view, scorer = mixture_view(own), batcher.proxy(k)
-        times = [0.0] * 5
-        t0 = time.time()
-        patch_list, _ = view.Apply_SRP_PHAT(hosts[k])
-        times[0] = time.time() - t0
-        patches, spot_times = [], 0
-        if len(patch_list) > 0:
-            t0 = time.time()
-            kept = view.Spotform_Big_Patch(stack[k], patch_list, scorer)
-            times[1] = time.time() - t0
-            if len(kept) > 0:
-                t0 = time.time()
-                pairs = view.Spotform_Small_Patch_Parallel(stack[k], kept, scorer)
-                times[2] = time.time() - t0
-                if len(pairs) > 0:
-                    t0 = time.time()
-                    _audio, patches, spot_times, _ = view.Clustering_new(pairs)
-                    times[3] = time.time() - t0
-        if len(patches) == 0:
-            patches, spot_times = [], 0                    # the reference's empty-result early returns (:151-199)
-        finals[k] = patches
-        results[k] = {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
-                      "powers": np.array([p[2] for p in patches]), "names": [p[3] for p in patches],
-                      "spot_times": spot_times, "times": times}
+        finals[k], results[k] = search_one(mixture_view(own), batcher.proxy(k), hosts[k], stack[k])
 
     worker_s = []
 

@@ -175,3 +175,20 @@ def max_avg_power(x: np.ndarray, window_size: int = 12000) -> float:
     n = sq.shape[0]
     hi = np.minimum(np.arange(n) + window_size, n)
     return float(np.sqrt(np.abs((c[hi] - c[:n]) / window_size)).max())
+
+
+def mean_removed_energies(sep: np.ndarray, in_place: bool = False):
+    """The reference's host energy loop over the candidate outputs ``sep`` [N,T] (local_utils_3d.py:349-354 /
+    Mic_Array.py:290-295): per row the mean is removed, then power = ``np.sum(x ** 2)`` in the array's own dtype and
+    power2 = ``max_avg_power(x)``.  -> (powers, powers2), two lists of N scalars.  ``in_place``: the mean-removed row
+    is written back into ``sep`` (Mic_Array.py:291 -- the fine stage hands these rows on as the heads' audio);
+    otherwise ``sep`` is left as it is."""
+    powers, powers2 = [], []
+    for i in range(sep.shape[0]):
+        x = sep[i, :] - np.mean(sep[i, :])
+        if in_place:
+            sep[i, :] = x
+            x = sep[i, :]
+        powers.append(np.sum(x ** 2))
+        powers2.append(max_avg_power(x))
+    return powers, powers2

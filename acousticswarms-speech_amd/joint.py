@@ -16,7 +16,7 @@ import time
 
 import numpy as np
 
-from .mic_array import MicArray
+from .mic_array import MicArray, run_search
 from .modes import MODE_NAMES, check_modes
 
 
@@ -194,7 +194,8 @@ class JointModel(object):
         return out
 
     def localize_by_separation(self, mix_data):
-        """The four search stages with the reference's empty-result early returns (:151-199)."""
+        """The four search stages with the reference's empty-result early returns (:151-199): ``mic_array.run_search``
+        under this model's device-synchronised timers, its one upload of the mixture and the reference's printed lines."""
         assert self.previous_config is not None, \
             "Microphone positions and spk range were not provided, did you forget to call .setup()?"
         mp = self.Mic_processor
@@ -208,23 +209,14 @@ class JointModel(object):
             self._mix_dev = self._resident(m)
             self._mix_src = m                             # the resident copy stands for THIS object only
             return mp.Apply_SRP_PHAT(m)
-        patch_list, _ = self._timed(0, srp_stage, mix_data)
-        if self._takes_resident(self.spot_model) and self._mix_dev is not None:
-            mix_data = self._mix_dev
-        if len(patch_list) <= 0:
-            print("No spk picked in SRP-PHAT")
-            return [], [], 0, 0, 0
-        patch_list = self._timed(1, mp.Spotform_Big_Patch, mix_data, patch_list, self.spot_model)
-        if len(patch_list) <= 0:
-            print("No spk picked in Spotform_Big_Patch")
-            return [], [], 0, 0, 0
-        output_pair = self._timed(2, mp.Spotform_Small_Patch_Parallel, mix_data, patch_list, self.spot_model)
-        if len(output_pair) <= 0:
-            print("No spk picked in Spotform_Small_Patch")
-            return [], [], 0, 0, 0
-        audio_final, patch_final, spot_times, _ = self._timed(3, mp.Clustering_new, output_pair)
-        if len(patch_final) <= 0:
-            print("No spk picked in Clustering")
+
+        def stage_mix():                                  # the scoring stages of a HIP model read the resident copy
+            resident = self._takes_resident(self.spot_model) and self._mix_dev is not None
+            return self._mix_dev if resident else mix_data
+        patch_final, audio_final, spot_times, empty = run_search(mp, self.spot_model, self._timed, mix_data,
+                                                                 stage_mix, srp_stage)
+        if empty is not None:
+            print(f"No spk picked in {empty}")
             return [], [], 0, 0, 0
         return patch_final, np.array(audio_final), 0, 0, spot_times
 

@@ -10,7 +10,7 @@ import numpy as np
 from .dense_grid import LatticePatches, lattice_patches
 from .fine_cluster import clusters_of_group
 from .global_cluster import clusters_of_labels
-from .hostdsp import max_avg_power, si_sdr, split_wav, split_wise_sisdr
+from .hostdsp import mean_removed_energies, si_sdr, split_wav, split_wise_sisdr
 from .modes import LATTICE_METHODS, MODE_NAMES, check_modes, need_methods
 from .native import read_back
 from .patch import FS, SPEED_OF_SOUND, Patch, pair_offsets
@@ -76,6 +76,38 @@ def find_merge_center(merged_offests, init_area, mic_positions, Big_patch_center
     else:
         patch.area_points = init_area[:, inside]
     return patch
+
+
+# the four stages as the "No spk picked in ..." lines of the reference name them (JointModel/network.py:151-199)
+SEARCH_STAGES = ("SRP-PHAT", "Spotform_Big_Patch", "Spotform_Small_Patch", "Clustering")
+
+
+def run_search(mic_array, spot_model, timed, mix_data, stage_mix=None, srp_stage=None):
+    """The four search stages on one mixture -- SRP-PHAT, coarse, fine, clustering -- with the reference's empty-result
+    early returns (:151-199), written once: ``JointModel.localize_by_separation`` and the searches of a batch
+    (``batching.search_one``) are this with their own timer and their own mixtures.
+    ``timed(slot, fn, *args)`` runs a stage and keeps its time in ``slot`` 0..3.  Stage 0 is
+    ``srp_stage(mix_data)`` (default: the array's ``Apply_SRP_PHAT``); the scoring stages read ``stage_mix()``, asked
+    for after stage 0 has run (default: ``mix_data``).
+    -> (final patches, their audio, spot_times, empty): ``empty`` is None after a full run, else the entry of
+    ``SEARCH_STAGES`` that came back with nothing, and the first three are then ``[], [], 0``."""
+    def nothing(stage):
+        return [], [], 0, SEARCH_STAGES[stage]
+    patch_list, _ = timed(0, srp_stage or mic_array.Apply_SRP_PHAT, mix_data)
+    if stage_mix is not None:
+        mix_data = stage_mix()
+    if len(patch_list) <= 0:
+        return nothing(0)
+    patch_list = timed(1, mic_array.Spotform_Big_Patch, mix_data, patch_list, spot_model)
+    if len(patch_list) <= 0:
+        return nothing(1)
+    output_pair = timed(2, mic_array.Spotform_Small_Patch_Parallel, mix_data, patch_list, spot_model)
+    if len(output_pair) <= 0:
+        return nothing(2)
+    audio_final, patch_final, spot_times, _ = timed(3, mic_array.Clustering_new, output_pair)
+    if len(patch_final) <= 0:
+        return nothing(3)
+    return patch_final, audio_final, spot_times, None
 
 
 class MicArray(object):
@@ -472,11 +504,7 @@ class MicArray(object):
             for g, big, patches, centre in zip(mine, bigs, fines, centres):
                 sep = sep_all[pos:pos + len(patches)]
                 pos += len(patches)
-                powers, powers2 = [], []
-                for j in range(len(patches)):
-                    sep[j, :] = sep[j, :] - np.mean(sep[j, :])             # in place, as :291
-                    powers.append(np.sum(sep[j, :] ** 2))
-                    powers2.append(max_avg_power(sep[j, :]))
+                powers, powers2 = mean_removed_energies(sep, in_place=True)    # in place, as :291: the heads' audio
                 output_pair.extend(self._cluster_group(
                     g, big, patches, powers, powers2, big.area_points, centre, T_len, thr_new, sample_gt,
                     lambda k, h, sep=sep: si_sdr(sep[k, :], sep[h]), lambda heads, sep=sep: [sep[h, :] for h in heads]))

@@ -8,7 +8,7 @@ candidate lists and applies the reference's thresholds to the returned energies.
 """
 import numpy as np
 
-from .hostdsp import max_avg_power
+from .hostdsp import mean_removed_energies
 from .patch import FS as FS_F, SPEED_OF_SOUND as SPEED_OF_SOUND_F, Patch, pair_offsets
 
 # sep/helpers/constants.py:31-41
@@ -150,12 +150,7 @@ def stage_energies(spot_model, mix_data, patch_list, strict):
     if hasattr(spot_model, "shift_and_score"):
         en = spot_model.shift_and_score(mix_data, patch_list, Strict=strict, keep_waveforms=False)
         return en[:, 0], en[:, 1]
-    sep = spot_model.shift_and_sep(mix_data, patch_list, Strict=strict)
-    p, pw = [], []
-    for i in range(sep.shape[0]):
-        x = sep[i, :] - np.mean(sep[i, :])
-        p.append(np.sum(x ** 2))
-        pw.append(max_avg_power(x))
+    p, pw = mean_removed_energies(spot_model.shift_and_sep(mix_data, patch_list, Strict=strict))
     return np.array(p), np.array(pw)
 
 

@@ -9,13 +9,11 @@ of mixtures in packed device calls (no counterpart in the reference).  All arith
 reached through ``torch.ops.asw.sep_infer`` / ``sep_forward``; PyTorch is used for device
 memory and streams only.  There is no CPU path.
 """
-from collections import OrderedDict
-from ctypes import byref, c_size_t, c_void_p
-
 import numpy as np
 
 from . import native
 from .config import SEP_FULL, SepConfig, sep_param_shapes
+from .device_model import DeviceModel
 
 MAX_SEQUENCES = 64       # S (or B*S) per library call
 
@@ -50,111 +48,35 @@ def pack_items(counts, cap: int = MAX_SEQUENCES):
     return calls
 
 
-def check_batch(mixes, sample_lists):
-    """Shapes of an ``infer_batch`` call, looked at before any device work: one sample list per mixture, every mixture
-    [M, T] of one shape.  ``ValueError`` otherwise.  -> (M, T), (0, 0) for an empty batch."""
-    if len(mixes) != len(sample_lists):
-        raise ValueError(f"{len(sample_lists)} sample lists for {len(mixes)} mixtures")
+def one_mixture_shape(mixes):
+    """Every mixture of a batch is [M, T] and all have one shape (they share a [K,M,T] device stack): ``ValueError``
+    otherwise.  Looks at shapes only.  -> (M, T), None for an empty batch."""
     shapes = [tuple(int(v) for v in np.shape(m)) for m in mixes]
     if any(len(sh) != 2 for sh in shapes):
         raise ValueError("every mixture must be [M, T]")
     if len(set(shapes)) > 1:
         raise ValueError(f"the mixtures of one batch must share M and T, got the shapes {sorted(set(shapes))}")
-    return shapes[0] if shapes else (0, 0)
+    return shapes[0] if shapes else None
 
 
-class SepModel:
-    PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2, "f16x3_safe": 3}   # as SpotModel.PRECISIONS
+def check_batch(mixes, sample_lists):
+    """Shapes of an ``infer_batch`` call, looked at before any device work: one sample list per mixture, every mixture
+    [M, T] of one shape (``one_mixture_shape``).  ``ValueError`` otherwise.  -> (M, T), (0, 0) for an empty batch."""
+    if len(mixes) != len(sample_lists):
+        raise ValueError(f"{len(sample_lists)} sample lists for {len(mixes)} mixtures")
+    return one_mixture_shape(mixes) or (0, 0)
+
+
+class SepModel(DeviceModel):
+    C_PREFIX, CONFIG_C, NAME, HOT_PATH = "sep", native.SepConfigC, "SepModel", "separation network"
+    param_shapes = staticmethod(sep_param_shapes)
 
     def __init__(self, cfg: SepConfig = SEP_FULL, state_dict=None, precision: str = "f32"):
-        if precision not in self.PRECISIONS:
-            raise RuntimeError(f"precision must be one of {list(self.PRECISIONS)}")
-        self.cfg = cfg
+        DeviceModel.__init__(self, cfg, precision)
         self.n_mics = cfg.n_mics
         self.max_n_speaker = cfg.max_speakers
-        self.precision = precision
-        self.device = None
-        self._h = None
-        self._sd = None
         if state_dict is not None:
             self.load_state_dict(state_dict)
-
-    # ---- weights -------------------------------------------------------------
-    def load_state_dict(self, sd, strict: bool = True):
-        """Reference-format state dict (numpy arrays or torch tensors), strict by default."""
-        want = OrderedDict(sep_param_shapes(self.cfg))
-        clean = OrderedDict()
-        for k, v in sd.items():
-            a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
-            clean[k] = np.ascontiguousarray(a, dtype=np.float32)
-        missing = [k for k in want if k not in clean]
-        extra = [k for k in clean if k not in want]
-        if strict and (missing or extra):
-            raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:3]} unexpected {extra[:3]}")
-        for k, shp in want.items():
-            if k in clean and tuple(clean[k].shape) != tuple(shp):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(clean[k].shape)} vs {tuple(shp)}")
-        self._sd = clean
-        if self._h is not None:
-            import torch
-            with torch.cuda.device(self.device):
-                self._upload()
-        return self
-
-    def _upload(self):
-        L = native.lib()
-        for k, a in self._sd.items():
-            native.check(L.asw_sep_set_param(self._h, k.encode(), c_void_p(a.ctypes.data), a.size))
-        native.check(L.asw_sep_finalize(self._h))
-
-    def to(self, device=None):
-        import torch
-        if device is None:
-            return self
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("SepModel runs only on an MI355X (device 'cuda'); there is no CPU path")
-        if not torch.cuda.is_available():
-            raise RuntimeError("no HIP device visible: the separation network has no CPU fallback")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        L = native.lib()
-        with torch.cuda.device(device):
-            if self._h is not None:
-                L.asw_sep_destroy(self._h)
-                self._h = None
-            h = c_void_p()
-            cc = native.SepConfigC.from_config(self.cfg)
-            native.check(L.asw_sep_create(byref(cc), byref(h)))
-            self._h = h
-            native.check(L.asw_sep_set_precision(self._h, self.PRECISIONS[self.precision]))
-            self.device = device
-            if self._sd is not None:
-                self._upload()
-        return self
-
-    def eval(self):
-        return self
-
-    def set_precision(self, precision: str):
-        if precision not in self.PRECISIONS:
-            raise RuntimeError(f"precision must be one of {list(self.PRECISIONS)}")
-        self.precision = precision
-        if self._h is not None:
-            native.check(native.lib().asw_sep_set_precision(self._h, self.PRECISIONS[precision]))
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                native.lib().asw_sep_destroy(self._h)
-        except Exception:
-            pass
-
-    def _need(self):
-        if self._h is None:
-            raise RuntimeError("SepModel.to('cuda') must be called before inference")
-        if self._sd is None:
-            raise RuntimeError("SepModel has no weights: call load_state_dict()")
 
     # ---- device-level entry (tensors stay on the GPU) --------------------------
     def infer_device(self, mix_dev, offsets_dev):
@@ -256,15 +178,3 @@ class SepModel:
         return native.torch_ops().sep_forward_counts(self._h.value, mix, [int(v) for v in ns], self.n_mics, self.max_n_speaker)
 
     __call__ = forward
-
-    def get_tap(self, name: str, shape=None):
-        """Intermediate activation of the last call (channels-last), for parity tests."""
-        import torch
-        n = c_size_t()
-        L = native.lib()
-        native.check(L.asw_sep_get_tap(self._h, name.encode(), None, 0, byref(n), None))
-        buf = torch.empty((n.value,), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            native.check(L.asw_sep_get_tap(self._h, name.encode(), native.ptr(buf), n.value, byref(n),
-                                           native.current_stream()))
-        return buf if shape is None else buf.view(*shape)

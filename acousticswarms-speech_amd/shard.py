@@ -39,10 +39,10 @@ def shard_groups(sizes: Sequence[int], world: int) -> List[List[int]]:
 def offsets_fingerprint(patches_or_offsets) -> int:
     """CRC32 of the rounded int32 offsets of a candidate list (ndarray [N,P] or patches)."""
     import zlib
+    from .spot import offsets_from_patches
     if len(patches_or_offsets) == 0:
         return 0
-    offs = np.stack([np.asarray(getattr(p, "sample_offset", p), dtype=np.float64) for p in patches_or_offsets])
-    return zlib.crc32(np.ascontiguousarray(np.rint(offs.astype(np.float32)).astype(np.int32)).tobytes())
+    return zlib.crc32(np.ascontiguousarray(offsets_from_patches(patches_or_offsets)).tobytes())
 
 
 def assert_same_on_all_ranks(dist, group, device, what: str, *values: int):
@@ -135,12 +135,10 @@ class ShardedSpotModel:
             return np.zeros((0, 2))
         if hasattr(self.inner, "shift_and_score"):
             return self.inner.shift_and_score(mix, patches, Strict=self._strict, keep_waveforms=False)
-        from .hostdsp import max_avg_power
+        from .hostdsp import mean_removed_energies
         sep = self.inner.shift_and_sep(mix, patches, Strict=self._strict)
         out = np.zeros((sep.shape[0], 2))
-        for i in range(sep.shape[0]):
-            x = sep[i, :] - np.mean(sep[i, :])
-            out[i] = (np.sum(x ** 2), max_avg_power(x))
+        out[:, 0], out[:, 1] = mean_removed_energies(sep)
         return out
 
     def shift_and_score(self, mix, patch_list, Strict=0, keep_waveforms=False):
@@ -239,7 +237,7 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
 
     ``joint_model.spot_model`` must be the plain per-rank model here.  Returns, on every rank and
     in mixture order, a list of dicts {centres [K,3], powers [K], names, spot_times, times[5]}."""
-    from .batching import check_geometries, no_full_collections
+    from .batching import check_geometries, no_full_collections, result_record
     check_geometries(mixes, geometries)
     if separate and getattr(joint_model, "sep_model", None) is None:
         raise RuntimeError("separate=True needs a separation model (JointModel(sep_model=None))")
@@ -276,10 +274,7 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
                     if own:
                         joint_model.use_geometry(geometries[k][0], geometries[k][1])
                     patches, _audio_loc, audio, _d0, _d1, spot_times = joint_model.forward(mixes[k])
-                    local.append((k, {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
-                                      "powers": np.array([p[2] for p in patches]),
-                                      "names": [p[3] for p in patches],
-                                      "spot_times": spot_times, "times": list(joint_model.times)}))
+                    local.append((k, result_record(patches, spot_times, list(joint_model.times))))
                     if separate:
                         local[-1][1]["audio"] = np.empty((0, np.shape(mixes[k])[-1]), dtype=np.float32) if audio is None \
                             else np.asarray(audio, dtype=np.float32)
