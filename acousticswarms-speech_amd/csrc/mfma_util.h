@@ -1,6 +1,6 @@
 // mfma_util.h -- device helpers shared by the MFMA kernels (convgemm.hip, pipegemm.hip, resconv.hip, resstack.hip, downconv.hip,
-// attention_mfma.hip, sep_kernels.hip): vector types, the buffer-descriptor activation load, the f32 row product of the
-// attention kernels and the fp32 -> fp16 hi / lo operand split of the f16x3 mode.
+// attention.hip): vector types, the accumulator row mapping, the buffer-descriptor activation load, the f32 row product of
+// the attention kernels and the fp32 -> fp16 hi / lo operand split of the f16x3 mode.
 #pragma once
 #include "asw_common.h"
 #include "wave_util.h"
@@ -12,6 +12,9 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 using asw::wave_sum;
+
+// row, within a 32 x 32 MFMA accumulator block, that register r of a lane in half lh = lane >> 5 holds (its column is lane & 31)
+__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
 // acc += A B^T of two row-major fp32 operands on v_mfma_f32_32x32x2_f32 (an fmaf chain: exact fp32): a_row / b_row
 // already include this lane's (row, 4 * (lane >> 5)) offset; 8 k per step, KSTEPS = K / 8

@@ -1,4 +1,4 @@
-// misc_kernels.hip -- the memory-bound / small kernels around the MFMA GEMMs.
+// misc_kernels.hip -- the memory-bound / small kernels around the MFMA GEMMs (the attention kernels are in attention.hip).
 #include "asw_common.h"
 #include "wave_util.h"
 
@@ -83,101 +83,6 @@ __global__ __launch_bounds__(256) void gn_glu_kernel(const float* __restrict__ r
     ASW_GLU(x) ASW_GLU(y) ASW_GLU(z) ASW_GLU(w)
 #undef ASW_GLU
     *reinterpret_cast<float4*>(ob + t * C + c) = o;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Self-attention core (nn.MultiheadAttention inside nn.TransformerEncoderLayer,
-// network.py:254): per (batch, head, 16-query tile) a flash-style sweep over 128-key
-// tiles held in LDS, online softmax, fp32 VALU.  The bottleneck is 1-4 % of the
-// forward's FLOPs (sequence T/256 = 188 or 563), so this kernel is written for
-// exactness and bounded LDS rather than MFMA rate.
-// thread = (query q = tid/16, sub-lane sl = tid%16): scores for keys sl+16*jj,
-// output dims sl+16*i.
-// ---------------------------------------------------------------------------
-constexpr int ATT_BQ = 16, ATT_KT = 128, ATT_MAXD = 8;   // head_dim <= 128
-
-__global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, int L, int d, int nhead,
-                                                        float* __restrict__ ctx) {
-  extern __shared__ __align__(16) float smem[];
-  const int hd = d / nhead;
-  const int ldk = hd + 1;
-  float* Qs = smem;                       // [BQ][hd+1]
-  float* Ks = Qs + ATT_BQ * ldk;          // [KT][hd+1]
-  float* Vs = Ks + ATT_KT * ldk;          // [KT][hd]
-  float* Ps = Vs + ATT_KT * hd;           // [BQ][KT]
-  const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * ATT_BQ;
-  const int tid = threadIdx.x, q = tid >> 4, sl = tid & 15;
-  const float* base = qkv + (long)b * L * 3 * d;
-  const float scale = 1.0f / sqrtf((float)hd);
-  const int nd = hd >> 4;                 // output dims per thread
-
-  for (int i = tid; i < ATT_BQ * hd; i += 256) {
-    const int r = i / hd, c = i - r * hd;
-    Qs[r * ldk + c] = (q0 + r < L) ? base[(long)(q0 + r) * 3 * d + h * hd + c] * scale : 0.f;
-  }
-  float acc[ATT_MAXD];
-#pragma unroll
-  for (int i = 0; i < ATT_MAXD; ++i) acc[i] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-
-  for (int k0 = 0; k0 < L; k0 += ATT_KT) {
-    const int kn = L - k0 < ATT_KT ? L - k0 : ATT_KT;
-    __syncthreads();                      // previous tile fully consumed (also covers Qs)
-    for (int i = tid; i < ATT_KT * hd; i += 256) {
-      const int r = i / hd, c = i - r * hd;
-      float kv = 0.f, vv = 0.f;
-      if (r < kn) {
-        const float* row = base + (long)(k0 + r) * 3 * d + h * hd + c;
-        kv = row[d];
-        vv = row[2 * d];
-      }
-      Ks[r * ldk + c] = kv;
-      Vs[r * hd + c] = vv;
-    }
-    __syncthreads();
-    // scores for this thread's keys
-    float sc[ATT_KT / 16];
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int jj = 0; jj < ATT_KT / 16; ++jj) {
-      const int j = sl + 16 * jj;
-      float s = 0.f;
-      for (int c = 0; c < hd; ++c) s = fmaf(Qs[q * ldk + c], Ks[j * ldk + c], s);
-      sc[jj] = (j < kn) ? s : -INFINITY;
-      tmax = fmaxf(tmax, sc[jj]);
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) tmax = fmaxf(tmax, __shfl_xor(tmax, o, 64));
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = (m_run == -INFINITY) ? 0.f : expf(m_run - m_new);
-    float psum = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < ATT_KT / 16; ++jj) {
-      const float pv = (sc[jj] == -INFINITY) ? 0.f : expf(sc[jj] - m_new);
-      Ps[q * ATT_KT + sl + 16 * jj] = pv;
-      psum += pv;
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) psum += __shfl_xor(psum, o, 64);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < ATT_MAXD; ++i) acc[i] *= alpha;
-    for (int j = 0; j < kn; ++j) {
-      const float pv = Ps[q * ATT_KT + j];
-#pragma unroll
-      for (int i = 0; i < ATT_MAXD; ++i)
-        if (i < nd) acc[i] = fmaf(pv, Vs[j * hd + sl + 16 * i], acc[i]);
-    }
-  }
-  if (q0 + q < L) {
-    const float inv = 1.0f / l_run;
-    float* o = ctx + ((long)b * L + q0 + q) * d + h * hd;
-#pragma unroll
-    for (int i = 0; i < ATT_MAXD; ++i)
-      if (i < nd) o[sl + 16 * i] = acc[i] * inv;
   }
 }
 
@@ -752,34 +657,6 @@ extern "C" int asw_gn_finalize(const float* stats, int n_partials, int B, int T,
   ASW_CHECK_ARG(stats && mr, "gn_finalize: null pointer");
   ASW_CHECK_ARG(B > 0 && T > 0 && C > 0 && n_partials > 0, "gn_finalize: bad shape");
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, asw::as_stream(stream), stats, n_partials, T, C, eps, mr);
-  ASW_LAUNCH_CHECK();
-  return ASW_OK;
-}
-
-namespace asw { int attention_mfma(const float* qkv, int B, int L, int d, int nhead, float* ctx, hipStream_t s, int precision); }
-
-extern "C" int asw_attention(const float* qkv, int B, int L, int d, int nhead, float* ctx, void* stream) {
-  return asw_attention_prec(qkv, B, L, d, nhead, 0, ctx, stream);
-}
-
-extern "C" int asw_attention_prec(const float* qkv, int B, int L, int d, int nhead, int precision, float* ctx, void* stream) {
-  ASW_CHECK_ARG(qkv && ctx, "attention: null pointer");
-  ASW_CHECK_ARG(precision >= 0 && precision <= 2, "attention: precision %d", precision);
-  ASW_CHECK_ARG(B > 0 && L > 0 && nhead > 0 && d % nhead == 0, "attention: bad shape");
-  ASW_CHECK_ARG(B <= 65535 && nhead <= 65535, "attention: grid too large");
-  {
-    const int rc = asw::attention_mfma(qkv, B, L, d, nhead, ctx, asw::as_stream(stream), precision);   // head_dim 128: MFMA kernels
-    if (rc != 1) return rc;
-  }
-  const int hd = d / nhead;
-  ASW_CHECK_ARG(hd % 16 == 0 && hd <= 16 * ATT_MAXD, "attention: head_dim %d must be a multiple of 16, <= 128", hd);
-  ASW_CHECK_ARG(B <= 65535 && nhead <= 65535, "attention: grid too large");
-  const size_t smem = sizeof(float) * ((size_t)ATT_BQ * (hd + 1) + (size_t)ATT_KT * (hd + 1) + (size_t)ATT_KT * hd +
-                                       (size_t)ATT_BQ * ATT_KT);
-  static asw::SmemAttr smem_attr;                      // per device
-  if (int rc = smem_attr.ensure(reinterpret_cast<const void*>(attention_kernel), smem)) return rc;
-  dim3 grid(asw::cdiv(L, ATT_BQ), nhead, B);
-  hipLaunchKernelGGL(attention_kernel, grid, dim3(256), smem, asw::as_stream(stream), qkv, L, d, nhead, ctx);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
 }

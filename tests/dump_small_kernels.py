@@ -63,6 +63,20 @@ def kernels(out):
     L, d, H = 70, 128, 2
     out["relpos_attention_L70_hd64"] = ops.relpos_attention(rand(2, L, 3 * d, scale=0.7), rand(2 * L - 1, d, scale=0.7),
                                                             rand(d, scale=0.3), rand(d, scale=0.3), H, 1.0 / d ** 0.5)
+    # attention over time, every kernel of csrc/attention.hip: the short MFMA kernels at 1, 3 and 5 key tiles and their
+    # last length (320), the flash kernel from its first length (321); the VALU kernel at head_dim 16, 32, 48, 64 and
+    # 1, 2, 3 key tiles of 128; rel-pos on VALU (head_dim 16, 32) and MFMA (64): one tile, exactly one, a ragged tail, four
+    for L in (5, 64, 188, 320, 321, 563):
+        qkv = rand(2, L, 3 * 256, scale=0.7)
+        for precision in ("f32", "f16x3", "f16"):
+            out[f"attention_{precision}_L{L}_hd128"] = ops.attention(qkv, 2, precision=precision)
+    for d in (128, 256, 96, 512):
+        for L in (5, 130, 300):
+            out[f"attention_f32_L{L}_hd{d // (2 if d == 96 else 8)}"] = ops.attention(rand(2, L, 3 * d, scale=0.7), 2 if d == 96 else 8)
+    for d in (128, 256, 512):
+        for L in (5, 64, 70, 200):
+            out[f"relpos_attention_L{L}_hd{d // 8}"] = ops.relpos_attention(
+                rand(2, L, 3 * d, scale=0.7), rand(2 * L - 1, d, scale=0.7), rand(d, scale=0.3), rand(d, scale=0.3), 8, 1.0 / d ** 0.5)
     for T in (4000, 4001):
         y = rand(5, T) + 0.1
         out[f"energies_T{T}_w1000"] = ops.energies(y, 1000)

@@ -163,11 +163,13 @@ def test_linear_residual_layernorm(ops, d, f, L, B):
 
 
 @pytest.mark.parametrize("L,d,nhead,B", [(19, 128, 8, 3), (188, 1024, 8, 2), (300, 1024, 8, 1), (150, 1024, 8, 2),
-                                         (192, 1024, 8, 1), (33, 1024, 8, 2), (47, 512, 4, 2), (563, 1024, 8, 1), (700, 1024, 8, 1)])
+                                         (192, 1024, 8, 1), (33, 1024, 8, 2), (47, 512, 4, 2), (563, 1024, 8, 1), (700, 1024, 8, 1),
+                                         (150, 256, 8, 2), (5, 256, 8, 2), (150, 96, 2, 1), (150, 512, 8, 1)])
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
 def test_attention(ops, L, d, nhead, B, precision):
     """f32: exact fp32 MFMA; f16x3: both products on the f16 MFMA with split operands (head_dim 128, L <= 352; other
-    shapes run the f32 kernels), the softmax in fp32 either way: same bar."""
+    shapes run the f32 kernels), the softmax in fp32 either way: same bar.  The last four shapes are the VALU kernel at
+    head_dim 32 (two key tiles; inside one query tile), 48 and 64; (19, 128, 8, 3) is head_dim 16."""
     qkv = _rand(B, L, 3 * d, seed=28)
     hd = d // nhead
     q, k, v = qkv.split(d, dim=-1)

@@ -86,9 +86,11 @@ def test_glu_and_dwconv(ops):
         assert _relerr(got.cpu(), want) < 2e-6
 
 
-@pytest.mark.parametrize("L,d,H", [(75, 128, 8), (200, 256, 8), (130, 512, 8), (64, 512, 8), (750, 512, 8)])
+@pytest.mark.parametrize("L,d,H", [(75, 128, 8), (200, 256, 8), (130, 512, 8), (64, 512, 8), (750, 512, 8),
+                                   (5, 128, 8), (64, 256, 8)])
 def test_relpos_attention(ops, L, d, H):
-    """RelPosMHAXL core against the pad-and-reshape rel_shift statement."""
+    """RelPosMHAXL core against the pad-and-reshape rel_shift statement.  The last two shapes: one partly filled query tile
+    of the VALU kernel (head_dim 16), exactly one key tile at head_dim 32."""
     B, hd = 2, d // H
     qkv = _rand(B, L, 3 * d, seed=11, scale=0.7)
     P = _rand(2 * L - 1, d, seed=12, scale=0.7)
