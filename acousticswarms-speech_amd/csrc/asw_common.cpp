@@ -83,6 +83,20 @@ extern "C" int asw_pack_fragments_f16(const float* Wt, int N, int K, uint16_t* h
   return rc;
 }
 
+// UpFeed (resstack.hip): register 8 s + j of a 32 x 32 accumulator block, lane half h, is its row 16 s + 8 (j >> 2) + 4 h +
+// (j & 3), and as an MFMA operand that register is k = 8 h + j of k-step s
+extern "C" int asw_up_feed_kperm(int k) { return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1); }
+
+extern "C" int asw_pack_up_feed_f16(const float* Wt, int N, int K, uint16_t* hi, uint16_t* lo, int32_t* w_shift) {
+  ASW_CHECK_ARG(Wt && N > 0 && K > 0 && K % 16 == 0, "pack_up_feed: K %% 16 required (N=%d K=%d)", N, K);
+  float* wp = new float[(size_t)N * K];
+  for (int n = 0; n < N; ++n)
+    for (int k = 0; k < K; ++k) wp[(size_t)n * K + k] = Wt[(size_t)n * K + (k & ~15) + asw_up_feed_kperm(k & 15)];
+  const int rc = asw_pack_fragments_f16(wp, N, K, hi, lo, w_shift);
+  delete[] wp;
+  return rc;
+}
+
 // ---- residue-image A feed: the schedule of pipe_mainloop_res, enumerated on the host ----
 namespace asw {
 bool residue_feed_on() {                  // like ASW_NO_RESSTACK: set to anything, "0" included, means off

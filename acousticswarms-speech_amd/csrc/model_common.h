@@ -89,6 +89,20 @@ struct WBuf {
     ASW_HIP(hipMemcpy(flo, vl.data(), h.size() * 2, hipMemcpyHostToDevice));
     return ASW_OK;
   }
+  // the K-permuted fragment copy alone, for the UpFeed of a residual stack (asw_resstack_args.up_hi): split and
+  // power-of-two pre-scale as upload_gemm's
+  int upload_up_feed(const std::vector<float>& h, int N, int K) {
+    std::vector<uint16_t> vh(h.size()), vl(h.size());
+    int rc = asw_pack_up_feed_f16(h.data(), N, K, vh.data(), vl.data(), &shift);
+    if (rc) return rc;
+    if (fhi) { (void)hipFree(fhi); fhi = nullptr; }
+    if (flo) { (void)hipFree(flo); flo = nullptr; }
+    if (hipMalloc(&fhi, h.size() * 2) != hipSuccess || hipMalloc(&flo, h.size() * 2) != hipSuccess)
+      return asw::set_error(ASW_ERR_NOMEM, "hipMalloc(%zu halves)", h.size());
+    ASW_HIP(hipMemcpy(fhi, vh.data(), h.size() * 2, hipMemcpyHostToDevice));
+    ASW_HIP(hipMemcpy(flo, vl.data(), h.size() * 2, hipMemcpyHostToDevice));
+    return ASW_OK;
+  }
   void bind(asw_convgemm_args& a, int precision) const {
     a.Wt = f32.p; a.Wt_hi = hi; a.Wt_lo = lo; a.w_shift = shift; a.precision = precision;
     a.Wf_hi = fhi; a.Wf_lo = flo;
@@ -191,13 +205,34 @@ inline size_t resstack_fuse_count(const std::vector<ResLayer>& res, size_t j, in
 // the two fp16 planes, the composed layer-0 weight and the 1x1 weight that rebuilds the residual.
 struct SrcFeed { const void* hi; const void* lo; const WBuf* comp; const WBuf* pre; };
 
+// Output of a residual stack taken as the raw rows of the next decoder block's transposed convolution
+// (asw_resstack_args.up_hi): the permuted-K weight, the bias, the skip tensor, the raw rows and their partial sums.
+// `tiles` receives the number of partial sums per item.
+struct UpFeed { const WBuf* w; const float* bias; const float* skip; float* out; float* stats; int tiles; };
+
+// the last launch of a 64-channel stack that runs through asw_resstack64_f16x3: its first layer and its layer count
+inline void resstack_last_launch(const std::vector<ResLayer>& res, int K, size_t& j0, size_t& n) {
+  j0 = 0;
+  n = resstack_fuse_count(res, 0, K);
+  while (j0 + n < res.size()) { j0 += n; n = resstack_fuse_count(res, j0, K); }
+}
+inline int up_feed_tiles(const std::vector<ResLayer>& res, int K, int T, bool glu) {
+  size_t j0, n;
+  resstack_last_launch(res, K, j0, n);
+  int32_t dil[3] = {1, 1, 1};
+  for (size_t i = 0; i < n; ++i) dil[i] = res[j0 + i].dil;
+  return asw_resstack_tiles(T, K, (int)n, dil, glu && j0 == 0);
+}
+
 inline int run_res(const std::vector<ResLayer>& res, int prec, int B, int T, int ch, int K, float* x, float* p, float* q,
-            float** final_out, hipStream_t s, const GluSrc* glu = nullptr, const SrcFeed* feed = nullptr) {
+            float** final_out, hipStream_t s, const GluSrc* glu = nullptr, const SrcFeed* feed = nullptr, UpFeed* up = nullptr) {
   // ping-pong: layer 0 reads x (kept intact), later layers alternate p/q
   const float* in = glu ? glu->raw : x;
   float* outb = p;
   if (feed && !(resstack_ok(res, prec, ch, K) && prec == 1 && resstack_fuse_count(res, 0, K) == 2))
     return asw::set_error(ASW_ERR_STATE, "run_res: the source-fed form needs the fused f16x3 pair");
+  if (up && !(resstack_ok(res, prec, ch, K) && prec == 1))
+    return asw::set_error(ASW_ERR_STATE, "run_res: UpFeed needs the f16x3 stack kernel");
   if (resstack_ok(res, prec, ch, K)) {
     size_t j = 0;
     while (j < res.size()) {
@@ -218,6 +253,15 @@ inline int run_res(const std::vector<ResLayer>& res, int prec, int B, int T, int
         a.src_hi = feed->hi; a.src_lo = feed->lo;
         a.layer[0].Wf_hi = feed->comp->fhi; a.layer[0].Wf_lo = feed->comp->flo; a.layer[0].w_shift = feed->comp->shift;
         a.pre_hi = feed->pre->fhi; a.pre_lo = feed->pre->flo; a.pre_shift = feed->pre->shift;
+      }
+      if (up && j + n == res.size()) {
+        // the last launch hands its rows to the next block's transposed convolution; the stack's output is not written
+        a.out = nullptr;
+        a.up_hi = up->w->fhi; a.up_lo = up->w->flo; a.up_shift = up->w->shift; a.up_bias = up->bias; a.up_skip = up->skip;
+        a.up_out = up->out; a.up_stats = up->stats;
+        up->tiles = up_feed_tiles(res, K, T, glu != nullptr);
+        if (up->tiles < 0) return up->tiles;
+        outb = nullptr;
       }
       int rc = asw_resstack64_f16x3(&a, s);
       if (rc) return rc;
@@ -324,7 +368,8 @@ struct DecBlock { std::vector<ResLayer> res; DevBuf gn_g, gn_b; };
 // The convolutions a window gate folds into (embed1, spot network.py:101,186): each encoder's down conv (gate per input
 // channel) and each decoder's transposed conv (gate per output channel).  The spot network packs one set per window
 // embedding, the separation network one without a gate.
-struct GatedConvs { std::vector<WBuf> down_wt, up_wt; std::vector<DevBuf> up_bias; };
+// up_feed[j]: up_wt[j] with the K order of a residual stack's UpFeed, where block j can be fed that way (Trunk::up_feed_shape).
+struct GatedConvs { std::vector<WBuf> down_wt, up_wt, up_feed; std::vector<DevBuf> up_bias; };
 struct Tap { const float* p; size_t numel; };
 using ParamList = std::vector<std::pair<std::string, size_t>>;
 
@@ -349,6 +394,8 @@ struct Trunk {
   bool fuse_mask = true;                   // f16x3: GroupNorm + GLU on load; bypass + mask encoder + decoder taps in one launch
   bool want_src = false;                   // the network has a source-fed front end (the spot network's candidate loop)
   bool src_stack = true;                   // ... and uses it (asw_spot_set_source_stack)
+  bool want_up = false;                    // the network feeds 64 -> 64 decoder blocks from the stack in front (the candidate loop)
+  bool up_fusion = true;                   // ... and uses it (asw_spot_set_up_fusion)
 
   std::vector<int> enc_cin, enc_cout;      // per encoder block
   std::vector<int> dec_cin, dec_cout, dec_stride;   // per decoder block, in execution order
@@ -531,6 +578,7 @@ struct Trunk {
     o.down_wt.clear(); o.down_wt.resize(tc.depth);
     o.up_wt.clear(); o.up_wt.resize(tc.depth);
     o.up_bias.clear(); o.up_bias.resize(tc.depth);
+    o.up_feed.clear(); o.up_feed.resize(tc.depth);
     for (int i = 0; i < tc.depth; ++i) {
       const std::string p = "encoder.module_list." + std::to_string(i);
       const std::vector<float> g = gate(p);
@@ -546,6 +594,7 @@ struct Trunk {
       pack_conv_transpose(P(p + ".upsample.conv.weight"), P(p + ".upsample.conv.bias"), ci, co2, s,
                           g.empty() ? nullptr : g.data(), wt, bb);
       if ((rc = o.up_wt[j].upload_gemm(wt, s * co2, ci))) return rc;
+      if (want_up && up_feed_shape(j) && (rc = o.up_feed[j].upload_up_feed(wt, s * co2, ci))) return rc;
       UP(o.up_bias[j], bb);
     }
     return ASW_OK;
@@ -562,6 +611,19 @@ struct Trunk {
     return want_src && src_stack && precision == 1 && src_wt.fhi && src_pre.fhi && !enc.empty() &&
            resstack_ok(enc[0].res, precision, enc_cin[0], tc.kernel_size) &&
            resstack_fuse_count(enc[0].res, 0, tc.kernel_size) == 2;
+  }
+  // decoder block j is a 64 -> 64 channel stride-2 block behind a 64-channel block: the shape a stack's UpFeed serves
+  bool up_feed_shape(int j) const {
+    return j >= 1 && dec_cin[j] == 64 && dec_cout[j] == 64 && dec_stride[j] == 2 && dec_cout[j - 1] == 64;
+  }
+  // the candidate loop lets block j - 1's stack apply block j's transposed convolution.  f16x3 and f16x3_safe alike: the
+  // operand is a LayerNorm output plus a skip tensor, a Normed site (site()), which both modes run on the split kernels,
+  // and the raw rows leave through a statistics epilogue, which has no range guard in either.
+  // ASW_NO_UP_FUSION=1 keeps the separate launch whatever the handle says (A/B measurements).
+  bool up_path(const GatedConvs& g, int j) const {
+    static const bool off = getenv("ASW_NO_UP_FUSION") != nullptr;
+    return !off && want_up && up_fusion && precision == 1 && up_feed_shape(j) && g.up_feed[j].fhi &&
+           resstack_ok(dec[j - 1].res, precision, 64, tc.kernel_size);
   }
   // the shape of a batch of B sequences of T samples and its level buffers: the head of the workspace
   void layout_levels(int B, int T, Arena& a, TrunkPlan& pl) const {
@@ -598,7 +660,13 @@ struct Trunk {
       const int lvl = depth - j;             // input level of decoder block j
       const int s = dec_stride[j], co2 = 2 * dec_cout[j];
       pl.raw_up[j] = a.take<float>((size_t)B * pl.Tl[lvl] * s * co2);
-      pl.st_up[j] = a.take<float>((size_t)B * 4 * asw_convgemm_stats_tiles(pl.Tl[lvl], s * co2));
+      int tiles = asw_convgemm_stats_tiles(pl.Tl[lvl], s * co2);
+      if (want_up && up_feed_shape(j))           // fed by block j - 1's stack: its row tiles, whichever is more
+        for (int glu = 0; glu < 2; ++glu) {
+          const int t = up_feed_tiles(dec[j - 1].res, tc.kernel_size, pl.Tl[lvl], glu != 0);
+          tiles = t > tiles ? t : tiles;
+        }
+      pl.st_up[j] = a.take<float>((size_t)B * 4 * tiles);
       pl.mr_up[j] = a.take<float>((size_t)B * 4);
     }
   }
@@ -652,22 +720,32 @@ struct Trunk {
   }
 
   // decoder (network.py:180-200,233-238): x, the bottleneck's output on entry, is the last block's output on return
-  int decode(TrunkPlan& pl, const GatedConvs& g, const float*& x, hipStream_t s) {
+  // up: the candidate loop; a 64 -> 64 block's transposed convolution is then applied by the stack in front of it
+  // (up_path), whose own output -- and with it the block's tap -- does not exist
+  int decode(TrunkPlan& pl, const GatedConvs& g, const float*& x, hipStream_t s, bool up = false) {
     const int B = pl.B, K = tc.kernel_size;
     int rc;
+    int fed_tiles = 0;                       // > 0: block j - 1's stack has written raw_up[j] and that many partial sums per item
     for (int j = 0; j < tc.depth; ++j) {
       const int lvl = tc.depth - j, ci = dec_cin[j], co = dec_cout[j], st = dec_stride[j];
-      asw_convgemm_args a = {};
-      a.A = x; a.A2 = pl.X[lvl]; g.up_wt[j].bind(a, precision); a.bias = g.up_bias[j].p; a.out = pl.raw_up[j];
-      a.stats = pl.st_up[j];
-      a.B = B; a.M_out = pl.Tl[lvl]; a.N = st * 2 * co; a.Cin = ci; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
-      a.a_row_stride = ci; a.a_batch_stride = (int64_t)pl.Tl[lvl] * ci; a.a_len = a.a_batch_stride;
-      a.chan_mod = 2 * co;
-      if ((rc = asw_convgemm_f32(&a, s))) return rc;
+      int tiles = fed_tiles;
+      if (!fed_tiles) {
+        asw_convgemm_args a = {};
+        a.A = x; a.A2 = pl.X[lvl]; g.up_wt[j].bind(a, precision); a.bias = g.up_bias[j].p; a.out = pl.raw_up[j];
+        a.stats = pl.st_up[j];
+        a.B = B; a.M_out = pl.Tl[lvl]; a.N = st * 2 * co; a.Cin = ci; a.taps = 1; a.stride = 1; a.dil = 1; a.pad = 0;
+        a.a_row_stride = ci; a.a_batch_stride = (int64_t)pl.Tl[lvl] * ci; a.a_len = a.a_batch_stride;
+        a.chan_mod = 2 * co;
+        if ((rc = asw_convgemm_f32(&a, s))) return rc;
+        tiles = asw_convgemm_stats_tiles(a.M_out, a.N);
+      }
       const int To = pl.Tl[lvl] * st;        // == pl.Tl[lvl-1]
-      const int tiles = asw_convgemm_stats_tiles(a.M_out, a.N);
       float* gb = pl.Qb[lvl - 1];
       float* r = nullptr;
+      const bool feed_next = up && j + 1 < tc.depth && up_path(g, j + 1);
+      UpFeed uf = {};
+      if (feed_next) uf = {&g.up_feed[j + 1], g.up_bias[j + 1].p, pl.X[lvl - 1], pl.raw_up[j + 1], pl.st_up[j + 1], 0};
+      UpFeed* ufp = feed_next ? &uf : nullptr;
       if (fuse_mask && glu_on_load_ok(dec[j].res, precision, co)) {
         // GroupNorm + GLU happen while the first residual layer stages its rows: at 64 channels the normalised
         // tensor is neither written nor read back (P -> gb -> P are the stack's own buffers), above that it is
@@ -675,15 +753,16 @@ struct Trunk {
         if ((rc = asw_gn_finalize(pl.st_up[j], tiles, B, To, co, 1e-5f, pl.mr_up[j], s))) return rc;
         // (gb: free until the second layer writes it; the wide layers read their residual from there)
         const GluSrc src = {pl.raw_up[j], pl.mr_up[j], dec[j].gn_g.p, dec[j].gn_b.p, co > 64 ? gb : nullptr};
-        if ((rc = run_res(dec[j].res, precision, B, To, co, K, gb, pl.Pb[lvl - 1], gb, &r, s, &src))) return rc;
+        if ((rc = run_res(dec[j].res, precision, B, To, co, K, gb, pl.Pb[lvl - 1], gb, &r, s, &src, nullptr, ufp))) return rc;
       } else {
         if ((rc = asw_gn_glu(pl.raw_up[j], pl.st_up[j], tiles, dec[j].gn_g.p, dec[j].gn_b.p, B, To, co, 1e-5f, gb, s)))
           return rc;
         // residual ping-pong: gb -> P -> gb -> P ...
-        if ((rc = run_res(dec[j].res, precision, B, To, co, K, gb, pl.Pb[lvl - 1], gb, &r, s))) return rc;
+        if ((rc = run_res(dec[j].res, precision, B, To, co, K, gb, pl.Pb[lvl - 1], gb, &r, s, nullptr, nullptr, ufp))) return rc;
       }
       x = r;
-      taps["dec" + std::to_string(j)] = {x, (size_t)B * To * co};
+      fed_tiles = feed_next ? uf.tiles : 0;
+      if (!feed_next) taps["dec" + std::to_string(j)] = {x, (size_t)B * To * co};
     }
     return ASW_OK;
   }

@@ -80,6 +80,19 @@ struct KArgs {
   LayerDev L[MAXL];
 };
 
+// UpFeed (asw_resstack_args.up_hi): the transposed convolution of the next decoder block, applied by the last layer
+constexpr int UPN = 256;                 // its GEMM width: stride 2 x (64 value + 64 gate) channels
+struct UpArgs {
+  const half8* Wh;                       // Wt[256][64] with the K order of asw_up_feed_kperm, fragment order
+  const half8* Wl;
+  const float* bias;                     // [256]
+  const float* skip;                     // [B][T][64], added to the stack's output before the GEMM
+  float* out;                            // [B][T][256] == [B][2 T][128] raw rows
+  float* stats;                          // [B][ntile][4]: sum, sum of squares of the value half, then of the gate half
+  float scale;                           // 2^-w_shift
+};
+struct KArgsUp : KArgs { UpArgs u; };    // the kernel argument of the UpFeed instantiations
+
 // One 16-byte row of a source plane through its buffer descriptor: rows outside [0, T) read as zeros.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t src_rsrc(const half8* base, long rows) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<half8*>(base), 0, (int)(rows * 16), 0x00020000);
@@ -97,9 +110,18 @@ __device__ __forceinline__ half8 src_load(__amdgpu_buffer_rsrc_t r, int row) {
 // taps x 4), its B operand loaded straight from the two fp16 planes of u~ -- a fragment is 32 consecutive 16-byte
 // rows -- with no LDS image and no staging pass; the residual x0 is one more k-step with Wpre~ (K = 8 padded to 16)
 // accumulated onto the ReLU'd accumulators.  x0 is never materialised.
-template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int NTERM, int QD, bool SRC = false>
+//
+// UP ("UpFeed", f16x3): the stack is the last of a decoder block and the next block is a 64 -> 64 channel stride-2
+// transposed convolution.  That convolution is a one-tap GEMM over channels of (x + skip), and a finished LayerNorm
+// row fragment already sits in registers in an MFMA operand layout (lane = time row; registers 8s .. 8s+7 of the
+// 32-channel block cb are k-step 2 cb + s, up to a fixed order of the 16 channels inside the step that the host
+// folds into the packed weight, asw_up_feed_kperm).  So the last layer adds the skip rows, splits the sum, runs
+// W_up (x + skip) + bias for the 256 output channels from registers and writes the raw rows and their GroupNorm
+// partial sums (UpArgs).  x is never stored: one write and one read of it and one launch less.
+template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int NTERM, int QD, bool SRC = false, bool UP = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(TM >= 4 ? 1 : 2)))
-void resstack64_kernel(const KArgs p) {
+void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
+  static_assert(!UP || (!SRC && NTERM == 3), "UpFeed: f16x3, never source-fed");
   static_assert(!POLY || NL == 1, "polyphase row sets: single layers only");
   static_assert(!SRC || (!POLY && !GLU && NTERM == 3), "source-fed layer 0: contiguous tiles, f16x3");
   static_assert(QD == 2 || QD == 4, "weight prefetch depth in k-steps");
@@ -403,6 +425,118 @@ void resstack64_kernel(const KArgs p) {
         }
       }
       __syncthreads();
+    } else if constexpr (UP) {
+      const UpArgs& u = p.u;
+      // ---- UpFeed.  The GEMM runs with the activation as the MFMA A operand (the same registers serve either side:
+      // lane = row, 8 k per lane half), so a result block has its output CHANNEL on the lane and 16 rows in registers:
+      // one store instruction writes two whole 128-byte lines, and a lane's 16 values share a GroupNorm group.
+      const __amdgpu_buffer_rsrc_t rS = act_rsrc(u.skip + (long)b * T * C, (long)T * C);
+      const int tstep = POLY ? dil0 : 1;                // sequence rows between two rows of a fragment
+      const int widu = __builtin_amdgcn_readfirstlane(wid);     // (the row bookkeeping and the store bases stay scalar)
+      half8 xh[TM][4], xl[TM][4];
+      int t0[TM], nv[TM];                               // sequence row of a fragment's row 0; its rows that exist (a prefix)
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int f0 = (widu * TM + i) * 32;
+        int lim;
+        if (!POLY) {
+          t0[i] = m0 + f0;
+          lim = min(p.BM, T - m0) - f0;
+        } else {
+          const int ph = pb * PH + f0 / BMJ;
+          t0[i] = dil0 * (jb * BMJ + f0 % BMJ) + ph;
+          lim = (ph < dil0 && t0[i] < T) ? (T - 1 - t0[i]) / dil0 + 1 : 0;
+        }
+        nv[i] = i < Ld.nfrag - widu * TM ? min(max(lim, 0), 32) : 0;
+        const bool ok = (lane & 31) < nv[i];
+        const long e0 = ((long)t0[i] + (long)(lane & 31) * tstep) * C + h * 4;
+        float4 sk[8];
+#pragma unroll
+        for (int c8 = 0; c8 < 8; ++c8) sk[c8] = act_load4(rS, e0 + c8 * 8, ok);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4 s4 = sk[cb * 4 + q];
+            const float4 v = make_float4(acc[i][cb][q * 4 + 0] + s4.x, acc[i][cb][q * 4 + 1] + s4.y,
+                                         acc[i][cb][q * 4 + 2] + s4.z, acc[i][cb][q * 4 + 3] + s4.w);
+            half4 hi, lo;
+            split4t<NTERM>(v, hi, lo);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              xh[i][cb * 2 + (q >> 1)][(q & 1) * 4 + j] = hi[j];
+              xl[i][cb * 2 + (q >> 1)][(q & 1) * 4 + j] = lo[j];
+            }
+          }
+      }
+      float st0 = 0.f, sq0 = 0.f, st1 = 0.f, sq1 = 0.f;
+      // Stores go through one buffer descriptor per fragment that covers exactly its rows that exist: the address is one
+      // 32-bit offset, and a row past the end (of the sequence, or of this tile's share) is dropped by the bounds
+      // check instead of by a branch.
+      __amdgpu_buffer_rsrc_t rO[TM];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+        rO[i] = __builtin_amdgcn_make_buffer_rsrc(u.out + ((long)b * T + t0[i]) * UPN, 0,
+                                                  nv[i] > 0 ? ((nv[i] - 1) * tstep + 1) * UPN * 4 : 0, 0x00020000);
+      const int voff = (4 * h * tstep * UPN + (lane & 31)) * 4; // this lane's part of a store address: its first row, its channel
+      const int rstep = tstep * UPN * 4;
+      half8 wh[2][2], wl[2][2];
+      auto wload = [&](int ks, int nb2, int slot) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) frag_load<NTERM>(u.Wh, u.Wl, (long)ks * (UPN / 32) + nb2 * 2 + e, lane, wh[slot][e], wl[slot][e]);
+      };
+      wload(0, 0, 0);
+#pragma unroll 1
+      for (int nb2 = 0; nb2 < UPN / 64; ++nb2) {        // two 32-channel blocks at a time: 0, 2 the value half, 1, 3 the gate half
+        floatx16 y[TM][2];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int e = 0; e < 2; ++e)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) y[i][e][r] = 0.f;
+        const float bv[2] = {u.bias[nb2 * 64 + (lane & 31)], u.bias[nb2 * 64 + 32 + (lane & 31)]};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          // the next k-step's weights (after the last one: the next pair's first, the last pair fetching its own again)
+          if (ks < 3) wload(ks + 1, nb2, (ks + 1) & 1);
+          else wload(0, nb2 + 1 < UPN / 64 ? nb2 + 1 : nb2, 0);
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) mma3<NTERM, false>(y[i][e], xh[i][ks], xl[i][ks], wh[ks & 1][e], wl[ks & 1][e]);
+        }
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const bool whole = nv[i] == 32;               // (wave-uniform) every row of the fragment exists
+#pragma unroll
+          for (int e = 0; e < 2; ++e)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const float v = y[i][e][r] * u.scale + bv[e];
+              // (the whole offset in the vector operand: that is the one the bounds check compares)
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rO[i],
+                                                    voff + ((r & 3) + 8 * (r >> 2)) * rstep + (nb2 * 64 + e * 32) * 4, 0, 0);
+              const float m = (whole || acc_row(r, h) < nv[i]) ? v : 0.f;
+              s1 += m;
+              s2 += m * m;
+            }
+        }
+        if (nb2 & 1) { st1 += s1; sq1 += s2; } else { st0 += s1; sq0 += s2; }
+      }
+      // GroupNorm partial sums of this tile: lanes, then waves, in a fixed order; one slot per (item, tile), no atomics
+      st0 = wave_sum(st0); sq0 = wave_sum(sq0); st1 = wave_sum(st1); sq1 = wave_sum(sq1);
+      __syncthreads();                                  // every wave is done with the image
+      float* red = reinterpret_cast<float*>(smem);
+      if (lane == 0) { red[wid * 4 + 0] = st0; red[wid * 4 + 1] = sq0; red[wid * 4 + 2] = st1; red[wid * 4 + 3] = sq1; }
+      __syncthreads();
+      if (tid < 4) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += red[w * 4 + tid];
+        u.stats[((long)b * p.ntile + tile) * 4 + tid] = s;
+      }
     } else {
       float* __restrict__ ob = p.out + (long)b * T * C;
 #pragma unroll
@@ -458,11 +592,22 @@ void resstack64_kernel(const KArgs p) {
 }
 
 template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int QD, bool SRC = false>
-int launch_stack(const KArgs& k, int precision, size_t smem, double flops, const char* tag, hipStream_t s) {
+int launch_stack(const KArgs& k, const UpArgs* up, int precision, size_t smem, double flops, const char* tag, hipStream_t s) {
   char nm[128], detail[48] = "";
-  snprintf(nm, sizeof nm, "resstack64<%s,%dx%d%s%s%s>", tag, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
-           GLU ? ",glu" : "", SRC ? ",src" : "");
+  snprintf(nm, sizeof nm, "resstack64<%s,%dx%d%s%s%s%s>", tag, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
+           GLU ? ",glu" : "", SRC ? ",src" : "", up ? ",up" : "");
   if (asw::prof_detail()) snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
+  if constexpr (!SRC) {
+    if (up) {
+      // algorithmic bytes: the stack's input and the skip rows read once, the raw rows written once
+      KArgsUp ku;
+      static_cast<KArgs&>(ku) = k;
+      ku.u = *up;
+      return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, false, true>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, false, true>>(
+          1, dim3(xcd_grid_run(k.B * k.ntile)), dim3(64 * NW), smem, 160 * 1024, nm, detail,
+          flops + 2.0 * k.B * (double)k.T * C * UPN, (double)k.B * k.T * 4 * ((GLU ? 3 : 2) * C + UPN), s, ku);
+    }
+  }
   if constexpr (SRC) {
     // f16x3 only; algorithmic bytes: the two source planes read once, the output written once
     return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, true>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, true>>(
@@ -476,31 +621,42 @@ int launch_stack(const KArgs& k, int precision, size_t smem, double flops, const
   }
 }
 
+// The row tiling of a launch whose layer 0 computes R0 rows (asw_resstack_tiles reports ntile to a caller that sizes
+// the UpFeed statistics).
+struct TilePlan { bool poly; int PH, BM, ntile; };
+TilePlan plan_tiles(int T, int n_layers, int dil0, int halo0, bool glu, int R0) {
+  // one layer of large dilation: polyphase row sets while every phase still fills its share of the tile
+  const int rpp = T / dil0;                              // rows per phase
+  if (n_layers == 1 && dil0 >= 7 && rpp >= 48 && !glu) {
+    const int PH = rpp >= R0 - 32 ? 1 : rpp >= R0 / 2 - 32 ? 2 : 4;
+    return {true, PH, R0, asw::cdiv(asw::cdiv(T, dil0), R0 / PH) * asw::cdiv(dil0, PH)};
+  }
+  // contiguous tiles: layer 0 computes R0 rows, the stack delivers BM = R0 - 2 * (halo after layer 0)
+  const int BM = R0 - 2 * halo0;
+  return {false, 1, BM, BM > 0 ? asw::cdiv(T, BM) : 0};
+}
+
 template <int NW, int TM>
-int dispatch(const asw_resstack_args& a, KArgs& k, bool glu, double flops, hipStream_t s) {
+int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, double flops, hipStream_t s) {
   constexpr int R0 = 32 * NW * TM;
   const int dil0 = k.L[0].dil;
-  // one layer of large dilation: polyphase row sets while every phase still fills its share of the tile
-  const int rpp = a.T / dil0;                            // rows per phase
-  if (a.n_layers == 1 && dil0 >= 7 && rpp >= 48 && !glu) {
-    const int PH = rpp >= R0 - 32 ? 1 : rpp >= R0 / 2 - 32 ? 2 : 4;
+  const TilePlan tp = plan_tiles(a.T, a.n_layers, dil0, k.L[0].halo, glu, R0);
+  k.BM = tp.BM;
+  k.ntile = tp.ntile;
+  if (tp.poly) {
+    const int PH = tp.PH;
     const int BMJ = R0 / PH;
-    k.BM = R0;
     k.L[0].nfrag = NW * TM;
-    k.ntile = asw::cdiv(asw::cdiv(a.T, dil0), BMJ) * asw::cdiv(dil0, PH);
     k.img_rows = PH * (BMJ + a.taps - 1);
     const size_t smem = (size_t)k.img_rows * RS + 3 * 64 * sizeof(float);
     switch (PH) {
-      case 1: return launch_stack<1, NW, TM, 1, true, false, 4>(k, a.precision, smem, flops, "1", s);
-      case 2: return launch_stack<1, NW, TM, 2, true, false, 4>(k, a.precision, smem, flops, "1", s);
-      default: return launch_stack<1, NW, TM, 4, true, false, 4>(k, a.precision, smem, flops, "1", s);
+      case 1: return launch_stack<1, NW, TM, 1, true, false, 4>(k, up, a.precision, smem, flops, "1", s);
+      case 2: return launch_stack<1, NW, TM, 2, true, false, 4>(k, up, a.precision, smem, flops, "1", s);
+      default: return launch_stack<1, NW, TM, 4, true, false, 4>(k, up, a.precision, smem, flops, "1", s);
     }
   }
-  // contiguous tiles: layer 0 computes R0 rows, the stack delivers BM = R0 - 2 * (halo after layer 0)
-  k.BM = R0 - 2 * k.L[0].halo;
   ASW_CHECK_ARG(k.BM >= R0 / 2, "resstack: the later layers' halo (%d rows per side) leaves %d of %d rows; fuse fewer layers",
                 k.L[0].halo, k.BM, R0);
-  k.ntile = asw::cdiv(a.T, k.BM);
   int rows = 0;
   for (int i = 0; i < a.n_layers; ++i) {
     k.L[i].nfrag = asw::cdiv(k.BM + 2 * k.L[i].halo, 32);
@@ -513,15 +669,15 @@ int dispatch(const asw_resstack_args& a, KArgs& k, bool glu, double flops, hipSt
                 rows, dil0, a.taps);
   if (k.src_h) {
     ASW_CHECK_ARG(k.L[0].nfrag == NW * TM, "resstack: source-fed layer 0 computes %d of %d fragments", k.L[0].nfrag, NW * TM);
-    return launch_stack<2, NW, TM, 1, false, false, 4, true>(k, a.precision, smem, flops, "2", s);
+    return launch_stack<2, NW, TM, 1, false, false, 4, true>(k, nullptr, a.precision, smem, flops, "2", s);
   }
   switch (a.n_layers) {
-    case 1: return glu ? launch_stack<1, NW, TM, 1, false, true, 4>(k, a.precision, smem, flops, "1", s)
-                       : launch_stack<1, NW, TM, 1, false, false, 4>(k, a.precision, smem, flops, "1", s);
-    case 2: return glu ? launch_stack<2, NW, TM, 1, false, true, 4>(k, a.precision, smem, flops, "2", s)
-                       : launch_stack<2, NW, TM, 1, false, false, 4>(k, a.precision, smem, flops, "2", s);
-    default: return glu ? launch_stack<3, NW, TM, 1, false, true, 4>(k, a.precision, smem, flops, "3", s)
-                        : launch_stack<3, NW, TM, 1, false, false, 4>(k, a.precision, smem, flops, "3", s);
+    case 1: return glu ? launch_stack<1, NW, TM, 1, false, true, 4>(k, up, a.precision, smem, flops, "1", s)
+                       : launch_stack<1, NW, TM, 1, false, false, 4>(k, up, a.precision, smem, flops, "1", s);
+    case 2: return glu ? launch_stack<2, NW, TM, 1, false, true, 4>(k, up, a.precision, smem, flops, "2", s)
+                       : launch_stack<2, NW, TM, 1, false, false, 4>(k, up, a.precision, smem, flops, "2", s);
+    default: return glu ? launch_stack<3, NW, TM, 1, false, true, 4>(k, up, a.precision, smem, flops, "3", s)
+                        : launch_stack<3, NW, TM, 1, false, false, 4>(k, up, a.precision, smem, flops, "3", s);
   }
 }
 
@@ -558,6 +714,15 @@ extern "C" int asw_compose_source_weights(const float* wc, const float* wpre, co
   return ASW_OK;
 }
 
+extern "C" int asw_resstack_tiles(int T, int taps, int n_layers, const int32_t* dil, int glu) {
+  ASW_CHECK_ARG(T > 0 && taps >= 3 && taps % 2 == 1 && n_layers >= 1 && n_layers <= MAXL && dil, "resstack_tiles: bad argument");
+  int halo0 = 0;
+  for (int i = 1; i < n_layers; ++i) halo0 += dil[i] * (taps - 1) / 2;
+  const TilePlan t = plan_tiles(T, n_layers, dil[0], halo0, glu != 0, 256);
+  ASW_CHECK_ARG(t.BM >= 128, "resstack_tiles: the later layers' halo (%d rows per side) is too wide", halo0);
+  return t.ntile;
+}
+
 extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream) {
   ASW_CHECK_ARG(args != nullptr, "resstack: null args");
   const asw_resstack_args& a = *args;
@@ -567,7 +732,7 @@ extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream)
   ASW_CHECK_ARG(a.taps >= 3 && a.taps <= 15 && a.taps % 2 == 1, "resstack: taps=%d (odd, 3..15)", a.taps);
   ASW_CHECK_ARG(a.precision == 1 || a.precision == 2, "resstack: precision 1 (f16x3) or 2 (single-pass f16)");
   ASW_CHECK_ARG(a.B > 0 && a.B <= (1 << 20) && a.T > 0 && (int64_t)a.T * 2 * C < ((int64_t)1 << 29), "resstack: bad B / T");
-  ASW_CHECK_ARG(a.out && (a.x || a.glu_raw || a.src_hi), "resstack: null tensor");
+  ASW_CHECK_ARG((a.out || a.up_hi) && (a.x || a.glu_raw || a.src_hi), "resstack: null tensor");
   const bool glu = a.glu_raw != nullptr;
   if (glu) ASW_CHECK_ARG(a.glu_mr && a.glu_gamma && a.glu_beta, "resstack: GroupNorm + GLU on load needs the statistics / affine arrays");
   KArgs k = {};
@@ -596,5 +761,13 @@ extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream)
     // the FLOPs executed: layer 0 is K = 64 (8 taps x 8 channels) plus the K = 16 residual step, layer 1 as always
     flops = 2.0 * a.B * (double)a.T * C * (64 + 16 + C * a.taps);
   }
-  return dispatch<4, 2>(a, k, glu, flops, s);            // 4 waves x 2 row fragments: 256 rows computed by layer 0
+  UpArgs up = {};
+  if (a.up_hi) {
+    ASW_CHECK_ARG(a.up_lo && a.up_bias && a.up_skip && a.up_out && a.up_stats, "resstack: UpFeed needs up_lo / up_bias / up_skip / up_out / up_stats");
+    ASW_CHECK_ARG(a.precision == 1 && !a.src_hi, "resstack: UpFeed is f16x3 and never source-fed");
+    up.Wh = reinterpret_cast<const half8*>(a.up_hi); up.Wl = reinterpret_cast<const half8*>(a.up_lo);
+    up.bias = a.up_bias; up.skip = a.up_skip; up.out = a.up_out; up.stats = a.up_stats;
+    up.scale = ldexpf(1.0f, -a.up_shift);
+  }
+  return dispatch<4, 2>(a, k, a.up_hi ? &up : nullptr, glu, flops, s);   // 4 waves x 2 row fragments: 256 rows computed by layer 0
 }

@@ -44,7 +44,7 @@ struct asw_spot : Trunk {
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
-  asw_spot() { want_src = true; }
+  asw_spot() { want_src = true; want_up = true; }
   ~asw_spot() {
     for (char* w : ws) if (w) (void)hipFree(w);
     if (side) (void)hipStreamDestroy(side);
@@ -164,8 +164,9 @@ int ensure_ws(asw_spot* m, int B, int T, Plan& pl, int lane = 0) {
 }
 
 // everything after the preproc stage; pl.X[0] (src0: the source planes instead) / pl.refn are filled
+// cand: the candidate loop (the decoder may feed its 64 -> 64 block from the stack in front, Trunk::decode)
 int run_network(asw_spot* m, Plan& pl, GateSet* gs, const float* mean, const float* stdv, float* out_wave,
-                hipStream_t s, bool src0 = false) {
+                hipStream_t s, bool src0 = false, bool cand = false) {
   const asw_spot_config& c = m->cfg;
   int rc;
   if ((rc = m->encode(pl, *gs, s, src0))) return rc;
@@ -181,7 +182,7 @@ int run_network(asw_spot* m, Plan& pl, GateSet* gs, const float* mean, const flo
     h = hout;
   }
   m->taps["bottleneck"] = {h, (size_t)rows * d};
-  if ((rc = m->decode(pl, *gs, h, s))) return rc;
+  if ((rc = m->decode(pl, *gs, h, s, cand))) return rc;
   return m->mask_path(pl, h, mean, stdv, out_wave, s);
 }
 
@@ -314,7 +315,7 @@ extern "C" int asw_spot_shift_and_sep_multi(asw_spot* m, const float* mix, int K
         return r;
       }
       float* y = out_wave ? out_wave + (size_t)i0 * T : p.ywave;
-      if ((r = run_network(m, p, gs, p.mean, p.stdv, y, q, src0))) return r;
+      if ((r = run_network(m, p, gs, p.mean, p.stdv, y, q, src0, true))) return r;
       if (out_energy && (r = asw_energies(y, B, T, energy_window, nullptr, out_energy + (size_t)i0 * 2, q))) return r;
     }
     return ASW_OK;
@@ -371,6 +372,12 @@ extern "C" int asw_spot_set_fused_mask(asw_spot* m, int on) {
 extern "C" int asw_spot_set_source_stack(asw_spot* m, int on) {
   ASW_CHECK_ARG(m, "set_source_stack: null model handle");
   m->src_stack = on != 0;
+  return ASW_OK;
+}
+
+extern "C" int asw_spot_set_up_fusion(asw_spot* m, int on) {
+  ASW_CHECK_ARG(m, "set_up_fusion: null model handle");
+  m->up_fusion = on != 0;
   return ASW_OK;
 }
 

@@ -150,7 +150,8 @@ class ResStackArgs(Structure):
                 ("n_layers", c_int32), ("precision", c_int32), ("ln_eps", c_float), ("layer", ResLayerDesc * 3),
                 ("glu_raw", c_void_p), ("glu_mr", c_void_p), ("glu_gamma", c_void_p), ("glu_beta", c_void_p),
                 ("glu_out", c_void_p), ("src_hi", c_void_p), ("src_lo", c_void_p), ("pre_hi", c_void_p), ("pre_lo", c_void_p),
-                ("pre_shift", c_int32)]
+                ("pre_shift", c_int32), ("up_hi", c_void_p), ("up_lo", c_void_p), ("up_shift", c_int32), ("up_bias", c_void_p),
+                ("up_skip", c_void_p), ("up_out", c_void_p), ("up_stats", c_void_p)]
 
 
 # name -> (restype, argtypes); must list every symbol declared in include/asw_hip.h
@@ -184,6 +185,7 @@ SIGNATURES = {
     "asw_spot_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), c_void_p, c_void_p]),
     "asw_spot_set_fused_mask": (c_int, [c_void_p, c_int]),
     "asw_spot_set_source_stack": (c_int, [c_void_p, c_int]),
+    "asw_spot_set_up_fusion": (c_int, [c_void_p, c_int]),
     "asw_spot_get_tap": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, POINTER(c_size_t), c_void_p]),
     "asw_sep_create": (c_int, [POINTER(SepConfigC), POINTER(c_void_p)]),
     "asw_sep_destroy": (None, [c_void_p]),
@@ -223,6 +225,9 @@ SIGNATURES = {
     "asw_mask_path_f16x3": (c_int, [POINTER(MaskPathArgs), c_void_p]),
     "asw_mask_path_f16x3_scaled": (c_int, [POINTER(MaskPathArgs), c_void_p]),
     "asw_resstack64_f16x3": (c_int, [POINTER(ResStackArgs), c_void_p]),
+    "asw_resstack_tiles": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_int]),
+    "asw_up_feed_kperm": (c_int, [c_int]),
+    "asw_pack_up_feed_f16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32)]),
     "asw_compose_source_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "asw_convgemm_stats_tiles": (c_int, [c_int, c_int]),
     "asw_f16x3_overflow_count": (c_int, [c_int, POINTER(c_int32)]),

@@ -99,6 +99,39 @@ def resstack(x, layers, taps=7, precision="f16x3", eps=1e-5, glu=None, out=None,
     return out
 
 
+def resstack_up(x, layers, up_wt, up_bias, skip, taps=7, eps=1e-5, glu=None):
+    """The stack with the next decoder block's 64 -> 64 channel stride-2 transposed convolution applied by its last
+    layer (include/asw_hip.h:asw_resstack_args.up_hi).  up_wt [256][64] (pack_conv_transpose layout), up_bias [256],
+    skip [B][T][64].  Returns (raw [B][T][256], partial sums [B][tiles][4]); the stack's own output is not written."""
+    import ctypes
+    src = x if glu is None else glu[0]
+    B, T = src.shape[0], src.shape[1]
+    dev = src.device
+    a = ResStackArgs()
+    a.x = _f32(x).data_ptr() if x is not None else None
+    a.B, a.T, a.C, a.taps, a.n_layers, a.precision, a.ln_eps = B, T, 64, taps, len(layers), 1, eps
+    keep = []
+    for i, (Wt, bias, gamma, beta, dil) in enumerate(layers):
+        fh, fl, sh = pack_fragments_f16(_f32(Wt), 64, taps * 64)
+        keep.append((fh, fl))
+        d = a.layer[i]
+        d.Wf_hi, d.Wf_lo, d.w_shift, d.dil = fh.data_ptr(), fl.data_ptr(), sh, dil
+        d.bias, d.ln_gamma, d.ln_beta = _f32(bias).data_ptr(), _f32(gamma).data_ptr(), _f32(beta).data_ptr()
+    if glu is not None:
+        a.glu_raw, a.glu_mr, a.glu_gamma, a.glu_beta = (_f32(t).data_ptr() for t in glu)
+    dils = (ctypes.c_int32 * 3)(*([l[4] for l in layers] + [1] * (3 - len(layers))))
+    tiles = lib().asw_resstack_tiles(T, taps, len(layers), dils, int(glu is not None))
+    check(min(tiles, 0))
+    uh, ul, ush = pack_fragments_f16(up_wt, 256, 64, up_feed=True)
+    raw = torch.full((B, T, 256), float("nan"), dtype=torch.float32, device=dev)
+    stats = torch.full((B, tiles, 4), float("nan"), dtype=torch.float32, device=dev)
+    a.up_hi, a.up_lo, a.up_shift = uh.data_ptr(), ul.data_ptr(), ush
+    a.up_bias, a.up_skip, a.up_out, a.up_stats = _f32(up_bias).data_ptr(), _f32(skip).data_ptr(), raw.data_ptr(), stats.data_ptr()
+    check(lib().asw_resstack64_f16x3(byref(a), current_stream()))
+    torch.cuda.current_stream().synchronize()
+    return raw, stats
+
+
 def resstack_src(src_hi, src_lo, pre_w, pre_b, layers, taps=7, eps=1e-5, out=None):
     """The fused pair with its first layer fed by the 8-channel source of the 1x1 convolution (pre_w [64][M], pre_b [64])
     in front of it (include/asw_hip.h:asw_resstack_args.src_hi).  src_hi / src_lo: the planes of shift_norm_src;
@@ -135,16 +168,18 @@ def resstack_src(src_hi, src_lo, pre_w, pre_b, layers, taps=7, eps=1e-5, out=Non
     return out
 
 
-def pack_fragments_f16(Wt, N, K):
-    """fp32 device Wt[N][K] -> fragment-major (hi, lo) device tensors + shift (asw_pack_fragments_f16)."""
+def pack_fragments_f16(Wt, N, K, up_feed=False):
+    """fp32 device Wt[N][K] -> fragment-major (hi, lo) device tensors + shift (asw_pack_fragments_f16; up_feed: with
+    the K order of a residual stack's UpFeed, asw_pack_up_feed_f16)."""
     import ctypes
     import numpy as np
     w = np.ascontiguousarray(Wt.detach().cpu().numpy(), dtype=np.float32).reshape(N, K)
     hi = np.empty(w.size, dtype=np.uint16)
     lo = np.empty(w.size, dtype=np.uint16)
     sh = ctypes.c_int32()
-    check(lib().asw_pack_fragments_f16(ctypes.c_void_p(w.ctypes.data), N, K, ctypes.c_void_p(hi.ctypes.data),
-                                       ctypes.c_void_p(lo.ctypes.data), byref(sh)))
+    pack = lib().asw_pack_up_feed_f16 if up_feed else lib().asw_pack_fragments_f16
+    check(pack(ctypes.c_void_p(w.ctypes.data), N, K, ctypes.c_void_p(hi.ctypes.data),
+               ctypes.c_void_p(lo.ctypes.data), byref(sh)))
     dev = Wt.device
     return (torch.from_numpy(hi.view(np.int16)).to(dev), torch.from_numpy(lo.view(np.int16)).to(dev), sh.value)
 

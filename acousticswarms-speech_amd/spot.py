@@ -215,3 +215,11 @@ class SpotModel(DeviceModel, DeviceScorer):
         self._need()
         native.check(native.lib().asw_spot_set_source_stack(self._h, int(bool(on))))
         return self
+
+    def set_up_fusion(self, on: bool = True):
+        """f16x3 mode: in shift_and_sep the residual stack in front of a 64 -> 64 channel decoder block applies that
+        block's upsampling itself (default; the tap of the block in front does not exist then) or leaves it to the
+        separate GEMM launch (asw_spot_set_up_fusion)."""
+        self._need()
+        native.check(native.lib().asw_spot_set_up_fusion(self._h, int(bool(on))))
+        return self

@@ -151,6 +151,15 @@ int asw_spot_set_fused_mask(asw_spot* m, int on);
  * asw_spot_forward, the f32 and the single-pass f16 modes always take the separate pass. */
 int asw_spot_set_source_stack(asw_spot* m, int on);
 
+/* f16x3 mode: in asw_spot_shift_and_sep[_multi] the residual stack of the decoder block in front of a 64 -> 64 channel
+ * stride-2 block applies that block's transposed convolution from its registers (asw_resstack_args.up_hi): its own
+ * output is never written, the separate GEMM launch and one round trip of that tensor disappear, and the tap "dec<j>"
+ * of the block in front does not exist after such a call ("no activation named dec<j>").  on = 0 selects the
+ * separate launch (default: on).  asw_spot_forward, the f32 and the single-pass f16 modes always take the separate
+ * launch; f16x3_safe takes the fused one as f16x3 does (the site reads a normalised tensor, which that mode runs on the
+ * same kernels, so the two modes' launch plans keep differing in the exact-f32 sites only). */
+int asw_spot_set_up_fusion(asw_spot* m, int on);
+
 /* Debug/parity tap: copy an intermediate activation of the LAST forward to `dst`
  * (channels-last [B][T_l][C] float32).  names: "preproc", "enc0".., "bottleneck",
  * "dec0".., "latent" (three-GEMM mask path only); "preproc" does not exist after a
@@ -483,8 +492,33 @@ typedef struct asw_resstack_args {
   const void* pre_hi;
   const void* pre_lo;
   int32_t pre_shift;
+  /* Optional ("UpFeed", precision 1, not with src_hi): the stack is the last of a decoder block and the next block
+   * upsamples 64 -> 64 channels with stride 2.  The last layer then applies that transposed convolution itself,
+   * up_out[b][t][r*128 + n] = up_bias[r*128 + n] + sum_c Wt[r*128 + n][c] (stack(x)[b][t][c] + up_skip[b][t][c]),
+   * from the registers that hold the finished LayerNorm rows, and the stack's own output is not written (out may be
+   * NULL).  up_hi / up_lo / up_shift: Wt[256][64] (pack_conv_transpose layout) packed by asw_pack_up_feed_f16;
+   * up_skip [B][T][64]; up_out [B][T][256], i.e. the raw rows [B][2T][128]; up_stats [B][tiles][4], tiles =
+   * asw_resstack_tiles(...): per (item, row tile) the sum and the sum of squares of the value half (n < 64) and of
+   * the gate half, every slot written, for asw_gn_finalize / asw_gn_glu with n_partials = tiles.  Deterministic (no
+   * atomics).  Launch names end in ",up>", e.g. resstack64<1,4x2,poly1,up>. */
+  const void* up_hi;
+  const void* up_lo;
+  int32_t up_shift;
+  const float* up_bias;
+  const float* up_skip;
+  float* up_out;
+  float* up_stats;
 } asw_resstack_args;
 int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream);
+/* Row tiles per batch item of the asw_resstack64_f16x3 launch with these T, taps, n_layers, dilations dil[n_layers] and
+ * GroupNorm + GLU on load or not: the number of UpFeed statistics slots per item.  Negative asw_status on a bad argument. */
+int asw_resstack_tiles(int T, int taps, int n_layers, const int32_t* dil, int glu);
+/* UpFeed hands the LayerNorm rows to the MFMA as they sit in the accumulator registers: position k of a 16-channel
+ * k-step holds channel asw_up_feed_kperm(k) of that step (k = 0..15; bits 2 and 3 of k exchanged).
+ * asw_pack_up_feed_f16 applies that order to the columns of Wt[N][K] (K % 16 == 0, N % 32 == 0) and packs the result
+ * with asw_pack_fragments_f16 (same split, same shift). */
+int asw_up_feed_kperm(int k);
+int asw_pack_up_feed_f16(const float* Wt, int N, int K, uint16_t* hi, uint16_t* lo, int32_t* w_shift);
 /* Host helper: the weights of the source-fed form (asw_resstack_args.src_hi) from the torch-layout parameters, composed
  * in double: wc [64][64][taps] (the first layer's Conv1d weight), wpre [64][M] and bpre [64] (the 1x1 convolution in
  * front of it), M <= 7, taps <= 7 -> comp Wt[64][64] (column tap*8 + j; j == 7 multiplies the constant channel and
