@@ -321,15 +321,25 @@ def separate_stack(sep_model, stack, patch_lists):
                                           for patches in patch_lists])
 
 
-def result_record(patches, spot_times, times):
+def result_record(patches, spot_times, times, details=False, mix_shape=None):
     """The per-mixture result dict of ``shard.localize_batch`` from the final patches of a search (tuples (patch, audio,
-    power, name)): centres [K,3] ((0, 3) without talkers), powers [K], names, and ``spot_times`` / ``times`` as given."""
-    return {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
-            "powers": np.array([p[2] for p in patches]), "names": [p[3] for p in patches],
-            "spot_times": spot_times, "times": times}
+    power, name, {"audio_offset", "localization_offset"}, ...)): centres [K,3] ((0, 3) without talkers), powers [K], names,
+    and ``spot_times`` / ``times`` as given.  ``details=True`` adds what an evaluation record needs
+    (``evalkit.record_from_result``): ``"offsets"``, the ``localization_offset`` rows [K, M-1], ``"audio_offsets"``
+    [K, M-1] and ``"audio_loc"``, the localisation-stage audio, float32 [K, T]; ``mix_shape`` = (M, T) of the mixture
+    gives the empty ones their shapes ((0, M-1), (0, T))."""
+    rec = {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
+           "powers": np.array([p[2] for p in patches]), "names": [p[3] for p in patches],
+           "spot_times": spot_times, "times": times}
+    if details:
+        M, T = (int(v) for v in mix_shape)
+        rec["offsets"] = np.array([np.asarray(p[4]["localization_offset"]) for p in patches]).reshape(-1, M - 1)
+        rec["audio_offsets"] = np.array([np.asarray(p[4]["audio_offset"]) for p in patches]).reshape(-1, M - 1)
+        rec["audio_loc"] = np.array([np.asarray(p[1]) for p in patches], dtype=np.float32).reshape(-1, T)
+    return rec
 
 
-def search_one(view, scorer, host_mix, dev_mix):
+def search_one(view, scorer, host_mix, dev_mix, details=False):
     """One search of a batch: ``mic_array.run_search`` on the mixture's own view and scorer, timed by the wall clock
     without touching the device and without a word printed -- SRP-PHAT reads the host copy of the mixture, the scoring
     stages its row of the device stack.  -> (final patches, ``result_record``)."""
@@ -341,10 +351,10 @@ def search_one(view, scorer, host_mix, dev_mix):
         times[slot] = time.time() - t0
         return out
     patches, _audio, spot_times, _empty = run_search(view, scorer, timed, host_mix, lambda: dev_mix)
-    return patches, result_record(patches, spot_times, times)
+    return patches, result_record(patches, spot_times, times, details, tuple(host_mix.shape) if details else None)
 
 
-def search_batched(joint_model, mixes, concurrent=2, geometries=None, separate=False):
+def search_batched(joint_model, mixes, concurrent=2, geometries=None, separate=False, details=False):
     """The complete localization search (SRP-PHAT -> coarse -> fine -> clustering) of every mixture in
     ``mixes`` on this rank's GPU: ``concurrent`` worker threads pull mixtures from a queue -- a finished
     search is replaced at once, so the GPU never waits for a group to drain -- and score through one
@@ -357,7 +367,10 @@ def search_batched(joint_model, mixes, concurrent=2, geometries=None, separate=F
 
     ``separate=True``: every result dict also holds ``"audio"``, the joint separation of the mixture's talkers
     (float32 [K_i, T], (0, T) without talkers).  The searches run as without it; after the last one the separation of all
-    mixtures runs from the device stack (``separate_stack``).  Needs ``joint_model.sep_model``."""
+    mixtures runs from the device stack (``separate_stack``).  Needs ``joint_model.sep_model``.
+
+    ``details=True``: every result dict also holds ``"offsets"``, ``"audio_offsets"`` and ``"audio_loc"``
+    (``result_record``)."""
     check_geometries(mixes, geometries)
     if separate and joint_model.sep_model is None:
         raise RuntimeError("separate=True needs a separation model (JointModel(sep_model=None))")
@@ -378,7 +391,7 @@ def search_batched(joint_model, mixes, concurrent=2, geometries=None, separate=F
 
     def search(k):
         own = mp if geometries is None else joint_model.mic_array_for(geometries[k][0], geometries[k][1], method)
-        finals[k], results[k] = search_one(mixture_view(own), batcher.proxy(k), hosts[k], stack[k])
+        finals[k], results[k] = search_one(mixture_view(own), batcher.proxy(k), hosts[k], stack[k], details)
 
     worker_s = []
 

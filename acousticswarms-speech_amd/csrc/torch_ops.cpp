@@ -738,6 +738,42 @@ std::tuple<Tensor, Tensor> bss_eval_sdr(const Tensor& ref, const Tensor& est, at
   return {sdr, status};
 }
 
+// -> out float64 [sum P_k S_k], status [K] int32: the SI-SDR of every (estimate, reference) pair of a ragged batch, item
+// k a row-major [P_k, S_k] block of out (hostdsp.si_sdr per pair).  Both count lists are read on the host; an item whose
+// status is 1 has to be recomputed by the caller (evalkit.cross_sisdr_batch does).
+std::tuple<Tensor, Tensor> cross_sisdr(const Tensor& est, const Tensor& ref, at::IntArrayRef est_counts,
+                                       at::IntArrayRef ref_counts) {
+  need(est, "est", at::kFloat, 2);
+  need(ref, "ref", at::kFloat, 2);
+  same_device(est, ref, "est and ref");
+  const int T = checked_int(est.size(1), "T");
+  const int K = checked_int(static_cast<int64_t>(est_counts.size()), "K");
+  TORCH_CHECK(ref.size(1) == T, "est [NE, ", T, "] and ref [NR, ", ref.size(1), "] differ in length");
+  TORCH_CHECK(static_cast<int64_t>(ref_counts.size()) == K, "est_counts holds ", K, " items, ref_counts ", ref_counts.size());
+  std::vector<int32_t> pc(K), sc(K);
+  int64_t ne = 0, nr = 0, np = 0;
+  for (int k = 0; k < K; ++k) {
+    TORCH_CHECK(est_counts[k] >= 0 && est_counts[k] <= 4096, "est_counts[", k, "] = ", est_counts[k], " outside 0..4096");
+    TORCH_CHECK(ref_counts[k] >= 0 && ref_counts[k] <= 64, "ref_counts[", k, "] = ", ref_counts[k], " outside 0..64");
+    pc[k] = static_cast<int32_t>(est_counts[k]), sc[k] = static_cast<int32_t>(ref_counts[k]);
+    ne += est_counts[k], nr += ref_counts[k], np += est_counts[k] * ref_counts[k];
+  }
+  TORCH_CHECK(ne == est.size(0), "est_counts sum to ", ne, ", est has ", est.size(0), " rows");
+  TORCH_CHECK(nr == ref.size(0), "ref_counts sum to ", nr, ", ref has ", ref.size(0), " rows");
+  Tensor out = at::empty({np}, est.options().dtype(at::kDouble));
+  Tensor status = at::empty({K}, est.options().dtype(at::kInt));
+  if (K == 0) return {out, status};
+  const size_t ws_bytes = asw_cross_sisdr_workspace_bytes(pc.data(), sc.data(), K, T);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_cross_sisdr_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, est.options().dtype(at::kDouble));
+  Launch l(est);
+  check_status(asw_cross_sisdr(ne > 0 ? est.data_ptr<float>() : nullptr, nr > 0 ? ref.data_ptr<float>() : nullptr, pc.data(),
+                               sc.data(), K, T, np > 0 ? out.data_ptr<double>() : nullptr, status.data_ptr<int32_t>(),
+                               ws.data_ptr(), ws_bytes, l.stream),
+               "asw_cross_sisdr");
+  return {out, status};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(asw, m) {
@@ -759,6 +795,7 @@ TORCH_LIBRARY(asw, m) {
   m.def("coarse_select(Tensor energies, Tensor dis1, Tensor? best=None, float thr1=0.008, bool relative=False, "
         "float rel=0.4, int cap=30) -> (Tensor, Tensor, Tensor)");
   m.def("bss_eval_sdr(Tensor ref, Tensor est, int[] counts, int flen=512) -> (Tensor, Tensor)");
+  m.def("cross_sisdr(Tensor est, Tensor ref, int[] est_counts, int[] ref_counts) -> (Tensor, Tensor)");
   m.def("center_rows_(Tensor(a!) y) -> Tensor(a!)");
   m.def("srp_phat_map(Tensor mix, Tensor twiddle, Tensor pair_i, Tensor pair_j, Tensor tau, Tensor omega, int window, "
         "int step, int n_windows, int nfft, int hop, float tol) -> Tensor");
@@ -795,6 +832,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("global_clusters", &global_clusters);
   m.impl("coarse_select", &coarse_select);
   m.impl("bss_eval_sdr", &bss_eval_sdr);
+  m.impl("cross_sisdr", &cross_sisdr);
   m.impl("center_rows_", &center_rows_);
   m.impl("srp_phat_map", &srp_phat_map);
   m.impl("pruner_covariance", &pruner_covariance);

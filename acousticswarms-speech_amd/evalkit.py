@@ -21,7 +21,7 @@ from .patch import FS, SPEED_OF_SOUND
 NO_MATCH = 10000.0
 
 
-def find_best_permutation(wav_gt, wav_pred, pos_gt, pos_pred, acceptable_range=1, accept_sisdr=-15):
+def find_best_permutation(wav_gt, wav_pred, pos_gt, pos_pred, acceptable_range=1, accept_sisdr=-15, sisdr=None):
     """Pairs (prediction index, ground-truth index), in ground-truth order, that maximise the
     number of inliers (xy distance < acceptable_range AND SI-SDR > accept_sisdr) and, among
     those, minimise the mean of (distance - SI-SDR) over the inlier pairs
@@ -29,7 +29,10 @@ def find_best_permutation(wav_gt, wav_pred, pos_gt, pos_pred, acceptable_range=1
 
     The reference scores every permutation of max(n_gt, n_pred) items; the same optimum is the
     maximum-cardinality, minimum-cost matching of the inlier graph, found here with the
-    Hungarian method (identical result up to exact ties, and usable beyond ~9 items)."""
+    Hungarian method (identical result up to exact ties, and usable beyond ~9 items).
+
+    ``sisdr``: an [n_pred, n_gt] matrix of the SI-SDRs (``cross_sisdr_batch``), used in place of the ``si_sdr`` calls;
+    the waveforms are then not looked at."""
     from scipy.optimize import linear_sum_assignment
     pos_gt, pos_pred = np.asarray(pos_gt, dtype=np.float64), np.asarray(pos_pred, dtype=np.float64)
     n_gt, n_pred = pos_gt.shape[0], pos_pred.shape[0]
@@ -40,7 +43,7 @@ def find_best_permutation(wav_gt, wav_pred, pos_gt, pos_pred, acceptable_range=1
     for i in range(n_gt):
         for j in range(n_pred):
             dis = np.linalg.norm(pos_gt[i][:2] - pos_pred[j][:2])
-            neg = -si_sdr(np.asarray(wav_pred[j]), np.asarray(wav_gt[i]))
+            neg = -si_sdr(np.asarray(wav_pred[j]), np.asarray(wav_gt[i])) if sisdr is None else -float(sisdr[j][i])
             loss[i, j] = neg + dis
             inlier[i, j] = dis < acceptable_range and neg < -accept_sisdr
     if not inlier.any():
@@ -226,14 +229,18 @@ def pack_bss_items(counts, lengths, R: int, flen: int = 512, budget: int = BSS_W
     return calls
 
 
-def _bss_device_op(device):
-    """(``torch.ops.asw.bss_eval_sdr``, device) or ``RuntimeError``: there is no quiet fall-back to the host metric."""
+def _device_op(name, device):
+    """(``torch.ops.asw.<name>``, device) or ``RuntimeError``: there is no quiet fall-back to the host metric."""
     import torch
     from . import native
-    op = native.torch_ops().bss_eval_sdr                   # RuntimeError when the library has not been built
+    op = getattr(native.torch_ops(), name)                 # RuntimeError when the library has not been built
     if not torch.cuda.is_available():
         raise RuntimeError('metrics="device" needs a GPU: none is visible to torch')
     return op, torch.device("cuda:0" if device is None else device)
+
+
+def _bss_device_op(device):
+    return _device_op("bss_eval_sdr", device)
 
 
 def bss_eval_sdr_batch(refs, est_sets, flen: int = 512, device=None, op=None, budget: int = BSS_WORKSPACE_BUDGET):
@@ -288,6 +295,71 @@ def bss_eval_sdr_device(reference_sources, estimated_sets, flen: int = 512, devi
     return out[0]
 
 
+# ---- SI-SDR matrices on the device (csrc/eval_kernels.hip: asw_cross_sisdr; DESIGN.md section 7o) ----------------------
+XS_MAX_ITEMS, XS_MAX_EST, XS_MAX_REF = 65535, 4096, 64          # the library's limits (include/asw_hip.h)
+
+
+def cross_sisdr_f64(est, ref):
+    """[P, S] float64: ``hostdsp.si_sdr(est_p, ref_s)`` of every pair, on the float32 values of ``est`` [P, T] and
+    ``ref`` [S, T] widened exactly -- the statement ``asw_cross_sisdr`` is pinned to.  What ``si_sdr`` does with a
+    silent reference (a division by zero) or an all-zero estimate (``ValueError`` from ``log10``) happens here too."""
+    est = np.atleast_2d(np.asarray(est, dtype=np.float32)).astype(np.float64)
+    ref = np.atleast_2d(np.asarray(ref, dtype=np.float32)).astype(np.float64)
+    out = np.zeros((est.shape[0], ref.shape[0]))
+    for p in range(est.shape[0]):
+        for s in range(ref.shape[0]):
+            out[p, s] = si_sdr(est[p], ref[s])
+    return out
+
+
+def cross_sisdr_batch(est_list, ref_list, device=None, op=None):
+    """``cross_sisdr_f64`` of many items on the device.  ``est_list[k]`` is [P_k, T_k], ``ref_list[k]`` is [S_k, T_k];
+    the counts and lengths may differ from item to item (P_k or S_k may be 0).  The rows are rounded to float32 (exact
+    for wav and network output) and the items of one length go out in ONE ``torch.ops.asw.cross_sisdr`` call (at most
+    65535 items each).  -> (list of [P_k, S_k] float64 arrays, sorted list of the items that were recomputed on the
+    host).  An item is recomputed with ``cross_sisdr_f64`` when the device reports status 1 for it -- a silent
+    reference, an all-zero estimate, a value that is not finite -- so it behaves exactly as the host statement does,
+    the exception included.  ``op`` replaces the device op (a stand-in on CPU tensors in the host tests); without it a
+    missing library or GPU is a ``RuntimeError``."""
+    import torch
+    if len(est_list) != len(ref_list):
+        raise ValueError(f"{len(est_list)} estimate sets for {len(ref_list)} reference sets")
+    if not est_list:
+        return [], []
+    ests = [np.ascontiguousarray(e, dtype=np.float32) for e in est_list]
+    refs = [np.ascontiguousarray(r, dtype=np.float32) for r in ref_list]
+    by_length = {}
+    for k, (e, r) in enumerate(zip(ests, refs)):
+        if e.ndim != 2 or r.ndim != 2 or e.shape[1] != r.shape[1]:
+            raise ValueError(f"item {k}: estimates {e.shape} and references {r.shape} are not [P, T] and [S, T]")
+        if e.shape[0] > XS_MAX_EST or r.shape[0] > XS_MAX_REF:
+            raise ValueError(f"item {k}: {e.shape[0]} estimates (at most {XS_MAX_EST}) or {r.shape[0]} references "
+                             f"(at most {XS_MAX_REF})")
+        by_length.setdefault(e.shape[1], []).append(k)
+    if op is None:
+        op, dev = _device_op("cross_sisdr", device)
+    else:
+        dev = torch.device("cpu" if device is None else device)
+    out, recomputed = [None] * len(ests), []
+    for T, members in by_length.items():
+        for first in range(0, len(members), XS_MAX_ITEMS):
+            ks = members[first:first + XS_MAX_ITEMS]
+            est = torch.from_numpy(np.concatenate([ests[k] for k in ks], axis=0)).to(dev)
+            ref = torch.from_numpy(np.concatenate([refs[k] for k in ks], axis=0)).to(dev)
+            vals, status = op(est, ref, [ests[k].shape[0] for k in ks], [refs[k].shape[0] for k in ks])
+            vals, status = vals.cpu().numpy(), status.cpu().numpy()
+            pos = 0
+            for q, k in enumerate(ks):
+                P, S = ests[k].shape[0], refs[k].shape[0]
+                if status[q] != 0:
+                    recomputed.append(k)
+                    out[k] = cross_sisdr_f64(ests[k], refs[k])
+                else:
+                    out[k] = np.array(vals[pos:pos + P * S], dtype=np.float64).reshape(P, S)
+                pos += P * S
+    return out, sorted(recomputed)
+
+
 def compute_metrics(input_signal, est_signal, gt, metrics="host"):
     """(input_sdr, output_sdr, input_sisdr, output_sisdr) per matched talker, as
     sep/eval/get_items.py:46-70 with permute=False: BSS-eval SDR and SI-SDR of the unprocessed
@@ -312,29 +384,69 @@ def evaluate_sample(model, metadata, mix, gt, metrics="host"):
     """Run ``model`` (a ``JointModel``) on one sample and build the reference's result record
     (sep/eval/eval_model.py:129-236).  Returns (record, tp, fp, fn).  ``metrics``: "host" or "device", where the
     record's two BSS-eval SDR fields come from (``compute_metrics``)."""
-    import torch
     check_metrics(metrics)
-    _mics, mic_positions, _voices, gt_pos, offsets_gt, roi = preprocess_metadata(metadata)
+    return record_from_result(metadata, mix, gt, search_result(model, metadata, mix), metrics)
+
+
+def search_result(model, metadata, mix):
+    """The first step of ``evaluate_sample``: ``model`` set up for the sample's array and run on ``mix``.  -> what the
+    record is built from, under the keys of ``shard.localize_batch(..., separate=, details=True)``: ``centres`` [K, 3],
+    ``offsets`` (the ``localization_offset`` of every talker), ``audio_offsets``, ``audio_loc`` [K, T] (the
+    localisation-stage audio) and ``audio`` (the separated audio, None without a separation model)."""
+    import torch
+    _mics, mic_positions, _voices, _gt_pos, _offsets_gt, roi = preprocess_metadata(metadata)
     model.setup(mic_positions=mic_positions, speaker_range=roi)
     patches, audio_loc, audio, _, _, _ = model(torch.from_numpy(np.ascontiguousarray(mix, dtype=np.float32)))
     n_out = len(patches)
-    est_pos = np.array([p[0].center_pos() for p in patches]).reshape(-1, 3)
-    est_off = [np.asarray(p[4]["localization_offset"]) for p in patches]
-    audio_loc = np.asarray(audio_loc).reshape(n_out, -1) if n_out else np.zeros((0, mix.shape[1]))
-    sep_audio = audio_loc if audio is None else np.asarray(audio)     # joint decoder output when plugged in
-    perm = find_best_permutation(gt, sep_audio, gt_pos, est_pos, acceptable_range=1) if n_out else []
+    return {"centres": np.array([p[0].center_pos() for p in patches]).reshape(-1, 3),
+            "offsets": [np.asarray(p[4]["localization_offset"]) for p in patches],
+            "audio_offsets": [np.asarray(p[4]["audio_offset"]) for p in patches],
+            "audio_loc": np.asarray(audio_loc).reshape(n_out, -1) if n_out else np.zeros((0, mix.shape[1])),
+            "audio": audio}
+
+
+def _separated(result):
+    """The audio the record scores: the joint decoder's output when there is one, else the localisation stage's."""
+    audio = result.get("audio")
+    return result["audio_loc"] if audio is None else np.asarray(audio)
+
+
+def record_from_result(metadata, mix, gt, result, metrics="host", scores=None):
+    """The second step of ``evaluate_sample``: the reference's result record (sep/eval/eval_model.py:129-236) from what
+    the search returned (``search_result``, or a dict of ``shard.localize_batch(..., details=True)``).  Returns
+    (record, tp, fp, fn).  Without ``scores`` every SI-SDR is ``hostdsp.si_sdr`` on the host and ``metrics`` says where
+    the two BSS-eval SDR fields come from (``compute_metrics``).  ``scores`` (``records_from_results``) holds them
+    ready-made: ``"sisdr"``, the [1 + K (+ K), n_gt] matrix of ``cross_sisdr_batch`` over the rows [mix[0]; separated;
+    localisation stage] (the third block only with a separation model), ``"perm"``, the matching found from it, and
+    ``"bss"``, the [2, matched] BSS-eval SDRs of the unprocessed and the separated set."""
+    check_metrics(metrics)
+    _mics, mic_positions, _voices, gt_pos, offsets_gt, roi = preprocess_metadata(metadata)
+    est_pos, audio_loc, sep_audio = result["centres"], result["audio_loc"], _separated(result)
+    n_out = len(est_pos)
+    est_off = [np.asarray(o) for o in result["offsets"]]
+    if scores is not None:
+        perm = scores["perm"]
+    else:
+        perm = find_best_permutation(gt, sep_audio, gt_pos, est_pos, acceptable_range=1) if n_out else []
     rec = {"mic_pos": mic_positions.tolist(), "speaker_pos": gt_pos.tolist(), "gt": [], "pred": [],
            "false_positive": [], "est_offsets": np.array(est_off).tolist(), "perm": perm}
     tp, fn, fp = len(perm), gt.shape[0] - len(perm), n_out - len(perm)
     for s in range(gt_pos.shape[0]):
         rec["gt"].append({"sample": offsets_gt[:, s].tolist(), "pos": gt_pos[s].tolist()})
     unmatched = list(range(n_out))
-    if perm:
+    if perm and scores is not None:
+        M, loc0 = scores["sisdr"], 1 + (n_out if result.get("audio") is not None else 0)
+        in_sdr, out_sdr = scores["bss"]
+        in_sisdr_l = [float(M[0, s]) for _o, s in perm]
+        out_sisdr_l = [float(M[1 + o, s]) for o, s in perm]
+        loc_sisdr_l = [float(M[loc0 + o, s]) for o, s in perm]
+    elif perm:
         # matched pairs in the reference's order (eval_model.py:162-187): separated output (joint
         # decoder when attached), localisation-stage output, ground truth, unprocessed mic 0
         pa = np.array(perm)
         ref_sig = np.repeat(mix[0:1].astype(np.float64), len(perm), axis=0)
         in_sdr, out_sdr, in_sisdr_l, out_sisdr_l = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics)
+        loc_sisdr_l = [si_sdr(audio_loc[o].astype(np.float64), gt[s].astype(np.float64)) for o, s in perm]
     for i, (out_id, s) in enumerate(perm):
         unmatched.remove(out_id)
         in_sisdr = in_sisdr_l[i]
@@ -346,25 +458,146 @@ def evaluate_sample(model, metadata, mix, gt, metrics="host"):
             "si_snr_in": in_sisdr,
             "si_snri": out_sisdr_l[i] - in_sisdr,
             "si_snr_in_old": in_sisdr,
-            "si_snri_old": si_sdr(audio_loc[out_id].astype(np.float64), gt[s].astype(np.float64)) - in_sisdr})
+            "si_snri_old": loc_sisdr_l[i] - in_sisdr})
     for rid in unmatched:
         rec["false_positive"].append({"pos": est_pos[rid].tolist(),
-                                      "sample": np.asarray(patches[rid][4]["audio_offset"]).tolist()})
+                                      "sample": np.asarray(result["audio_offsets"][rid]).tolist()})
     return rec, tp, fp, fn
 
 
-def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host"):
-    """Every sample directory of ``dataset_dir``; writes ``result_<sample>.json`` like the
-    reference and returns overall (tp, fp, fn, precision, recall).  ``metrics`` as in ``evaluate_sample``."""
+def records_from_results(samples, results, metrics="host", ops=None, stats=None):
+    """The records of a batch: ``samples[k]`` = (metadata, mix, gt) as ``get_items`` reads them, ``results[k]`` what the
+    search returned for it (``search_result`` / ``shard.localize_batch(..., details=True)``).  -> [(record, tp, fp, fn)]
+    in sample order.  ``metrics="host"``: ``record_from_result`` per sample, the host statements throughout.
+    ``metrics="device"``, three steps:
+      1. ONE ``cross_sisdr_batch`` call: the estimate rows of a sample are [mix[0]; separated_0..K-1;
+         localisation-stage_0..K-1] (the third block only with a separation model), the references its ground truth;
+         the matcher's matrix and the record's four SI-SDR fields are entries of that one matrix;
+      2. the matching of every sample on the host (``find_best_permutation(sisdr=...)``);
+      3. ONE ``bss_eval_sdr_batch`` call over the matched rows of all samples (R = 2: unprocessed and separated).
+    ``ops``: stand-ins (cross op, BSS op) for the two device ops (host tests).  ``stats``: a dict that receives the
+    seconds of the steps (``"sisdr_s"``, ``"match_s"``, ``"bss_s"``)."""
+    import time
     check_metrics(metrics)
+    if len(samples) != len(results):
+        raise ValueError(f"{len(results)} results for {len(samples)} samples")
+    if metrics == "host":
+        return [record_from_result(meta, mix, gt, res, "host") for (meta, mix, gt), res in zip(samples, results)]
+    cross_op, bss_op = ops if ops is not None else (None, None)
+    t0 = time.perf_counter()
+    est_rows = []
+    for (_meta, mix, _gt), res in zip(samples, results):
+        rows = [np.asarray(mix[0:1], dtype=np.float32), np.asarray(_separated(res), dtype=np.float32)]
+        if res.get("audio") is not None:
+            rows.append(np.asarray(res["audio_loc"], dtype=np.float32))
+        est_rows.append(np.concatenate([r.reshape(-1, mix.shape[1]) for r in rows], axis=0))
+    mats, _ = cross_sisdr_batch(est_rows, [gt for _meta, _mix, gt in samples], op=cross_op)
+    t1 = time.perf_counter()
+    perms = []
+    for (meta, _mix, gt), res, M in zip(samples, results, mats):
+        K = len(res["centres"])
+        gt_pos = preprocess_metadata(meta)[3]
+        perms.append(find_best_permutation(gt, None, gt_pos, res["centres"], acceptable_range=1, sisdr=M[1:1 + K])
+                     if K else [])
+    t2 = time.perf_counter()
+    matched = [k for k, perm in enumerate(perms) if perm]
+    refs, sets = [], []
+    for k in matched:
+        (_meta, mix, gt), pa = samples[k], np.array(perms[k])
+        ref_sig = np.repeat(np.asarray(mix[0:1], dtype=np.float32), len(pa), axis=0)
+        refs.append(np.asarray(gt)[pa[:, 1]])
+        sets.append(np.stack([ref_sig, np.asarray(_separated(results[k]), dtype=np.float32)[pa[:, 0]]]))
+    bss, _ = bss_eval_sdr_batch(refs, sets, op=bss_op)
+    bss = dict(zip(matched, bss))
+    if stats is not None:
+        stats.update(sisdr_s=t1 - t0, match_s=t2 - t1, bss_s=time.perf_counter() - t2)
+    return [record_from_result(meta, mix, gt, res, "device", {"sisdr": mats[k], "perm": perms[k], "bss": bss.get(k)})
+            for k, ((meta, mix, gt), res) in enumerate(zip(samples, results))]
+
+
+def group_samples(shapes, batch):
+    """The calls of ``evaluate_dataset(batch=)``: ``shapes[k]`` = (M, T) of sample k in sorted order; consecutive
+    samples of equal shape go together, at most ``batch`` to a call.  -> list of (first, last) ranges, ``last``
+    exclusive, covering every sample once and in order."""
+    if batch < 1:
+        raise ValueError(f"batch = {batch} < 1")
+    groups, first = [], 0
+    for k in range(1, len(shapes) + 1):
+        if k == len(shapes) or tuple(shapes[k]) != tuple(shapes[first]) or k - first == batch:
+            groups.append((first, k))
+            first = k
+    return groups
+
+
+def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", batch=1, concurrent=2, stats=None):
+    """Every sample directory of ``dataset_dir``; writes ``result_<sample>.json`` like the
+    reference and returns overall (tp, fp, fn, precision, recall).  ``metrics`` as in ``evaluate_sample``.
+
+    ``batch=1``: one ``evaluate_sample`` per directory.  ``batch=N``: the directories in sorted order, consecutive
+    samples of equal (M, T) in calls of at most N (``group_samples``); a call is ONE
+    ``shard.localize_batch(..., geometries=, separate=, details=True, concurrent=concurrent)`` -- every sample on its
+    own array -- followed by ONE ``records_from_results``.  Same files, same totals.  ``stats``: a dict that receives
+    the summed seconds of reading, searching, the metrics steps and writing (tests/perf_eval_dataset.py)."""
+    import time
+    check_metrics(metrics)
+    if batch < 1:
+        raise ValueError(f"batch = {batch} < 1")
     tot = np.zeros(3, dtype=np.int64)
-    for name in sorted(d for d in os.listdir(dataset_dir) if os.path.isdir(os.path.join(dataset_dir, d))):
-        metadata, mix, gt = get_items(os.path.join(dataset_dir, name))
-        rec, tp, fp, fn = evaluate_sample(model, metadata, mix, gt, metrics)
-        tot += (tp, fp, fn)
+    spent = {"read_s": 0.0, "search_s": 0.0, "sisdr_s": 0.0, "match_s": 0.0, "bss_s": 0.0, "record_s": 0.0, "write_s": 0.0}
+
+    def write(name, rec, tp, fp, fn):
+        tot[:] += (tp, fp, fn)
         if results_folder is not None:
+            t0 = time.perf_counter()
             os.makedirs(results_folder, exist_ok=True)
             with open(os.path.join(results_folder, f"result_{name}.json"), "w") as f:
                 json.dump(rec, f, indent=4)
+            spent["write_s"] += time.perf_counter() - t0
+
+    def flush(group):
+        from .shard import localize_batch
+        samples = [item for _name, item in group]
+        geometries = []
+        for meta, _mix, _gt in samples:
+            _mics, mic_positions, _voices, _gt_pos, _offsets_gt, roi = preprocess_metadata(meta)
+            geometries.append((mic_positions, roi))
+        import torch
+        mixes = [torch.from_numpy(np.ascontiguousarray(mix, dtype=np.float32)) for _meta, mix, _gt in samples]
+        t0 = time.perf_counter()
+        results = localize_batch(model, mixes, geometries=geometries,
+                                 separate=model.sep_model is not None, details=True, concurrent=concurrent)
+        t1 = time.perf_counter()
+        step = {}
+        records = records_from_results(samples, results, metrics, stats=step)
+        spent["search_s"] += t1 - t0
+        spent["record_s"] += time.perf_counter() - t1
+        for key, value in step.items():
+            spent[key] += value
+        for (name, _item), out in zip(group, records):
+            write(name, *out)
+
+    group = []
+    for name in sorted(d for d in os.listdir(dataset_dir) if os.path.isdir(os.path.join(dataset_dir, d))):
+        t0 = time.perf_counter()
+        metadata, mix, gt = get_items(os.path.join(dataset_dir, name))
+        spent["read_s"] += time.perf_counter() - t0
+        if batch == 1:
+            t0 = time.perf_counter()                         # evaluate_sample, its two steps timed apart
+            result = search_result(model, metadata, mix)
+            t1 = time.perf_counter()
+            rec, tp, fp, fn = record_from_result(metadata, mix, gt, result, metrics)
+            spent["search_s"] += t1 - t0
+            spent["record_s"] += time.perf_counter() - t1
+            write(name, rec, tp, fp, fn)
+            continue
+        # the grouping rule applied as the samples arrive: a second group means this sample opens a new call
+        if len(group_samples([item[1].shape for _n, item in group] + [mix.shape], batch)) > 1:
+            flush(group)
+            group = []
+        group.append((name, (metadata, mix, gt)))
+    if group:
+        flush(group)
+    if stats is not None:
+        stats.update(spent)
     tp, fp, fn = (int(v) for v in tot)
     return {"tp": tp, "fp": fp, "fn": fn, "precision": tp / max(tp + fp, 1), "recall": tp / max(tp + fn, 1)}

@@ -18,10 +18,12 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["asw_common.cpp", "convgemm.hip", "resconv.hip", "pipegemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip",
            "misc_kernels.hip", "attention.hip", "srp_kernels.hip",
            "pruner_kernels.hip", "geometry_kernels.hip", "cluster_kernels.hip",
-           "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip", "bss_kernels.hip"]
+           "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip", "bss_kernels.hip", "eval_kernels.hip"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
-# (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out)
-EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"], "cluster_kernels.hip": ["-ffp-contract=off"]}
+# (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out; eval_kernels.hip
+# rounds a * ref before it subtracts, as hostdsp.si_sdr does)
+EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"], "cluster_kernels.hip": ["-ffp-contract=off"],
+               "eval_kernels.hip": ["-ffp-contract=off"]}
 OPS_PATH = os.path.join(_HERE, "libasw_torch_ops.so")      # TORCH_LIBRARY(asw, ...) adapters over the C ABI
 OPS_SOURCE = "torch_ops.cpp"
 
@@ -261,6 +263,9 @@ SIGNATURES = {
     "asw_bss_eval_sdr_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "asw_bss_eval_sdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    "asw_cross_sisdr_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int, c_int]),
+    "asw_cross_sisdr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
     "asw_add_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "asw_search_area": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double,
                                 POINTER(c_int), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

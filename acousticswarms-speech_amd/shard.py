@@ -211,7 +211,7 @@ class ShardedSpotModel:
         return sorted(merged, key=key)
 
 
-def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None, separate=False):
+def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None, separate=False, details=False):
     """A batch of mixtures over the ranks of one node (BASELINE config "batch of 64 mixtures"):
     with at least as many mixtures as ranks the cheapest partition is by whole mixture --
     contiguous balanced blocks, each rank runs the complete search of its mixtures on its own
@@ -235,6 +235,11 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
     (batching.separate_stack), in the plain loop the ``audio`` of ``forward``.  Needs ``joint_model.sep_model`` and a
     single rank (``RuntimeError`` otherwise: audio does not travel over the object all-gather).
 
+    ``details=True``: every dict also holds what an evaluation record needs (``evalkit.record_from_result``):
+    ``"offsets"``, the ``localization_offset`` rows [K, M-1], ``"audio_offsets"`` [K, M-1] and ``"audio_loc"``, the
+    localisation-stage audio (float32 [K, T]; (0, T) when no talker was found) -- in the batched form and in the plain
+    loop alike.  A single rank only, like ``separate=True`` (``RuntimeError`` otherwise).
+
     ``joint_model.spot_model`` must be the plain per-rank model here.  Returns, on every rank and
     in mixture order, a list of dicts {centres [K,3], powers [K], names, spot_times, times[5]}."""
     from .batching import check_geometries, no_full_collections, result_record
@@ -248,6 +253,8 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
     world = dist.get_world_size(group) if on else 1
     if separate and world > 1:
         raise RuntimeError("separate=True runs on one rank only: the audio is not gathered across ranks")
+    if details and world > 1:
+        raise RuntimeError("details=True runs on one rank only: the audio is not gathered across ranks")
     if getattr(joint_model.spot_model, "world", 1) > 1:
         raise RuntimeError("localize_batch shards by mixture: pass the un-sharded per-rank spot model")
     b = shard_bounds(len(mixes), world)
@@ -260,7 +267,7 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
         from .batching import search_batched
         res, stats = search_batched(joint_model, [mixes[k] for k in mine], concurrent=concurrent,
                                     geometries=None if geometries is None else [geometries[k] for k in mine],
-                                    separate=separate)
+                                    separate=separate, details=details)
         localize_batch.last_stats = stats                    # diagnostic: launches, candidates, GPU seconds inside them
         local = list(zip(mine, res))
     else:
@@ -274,7 +281,8 @@ def localize_batch(joint_model, mixes, group=None, concurrent=2, geometries=None
                     if own:
                         joint_model.use_geometry(geometries[k][0], geometries[k][1])
                     patches, _audio_loc, audio, _d0, _d1, spot_times = joint_model.forward(mixes[k])
-                    local.append((k, result_record(patches, spot_times, list(joint_model.times))))
+                    local.append((k, result_record(patches, spot_times, list(joint_model.times), details,
+                                                   tuple(np.shape(mixes[k])))))
                     if separate:
                         local[-1][1]["audio"] = np.empty((0, np.shape(mixes[k])[-1]), dtype=np.float32) if audio is None \
                             else np.asarray(audio, dtype=np.float32)

@@ -778,6 +778,38 @@ size_t asw_bss_eval_sdr_workspace_bytes(const int32_t* counts_host, int K, int R
 int asw_bss_eval_sdr(const float* ref, const float* est, const int32_t* counts_host, int K, int R, int T, int flen,
                      double* sdr, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* SI-SDR of every (estimate, reference) pair of a ragged batch of K samples on the device, as hostdsp.si_sdr states it
+ * in float64: for estimate e and reference r of one item, rr = sum r^2, a = sum r e / rr, te = sum (a r)^2,
+ * ne = sum (e - a r)^2, value 10 log10(te / (ne + 1e-8)).  est float32 [NE][T] and ref float32 [NR][T] (device): item k
+ * owns the next P_k = est_counts_host[k] rows of est and the next S_k = ref_counts_host[k] rows of ref, with no padding;
+ * both count arrays are HOST arrays read before the call returns.  out float64 (device), packed with no padding: item k
+ * is a row-major [P_k][S_k] block at offset sum_{j<k} P_j S_j, entry (p, s) = si_sdr(est_p, ref_s).  status int32 [K]
+ * (device).  The float32 inputs are widened exactly; everything after is float64.
+ *   Two passes, as the statement: pass A sums rr and sum r e (a float32 x float32 product is exact in double), pass B
+ *   sums te and ne element by element from a r and e - a r with a known -- ne is NOT formed as sum e^2 - (sum r e)^2 / rr,
+ *   which loses the value from about 57 dB up.  The file is compiled without floating-point contraction: a r is rounded
+ *   before it is subtracted, as numpy rounds it, so only the order of the sums differs from the statement.
+ *   T is cut into chunks of 512; a workgroup owns a tile of 8 estimate rows x 8 reference rows of one item and a run of
+ *   whole chunks (at most 8 runs), stages every row of the tile once per chunk and pass in LDS (a row beyond the item's
+ *   own and samples beyond T as zeros, never read from memory), sums its run in order -- a lane per pair, each of the
+ *   four waves a fixed quarter of every chunk, the quarters folded in order -- and a second launch folds the runs left
+ *   to right.
+ *   status[k] = 1 when some pair of item k has rr == 0, te == 0 or a value that is not finite (a silent reference
+ *   divides by zero in the statement, an all-zero estimate raises in its log10): the caller recomputes the item with
+ *   the host statement (evalkit.cross_sisdr_batch does); its out block is written but meaningless.  status[k] = 0
+ *   otherwise, also for an item with P_k = 0 or S_k = 0, which rides along and writes nothing else.
+ * workspace: asw_cross_sisdr_workspace_bytes(est_counts_host, ref_counts_host, K, T) bytes, 8-byte aligned (the
+ * lists, (a, rr) per pair, the partial sums, a flag per tile; 0 with the error message set for arguments this call
+ * would refuse).  One small host-to-device copy of the lists on the stream.  No atomics, no cross-lane operations, no
+ * device-side assert, plain vector stores, one writer per address; workgroups hand nothing to each other inside a
+ * launch: two calls give identical bytes, every output slot is written, every workspace word that is read is written
+ * first, and the result does not depend on what out, status or the workspace held.  Every refusal -- a null pointer,
+ * K < 0 or K > 65535, T < 1 or T > 2^25, a negative count, P_k > 4096 or S_k > 64, a short or misaligned workspace --
+ * happens on the host before the copy and the first launch; K = 0 succeeds and touches nothing. */
+size_t asw_cross_sisdr_workspace_bytes(const int32_t* est_counts_host, const int32_t* ref_counts_host, int K, int T);
+int asw_cross_sisdr(const float* est, const float* ref, const int32_t* est_counts_host, const int32_t* ref_counts_host,
+                    int K, int T, double* out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* HOST function (no GPU): breadth-first subdivision of one coarse hypercube into the fine
  * candidate hypercubes -- search_area / binary_area_divide_width
  * (sep/helpers/local_utils_3d.py:212-335) with Patch.check_out / hyperbola_sample
