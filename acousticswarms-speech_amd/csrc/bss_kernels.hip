@@ -1,11 +1,14 @@
-// bss_kernels.hip -- BSS-eval SDR (the "mtifilt" decomposition of evalkit._project / evalkit.bss_eval_sdr) of a ragged
-// batch of samples on the device, float64 throughout (include/asw_hip.h: asw_bss_eval_sdr).
+// bss_kernels.hip -- BSS-eval SDR, SIR and SAR (the "mtifilt" decomposition of evalkit._project / evalkit.bss_eval_sdr /
+// evalkit.bss_eval_sources) of a ragged batch of samples on the device, float64 throughout (include/asw_hip.h:
+// asw_bss_eval_sources and its view asw_bss_eval_sdr; DESIGN.md sections 7j and 7p).
 //
 // Per item (S references, R estimate sets) the work is: direct correlations of every reference against every reference
 // and every estimate (bss_corr, bss_fold), the block-Toeplitz Gram matrix of the S references and the S single-reference
 // Toeplitz matrices (bss_gram), one blocked Cholesky over that whole ragged list of symmetric systems (bss_potrf,
 // bss_trsm, bss_update per 64-wide step), forward and backward substitution of every right-hand side (bss_solve), the
-// two projections as direct flen-tap FIRs with the energies of the decomposition (bss_project) and the ratio (bss_sdr).
+// two projections as direct flen-tap FIRs with the energies of the decomposition (bss_project) and the ratios (bss_sdr).
+// Matched mode scores estimate j against reference j; all-pairs mode every estimate against every reference, which adds
+// single-reference right-hand sides (they are rows of corr already) and rows of the projection, nothing else.
 // Every launch is a grid over list entries; workgroups hand nothing to each other inside a launch, there are no
 // atomics, no cross-lane operations and no device-side asserts, and every sum has one fixed order.
 #include "asw_common.h"
@@ -27,36 +30,37 @@ constexpr double PIVOT_GUARD = 0x1p-40;
 
 struct Item {                          // one sample of the batch
   int64_t corr_off;                    // corr + corr_off: [(R + 1) S][S][flen], (b row, reference, lag)
-  int64_t x_off;                       // xsol + x_off: x1 [R S][flen], then (S > 1) xF [R S][S flen]
-  int32_t n0, S, sys0, pair0;          // first row, talkers, first system (S singles, then the full one when S > 1)
-};
+  int64_t x_off;                       // xsol + x_off: x1 [rows of the item][flen], then (S > 1) xF [R S][S flen]
+  int32_t n0, S, sys0, out0;           // first row, talkers, first system (S singles, then the full one when S > 1),
+};                                     // first output column (n0 matched, the sum of the earlier S^2 all pairs)
 struct System {
   int64_t g_off;                       // gram + g_off: order x order, row-major, lower triangle in use
   int32_t order, item, src, nt;        // src = the reference of a single system, -1 for the full one; nt = tiles
 };
 struct Pair { int32_t item, brow, i, pad; };        // b row (reference < S <= estimate S + r S + j) against reference i
-struct Solve {                         // estimate row e = r S + j of the item against the full or its single system
+struct Solve {                         // estimate row e = r S + e' of the item against the full system or that of reference j
   int64_t x_off;                       // xsol + x_off: the solution, order doubles
-  int32_t item, e, full, pad;
+  int32_t item, e, full, j;            // j = -1 with the full system
 };
-struct Row { int32_t item, e; };
+struct Row { int32_t item, ej; };      // ej = e S + j: estimate row e of the item scored against its reference j
 
 struct Plan {
-  int K, R, T, flen, N;
-  long P, nsys, nsolve, E;
+  int K, R, T, flen, N, all_pairs, nw;                                   // nw: sums per row and chunk, 2 (SDR) or 5
+  long P, nsys, nsolve, E, Q;                                            // E rows; Q = sum S^2
   int nchunk, nsplit, cps, nchunk_p, ntmax;
   size_t tab_bytes, o_items, o_sys, o_pairs, o_solves, o_rows;           // inside the table blob
   size_t o_part, o_corr, o_gram, o_x, o_proj, total;                     // byte offsets in the workspace
 };
 
 // null on success, else the refusal.  Sizes only: no pointer is looked at.
-const char* make_plan(const int32_t* counts, int K, int R, int T, int flen, Plan& p, char* msg, size_t msg_len) {
+const char* make_plan(const int32_t* counts, int K, int R, int T, int flen, int all_pairs, int nw, Plan& p, char* msg,
+                      size_t msg_len) {
   if (K < 0 || R < 1) { snprintf(msg, msg_len, "K = %d < 0 or R = %d < 1", K, R); return msg; }
   if (flen < 1 || flen > MAX_FLEN) { snprintf(msg, msg_len, "flen = %d outside 1..%d", flen, MAX_FLEN); return msg; }
   if (T < flen || T > MAX_T) { snprintf(msg, msg_len, "T = %d outside flen = %d .. %d", T, flen, MAX_T); return msg; }
   if (K > 0 && !counts) { snprintf(msg, msg_len, "null counts"); return msg; }
   p = Plan{};
-  p.K = K, p.R = R, p.T = T, p.flen = flen;
+  p.K = K, p.R = R, p.T = T, p.flen = flen, p.all_pairs = all_pairs, p.nw = nw;
   size_t gram = 0, x = 0;
   for (int k = 0; k < K; ++k) {
     const long S = counts[k];
@@ -65,16 +69,18 @@ const char* make_plan(const int32_t* counts, int K, int R, int T, int flen, Plan
       snprintf(msg, msg_len, "item %d: %ld references of %d taps make a system of order %ld > %d", k, S, flen, S * flen, MAX_ORDER);
       return msg;
     }
+    const long rows = (long)R * S * (all_pairs ? S : 1);                 // single-reference solves = rows of the projection
     p.N += (int)S;
+    p.Q += S * S;
+    p.E += rows;
     p.P += (long)(R + 1) * S * S;
     p.nsys += S > 1 ? S + 1 : S;
-    p.nsolve += (long)R * S * (S > 1 ? 2 : 1);
+    p.nsolve += rows + (S > 1 ? (long)R * S : 0);
     gram += (size_t)S * flen * flen + (S > 1 ? (size_t)(S * flen) * (S * flen) : 0);
-    x += (size_t)R * S * ((size_t)flen + (S > 1 ? (size_t)S * flen : 0));
+    x += (size_t)rows * flen + (S > 1 ? (size_t)R * S * S * flen : 0);
     const int nt = asw::cdiv(S * flen, NB);
     if (S > 0 && nt > p.ntmax) p.ntmax = nt;
   }
-  p.E = (long)R * p.N;
   if (p.P > (1L << 30) || p.nsolve > (1L << 30)) { snprintf(msg, msg_len, "R = %d sets of %d rows are too many", R, p.N); return msg; }
   p.nchunk = asw::cdiv(T, TC);
   const int split = p.nchunk < MAX_SPLIT ? p.nchunk : MAX_SPLIT;
@@ -92,7 +98,7 @@ const char* make_plan(const int32_t* counts, int K, int R, int T, int flen, Plan
   p.o_corr = o, o += (size_t)p.P * flen * sizeof(double);
   p.o_gram = o, o += gram * sizeof(double);
   p.o_x = o, o += x * sizeof(double);
-  p.o_proj = o, o += (size_t)p.E * p.nchunk_p * 2 * sizeof(double);
+  p.o_proj = o, o += (size_t)p.E * p.nchunk_p * nw * sizeof(double);
   p.total = o;
   return nullptr;
 }
@@ -315,12 +321,12 @@ __global__ __launch_bounds__(256) void bss_solve_kernel(const Item* __restrict__
   __shared__ double pv;
   const Solve so = solves[blockIdx.x];
   const Item it = items[so.item];
-  const int S = it.S, j_src = so.e % S, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const System sy = systems[it.sys0 + (so.full ? S : j_src)];
+  const int S = it.S, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const System sy = systems[it.sys0 + (so.full ? S : so.j)];
   const int M = sy.order, nt = sy.nt;
   const double* G = gram + sy.g_off;
-  // d: the lags of estimate row e against every reference (full) or against its own reference (single)
-  const double* d = corr + it.corr_off + ((size_t)(S + so.e) * S + (so.full ? 0 : j_src)) * flen;
+  // d: the lags of estimate row e against every reference (full) or against reference j (single)
+  const double* d = corr + it.corr_off + ((size_t)(S + so.e) * S + (so.full ? 0 : so.j)) * flen;
   for (int t = 0; t < nt; ++t) {                                         // forward
     const int base = t * NB, nr = M - base < NB ? M - base : NB;
     __syncthreads();
@@ -381,21 +387,26 @@ __global__ __launch_bounds__(256) void bss_solve_kernel(const Item* __restrict__
   for (int m = tid; m < M; m += 256) out[m] = yl[m];
 }
 
-// ---- 5. projections and energies of one estimate row over one chunk of the T + flen - 1 output samples:
-// sp1 = x1 * ref_j, spF = sum_i xF_i * ref_i (S = 1: spF is sp1), then the decomposition as evalkit.bss_eval_sdr forms it
+// ---- 5. projections and energies of one row (estimate row e against reference j) over one chunk of the T + flen - 1
+// output samples: sp1 = x1 * ref_j, spF = sum_i xF_i * ref_i (S = 1: spF is sp1), then the decomposition as
+// evalkit.bss_eval_sdr forms it.  FULL adds the three sums SIR and SAR need to the two of the SDR.  In all-pairs mode the
+// S rows of an estimate each form its spF again.
+template <bool FULL>
 __global__ __launch_bounds__(256) void bss_project_kernel(const float* __restrict__ ref, const float* __restrict__ est,
                                                           const Item* __restrict__ items, const Row* __restrict__ rows,
                                                           const double* __restrict__ xsol, int N, int R, int T, int flen,
-                                                          int nchunk_p, double* __restrict__ proj) {
+                                                          int all_pairs, int nchunk_p, double* __restrict__ proj) {
+  constexpr int NW = FULL ? 5 : 2;
   __shared__ double rs[TC + MAX_FLEN - 1];                               // ref_i[t0 - (flen - 1) .. t0 + TC)
   __shared__ double cf[MAX_FLEN], c1[MAX_FLEN];
-  __shared__ double rn[256], rd[256];
+  __shared__ double red[NW][256];
   const int tid = threadIdx.x;
   const Row rw = rows[blockIdx.x];
   const Item it = items[rw.item];
-  const int S = it.S, j = rw.e % S, r = rw.e / S, t0 = blockIdx.y * TC;
-  const double* x1 = xsol + it.x_off + (size_t)rw.e * flen;
-  const double* xF = xsol + it.x_off + (size_t)R * S * flen + (size_t)rw.e * S * flen;
+  const int S = it.S, e = rw.ej / S, j = rw.ej % S, t0 = blockIdx.y * TC;
+  const int nrow = R * S * (all_pairs ? S : 1);                          // x1 of the item: one per row
+  const double* x1 = xsol + it.x_off + (size_t)(all_pairs ? rw.ej : e) * flen;
+  const double* xF = xsol + it.x_off + (size_t)nrow * flen + (size_t)e * S * flen;
   double spF[4] = {0.0, 0.0, 0.0, 0.0}, sp1[4] = {0.0, 0.0, 0.0, 0.0};
   for (int i = 0; i < S; ++i) {
     const float* a = ref + (size_t)(it.n0 + i) * T;
@@ -423,8 +434,8 @@ __global__ __launch_bounds__(256) void bss_project_kernel(const float* __restric
       }
   }
   const float* rj = ref + (size_t)(it.n0 + j) * T;
-  const float* ev = est + ((size_t)r * N + it.n0 + j) * T;
-  double num = 0.0, den = 0.0;
+  const float* ev = est + ((size_t)(e / S) * N + it.n0 + e % S) * T;
+  double num = 0.0, den = 0.0, si = 0.0, sn = 0.0, sa = 0.0;
   for (int q = 0; q < 4; ++q) {
     const int t = t0 + tid + 256 * q;
     if (t >= T + flen - 1) continue;
@@ -435,57 +446,70 @@ __global__ __launch_bounds__(256) void bss_project_kernel(const float* __restric
     if (t < T) e_artif += (double)ev[t];
     const double u = s_true + e_spat, v = e_interf + e_artif;
     num += u * u, den += v * v;
+    if constexpr (FULL) {
+      const double w = u + e_interf;
+      si += e_interf * e_interf, sn += w * w, sa += e_artif * e_artif;
+    }
   }
-  rn[tid] = num, rd[tid] = den;
+  red[0][tid] = num, red[1][tid] = den;
+  if constexpr (FULL) red[2][tid] = si, red[3][tid] = sn, red[4][tid] = sa;
   for (int s = 128; s >= 1; s >>= 1) {
     __syncthreads();
-    if (tid < s) rn[tid] += rn[tid + s], rd[tid] += rd[tid + s];
+    if (tid < s)
+#pragma unroll
+      for (int k = 0; k < NW; ++k) red[k][tid] += red[k][tid + s];
   }
   if (tid == 0) {
-    double* out = proj + ((size_t)blockIdx.x * nchunk_p + blockIdx.y) * 2;
-    out[0] = rn[0], out[1] = rd[0];
+    double* out = proj + ((size_t)blockIdx.x * nchunk_p + blockIdx.y) * NW;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) out[k] = red[k][0];
   }
 }
 
-// sdr[r][n] = 10 log10(num / den), +inf when den == 0; the chunks folded left to right
+__device__ __forceinline__ double ratio_db(double num, double den) { return den == 0.0 ? HUGE_VAL : 10.0 * log10(num / den); }
+
+// the ratios of every row, the chunks folded left to right, +inf when a denominator is 0: sdr = sum u^2 / sum (e_i + e_a)^2
+// and with FULL sir = sum u^2 / sum e_i^2, sar = sum (u + e_i)^2 / sum e_a^2.  Row (e, j) of an item lands in column
+// out0 + j (matched) or out0 + e' S + j (all pairs) of set r's line of ncol entries, e = r S + e'.
+template <bool FULL>
 __global__ __launch_bounds__(256) void bss_sdr_kernel(const Item* __restrict__ items, const Row* __restrict__ rows,
-                                                      const double* __restrict__ proj, long E, int N, int nchunk_p,
-                                                      double* __restrict__ sdr) {
+                                                      const double* __restrict__ proj, long E, long ncol, int all_pairs,
+                                                      int nchunk_p, double* __restrict__ sdr, double* __restrict__ sir,
+                                                      double* __restrict__ sar) {
+  constexpr int NW = FULL ? 5 : 2;
   const long q = (long)blockIdx.x * 256 + threadIdx.x;
   if (q >= E) return;
   const Row rw = rows[q];
   const Item it = items[rw.item];
-  const double* in = proj + (size_t)q * nchunk_p * 2;
-  double num = in[0], den = in[1];
-  for (int c = 1; c < nchunk_p; ++c) num += in[2 * c], den += in[2 * c + 1];
-  sdr[(size_t)(rw.e / it.S) * N + it.n0 + rw.e % it.S] = den == 0.0 ? HUGE_VAL : 10.0 * log10(num / den);
+  const double* in = proj + (size_t)q * nchunk_p * NW;
+  double s[NW];
+#pragma unroll
+  for (int k = 0; k < NW; ++k) s[k] = in[k];
+  for (int c = 1; c < nchunk_p; ++c)
+#pragma unroll
+    for (int k = 0; k < NW; ++k) s[k] += in[NW * c + k];
+  const int e = rw.ej / it.S, j = rw.ej % it.S;
+  const size_t o = (size_t)(e / it.S) * ncol + it.out0 + (all_pairs ? (e % it.S) * it.S + j : j);
+  sdr[o] = ratio_db(s[0], s[1]);
+  if constexpr (FULL) sir[o] = ratio_db(s[0], s[2]), sar[o] = ratio_db(s[3], s[4]);
 }
 
-}  // namespace
-
-extern "C" size_t asw_bss_eval_sdr_workspace_bytes(const int32_t* counts, int K, int R, int T, int flen) {
+// the general call: matched or all pairs, one output (sir and sar null) or three
+int run(const char* who, const float* ref, const float* est, const int32_t* counts, int K, int R, int T, int flen, int all_pairs,
+        double* sdr, double* sir, double* sar, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
   Plan p;
   char msg[160];
-  if (make_plan(counts, K, R, T, flen, p, msg, sizeof msg)) {
-    asw::set_error(ASW_ERR_ARG, "bss_eval_sdr_workspace_bytes: %s", msg);
-    return 0;
-  }
-  return p.total;
-}
-
-extern "C" int asw_bss_eval_sdr(const float* ref, const float* est, const int32_t* counts, int K, int R, int T, int flen,
-                                double* sdr, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-  Plan p;
-  char msg[160];
-  if (make_plan(counts, K, R, T, flen, p, msg, sizeof msg)) return asw::set_error(ASW_ERR_ARG, "bss_eval_sdr: %s", msg);
+  ASW_CHECK_ARG(all_pairs == 0 || all_pairs == 1, "%s: all_pairs = %d is neither 0 nor 1", who, all_pairs);
+  ASW_CHECK_ARG((sir == nullptr) == (sar == nullptr), "%s: sir and sar go together: one of them alone is null", who);
+  const bool full = sir != nullptr;
+  if (make_plan(counts, K, R, T, flen, all_pairs, full ? 5 : 2, p, msg, sizeof msg)) return asw::set_error(ASW_ERR_ARG, "%s: %s", who, msg);
   if (K == 0) return ASW_OK;
-  ASW_CHECK_ARG(status, "bss_eval_sdr: null status");
+  ASW_CHECK_ARG(status, "%s: null status", who);
   hipStream_t s = asw::as_stream(stream);
   if (p.N > 0) {
-    ASW_CHECK_ARG(ref && est && sdr && workspace, "bss_eval_sdr: null pointer");
-    ASW_CHECK_ARG(workspace_bytes >= p.total, "bss_eval_sdr: workspace of %zu bytes too small, %zu needed", workspace_bytes,
-                  p.total);
-    ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "bss_eval_sdr: workspace not 8-byte aligned");
+    ASW_CHECK_ARG(ref && est && sdr && workspace, "%s: null pointer", who);
+    ASW_CHECK_ARG(workspace_bytes >= p.total, "%s: workspace of %zu bytes too small, %zu needed", who, workspace_bytes, p.total);
+    ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: workspace not 8-byte aligned", who);
   }
   ASW_HIP(hipMemsetAsync(status, 0, (size_t)K * sizeof(int32_t), s));
   if (p.N == 0) return ASW_OK;
@@ -497,11 +521,12 @@ extern "C" int asw_bss_eval_sdr(const float* ref, const float* est, const int32_
   Pair* hp = reinterpret_cast<Pair*>(blob.data() + p.o_pairs);
   Solve* hv = reinterpret_cast<Solve*>(blob.data() + p.o_solves);
   Row* hr = reinterpret_cast<Row*>(blob.data() + p.o_rows);
-  long n0 = 0, np = 0, ns = 0, nv = 0, nr = 0;
+  long n0 = 0, q0 = 0, np = 0, ns = 0, nv = 0, nr = 0;
   int64_t g = 0, x = 0;
   for (int k = 0; k < K; ++k) {
     const int S = counts[k], E = R * S;
-    hi[k] = Item{(int64_t)np * flen, x, (int32_t)n0, S, (int32_t)ns, (int32_t)np};
+    const int64_t rows = (int64_t)E * (all_pairs ? S : 1);
+    hi[k] = Item{(int64_t)np * flen, x, (int32_t)n0, S, (int32_t)ns, (int32_t)(all_pairs ? q0 : n0)};
     for (int b = 0; b < (R + 1) * S; ++b)
       for (int i = 0; i < S; ++i) hp[np++] = Pair{k, b, i, 0};
     for (int i = 0; i < S; ++i) {
@@ -513,12 +538,15 @@ extern "C" int asw_bss_eval_sdr(const float* ref, const float* est, const int32_
       g += (int64_t)S * flen * S * flen;
     }
     for (int e = 0; e < E; ++e) {
-      hv[nv++] = Solve{x + (int64_t)e * flen, k, e, 0, 0};
-      if (S > 1) hv[nv++] = Solve{x + (int64_t)E * flen + (int64_t)e * S * flen, k, e, 1, 0};
-      hr[nr++] = Row{k, e};
+      for (int j = all_pairs ? 0 : e % S; j < (all_pairs ? S : e % S + 1); ++j) {
+        const int64_t row = all_pairs ? (int64_t)e * S + j : e;          // of the item: where its x1 lies
+        hv[nv++] = Solve{x + row * flen, k, e, 0, j};
+        hr[nr++] = Row{k, e * S + j};
+      }
+      if (S > 1) hv[nv++] = Solve{x + rows * flen + (int64_t)e * S * flen, k, e, 1, -1};
     }
-    x += (int64_t)E * (flen + (S > 1 ? S * flen : 0));
-    n0 += S;
+    x += rows * flen + (S > 1 ? (int64_t)E * S * flen : 0);
+    n0 += S, q0 += S * S;
   }
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const Item* di = reinterpret_cast<const Item*>(ws + p.o_items);
@@ -574,14 +602,61 @@ extern "C" int asw_bss_eval_sdr(const float* ref, const float* est, const int32_
     hipLaunchKernelGGL(bss_solve_kernel, dim3((unsigned)p.nsolve), dim3(256), 0, s, di, ds, dv, corr, gram, flen, xsol);
     ASW_LAUNCH_CHECK();
   }
+  const dim3 gp((unsigned)p.E, (unsigned)p.nchunk_p), gr((unsigned)asw::cdiv(p.E, 256));
+  const long ncol = all_pairs ? p.Q : (long)N;
   {
     asw::ProfScope prof(s, "bss_project", 0.0, 0.0);
-    hipLaunchKernelGGL(bss_project_kernel, dim3((unsigned)p.E, (unsigned)p.nchunk_p), dim3(256), 0, s, ref, est, di, dr, xsol, N, R,
-                       T, flen, p.nchunk_p, proj);
+    if (full)
+      hipLaunchKernelGGL(bss_project_kernel<true>, gp, dim3(256), 0, s, ref, est, di, dr, xsol, N, R, T, flen, all_pairs,
+                         p.nchunk_p, proj);
+    else
+      hipLaunchKernelGGL(bss_project_kernel<false>, gp, dim3(256), 0, s, ref, est, di, dr, xsol, N, R, T, flen, all_pairs,
+                         p.nchunk_p, proj);
     ASW_LAUNCH_CHECK();
   }
   asw::ProfScope prof(s, "bss_sdr", 0.0, 0.0);
-  hipLaunchKernelGGL(bss_sdr_kernel, dim3((unsigned)asw::cdiv(p.E, 256)), dim3(256), 0, s, di, dr, proj, p.E, N, p.nchunk_p, sdr);
+  if (full)
+    hipLaunchKernelGGL(bss_sdr_kernel<true>, gr, dim3(256), 0, s, di, dr, proj, p.E, ncol, all_pairs, p.nchunk_p, sdr, sir, sar);
+  else
+    hipLaunchKernelGGL(bss_sdr_kernel<false>, gr, dim3(256), 0, s, di, dr, proj, p.E, ncol, all_pairs, p.nchunk_p, sdr, sir, sar);
   ASW_LAUNCH_CHECK();
   return ASW_OK;
+}
+
+size_t plan_bytes(const char* who, const int32_t* counts, int K, int R, int T, int flen, int all_pairs, int nw) {
+  Plan p;
+  char msg[160];
+  if (all_pairs != 0 && all_pairs != 1) {
+    asw::set_error(ASW_ERR_ARG, "%s: all_pairs = %d is neither 0 nor 1", who, all_pairs);
+    return 0;
+  }
+  if (make_plan(counts, K, R, T, flen, all_pairs, nw, p, msg, sizeof msg)) {
+    asw::set_error(ASW_ERR_ARG, "%s: %s", who, msg);
+    return 0;
+  }
+  return p.total;
+}
+
+}  // namespace
+
+// the size with sir and sar wanted; a call without them needs the 3/5 smaller energy partials and accepts this size too
+extern "C" size_t asw_bss_eval_sources_workspace_bytes(const int32_t* counts, int K, int R, int T, int flen, int all_pairs) {
+  return plan_bytes("bss_eval_sources_workspace_bytes", counts, K, R, T, flen, all_pairs, 5);
+}
+
+extern "C" int asw_bss_eval_sources(const float* ref, const float* est, const int32_t* counts, int K, int R, int T, int flen,
+                                    int all_pairs, double* sdr, double* sir, double* sar, int32_t* status, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return run("bss_eval_sources", ref, est, counts, K, R, T, flen, all_pairs, sdr, sir, sar, status, workspace, workspace_bytes,
+             stream);
+}
+
+// the SDR alone, matched: the general call with all_pairs = 0 and neither sir nor sar
+extern "C" size_t asw_bss_eval_sdr_workspace_bytes(const int32_t* counts, int K, int R, int T, int flen) {
+  return plan_bytes("bss_eval_sdr_workspace_bytes", counts, K, R, T, flen, 0, 2);
+}
+
+extern "C" int asw_bss_eval_sdr(const float* ref, const float* est, const int32_t* counts, int K, int R, int T, int flen,
+                                double* sdr, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  return run("bss_eval_sdr", ref, est, counts, K, R, T, flen, 0, sdr, nullptr, nullptr, status, workspace, workspace_bytes, stream);
 }

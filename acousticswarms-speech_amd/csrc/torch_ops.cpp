@@ -738,6 +738,46 @@ std::tuple<Tensor, Tensor> bss_eval_sdr(const Tensor& ref, const Tensor& est, at
   return {sdr, status};
 }
 
+// -> sdr, sir, sar float64 [R, N] (all_pairs: [R, sum S_k^2], item k a row-major [S_k, S_k] block of (estimate, reference)
+// per set), status [K] int32: the full BSS-eval of a ragged batch (evalkit.bss_eval_sources / bss_eval_matrices per item).
+// The checks of bss_eval_sdr; an item whose status is 1 has to be recomputed by the caller (evalkit.bss_eval_sources_batch
+// does).
+std::tuple<Tensor, Tensor, Tensor, Tensor> bss_eval_sources(const Tensor& ref, const Tensor& est, at::IntArrayRef counts,
+                                                            int64_t flen, bool all_pairs) {
+  need(ref, "ref", at::kFloat, 2);
+  need(est, "est", at::kFloat, 3);
+  same_device(ref, est, "ref and est");
+  const int N = checked_int(ref.size(0), "N"), T = checked_int(ref.size(1), "T"), R = checked_int(est.size(0), "R");
+  const int K = checked_int(static_cast<int64_t>(counts.size()), "K");
+  TORCH_CHECK(R >= 1, "est must hold at least one estimate set");
+  TORCH_CHECK(est.size(1) == N && est.size(2) == T, "est must be [R, N, T] = [R, ", N, ", ", T, "]");
+  std::vector<int32_t> c(K);
+  int64_t total = 0, Q = 0;
+  for (int k = 0; k < K; ++k) {
+    TORCH_CHECK(counts[k] >= 0 && counts[k] <= 16, "counts[", k, "] = ", counts[k], " outside 0..16");
+    c[k] = static_cast<int32_t>(counts[k]);
+    total += counts[k], Q += counts[k] * counts[k];
+  }
+  TORCH_CHECK(total == N, "counts sum to ", total, ", ref has ", N, " rows");
+  const int64_t ncol = all_pairs ? Q : N;
+  Tensor sdr = at::empty({R, ncol}, ref.options().dtype(at::kDouble));
+  Tensor sir = at::empty({R, ncol}, ref.options().dtype(at::kDouble));
+  Tensor sar = at::empty({R, ncol}, ref.options().dtype(at::kDouble));
+  Tensor status = at::empty({K}, ref.options().dtype(at::kInt));
+  if (K == 0) return {sdr, sir, sar, status};
+  const int f = checked_int(flen, "flen");
+  const size_t ws_bytes = asw_bss_eval_sources_workspace_bytes(c.data(), K, R, T, f, all_pairs ? 1 : 0);
+  TORCH_CHECK(ws_bytes > 0 || N == 0, "libasw_hip: asw_bss_eval_sources_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, ref.options().dtype(at::kDouble));
+  Launch l(ref);
+  check_status(asw_bss_eval_sources(N > 0 ? ref.data_ptr<float>() : nullptr, N > 0 ? est.data_ptr<float>() : nullptr, c.data(), K,
+                                    R, T, f, all_pairs ? 1 : 0, N > 0 ? sdr.data_ptr<double>() : nullptr,
+                                    N > 0 ? sir.data_ptr<double>() : nullptr, N > 0 ? sar.data_ptr<double>() : nullptr,
+                                    status.data_ptr<int32_t>(), N > 0 ? ws.data_ptr() : nullptr, ws_bytes, l.stream),
+               "asw_bss_eval_sources");
+  return {sdr, sir, sar, status};
+}
+
 // -> out float64 [sum P_k S_k], status [K] int32: the SI-SDR of every (estimate, reference) pair of a ragged batch, item
 // k a row-major [P_k, S_k] block of out (hostdsp.si_sdr per pair).  Both count lists are read on the host; an item whose
 // status is 1 has to be recomputed by the caller (evalkit.cross_sisdr_batch does).
@@ -795,6 +835,8 @@ TORCH_LIBRARY(asw, m) {
   m.def("coarse_select(Tensor energies, Tensor dis1, Tensor? best=None, float thr1=0.008, bool relative=False, "
         "float rel=0.4, int cap=30) -> (Tensor, Tensor, Tensor)");
   m.def("bss_eval_sdr(Tensor ref, Tensor est, int[] counts, int flen=512) -> (Tensor, Tensor)");
+  m.def("bss_eval_sources(Tensor ref, Tensor est, int[] counts, int flen=512, bool all_pairs=False) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
   m.def("cross_sisdr(Tensor est, Tensor ref, int[] est_counts, int[] ref_counts) -> (Tensor, Tensor)");
   m.def("center_rows_(Tensor(a!) y) -> Tensor(a!)");
   m.def("srp_phat_map(Tensor mix, Tensor twiddle, Tensor pair_i, Tensor pair_j, Tensor tau, Tensor omega, int window, "
@@ -832,6 +874,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("global_clusters", &global_clusters);
   m.impl("coarse_select", &coarse_select);
   m.impl("bss_eval_sdr", &bss_eval_sdr);
+  m.impl("bss_eval_sources", &bss_eval_sources);
   m.impl("cross_sisdr", &cross_sisdr);
   m.impl("center_rows_", &center_rows_);
   m.impl("srp_phat_map", &srp_phat_map);

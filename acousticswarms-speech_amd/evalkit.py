@@ -171,6 +171,91 @@ def bss_eval_sdr(reference_sources, estimated_sources, flen: int = 512):
     return out
 
 
+def _bss_ratios(ref, est_row, j, flen, full_projection):
+    """(sdr, sir, sar) of one estimate against reference ``j``: the decomposition as ``bss_eval_sdr`` forms it (same
+    expressions, same order), ``full_projection`` being ``_project(ref, est_row, flen)``."""
+    nsampl = est_row.shape[0]
+    s_true = np.hstack((ref[j], np.zeros(flen - 1)))
+    e_spat = _project(ref[j:j + 1], est_row, flen) - s_true
+    e_interf = full_projection - s_true - e_spat
+    e_artif = -s_true - e_spat - e_interf
+    e_artif[:nsampl] += est_row
+    num, den = np.sum((s_true + e_spat) ** 2), np.sum((e_interf + e_artif) ** 2)
+    den_i = np.sum(e_interf ** 2)
+    num_a, den_a = np.sum((s_true + e_spat + e_interf) ** 2), np.sum(e_artif ** 2)
+    return (np.inf if den == 0 else 10 * np.log10(num / den), np.inf if den_i == 0 else 10 * np.log10(num / den_i),
+            np.inf if den_a == 0 else 10 * np.log10(num_a / den_a))
+
+
+def _bss_inputs(reference_sources, estimated_sources):
+    ref = np.atleast_2d(np.asarray(reference_sources, dtype=np.float64))
+    est = np.atleast_2d(np.asarray(estimated_sources, dtype=np.float64))
+    if ref.shape != est.shape:
+        raise ValueError(f"reference {ref.shape} and estimate {est.shape} shapes differ")
+    return ref, est
+
+
+def bss_eval_matrices(reference_sources, estimated_sources, flen: int = 512):
+    """(sdr, sir, sar), each [S_est, S_ref] float64: entry (e, j) scores estimate ``e`` against reference ``j`` with the
+    decomposition of ``bss_eval_sdr`` -- s_true, e_spat, e_interf, e_artif, in that order and with those expressions --
+    and sdr = 10 log10(sum (s_true + e_spat)^2 / sum (e_interf + e_artif)^2), sir = 10 log10(sum (s_true + e_spat)^2 /
+    sum e_interf^2), sar = 10 log10(sum (s_true + e_spat + e_interf)^2 / sum e_artif^2); a ratio is +inf when its
+    denominator is exactly 0 (one talker: e_interf is exactly 0 and sir is +inf)."""
+    ref, est = _bss_inputs(reference_sources, estimated_sources)
+    S = ref.shape[0]
+    out = np.zeros((3, S, S))
+    for e in range(S):
+        full = _project(ref, est[e], flen)
+        for j in range(S):
+            out[:, e, j] = _bss_ratios(ref, est[e], j, flen, full)
+    return out[0], out[1], out[2]
+
+
+def best_permutation(sir_matrix):
+    """``perm`` with ``perm[j]`` the estimate assigned to reference ``j``: the permutation that maximises the mean of
+    ``sir_matrix[perm[j], j]`` ([S_est, S_ref]), the published rule.  Up to 6 talkers every permutation is scored in
+    ``itertools.permutations`` order and the first maximum taken, as the published code does; above that the same optimum
+    comes from ``scipy.optimize.linear_sum_assignment(maximize=True)``, for which +inf entries are replaced by a finite
+    value larger than any sum of the others (so that an assignment through a +inf entry still beats every one without)."""
+    import itertools
+    sir = np.asarray(sir_matrix, dtype=np.float64)
+    S = sir.shape[0]
+    if sir.shape != (S, S):
+        raise ValueError(f"sir matrix {sir.shape} is not square")
+    if S <= 6:
+        perms = list(itertools.permutations(range(S)))
+        idx = np.arange(S)
+        with np.errstate(invalid="ignore"):
+            means = [np.mean(sir[list(p), idx]) if S else 0.0 for p in perms]
+        return np.array(perms[int(np.argmax(means))], dtype=np.int64)
+    from scipy.optimize import linear_sum_assignment
+    finite = sir[np.isfinite(sir)]
+    big = (S + 1) * (float(np.max(np.abs(finite))) + 1.0) if finite.size else 1.0
+    est_of, ref_of = linear_sum_assignment(np.where(sir == np.inf, big, sir), maximize=True)
+    perm = np.zeros(S, dtype=np.int64)
+    perm[ref_of] = est_of
+    return perm
+
+
+def bss_eval_sources(reference_sources, estimated_sources, flen: int = 512, compute_permutation: bool = False):
+    """(sdr, sir, sar, perm) as ``mir_eval.separation.bss_eval_sources(reference_sources, estimated_sources,
+    compute_permutation)`` answers (sep/eval/get_items.py:50-52) -- like ``bss_eval_sdr`` a restatement of the published
+    BSS-eval v3 algorithm, mir_eval being absent: "parity unpinned".  ``compute_permutation=False``: estimate j against
+    reference j, ``perm = arange(S)``, and ``sdr`` is ``bss_eval_sdr`` byte for byte.  ``True``: ``bss_eval_matrices``,
+    then ``perm = best_permutation(sir)`` and the three vectors ``m[perm[j], j]``."""
+    ref, est = _bss_inputs(reference_sources, estimated_sources)
+    S = ref.shape[0]
+    if compute_permutation:
+        sdr, sir, sar = bss_eval_matrices(ref, est, flen)
+        perm = best_permutation(sir)
+        idx = np.arange(S)
+        return sdr[perm, idx], sir[perm, idx], sar[perm, idx], perm
+    out = np.zeros((3, S))
+    for j in range(S):
+        out[:, j] = _bss_ratios(ref, est[j], j, flen, _project(ref, est[j], flen))
+    return out[0], out[1], out[2], np.arange(S)
+
+
 # ---- BSS-eval SDR on the device (csrc/bss_kernels.hip: asw_bss_eval_sdr; DESIGN.md section 7j) -------------------------
 METRICS = ("host", "device")
 BSS_WORKSPACE_BUDGET = 1 << 30          # bytes of device workspace one call may ask for (G at 5 talkers is 52 MB)
@@ -181,6 +266,14 @@ _BSS_TILE, _BSS_CHUNK, _BSS_SPLIT = 64, 1024, 8
 def check_metrics(metrics):
     if metrics not in METRICS:
         raise ValueError(f"metrics must be one of {METRICS}, got {metrics!r}")
+
+
+BSS_FIELDS = ("sdr", "all")             # what the record takes from BSS-eval: the SDR alone, or SIR and SAR too
+
+
+def check_bss(bss):
+    if bss not in BSS_FIELDS:
+        raise ValueError(f"bss must be one of {BSS_FIELDS}, got {bss!r}")
 
 
 def bss_workspace_bytes(counts, R: int, T: int, flen: int) -> int:
@@ -203,11 +296,36 @@ def bss_workspace_bytes(counts, R: int, T: int, flen: int) -> int:
     return tables + 8 * (P * nsplit * flen + P * flen + gram + x + 2 * E * nchunk_p)
 
 
-def pack_bss_items(counts, lengths, R: int, flen: int = 512, budget: int = BSS_WORKSPACE_BUDGET):
+def bss_sources_workspace_bytes(counts, R: int, T: int, flen: int, all_pairs: bool = False, sdr_only: bool = False) -> int:
+    """What ``asw_bss_eval_sources_workspace_bytes`` answers for one call, restated as ``bss_workspace_bytes`` is
+    (tests/test_bss_sources_host.py holds the two equal).  ``all_pairs``: R S^2 single-reference solves and projection
+    rows per item instead of R S.  ``sdr_only``: what a call with neither ``sir`` nor ``sar`` needs -- two energy partials
+    per row and chunk instead of five; with ``all_pairs=False`` that is ``bss_workspace_bytes``."""
+    counts = [int(c) for c in counts]
+    rows = sum(R * S * (S if all_pairs else 1) for S in counts)
+    P = sum((R + 1) * S * S for S in counts)
+    nsys = sum(S + 1 if S > 1 else S for S in counts)
+    nsolve = rows + sum(R * S for S in counts if S > 1)
+    nchunk = -(-T // _BSS_CHUNK)
+    cps = -(-nchunk // min(nchunk, _BSS_SPLIT))
+    nsplit = -(-nchunk // cps)
+    nchunk_p = -(-(T + flen - 1) // _BSS_CHUNK)
+    gram = sum(S * flen * flen + ((S * flen) ** 2 if S > 1 else 0) for S in counts)
+    x = rows * flen + sum(R * S * S * flen for S in counts if S > 1)
+    tables = 32 * len(counts) + 24 * nsys + 16 * P + 24 * nsolve + 8 * rows
+    return tables + 8 * (P * nsplit * flen + P * flen + gram + x + (2 if sdr_only else 5) * rows * nchunk_p)
+
+
+def pack_bss_items(counts, lengths, R: int, flen: int = 512, budget: int = BSS_WORKSPACE_BUDGET, all_pairs: bool = False,
+                   sdr_only: bool = True):
     """The device calls of a batch: items stay whole and in order, a call holds items of one length only and takes as
     many as its workspace (``bss_workspace_bytes``) fits into ``budget``.  -> list of (first, last) item ranges,
     ``last`` exclusive, covering every item once.  ``ValueError`` for an item the library refuses (talkers outside
-    0..16, talkers * flen > 8192, T < flen), ``RuntimeError`` for one whose workspace alone exceeds the budget."""
+    0..16, talkers * flen > 8192, T < flen), ``RuntimeError`` for one whose workspace alone exceeds the budget.
+    ``all_pairs`` and ``sdr_only`` size the calls of ``bss_eval_sources`` (``bss_sources_workspace_bytes``); the
+    defaults are the calls of ``bss_eval_sdr``."""
+    def bss_workspace_bytes(c, R, T, flen):                            # equal to the module's with the defaults
+        return bss_sources_workspace_bytes(c, R, T, flen, all_pairs, sdr_only)
     if R < 1 or not 1 <= flen <= BSS_MAX_FLEN:
         raise ValueError(f"R = {R} < 1 or flen = {flen} outside 1..{BSS_MAX_FLEN}")
     if len(counts) != len(lengths):
@@ -295,6 +413,68 @@ def bss_eval_sdr_device(reference_sources, estimated_sets, flen: int = 512, devi
     return out[0]
 
 
+# ---- SDR, SIR, SAR and the best permutation on the device (asw_bss_eval_sources) -----------------
+def bss_eval_sources_batch(refs, est_sets, flen: int = 512, compute_permutation: bool = False, device=None, op=None,
+                           budget: int = BSS_WORKSPACE_BUDGET):
+    """``bss_eval_sources`` of many samples on the device: inputs, float32 rounding and packing as ``bss_eval_sdr_batch``
+    (``pack_bss_items`` sized for ``torch.ops.asw.bss_eval_sources`` in the mode asked for).  -> (list of (sdr, sir, sar,
+    perm) per sample, the first three [R, S_k] float64 and ``perm`` [R, S_k] int64, sorted list of the items that were
+    recomputed on the host).  ``compute_permutation=True`` takes the all-pairs form of the op, reads the [S, S]
+    matrices back and lets ``best_permutation`` decide on the host, per estimate set.  An item the device marks
+    ``status = 1`` is recomputed with ``bss_eval_sources``, so its values are exactly the host's.  ``op`` replaces the
+    device op (a stand-in on CPU tensors in the host tests); without it a missing library or GPU is a ``RuntimeError``."""
+    import torch
+    if len(refs) != len(est_sets):
+        raise ValueError(f"{len(est_sets)} estimate sets for {len(refs)} samples")
+    if not refs:
+        return [], []
+    refs = [np.ascontiguousarray(np.atleast_2d(r), dtype=np.float32) for r in refs]
+    ests = [np.ascontiguousarray(e, dtype=np.float32) for e in est_sets]
+    R = ests[0].shape[0] if ests[0].ndim == 3 else -1
+    for k, (r, e) in enumerate(zip(refs, ests)):
+        if e.ndim != 3 or e.shape[0] != R or e.shape[1:] != r.shape:
+            raise ValueError(f"sample {k}: estimates {e.shape} do not go with references {r.shape} as [R = {R}, S, T]")
+    if op is None:
+        op, dev = _device_op("bss_eval_sources", device)
+    else:
+        dev = torch.device("cpu" if device is None else device)
+    all_pairs = bool(compute_permutation)
+    counts, lengths = [r.shape[0] for r in refs], [r.shape[1] for r in refs]
+    calls = pack_bss_items(counts, lengths, R, flen, budget, all_pairs=all_pairs, sdr_only=False)
+    out, recomputed = [None] * len(refs), []
+    for first, last in calls:
+        ref = torch.from_numpy(np.concatenate(refs[first:last], axis=0)).to(dev)
+        est = torch.from_numpy(np.concatenate(ests[first:last], axis=1)).to(dev)
+        *vals, status = op(ref, est, counts[first:last], int(flen), all_pairs)
+        vals, status = np.stack([v.cpu().numpy() for v in vals]), status.cpu().numpy()          # [3, R, N or Q]
+        c0 = 0
+        for k in range(first, last):
+            S = counts[k]
+            width = S * S if all_pairs else S
+            if status[k - first] != 0:
+                recomputed.append(k)
+                sets = [bss_eval_sources(refs[k], ests[k][r], flen, compute_permutation) for r in range(R)]
+                out[k] = tuple(np.stack([s[q] for s in sets]) for q in range(4))
+            elif all_pairs:
+                mats = np.array(vals[:, :, c0:c0 + width], dtype=np.float64).reshape(3, R, S, S)
+                perm = np.stack([best_permutation(mats[1, r]) for r in range(R)]).reshape(R, S)
+                idx = np.arange(S)
+                out[k] = tuple(np.stack([mats[q, r][perm[r], idx] for r in range(R)]).reshape(R, S) for q in range(3)) + (perm,)
+            else:
+                m = np.array(vals[:, :, c0:c0 + width], dtype=np.float64)
+                out[k] = (m[0], m[1], m[2], np.tile(np.arange(S), (R, 1)))
+            c0 += width
+    return out, recomputed
+
+
+def bss_eval_sources_device(reference_sources, estimated_sets, flen: int = 512, compute_permutation: bool = False,
+                            device=None, op=None):
+    """(sdr, sir, sar, perm), each [R, S]: ``bss_eval_sources(reference_sources, estimated_sets[r], flen,
+    compute_permutation)`` for every set r, on the device (one ``bss_eval_sources_batch`` call of one sample)."""
+    out, _ = bss_eval_sources_batch([reference_sources], [estimated_sets], flen, compute_permutation, device, op)
+    return out[0]
+
+
 # ---- SI-SDR matrices on the device (csrc/eval_kernels.hip: asw_cross_sisdr; DESIGN.md section 7o) ----------------------
 XS_MAX_ITEMS, XS_MAX_EST, XS_MAX_REF = 65535, 4096, 64          # the library's limits (include/asw_hip.h)
 
@@ -360,32 +540,43 @@ def cross_sisdr_batch(est_list, ref_list, device=None, op=None):
     return out, sorted(recomputed)
 
 
-def compute_metrics(input_signal, est_signal, gt, metrics="host"):
+def compute_metrics(input_signal, est_signal, gt, metrics="host", bss="sdr"):
     """(input_sdr, output_sdr, input_sisdr, output_sisdr) per matched talker, as
     sep/eval/get_items.py:46-70 with permute=False: BSS-eval SDR and SI-SDR of the unprocessed
     reference-microphone signal and of the separated output against the ground truth.
     ``metrics="device"`` takes the two BSS-eval SDRs from one ``bss_eval_sdr_device`` call (R = 2: the
-    unprocessed set and the separated set); the signals are read as float32 there."""
+    unprocessed set and the separated set); the signals are read as float32 there.  ``bss="all"`` appends a fifth
+    entry, ``(input_sir, output_sir, input_sar, output_sar)``, from ``bss_eval_sources`` (host) or one
+    ``bss_eval_sources_device`` call (device), which then gives the two SDRs as well."""
     check_metrics(metrics)
+    check_bss(bss)
     gt = np.asarray(gt, dtype=np.float64)
     inp = np.asarray(input_signal, dtype=np.float64)
     est = np.asarray(est_signal, dtype=np.float64)
+    input_sisdr = [si_sdr(inp[i], gt[i]) for i in range(gt.shape[0])]
+    output_sisdr = [si_sdr(est[i], gt[i]) for i in range(gt.shape[0])]
+    if bss == "all":
+        if metrics == "device":
+            sdr, sir, sar, _perm = bss_eval_sources_device(gt, np.stack([inp, est]))
+        else:
+            sdr, sir, sar = (np.stack(v) for v in zip(bss_eval_sources(gt, inp)[:3], bss_eval_sources(gt, est)[:3]))
+        return sdr[0], sdr[1], input_sisdr, output_sisdr, (sir[0], sir[1], sar[0], sar[1])
     if metrics == "device":
         input_sdr, output_sdr = bss_eval_sdr_device(gt, np.stack([inp, est]))
     else:
         input_sdr, output_sdr = bss_eval_sdr(gt, inp), bss_eval_sdr(gt, est)
-    input_sisdr = [si_sdr(inp[i], gt[i]) for i in range(gt.shape[0])]
-    output_sisdr = [si_sdr(est[i], gt[i]) for i in range(gt.shape[0])]
     return input_sdr, output_sdr, input_sisdr, output_sisdr
 
 
 # ---- one sample --------------------------------------------------------------------------------
-def evaluate_sample(model, metadata, mix, gt, metrics="host"):
+def evaluate_sample(model, metadata, mix, gt, metrics="host", bss="sdr"):
     """Run ``model`` (a ``JointModel``) on one sample and build the reference's result record
     (sep/eval/eval_model.py:129-236).  Returns (record, tp, fp, fn).  ``metrics``: "host" or "device", where the
-    record's two BSS-eval SDR fields come from (``compute_metrics``)."""
+    record's two BSS-eval SDR fields come from (``compute_metrics``).  ``bss``: "sdr" (the record as it was) or "all"
+    (``sir_in_mir``, ``sir_mir``, ``sar_in_mir``, ``sar_mir`` added to every matched talker's entry)."""
     check_metrics(metrics)
-    return record_from_result(metadata, mix, gt, search_result(model, metadata, mix), metrics)
+    check_bss(bss)
+    return record_from_result(metadata, mix, gt, search_result(model, metadata, mix), metrics, bss=bss)
 
 
 def search_result(model, metadata, mix):
@@ -411,15 +602,19 @@ def _separated(result):
     return result["audio_loc"] if audio is None else np.asarray(audio)
 
 
-def record_from_result(metadata, mix, gt, result, metrics="host", scores=None):
+def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, bss="sdr"):
     """The second step of ``evaluate_sample``: the reference's result record (sep/eval/eval_model.py:129-236) from what
     the search returned (``search_result``, or a dict of ``shard.localize_batch(..., details=True)``).  Returns
     (record, tp, fp, fn).  Without ``scores`` every SI-SDR is ``hostdsp.si_sdr`` on the host and ``metrics`` says where
     the two BSS-eval SDR fields come from (``compute_metrics``).  ``scores`` (``records_from_results``) holds them
     ready-made: ``"sisdr"``, the [1 + K (+ K), n_gt] matrix of ``cross_sisdr_batch`` over the rows [mix[0]; separated;
     localisation stage] (the third block only with a separation model), ``"perm"``, the matching found from it, and
-    ``"bss"``, the [2, matched] BSS-eval SDRs of the unprocessed and the separated set."""
+    ``"bss"``, the [2, matched] BSS-eval SDRs of the unprocessed and the separated set.  ``bss="all"`` adds four fields
+    to every matched talker's entry: ``sir_in_mir`` / ``sar_in_mir`` of the unprocessed set and ``sir_mir`` / ``sar_mir``
+    of the separated set, the raw values and no differences (one talker has SIR +inf on both sides); ``scores`` then
+    holds them too, as ``"sir"`` and ``"sar"``, each [2, matched]."""
     check_metrics(metrics)
+    check_bss(bss)
     _mics, mic_positions, _voices, gt_pos, offsets_gt, roi = preprocess_metadata(metadata)
     est_pos, audio_loc, sep_audio = result["centres"], result["audio_loc"], _separated(result)
     n_out = len(est_pos)
@@ -437,6 +632,8 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None):
     if perm and scores is not None:
         M, loc0 = scores["sisdr"], 1 + (n_out if result.get("audio") is not None else 0)
         in_sdr, out_sdr = scores["bss"]
+        if bss == "all":
+            extra = (*scores["sir"], *scores["sar"])
         in_sisdr_l = [float(M[0, s]) for _o, s in perm]
         out_sisdr_l = [float(M[1 + o, s]) for o, s in perm]
         loc_sisdr_l = [float(M[loc0 + o, s]) for o, s in perm]
@@ -445,7 +642,9 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None):
         # decoder when attached), localisation-stage output, ground truth, unprocessed mic 0
         pa = np.array(perm)
         ref_sig = np.repeat(mix[0:1].astype(np.float64), len(perm), axis=0)
-        in_sdr, out_sdr, in_sisdr_l, out_sisdr_l = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics)
+        in_sdr, out_sdr, in_sisdr_l, out_sisdr_l, *more = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics,
+                                                                          bss)
+        extra = more[0] if more else None
         loc_sisdr_l = [si_sdr(audio_loc[o].astype(np.float64), gt[s].astype(np.float64)) for o, s in perm]
     for i, (out_id, s) in enumerate(perm):
         unmatched.remove(out_id)
@@ -459,13 +658,16 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None):
             "si_snri": out_sisdr_l[i] - in_sisdr,
             "si_snr_in_old": in_sisdr,
             "si_snri_old": loc_sisdr_l[i] - in_sisdr})
+        if bss == "all":
+            rec["pred"][-1].update(sir_in_mir=float(extra[0][i]), sir_mir=float(extra[1][i]),
+                                   sar_in_mir=float(extra[2][i]), sar_mir=float(extra[3][i]))
     for rid in unmatched:
         rec["false_positive"].append({"pos": est_pos[rid].tolist(),
                                       "sample": np.asarray(result["audio_offsets"][rid]).tolist()})
     return rec, tp, fp, fn
 
 
-def records_from_results(samples, results, metrics="host", ops=None, stats=None):
+def records_from_results(samples, results, metrics="host", ops=None, stats=None, bss="sdr"):
     """The records of a batch: ``samples[k]`` = (metadata, mix, gt) as ``get_items`` reads them, ``results[k]`` what the
     search returned for it (``search_result`` / ``shard.localize_batch(..., details=True)``).  -> [(record, tp, fp, fn)]
     in sample order.  ``metrics="host"``: ``record_from_result`` per sample, the host statements throughout.
@@ -474,15 +676,18 @@ def records_from_results(samples, results, metrics="host", ops=None, stats=None)
          localisation-stage_0..K-1] (the third block only with a separation model), the references its ground truth;
          the matcher's matrix and the record's four SI-SDR fields are entries of that one matrix;
       2. the matching of every sample on the host (``find_best_permutation(sisdr=...)``);
-      3. ONE ``bss_eval_sdr_batch`` call over the matched rows of all samples (R = 2: unprocessed and separated).
+      3. ONE ``bss_eval_sdr_batch`` call over the matched rows of all samples (R = 2: unprocessed and separated);
+         with ``bss="all"`` ONE ``bss_eval_sources_batch`` call in its place (the BSS stand-in of ``ops`` then has that
+         op's signature).
     ``ops``: stand-ins (cross op, BSS op) for the two device ops (host tests).  ``stats``: a dict that receives the
     seconds of the steps (``"sisdr_s"``, ``"match_s"``, ``"bss_s"``)."""
     import time
     check_metrics(metrics)
+    check_bss(bss)
     if len(samples) != len(results):
         raise ValueError(f"{len(results)} results for {len(samples)} samples")
     if metrics == "host":
-        return [record_from_result(meta, mix, gt, res, "host") for (meta, mix, gt), res in zip(samples, results)]
+        return [record_from_result(meta, mix, gt, res, "host", bss=bss) for (meta, mix, gt), res in zip(samples, results)]
     cross_op, bss_op = ops if ops is not None else (None, None)
     t0 = time.perf_counter()
     est_rows = []
@@ -507,11 +712,16 @@ def records_from_results(samples, results, metrics="host", ops=None, stats=None)
         ref_sig = np.repeat(np.asarray(mix[0:1], dtype=np.float32), len(pa), axis=0)
         refs.append(np.asarray(gt)[pa[:, 1]])
         sets.append(np.stack([ref_sig, np.asarray(_separated(results[k]), dtype=np.float32)[pa[:, 0]]]))
-    bss, _ = bss_eval_sdr_batch(refs, sets, op=bss_op)
-    bss = dict(zip(matched, bss))
+    if bss == "all":
+        vals, _ = bss_eval_sources_batch(refs, sets, op=bss_op)
+        scored = {k: {"bss": v[0], "sir": v[1], "sar": v[2]} for k, v in zip(matched, vals)}
+    else:
+        vals, _ = bss_eval_sdr_batch(refs, sets, op=bss_op)
+        scored = {k: {"bss": v} for k, v in zip(matched, vals)}
     if stats is not None:
         stats.update(sisdr_s=t1 - t0, match_s=t2 - t1, bss_s=time.perf_counter() - t2)
-    return [record_from_result(meta, mix, gt, res, "device", {"sisdr": mats[k], "perm": perms[k], "bss": bss.get(k)})
+    return [record_from_result(meta, mix, gt, res, "device",
+                               {"sisdr": mats[k], "perm": perms[k], "bss": None, **scored.get(k, {})}, bss=bss)
             for k, ((meta, mix, gt), res) in enumerate(zip(samples, results))]
 
 
@@ -529,9 +739,10 @@ def group_samples(shapes, batch):
     return groups
 
 
-def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", batch=1, concurrent=2, stats=None):
+def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", batch=1, concurrent=2, stats=None,
+                     bss="sdr"):
     """Every sample directory of ``dataset_dir``; writes ``result_<sample>.json`` like the
-    reference and returns overall (tp, fp, fn, precision, recall).  ``metrics`` as in ``evaluate_sample``.
+    reference and returns overall (tp, fp, fn, precision, recall).  ``metrics`` and ``bss`` as in ``evaluate_sample``.
 
     ``batch=1``: one ``evaluate_sample`` per directory.  ``batch=N``: the directories in sorted order, consecutive
     samples of equal (M, T) in calls of at most N (``group_samples``); a call is ONE
@@ -540,6 +751,7 @@ def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", ba
     the summed seconds of reading, searching, the metrics steps and writing (tests/perf_eval_dataset.py)."""
     import time
     check_metrics(metrics)
+    check_bss(bss)
     if batch < 1:
         raise ValueError(f"batch = {batch} < 1")
     tot = np.zeros(3, dtype=np.int64)
@@ -568,7 +780,7 @@ def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", ba
                                  separate=model.sep_model is not None, details=True, concurrent=concurrent)
         t1 = time.perf_counter()
         step = {}
-        records = records_from_results(samples, results, metrics, stats=step)
+        records = records_from_results(samples, results, metrics, stats=step, bss=bss)
         spent["search_s"] += t1 - t0
         spent["record_s"] += time.perf_counter() - t1
         for key, value in step.items():
@@ -585,7 +797,7 @@ def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", ba
             t0 = time.perf_counter()                         # evaluate_sample, its two steps timed apart
             result = search_result(model, metadata, mix)
             t1 = time.perf_counter()
-            rec, tp, fp, fn = record_from_result(metadata, mix, gt, result, metrics)
+            rec, tp, fp, fn = record_from_result(metadata, mix, gt, result, metrics, bss=bss)
             spent["search_s"] += t1 - t0
             spent["record_s"] += time.perf_counter() - t1
             write(name, rec, tp, fp, fn)

@@ -1,7 +1,7 @@
 """The evaluation program, the counterpart of the reference's ``python sep/eval/eval_model.py``:
 
     python -m acousticswarms_speech_amd.evaluate DATASET --spot_experiment_dir D --sep_experiment_dir D
-        [--results_folder F] [--spot_batch_size 128] [--batch N] [--metrics host|device]
+        [--results_folder F] [--spot_batch_size 128] [--batch N] [--metrics host|device] [--bss sdr|all]
         [--precision f16x3|f16x3_safe|f32] [--geometry host|device] [--use_cuda] [--cached_init]
 
 Loads both networks with ``experiment.load_model_from_exp``, moves them to the GPU, builds the ``JointModel`` and runs
@@ -31,6 +31,8 @@ def build_parser():
                    help="Samples per batched call (evaluate_dataset(batch=)); 1: one sample at a time")
     p.add_argument("--metrics", choices=("host", "device"), default="host",
                    help="Where the BSS-eval SDR (and with --batch > 1 the SI-SDR matrices) are computed")
+    p.add_argument("--bss", choices=("sdr", "all"), default="sdr",
+                   help="BSS-eval fields of the record: the SDR alone, or SIR and SAR of both sets too")
     p.add_argument("--precision", choices=PRECISIONS, default="f32", help="Arithmetic of both networks")
     p.add_argument("--geometry", choices=("host", "device"), default="host", help="Where the array geometry is built")
     return p
@@ -47,7 +49,8 @@ def main(argv=None):
     spot = load_model_from_exp(args.spot_experiment_dir, precision=args.precision, batch_size=args.spot_batch_size)
     sep = load_model_from_exp(args.sep_experiment_dir, precision=args.precision)
     model = JointModel(spot, sep, device=device, geometry=args.geometry).to(device)
-    tot = evalkit.evaluate_dataset(model, args.dataset, args.results_folder, metrics=args.metrics, batch=args.batch)
+    tot = evalkit.evaluate_dataset(model, args.dataset, args.results_folder, metrics=args.metrics, batch=args.batch,
+                                   bss=args.bss)
     print("Overall tp: {}, fp: {}, fn: {}".format(tot["tp"], tot["fp"], tot["fn"]))
     print("Overall Precision: {} Recall: {}".format(tot["precision"], tot["recall"]))
     return tot

@@ -263,6 +263,9 @@ SIGNATURES = {
     "asw_bss_eval_sdr_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "asw_bss_eval_sdr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    "asw_bss_eval_sources_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "asw_bss_eval_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "asw_cross_sisdr_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int, c_int]),
     "asw_cross_sisdr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),

@@ -778,6 +778,35 @@ size_t asw_bss_eval_sdr_workspace_bytes(const int32_t* counts_host, int K, int R
 int asw_bss_eval_sdr(const float* ref, const float* est, const int32_t* counts_host, int K, int R, int T, int flen,
                      double* sdr, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Full BSS-eval of a ragged batch on the device: SDR, SIR and SAR as evalkit.bss_eval_sources / evalkit.bss_eval_matrices
+ * state them (the same restatement of BSS-eval v3, so parity with mir_eval stays unpinned here too).  asw_bss_eval_sdr
+ * above is this call with all_pairs = 0 and sir = sar = null; inputs, limits, the packed ragged layout, status, the
+ * correlation, Gram, Cholesky and solve steps and every guarantee stated there hold here unchanged.  With u = s_true +
+ * e_spat, e_i = e_interf and e_a = e_artif of the decomposition:
+ *   sdr = 10 log10(sum u^2 / sum (e_i + e_a)^2), sir = 10 log10(sum u^2 / sum e_i^2),
+ *   sar = 10 log10(sum (u + e_i)^2 / sum e_a^2), each +inf when its denominator is exactly 0 (an item with S = 1 has
+ *   e_i exactly 0, so its sir is +inf).
+ * all_pairs = 0: estimate j of a set goes against reference j; sdr, sir, sar float64 [R][N] (device), as sdr above.
+ * all_pairs = 1: every estimate against every reference; the outputs are [R][Q], Q = sum_k S_k^2; item k owns columns
+ *   q0_k = sum_{k' < k} S_k'^2 onward and entry [r][q0_k + e S_k + j] is estimate e of set r against reference j (a
+ *   row-major [S_k][S_k] matrix per set and item, what evalkit.bss_eval_matrices(ref_k, est_k[r], flen) returns).
+ *   The single-reference right-hand side of (e, j) is c(j, est_e, .), which the correlations hold already: R S_k^2
+ *   single solves instead of R S_k, the R S_k full solves unchanged, R S_k^2 rows in the projection, each of which
+ *   forms the full projection of its estimate again.  x grows by R S_k (S_k - 1) flen doubles per item.
+ * sir and sar may both be null (only the SDR is produced: two sums per row and chunk, the kernels of asw_bss_eval_sdr),
+ * but not one alone.  With both, the projection sums five squares through the same fixed tree -- u^2, (e_i + e_a)^2,
+ * e_i^2, (u + e_i)^2, e_a^2 -- the first two by the same expressions in the same order, so sdr holds the same bytes
+ * either way.
+ * workspace: asw_bss_eval_sources_workspace_bytes(counts_host, K, R, T, flen, all_pairs) bytes, 8-byte aligned: the
+ * size with sir and sar wanted (five energy partials per row and chunk); a call without them needs 24 bytes per row and
+ * chunk less and accepts this size too (all_pairs = 0: exactly asw_bss_eval_sdr_workspace_bytes).  0 with the error
+ * message set for arguments the call would refuse.  Refusals beyond those of asw_bss_eval_sdr, on the host before the
+ * copy and the first launch: all_pairs other than 0 or 1; one of sir, sar null alone. */
+size_t asw_bss_eval_sources_workspace_bytes(const int32_t* counts_host, int K, int R, int T, int flen, int all_pairs);
+int asw_bss_eval_sources(const float* ref, const float* est, const int32_t* counts_host, int K, int R, int T, int flen,
+                         int all_pairs, double* sdr, double* sir, double* sar, int32_t* status, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* SI-SDR of every (estimate, reference) pair of a ragged batch of K samples on the device, as hostdsp.si_sdr states it
  * in float64: for estimate e and reference r of one item, rr = sum r^2, a = sum r e / rr, te = sum (a r)^2,
  * ne = sum (e - a r)^2, value 10 log10(te / (ne + 1e-8)).  est float32 [NE][T] and ref float32 [NR][T] (device): item k
