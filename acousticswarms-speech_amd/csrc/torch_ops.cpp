@@ -21,6 +21,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cmath>
 #include <tuple>
 #include <vector>
@@ -58,6 +59,23 @@ struct Launch {
 int checked_int(int64_t v, const char* name) {
   TORCH_CHECK(v >= INT32_MIN && v <= INT32_MAX, name, " out of int32 range");
   return static_cast<int>(v);
+}
+
+// A count list as the C ABI takes it: every entry inside lo..hi, with the sum of the entries and of their squares.
+struct Counts {
+  std::vector<int32_t> v;
+  int64_t sum = 0, squares = 0;
+};
+
+Counts checked_counts(at::IntArrayRef counts, const char* name, int64_t lo = INT32_MIN, int64_t hi = INT32_MAX) {
+  Counts c;
+  c.v.reserve(counts.size());
+  for (size_t k = 0; k < counts.size(); ++k) {
+    TORCH_CHECK(counts[k] >= lo && counts[k] <= hi, name, "[", k, "] = ", counts[k], " outside ", lo, "..", hi);
+    c.v.push_back(static_cast<int32_t>(counts[k]));
+    c.sum += counts[k], c.squares += counts[k] * counts[k];
+  }
+  return c;
 }
 
 // ---- spot network -------------------------------------------------------------------------
@@ -640,18 +658,13 @@ Tensor sep_infer_batch(int64_t model, const Tensor& mix, const Tensor& offsets, 
   const int K = checked_int(mix.size(0), "K"), M = checked_int(mix.size(1), "M"), T = checked_int(mix.size(2), "T");
   const int N = checked_int(offsets.size(0), "N");
   TORCH_CHECK((int64_t)counts.size() == K, "counts must hold one entry per mixture: ", counts.size(), " for ", K);
-  std::vector<int32_t> c(K);
-  int64_t total = 0;
-  for (int k = 0; k < K; ++k) {
-    c[k] = checked_int(counts[k], "count");
-    total += c[k];
-  }
-  TORCH_CHECK(total == N && offsets.size(1) == M - 1, "offsets must be [sum(counts), M-1] = [", total, ", ", M - 1, "], got [", N,
+  const Counts c = checked_counts(counts, "counts");
+  TORCH_CHECK(c.sum == N && offsets.size(1) == M - 1, "offsets must be [sum(counts), M-1] = [", c.sum, ", ", M - 1, "], got [", N,
               ", ", offsets.size(1), "]");
   Tensor out = at::empty({N, T}, mix.options());
   Launch l(mix);
   check_status(asw_sep_infer_batch(reinterpret_cast<asw_sep*>(model), mix.data_ptr<float>(), K, M, T,
-                                   offsets.data_ptr<int32_t>(), c.data(), out.data_ptr<float>(), l.stream),
+                                   offsets.data_ptr<int32_t>(), c.v.data(), out.data_ptr<float>(), l.stream),
                "asw_sep_infer_batch");
   return out;
 }
@@ -685,12 +698,8 @@ Tensor sep_forward_counts(int64_t model, const Tensor& mix_norm, at::IntArrayRef
   need(mix_norm, "mix", at::kFloat, 3);
   const int B = checked_int(mix_norm.size(0), "B"), t = checked_int(mix_norm.size(2), "t"), M = checked_int(n_mics, "M");
   TORCH_CHECK((int64_t)counts.size() == B && B >= 1, "counts must hold one entry per batch item");
-  std::vector<int32_t> c(B);
-  int S = 0;
-  for (int b = 0; b < B; ++b) {
-    c[b] = checked_int(counts[b], "count");
-    S = c[b] > S ? c[b] : S;
-  }
+  const Counts c = checked_counts(counts, "counts");
+  const int S = std::max(0, *std::max_element(c.v.begin(), c.v.end()));
   TORCH_CHECK(S >= 1 && mix_norm.size(1) == (int64_t)S * M, "mix must be [B, max(counts)*M, t]");
   asw_sep_config cfg;
   check_status(asw_sep_get_config(reinterpret_cast<asw_sep*>(model), &cfg), "asw_sep_get_config");
@@ -698,16 +707,19 @@ Tensor sep_forward_counts(int64_t model, const Tensor& mix_norm, at::IntArrayRef
   const int64_t R = S > cfg.max_speakers ? S : cfg.max_speakers;
   Tensor out = at::empty({B, R, t}, mix_norm.options());
   Launch l(mix_norm);
-  check_status(asw_sep_forward_counts(reinterpret_cast<asw_sep*>(model), mix_norm.data_ptr<float>(), B, S, M, t, c.data(),
+  check_status(asw_sep_forward_counts(reinterpret_cast<asw_sep*>(model), mix_norm.data_ptr<float>(), B, S, M, t, c.v.data(),
                                       out.data_ptr<float>(), l.stream),
                "asw_sep_forward_counts");
   return out;
 }
 
-// -> sdr [R, N] float64, status [K] int32: the BSS-eval SDR of every estimate set of a ragged batch against its
-// references (evalkit.bss_eval_sdr per item).  counts is read on the host; an item whose status is 1 has to be recomputed
-// by the caller (evalkit.bss_eval_sdr_batch does).
-std::tuple<Tensor, Tensor> bss_eval_sdr(const Tensor& ref, const Tensor& est, at::IntArrayRef counts, int64_t flen) {
+// The adapter of both BSS-eval ops over asw_bss_eval_sources.  -> sdr, sir, sar float64 [R, N] (all_pairs: [R, sum S_k^2], item
+// k a row-major [S_k, S_k] block of (estimate, reference) per set) and status [K] int32; without want_all sir and sar stay
+// undefined, the call gets null for them and the smaller workspace of asw_bss_eval_sdr_workspace_bytes.  counts is read on
+// the host; an item whose status is 1 has to be recomputed by the caller (evalkit.bss_eval_sdr_batch and
+// bss_eval_sources_batch do).
+std::tuple<Tensor, Tensor, Tensor, Tensor> bss_eval(const Tensor& ref, const Tensor& est, at::IntArrayRef counts, int64_t flen,
+                                                    bool all_pairs, bool want_all) {
   need(ref, "ref", at::kFloat, 2);
   need(est, "est", at::kFloat, 3);
   same_device(ref, est, "ref and est");
@@ -715,67 +727,42 @@ std::tuple<Tensor, Tensor> bss_eval_sdr(const Tensor& ref, const Tensor& est, at
   const int K = checked_int(static_cast<int64_t>(counts.size()), "K");
   TORCH_CHECK(R >= 1, "est must hold at least one estimate set");
   TORCH_CHECK(est.size(1) == N && est.size(2) == T, "est must be [R, N, T] = [R, ", N, ", ", T, "]");
-  std::vector<int32_t> c(K);
-  int64_t total = 0;
-  for (int k = 0; k < K; ++k) {
-    TORCH_CHECK(counts[k] >= 0 && counts[k] <= 16, "counts[", k, "] = ", counts[k], " outside 0..16");
-    c[k] = static_cast<int32_t>(counts[k]);
-    total += counts[k];
-  }
-  TORCH_CHECK(total == N, "counts sum to ", total, ", ref has ", N, " rows");
-  Tensor sdr = at::empty({R, N}, ref.options().dtype(at::kDouble));
+  const Counts c = checked_counts(counts, "counts", 0, 16);
+  TORCH_CHECK(c.sum == N, "counts sum to ", c.sum, ", ref has ", N, " rows");
+  const int64_t ncol = all_pairs ? c.squares : N;
+  const auto f64 = ref.options().dtype(at::kDouble);
+  Tensor sdr = at::empty({R, ncol}, f64), sir, sar;
+  if (want_all) sir = at::empty({R, ncol}, f64), sar = at::empty({R, ncol}, f64);
   Tensor status = at::empty({K}, ref.options().dtype(at::kInt));
-  if (K == 0) return {sdr, status};
-  const int f = checked_int(flen, "flen");
-  const size_t ws_bytes = asw_bss_eval_sdr_workspace_bytes(c.data(), K, R, T, f);
-  TORCH_CHECK(ws_bytes > 0 || N == 0, "libasw_hip: asw_bss_eval_sdr_workspace_bytes failed: ", asw_last_error());
-  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, ref.options().dtype(at::kDouble));
+  if (K == 0) return {sdr, sir, sar, status};
+  const int f = checked_int(flen, "flen"), pairs = all_pairs ? 1 : 0;
+  const size_t ws_bytes = want_all ? asw_bss_eval_sources_workspace_bytes(c.v.data(), K, R, T, f, pairs)
+                                   : asw_bss_eval_sdr_workspace_bytes(c.v.data(), K, R, T, f);
+  TORCH_CHECK(ws_bytes > 0 || N == 0, "libasw_hip: asw_bss_eval_", want_all ? "sources" : "sdr",
+              "_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, f64);
+  const bool some = N > 0;
   Launch l(ref);
-  check_status(asw_bss_eval_sdr(N > 0 ? ref.data_ptr<float>() : nullptr, N > 0 ? est.data_ptr<float>() : nullptr, c.data(), K, R,
-                                T, f, N > 0 ? sdr.data_ptr<double>() : nullptr, status.data_ptr<int32_t>(),
-                                N > 0 ? ws.data_ptr() : nullptr, ws_bytes, l.stream),
-               "asw_bss_eval_sdr");
+  check_status(asw_bss_eval_sources(some ? ref.data_ptr<float>() : nullptr, some ? est.data_ptr<float>() : nullptr, c.v.data(), K, R,
+                                    T, f, pairs, some ? sdr.data_ptr<double>() : nullptr,
+                                    some && want_all ? sir.data_ptr<double>() : nullptr,
+                                    some && want_all ? sar.data_ptr<double>() : nullptr, status.data_ptr<int32_t>(),
+                                    some ? ws.data_ptr() : nullptr, ws_bytes, l.stream),
+               "asw_bss_eval_sources");
+  return {sdr, sir, sar, status};
+}
+
+// -> sdr [R, N] float64, status [K] int32: the BSS-eval SDR of every estimate set of a ragged batch against its
+// references (evalkit.bss_eval_sdr per item).
+std::tuple<Tensor, Tensor> bss_eval_sdr(const Tensor& ref, const Tensor& est, at::IntArrayRef counts, int64_t flen) {
+  auto [sdr, sir, sar, status] = bss_eval(ref, est, counts, flen, false, false);
   return {sdr, status};
 }
 
-// -> sdr, sir, sar float64 [R, N] (all_pairs: [R, sum S_k^2], item k a row-major [S_k, S_k] block of (estimate, reference)
-// per set), status [K] int32: the full BSS-eval of a ragged batch (evalkit.bss_eval_sources / bss_eval_matrices per item).
-// The checks of bss_eval_sdr; an item whose status is 1 has to be recomputed by the caller (evalkit.bss_eval_sources_batch
-// does).
+// -> sdr, sir, sar, status: the full BSS-eval of a ragged batch (evalkit.bss_eval_sources / bss_eval_matrices per item).
 std::tuple<Tensor, Tensor, Tensor, Tensor> bss_eval_sources(const Tensor& ref, const Tensor& est, at::IntArrayRef counts,
                                                             int64_t flen, bool all_pairs) {
-  need(ref, "ref", at::kFloat, 2);
-  need(est, "est", at::kFloat, 3);
-  same_device(ref, est, "ref and est");
-  const int N = checked_int(ref.size(0), "N"), T = checked_int(ref.size(1), "T"), R = checked_int(est.size(0), "R");
-  const int K = checked_int(static_cast<int64_t>(counts.size()), "K");
-  TORCH_CHECK(R >= 1, "est must hold at least one estimate set");
-  TORCH_CHECK(est.size(1) == N && est.size(2) == T, "est must be [R, N, T] = [R, ", N, ", ", T, "]");
-  std::vector<int32_t> c(K);
-  int64_t total = 0, Q = 0;
-  for (int k = 0; k < K; ++k) {
-    TORCH_CHECK(counts[k] >= 0 && counts[k] <= 16, "counts[", k, "] = ", counts[k], " outside 0..16");
-    c[k] = static_cast<int32_t>(counts[k]);
-    total += counts[k], Q += counts[k] * counts[k];
-  }
-  TORCH_CHECK(total == N, "counts sum to ", total, ", ref has ", N, " rows");
-  const int64_t ncol = all_pairs ? Q : N;
-  Tensor sdr = at::empty({R, ncol}, ref.options().dtype(at::kDouble));
-  Tensor sir = at::empty({R, ncol}, ref.options().dtype(at::kDouble));
-  Tensor sar = at::empty({R, ncol}, ref.options().dtype(at::kDouble));
-  Tensor status = at::empty({K}, ref.options().dtype(at::kInt));
-  if (K == 0) return {sdr, sir, sar, status};
-  const int f = checked_int(flen, "flen");
-  const size_t ws_bytes = asw_bss_eval_sources_workspace_bytes(c.data(), K, R, T, f, all_pairs ? 1 : 0);
-  TORCH_CHECK(ws_bytes > 0 || N == 0, "libasw_hip: asw_bss_eval_sources_workspace_bytes failed: ", asw_last_error());
-  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, ref.options().dtype(at::kDouble));
-  Launch l(ref);
-  check_status(asw_bss_eval_sources(N > 0 ? ref.data_ptr<float>() : nullptr, N > 0 ? est.data_ptr<float>() : nullptr, c.data(), K,
-                                    R, T, f, all_pairs ? 1 : 0, N > 0 ? sdr.data_ptr<double>() : nullptr,
-                                    N > 0 ? sir.data_ptr<double>() : nullptr, N > 0 ? sar.data_ptr<double>() : nullptr,
-                                    status.data_ptr<int32_t>(), N > 0 ? ws.data_ptr() : nullptr, ws_bytes, l.stream),
-               "asw_bss_eval_sources");
-  return {sdr, sir, sar, status};
+  return bss_eval(ref, est, counts, flen, all_pairs, true);
 }
 
 // -> out float64 [sum P_k S_k], status [K] int32: the SI-SDR of every (estimate, reference) pair of a ragged batch, item
@@ -790,25 +777,21 @@ std::tuple<Tensor, Tensor> cross_sisdr(const Tensor& est, const Tensor& ref, at:
   const int K = checked_int(static_cast<int64_t>(est_counts.size()), "K");
   TORCH_CHECK(ref.size(1) == T, "est [NE, ", T, "] and ref [NR, ", ref.size(1), "] differ in length");
   TORCH_CHECK(static_cast<int64_t>(ref_counts.size()) == K, "est_counts holds ", K, " items, ref_counts ", ref_counts.size());
-  std::vector<int32_t> pc(K), sc(K);
-  int64_t ne = 0, nr = 0, np = 0;
-  for (int k = 0; k < K; ++k) {
-    TORCH_CHECK(est_counts[k] >= 0 && est_counts[k] <= 4096, "est_counts[", k, "] = ", est_counts[k], " outside 0..4096");
-    TORCH_CHECK(ref_counts[k] >= 0 && ref_counts[k] <= 64, "ref_counts[", k, "] = ", ref_counts[k], " outside 0..64");
-    pc[k] = static_cast<int32_t>(est_counts[k]), sc[k] = static_cast<int32_t>(ref_counts[k]);
-    ne += est_counts[k], nr += ref_counts[k], np += est_counts[k] * ref_counts[k];
-  }
+  const Counts pc = checked_counts(est_counts, "est_counts", 0, 4096), sc = checked_counts(ref_counts, "ref_counts", 0, 64);
+  const int64_t ne = pc.sum, nr = sc.sum;
+  int64_t np = 0;
+  for (int k = 0; k < K; ++k) np += static_cast<int64_t>(pc.v[k]) * sc.v[k];
   TORCH_CHECK(ne == est.size(0), "est_counts sum to ", ne, ", est has ", est.size(0), " rows");
   TORCH_CHECK(nr == ref.size(0), "ref_counts sum to ", nr, ", ref has ", ref.size(0), " rows");
   Tensor out = at::empty({np}, est.options().dtype(at::kDouble));
   Tensor status = at::empty({K}, est.options().dtype(at::kInt));
   if (K == 0) return {out, status};
-  const size_t ws_bytes = asw_cross_sisdr_workspace_bytes(pc.data(), sc.data(), K, T);
+  const size_t ws_bytes = asw_cross_sisdr_workspace_bytes(pc.v.data(), sc.v.data(), K, T);
   TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_cross_sisdr_workspace_bytes failed: ", asw_last_error());
   Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, est.options().dtype(at::kDouble));
   Launch l(est);
-  check_status(asw_cross_sisdr(ne > 0 ? est.data_ptr<float>() : nullptr, nr > 0 ? ref.data_ptr<float>() : nullptr, pc.data(),
-                               sc.data(), K, T, np > 0 ? out.data_ptr<double>() : nullptr, status.data_ptr<int32_t>(),
+  check_status(asw_cross_sisdr(ne > 0 ? est.data_ptr<float>() : nullptr, nr > 0 ? ref.data_ptr<float>() : nullptr, pc.v.data(),
+                               sc.v.data(), K, T, np > 0 ? out.data_ptr<double>() : nullptr, status.data_ptr<int32_t>(),
                                ws.data_ptr(), ws_bytes, l.stream),
                "asw_cross_sisdr");
   return {out, status};

@@ -154,26 +154,12 @@ def bss_eval_sdr(reference_sources, estimated_sources, flen: int = 512):
     ``mir_eval.separation.bss_eval_sources(..., compute_permutation=False)``
     (sep/eval/get_items.py:50-52).  mir_eval is absent from the image and unpinned upstream; this
     is a restatement of the published BSS-eval v3 algorithm: "parity unpinned"."""
-    ref = np.atleast_2d(np.asarray(reference_sources, dtype=np.float64))
-    est = np.atleast_2d(np.asarray(estimated_sources, dtype=np.float64))
-    if ref.shape != est.shape:
-        raise ValueError(f"reference {ref.shape} and estimate {est.shape} shapes differ")
-    out = np.zeros(ref.shape[0])
-    for j in range(ref.shape[0]):
-        nsampl = est.shape[1]
-        s_true = np.hstack((ref[j], np.zeros(flen - 1)))
-        e_spat = _project(ref[j:j + 1], est[j], flen) - s_true
-        e_interf = _project(ref, est[j], flen) - s_true - e_spat
-        e_artif = -s_true - e_spat - e_interf
-        e_artif[:nsampl] += est[j]
-        num, den = np.sum((s_true + e_spat) ** 2), np.sum((e_interf + e_artif) ** 2)
-        out[j] = np.inf if den == 0 else 10 * np.log10(num / den)
-    return out
+    return bss_eval_sources(reference_sources, estimated_sources, flen)[0]
 
 
 def _bss_ratios(ref, est_row, j, flen, full_projection):
-    """(sdr, sir, sar) of one estimate against reference ``j``: the decomposition as ``bss_eval_sdr`` forms it (same
-    expressions, same order), ``full_projection`` being ``_project(ref, est_row, flen)``."""
+    """(sdr, sir, sar) of one estimate against reference ``j`` -- the one place the BSS-eval decomposition is written:
+    s_true, e_spat, e_interf, e_artif, in that order; ``full_projection`` is ``_project(ref, est_row, flen)``."""
     nsampl = est_row.shape[0]
     s_true = np.hstack((ref[j], np.zeros(flen - 1)))
     e_spat = _project(ref[j:j + 1], est_row, flen) - s_true
@@ -197,7 +183,7 @@ def _bss_inputs(reference_sources, estimated_sources):
 
 def bss_eval_matrices(reference_sources, estimated_sources, flen: int = 512):
     """(sdr, sir, sar), each [S_est, S_ref] float64: entry (e, j) scores estimate ``e`` against reference ``j`` with the
-    decomposition of ``bss_eval_sdr`` -- s_true, e_spat, e_interf, e_artif, in that order and with those expressions --
+    decomposition of ``_bss_ratios`` -- s_true, e_spat, e_interf, e_artif, in that order and with those expressions --
     and sdr = 10 log10(sum (s_true + e_spat)^2 / sum (e_interf + e_artif)^2), sir = 10 log10(sum (s_true + e_spat)^2 /
     sum e_interf^2), sar = 10 log10(sum (s_true + e_spat + e_interf)^2 / sum e_artif^2); a ratio is +inf when its
     denominator is exactly 0 (one talker: e_interf is exactly 0 and sir is +inf)."""
@@ -241,7 +227,7 @@ def bss_eval_sources(reference_sources, estimated_sources, flen: int = 512, comp
     """(sdr, sir, sar, perm) as ``mir_eval.separation.bss_eval_sources(reference_sources, estimated_sources,
     compute_permutation)`` answers (sep/eval/get_items.py:50-52) -- like ``bss_eval_sdr`` a restatement of the published
     BSS-eval v3 algorithm, mir_eval being absent: "parity unpinned".  ``compute_permutation=False``: estimate j against
-    reference j, ``perm = arange(S)``, and ``sdr`` is ``bss_eval_sdr`` byte for byte.  ``True``: ``bss_eval_matrices``,
+    reference j, ``perm = arange(S)``, and ``sdr`` is what ``bss_eval_sdr`` returns.  ``True``: ``bss_eval_matrices``,
     then ``perm = best_permutation(sir)`` and the three vectors ``m[perm[j], j]``."""
     ref, est = _bss_inputs(reference_sources, estimated_sources)
     S = ref.shape[0]
@@ -276,31 +262,12 @@ def check_bss(bss):
         raise ValueError(f"bss must be one of {BSS_FIELDS}, got {bss!r}")
 
 
-def bss_workspace_bytes(counts, R: int, T: int, flen: int) -> int:
-    """What ``asw_bss_eval_sdr_workspace_bytes`` answers for one call, restated so that the packing rule below is a pure
-    function (tests/test_bss_eval_host.py holds the two equal): the lists, the correlations and their partial sums,
-    the dense systems, the solutions and the energy partials."""
-    counts = [int(c) for c in counts]
-    N = sum(counts)
-    P = sum((R + 1) * S * S for S in counts)
-    nsys = sum(S + 1 if S > 1 else S for S in counts)
-    nsolve = sum(R * S * (2 if S > 1 else 1) for S in counts)
-    E = R * N
-    nchunk = -(-T // _BSS_CHUNK)
-    cps = -(-nchunk // min(nchunk, _BSS_SPLIT))
-    nsplit = -(-nchunk // cps)
-    nchunk_p = -(-(T + flen - 1) // _BSS_CHUNK)
-    gram = sum(S * flen * flen + ((S * flen) ** 2 if S > 1 else 0) for S in counts)
-    x = sum(R * S * (flen + (S * flen if S > 1 else 0)) for S in counts)
-    tables = 32 * len(counts) + 24 * nsys + 16 * P + 24 * nsolve + 8 * E
-    return tables + 8 * (P * nsplit * flen + P * flen + gram + x + 2 * E * nchunk_p)
-
-
 def bss_sources_workspace_bytes(counts, R: int, T: int, flen: int, all_pairs: bool = False, sdr_only: bool = False) -> int:
-    """What ``asw_bss_eval_sources_workspace_bytes`` answers for one call, restated as ``bss_workspace_bytes`` is
-    (tests/test_bss_sources_host.py holds the two equal).  ``all_pairs``: R S^2 single-reference solves and projection
-    rows per item instead of R S.  ``sdr_only``: what a call with neither ``sir`` nor ``sar`` needs -- two energy partials
-    per row and chunk instead of five; with ``all_pairs=False`` that is ``bss_workspace_bytes``."""
+    """What ``asw_bss_eval_sources_workspace_bytes`` answers for one call, restated so that the packing rule below is a
+    pure function (tests/test_bss_sources_host.py holds the two equal): the lists, the correlations and their partial
+    sums, the dense systems, the solutions and the energy partials.  ``all_pairs``: R S^2 single-reference solves and
+    projection rows per item instead of R S.  ``sdr_only``: what a call with neither ``sir`` nor ``sar`` needs -- two
+    energy partials per row and chunk instead of five."""
     counts = [int(c) for c in counts]
     rows = sum(R * S * (S if all_pairs else 1) for S in counts)
     P = sum((R + 1) * S * S for S in counts)
@@ -316,15 +283,20 @@ def bss_sources_workspace_bytes(counts, R: int, T: int, flen: int, all_pairs: bo
     return tables + 8 * (P * nsplit * flen + P * flen + gram + x + (2 if sdr_only else 5) * rows * nchunk_p)
 
 
+def bss_workspace_bytes(counts, R: int, T: int, flen: int) -> int:
+    """What ``asw_bss_eval_sdr_workspace_bytes`` answers for one call (tests/test_bss_eval_host.py holds the two equal):
+    the formula above for matched pairs and the SDR alone."""
+    return bss_sources_workspace_bytes(counts, R, T, flen, all_pairs=False, sdr_only=True)
+
+
 def pack_bss_items(counts, lengths, R: int, flen: int = 512, budget: int = BSS_WORKSPACE_BUDGET, all_pairs: bool = False,
                    sdr_only: bool = True):
     """The device calls of a batch: items stay whole and in order, a call holds items of one length only and takes as
-    many as its workspace (``bss_workspace_bytes``) fits into ``budget``.  -> list of (first, last) item ranges,
+    many as its workspace (``bss_sources_workspace_bytes``) fits into ``budget``.  -> list of (first, last) item ranges,
     ``last`` exclusive, covering every item once.  ``ValueError`` for an item the library refuses (talkers outside
     0..16, talkers * flen > 8192, T < flen), ``RuntimeError`` for one whose workspace alone exceeds the budget.
-    ``all_pairs`` and ``sdr_only`` size the calls of ``bss_eval_sources`` (``bss_sources_workspace_bytes``); the
-    defaults are the calls of ``bss_eval_sdr``."""
-    def bss_workspace_bytes(c, R, T, flen):                            # equal to the module's with the defaults
+    ``all_pairs`` and ``sdr_only`` say which call is sized; the defaults are the calls of ``bss_eval_sdr``."""
+    def call_bytes(c, T):
         return bss_sources_workspace_bytes(c, R, T, flen, all_pairs, sdr_only)
     if R < 1 or not 1 <= flen <= BSS_MAX_FLEN:
         raise ValueError(f"R = {R} < 1 or flen = {flen} outside 1..{BSS_MAX_FLEN}")
@@ -337,9 +309,9 @@ def pack_bss_items(counts, lengths, R: int, flen: int = 512, budget: int = BSS_W
             raise ValueError(f"item {k}: {S} talkers of {flen} taps (at most {BSS_MAX_TALKERS} and {BSS_MAX_ORDER} in all)")
         if T < flen:
             raise ValueError(f"item {k}: {T} samples are fewer than flen = {flen}")
-        if bss_workspace_bytes([S], R, T, flen) > budget:
-            raise RuntimeError(f"item {k} alone needs {bss_workspace_bytes([S], R, T, flen)} bytes of workspace, budget {budget}")
-        if k > first and (T != int(lengths[first]) or bss_workspace_bytes(counts[first:k + 1], R, T, flen) > budget):
+        if call_bytes([S], T) > budget:
+            raise RuntimeError(f"item {k} alone needs {call_bytes([S], T)} bytes of workspace, budget {budget}")
+        if k > first and (T != int(lengths[first]) or call_bytes(counts[first:k + 1], T) > budget):
             calls.append((first, k))
             first = k
     if first < len(counts):
@@ -347,9 +319,13 @@ def pack_bss_items(counts, lengths, R: int, flen: int = 512, budget: int = BSS_W
     return calls
 
 
-def _device_op(name, device):
-    """(``torch.ops.asw.<name>``, device) or ``RuntimeError``: there is no quiet fall-back to the host metric."""
+def _device_op(name, device, op=None):
+    """(op, device) of a batch route: ``torch.ops.asw.<name>`` on a GPU, or the stand-in ``op`` on CPU tensors (host
+    tests).  Without a stand-in a missing library or GPU is a ``RuntimeError``: there is no quiet fall-back to the host
+    metric."""
     import torch
+    if op is not None:
+        return op, torch.device("cpu" if device is None else device)
     from . import native
     op = getattr(native.torch_ops(), name)                 # RuntimeError when the library has not been built
     if not torch.cuda.is_available():
@@ -357,8 +333,44 @@ def _device_op(name, device):
     return op, torch.device("cuda:0" if device is None else device)
 
 
-def _bss_device_op(device):
-    return _device_op("bss_eval_sdr", device)
+def _bss_batch(name, all_pairs, unpack, on_host, refs, est_sets, flen, device, op, budget):
+    """The batch route of both BSS ops: checks, float32 rounding, op and device, packing, one upload and one
+    ``torch.ops.asw.<name>`` call per range of ``pack_bss_items``, then item after item ``on_host(ref, est)`` where the
+    device reports status 1 and else ``unpack(rows, S)`` of the item's float64 [R, width] slices, one per value the op
+    returns.  ``all_pairs`` None: the op takes no such argument and gives the SDR alone (``bss_eval_sdr``); else width is
+    S^2 when it is true."""
+    import torch
+    if len(refs) != len(est_sets):
+        raise ValueError(f"{len(est_sets)} estimate sets for {len(refs)} samples")
+    if not refs:
+        return [], []
+    refs = [np.ascontiguousarray(np.atleast_2d(r), dtype=np.float32) for r in refs]
+    ests = [np.ascontiguousarray(e, dtype=np.float32) for e in est_sets]
+    R = ests[0].shape[0] if ests[0].ndim == 3 else -1
+    for k, (r, e) in enumerate(zip(refs, ests)):
+        if e.ndim != 3 or e.shape[0] != R or e.shape[1:] != r.shape:
+            raise ValueError(f"sample {k}: estimates {e.shape} do not go with references {r.shape} as [R = {R}, S, T]")
+    op, dev = _device_op(name, device, op)
+    mode = () if all_pairs is None else (all_pairs,)
+    counts, lengths = [r.shape[0] for r in refs], [r.shape[1] for r in refs]
+    calls = pack_bss_items(counts, lengths, R, flen, budget, all_pairs=bool(all_pairs), sdr_only=all_pairs is None)
+    out, recomputed = [None] * len(refs), []
+    for first, last in calls:
+        ref = torch.from_numpy(np.concatenate(refs[first:last], axis=0)).to(dev)
+        est = torch.from_numpy(np.concatenate(ests[first:last], axis=1)).to(dev)
+        *vals, status = op(ref, est, counts[first:last], int(flen), *mode)
+        vals, status = [v.cpu().numpy() for v in vals], status.cpu().numpy()
+        c0 = 0
+        for k in range(first, last):
+            S = counts[k]
+            width = S * S if all_pairs else S
+            if status[k - first] != 0:
+                recomputed.append(k)
+                out[k] = on_host(refs[k], ests[k])
+            else:
+                out[k] = unpack([np.array(v[:, c0:c0 + width], dtype=np.float64) for v in vals], S)
+            c0 += width
+    return out, recomputed
 
 
 def bss_eval_sdr_batch(refs, est_sets, flen: int = 512, device=None, op=None, budget: int = BSS_WORKSPACE_BUDGET):
@@ -371,39 +383,9 @@ def bss_eval_sdr_batch(refs, est_sets, flen: int = 512, device=None, op=None, bu
     host statement itself leaves ``solve`` for ``lstsq`` -- so its values are exactly the host result.
     ``op`` replaces the device op (a stand-in on CPU tensors in the host tests); without it a missing library or GPU
     is a ``RuntimeError``."""
-    import torch
-    if len(refs) != len(est_sets):
-        raise ValueError(f"{len(est_sets)} estimate sets for {len(refs)} samples")
-    if not refs:
-        return [], []
-    refs = [np.ascontiguousarray(np.atleast_2d(r), dtype=np.float32) for r in refs]
-    ests = [np.ascontiguousarray(e, dtype=np.float32) for e in est_sets]
-    R = ests[0].shape[0] if ests[0].ndim == 3 else -1
-    for k, (r, e) in enumerate(zip(refs, ests)):
-        if e.ndim != 3 or e.shape[0] != R or e.shape[1:] != r.shape:
-            raise ValueError(f"sample {k}: estimates {e.shape} do not go with references {r.shape} as [R = {R}, S, T]")
-    if op is None:
-        op, dev = _bss_device_op(device)
-    else:
-        dev = torch.device("cpu" if device is None else device)
-    counts, lengths = [r.shape[0] for r in refs], [r.shape[1] for r in refs]
-    calls = pack_bss_items(counts, lengths, R, flen, budget)
-    out, recomputed = [None] * len(refs), []
-    for first, last in calls:
-        ref = torch.from_numpy(np.concatenate(refs[first:last], axis=0)).to(dev)
-        est = torch.from_numpy(np.concatenate(ests[first:last], axis=1)).to(dev)
-        sdr, status = op(ref, est, counts[first:last], int(flen))
-        sdr, status = sdr.cpu().numpy(), status.cpu().numpy()
-        n0 = 0
-        for k in range(first, last):
-            S = counts[k]
-            if status[k - first] != 0:
-                recomputed.append(k)
-                out[k] = np.stack([bss_eval_sdr(refs[k], ests[k][r], flen) for r in range(R)])
-            else:
-                out[k] = np.array(sdr[:, n0:n0 + S], dtype=np.float64)
-            n0 += S
-    return out, recomputed
+    def on_host(ref, est):
+        return np.stack([bss_eval_sdr(ref, e, flen) for e in est])
+    return _bss_batch("bss_eval_sdr", None, lambda rows, S: rows[0], on_host, refs, est_sets, flen, device, op, budget)
 
 
 def bss_eval_sdr_device(reference_sources, estimated_sets, flen: int = 512, device=None, op=None):
@@ -423,48 +405,20 @@ def bss_eval_sources_batch(refs, est_sets, flen: int = 512, compute_permutation:
     matrices back and lets ``best_permutation`` decide on the host, per estimate set.  An item the device marks
     ``status = 1`` is recomputed with ``bss_eval_sources``, so its values are exactly the host's.  ``op`` replaces the
     device op (a stand-in on CPU tensors in the host tests); without it a missing library or GPU is a ``RuntimeError``."""
-    import torch
-    if len(refs) != len(est_sets):
-        raise ValueError(f"{len(est_sets)} estimate sets for {len(refs)} samples")
-    if not refs:
-        return [], []
-    refs = [np.ascontiguousarray(np.atleast_2d(r), dtype=np.float32) for r in refs]
-    ests = [np.ascontiguousarray(e, dtype=np.float32) for e in est_sets]
-    R = ests[0].shape[0] if ests[0].ndim == 3 else -1
-    for k, (r, e) in enumerate(zip(refs, ests)):
-        if e.ndim != 3 or e.shape[0] != R or e.shape[1:] != r.shape:
-            raise ValueError(f"sample {k}: estimates {e.shape} do not go with references {r.shape} as [R = {R}, S, T]")
-    if op is None:
-        op, dev = _device_op("bss_eval_sources", device)
-    else:
-        dev = torch.device("cpu" if device is None else device)
     all_pairs = bool(compute_permutation)
-    counts, lengths = [r.shape[0] for r in refs], [r.shape[1] for r in refs]
-    calls = pack_bss_items(counts, lengths, R, flen, budget, all_pairs=all_pairs, sdr_only=False)
-    out, recomputed = [None] * len(refs), []
-    for first, last in calls:
-        ref = torch.from_numpy(np.concatenate(refs[first:last], axis=0)).to(dev)
-        est = torch.from_numpy(np.concatenate(ests[first:last], axis=1)).to(dev)
-        *vals, status = op(ref, est, counts[first:last], int(flen), all_pairs)
-        vals, status = np.stack([v.cpu().numpy() for v in vals]), status.cpu().numpy()          # [3, R, N or Q]
-        c0 = 0
-        for k in range(first, last):
-            S = counts[k]
-            width = S * S if all_pairs else S
-            if status[k - first] != 0:
-                recomputed.append(k)
-                sets = [bss_eval_sources(refs[k], ests[k][r], flen, compute_permutation) for r in range(R)]
-                out[k] = tuple(np.stack([s[q] for s in sets]) for q in range(4))
-            elif all_pairs:
-                mats = np.array(vals[:, :, c0:c0 + width], dtype=np.float64).reshape(3, R, S, S)
-                perm = np.stack([best_permutation(mats[1, r]) for r in range(R)]).reshape(R, S)
-                idx = np.arange(S)
-                out[k] = tuple(np.stack([mats[q, r][perm[r], idx] for r in range(R)]).reshape(R, S) for q in range(3)) + (perm,)
-            else:
-                m = np.array(vals[:, :, c0:c0 + width], dtype=np.float64)
-                out[k] = (m[0], m[1], m[2], np.tile(np.arange(S), (R, 1)))
-            c0 += width
-    return out, recomputed
+
+    def on_host(ref, est):
+        sets = [bss_eval_sources(ref, e, flen, compute_permutation) for e in est]
+        return tuple(np.stack([s[q] for s in sets]) for q in range(4))
+
+    def unpack(rows, S):
+        R, idx = rows[0].shape[0], np.arange(S)
+        if not all_pairs:
+            return (*rows, np.tile(idx, (R, 1)))
+        mats = [m.reshape(R, S, S) for m in rows]
+        perm = np.stack([best_permutation(mats[1][r]) for r in range(R)]).reshape(R, S)
+        return tuple(np.stack([m[r][perm[r], idx] for r in range(R)]).reshape(R, S) for m in mats) + (perm,)
+    return _bss_batch("bss_eval_sources", all_pairs, unpack, on_host, refs, est_sets, flen, device, op, budget)
 
 
 def bss_eval_sources_device(reference_sources, estimated_sets, flen: int = 512, compute_permutation: bool = False,
@@ -516,10 +470,7 @@ def cross_sisdr_batch(est_list, ref_list, device=None, op=None):
             raise ValueError(f"item {k}: {e.shape[0]} estimates (at most {XS_MAX_EST}) or {r.shape[0]} references "
                              f"(at most {XS_MAX_REF})")
         by_length.setdefault(e.shape[1], []).append(k)
-    if op is None:
-        op, dev = _device_op("cross_sisdr", device)
-    else:
-        dev = torch.device("cpu" if device is None else device)
+    op, dev = _device_op("cross_sisdr", device, op)
     out, recomputed = [None] * len(ests), []
     for T, members in by_length.items():
         for first in range(0, len(members), XS_MAX_ITEMS):
@@ -555,17 +506,14 @@ def compute_metrics(input_signal, est_signal, gt, metrics="host", bss="sdr"):
     est = np.asarray(est_signal, dtype=np.float64)
     input_sisdr = [si_sdr(inp[i], gt[i]) for i in range(gt.shape[0])]
     output_sisdr = [si_sdr(est[i], gt[i]) for i in range(gt.shape[0])]
-    if bss == "all":
-        if metrics == "device":
-            sdr, sir, sar, _perm = bss_eval_sources_device(gt, np.stack([inp, est]))
-        else:
-            sdr, sir, sar = (np.stack(v) for v in zip(bss_eval_sources(gt, inp)[:3], bss_eval_sources(gt, est)[:3]))
-        return sdr[0], sdr[1], input_sisdr, output_sisdr, (sir[0], sir[1], sar[0], sar[1])
-    if metrics == "device":
-        input_sdr, output_sdr = bss_eval_sdr_device(gt, np.stack([inp, est]))
+    if metrics == "host":
+        sdr, sir, sar = (np.stack(v) for v in zip(bss_eval_sources(gt, inp)[:3], bss_eval_sources(gt, est)[:3]))
+    elif bss == "all":
+        sdr, sir, sar, _perm = bss_eval_sources_device(gt, np.stack([inp, est]))
     else:
-        input_sdr, output_sdr = bss_eval_sdr(gt, inp), bss_eval_sdr(gt, est)
-    return input_sdr, output_sdr, input_sisdr, output_sisdr
+        sdr = bss_eval_sdr_device(gt, np.stack([inp, est]))
+    out = (sdr[0], sdr[1], input_sisdr, output_sisdr)
+    return out + ((sir[0], sir[1], sar[0], sar[1]),) if bss == "all" else out
 
 
 # ---- one sample --------------------------------------------------------------------------------
@@ -609,10 +557,10 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, b
     the two BSS-eval SDR fields come from (``compute_metrics``).  ``scores`` (``records_from_results``) holds them
     ready-made: ``"sisdr"``, the [1 + K (+ K), n_gt] matrix of ``cross_sisdr_batch`` over the rows [mix[0]; separated;
     localisation stage] (the third block only with a separation model), ``"perm"``, the matching found from it, and
-    ``"bss"``, the [2, matched] BSS-eval SDRs of the unprocessed and the separated set.  ``bss="all"`` adds four fields
-    to every matched talker's entry: ``sir_in_mir`` / ``sar_in_mir`` of the unprocessed set and ``sir_mir`` / ``sar_mir``
-    of the separated set, the raw values and no differences (one talker has SIR +inf on both sides); ``scores`` then
-    holds them too, as ``"sir"`` and ``"sar"``, each [2, matched]."""
+    ``"bss"``, the BSS-eval SDRs of the unprocessed and of the separated set, one row of ``matched`` values each.
+    ``bss="all"`` adds four fields to every matched talker's entry: ``sir_in_mir`` / ``sar_in_mir`` of the unprocessed
+    set and ``sir_mir`` / ``sar_mir`` of the separated set, the raw values and no differences (one talker has SIR +inf on
+    both sides); ``scores["bss"]`` then holds their four rows too, after the two SDR rows and in the fields' order."""
     check_metrics(metrics)
     check_bss(bss)
     _mics, mic_positions, _voices, gt_pos, offsets_gt, roi = preprocess_metadata(metadata)
@@ -629,38 +577,34 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, b
     for s in range(gt_pos.shape[0]):
         rec["gt"].append({"sample": offsets_gt[:, s].tolist(), "pos": gt_pos[s].tolist()})
     unmatched = list(range(n_out))
+    # cols: per matched pair the SDR of the unprocessed and of the separated set, their SI-SDRs, the SI-SDR of the
+    # localisation stage and, with bss="all", the four SIR / SAR values in the order of the fields below
+    cols = []
     if perm and scores is not None:
         M, loc0 = scores["sisdr"], 1 + (n_out if result.get("audio") is not None else 0)
-        in_sdr, out_sdr = scores["bss"]
-        if bss == "all":
-            extra = (*scores["sir"], *scores["sar"])
-        in_sisdr_l = [float(M[0, s]) for _o, s in perm]
-        out_sisdr_l = [float(M[1 + o, s]) for o, s in perm]
-        loc_sisdr_l = [float(M[loc0 + o, s]) for o, s in perm]
+        cols = [*scores["bss"][:2], [float(M[0, s]) for _o, s in perm], [float(M[1 + o, s]) for o, s in perm],
+                [float(M[loc0 + o, s]) for o, s in perm], *scores["bss"][2:]]
     elif perm:
         # matched pairs in the reference's order (eval_model.py:162-187): separated output (joint
         # decoder when attached), localisation-stage output, ground truth, unprocessed mic 0
         pa = np.array(perm)
         ref_sig = np.repeat(mix[0:1].astype(np.float64), len(perm), axis=0)
-        in_sdr, out_sdr, in_sisdr_l, out_sisdr_l, *more = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics,
-                                                                          bss)
-        extra = more[0] if more else None
-        loc_sisdr_l = [si_sdr(audio_loc[o].astype(np.float64), gt[s].astype(np.float64)) for o, s in perm]
+        m = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics, bss)
+        loc_sisdr = [si_sdr(audio_loc[o].astype(np.float64), gt[s].astype(np.float64)) for o, s in perm]
+        cols = [*m[:4], loc_sisdr, *(m[4] if bss == "all" else ())]
     for i, (out_id, s) in enumerate(perm):
         unmatched.remove(out_id)
-        in_sisdr = in_sisdr_l[i]
+        in_sdr, out_sdr, in_sisdr, out_sisdr, loc_sisdr, *extra = (c[i] for c in cols)
         rec["pred"].append({
             "voice_id": s, "shifts": est_off[out_id].tolist(), "pos": est_pos[out_id].tolist(),
             "sample_err": float(np.mean(np.abs(est_off[out_id] - offsets_gt[:, s]))),
             "dis_err": float(np.linalg.norm(est_pos[out_id][:2] - gt_pos[s][:2])),
-            "si_snr_in_mir": float(in_sdr[i]), "si_snri_mir": float(out_sdr[i] - in_sdr[i]),   # BSS-eval SDR (restated)
+            "si_snr_in_mir": float(in_sdr), "si_snri_mir": float(out_sdr - in_sdr),   # BSS-eval SDR (restated)
             "si_snr_in": in_sisdr,
-            "si_snri": out_sisdr_l[i] - in_sisdr,
+            "si_snri": out_sisdr - in_sisdr,
             "si_snr_in_old": in_sisdr,
-            "si_snri_old": loc_sisdr_l[i] - in_sisdr})
-        if bss == "all":
-            rec["pred"][-1].update(sir_in_mir=float(extra[0][i]), sir_mir=float(extra[1][i]),
-                                   sar_in_mir=float(extra[2][i]), sar_mir=float(extra[3][i]))
+            "si_snri_old": loc_sisdr - in_sisdr,
+            **{k: float(v) for k, v in zip(("sir_in_mir", "sir_mir", "sar_in_mir", "sar_mir"), extra)}})
     for rid in unmatched:
         rec["false_positive"].append({"pos": est_pos[rid].tolist(),
                                       "sample": np.asarray(result["audio_offsets"][rid]).tolist()})
@@ -714,14 +658,14 @@ def records_from_results(samples, results, metrics="host", ops=None, stats=None,
         sets.append(np.stack([ref_sig, np.asarray(_separated(results[k]), dtype=np.float32)[pa[:, 0]]]))
     if bss == "all":
         vals, _ = bss_eval_sources_batch(refs, sets, op=bss_op)
-        scored = {k: {"bss": v[0], "sir": v[1], "sar": v[2]} for k, v in zip(matched, vals)}
+        scored = {k: (*sdr, *sir, *sar) for k, (sdr, sir, sar, _perm) in zip(matched, vals)}
     else:
         vals, _ = bss_eval_sdr_batch(refs, sets, op=bss_op)
-        scored = {k: {"bss": v} for k, v in zip(matched, vals)}
+        scored = {k: tuple(sdr) for k, sdr in zip(matched, vals)}
     if stats is not None:
         stats.update(sisdr_s=t1 - t0, match_s=t2 - t1, bss_s=time.perf_counter() - t2)
     return [record_from_result(meta, mix, gt, res, "device",
-                               {"sisdr": mats[k], "perm": perms[k], "bss": None, **scored.get(k, {})}, bss=bss)
+                               {"sisdr": mats[k], "perm": perms[k], "bss": scored.get(k)}, bss=bss)
             for k, ((meta, mix, gt), res) in enumerate(zip(samples, results))]
 
 

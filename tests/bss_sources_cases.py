@@ -5,7 +5,11 @@ handed out read-only.
 SIR and SAR are differences of nearly equal projections, so the inputs are chosen to keep the statement's own values
 moderate (``tests/test_bss_sources_host.py`` asserts -30 .. +50 dB on every finite SIR and SAR of the cases below).  The
 "mixture" kind makes every estimate of a set identical, so its permutations tie: the permutation cases use "noisy" and
-"filtered" estimates only, their rows shuffled by a known permutation."""
+"filtered" estimates only, their rows shuffled by a known permutation.
+
+Also the helpers that the tests of both BSS ops share: the stand-in for the device op, the library's workspace query, a
+call of either C entry point on host memory, and a model whose forward pass runs once."""
+import ctypes
 import functools
 
 import numpy as np
@@ -106,3 +110,90 @@ def shuffled(seed, counts, T, flen):
 
 def pack(refs, ests):
     return cases.pack(refs, ests)
+
+
+# ---- helpers shared by the tests of torch.ops.asw.bss_eval_sdr and torch.ops.asw.bss_eval_sources -----------------------
+def stand_in(marked=(), seen=None):
+    """Either device op on CPU tensors: ``op(ref, est, counts, flen)`` -> (sdr, status) as ``bss_eval_sdr`` and
+    ``op(ref, est, counts, flen, all_pairs)`` -> (sdr, sir, sar, status) as ``bss_eval_sources``.  The host statement per
+    item; status 1 and NaN for the items of ``marked`` (indices within the call); ``seen`` receives the shapes and
+    arguments of every call."""
+    import torch
+    from acousticswarms_speech_amd import evalkit
+
+    def op(ref, est, counts, flen, *mode):
+        if seen is not None:
+            seen.append((tuple(ref.shape), tuple(est.shape), list(counts), flen, *mode))
+        all_pairs = bool(mode and mode[0])
+        R, N, _T = est.shape
+        ncol = sum(S * S for S in counts) if all_pairs else N
+        vals, status, n0, c0 = np.zeros((3, R, ncol)), np.zeros(len(counts), dtype=np.int32), 0, 0
+        for k, S in enumerate(counts):
+            width = S * S if all_pairs else S
+            for r in range(R if S else 0):
+                r_k, e_k = ref[n0:n0 + S].numpy(), est[r, n0:n0 + S].numpy()
+                if k in marked:
+                    vals[:, r, c0:c0 + width] = np.nan
+                elif all_pairs:
+                    vals[:, r, c0:c0 + width] = np.stack(evalkit.bss_eval_matrices(r_k, e_k, flen)).reshape(3, width)
+                else:
+                    vals[:, r, c0:c0 + width] = evalkit.bss_eval_sources(r_k, e_k, flen)[:3]
+            status[k] = int(k in marked)
+            n0, c0 = n0 + S, c0 + width
+        return tuple(torch.from_numpy(v) for v in (vals if mode else vals[:1])) + (torch.from_numpy(status),)
+    return op
+
+
+def c_bytes(counts, R, T, flen, all_pairs=None):
+    """The library's workspace query: ``asw_bss_eval_sdr_workspace_bytes`` without ``all_pairs``, else
+    ``asw_bss_eval_sources_workspace_bytes``."""
+    from acousticswarms_speech_amd import native
+    c = (ctypes.c_int32 * max(1, len(counts)))(*counts)
+    if all_pairs is None:
+        return native.lib().asw_bss_eval_sdr_workspace_bytes(c, len(counts), R, T, flen)
+    return native.lib().asw_bss_eval_sources_workspace_bytes(c, len(counts), R, T, flen, int(all_pairs))
+
+
+def c_call(entry, counts=(2, 1), R=2, T=100, flen=8, all_pairs=0, null=(), ws_delta=0, ws_shift=0, K=None, sdr_only_size=False):
+    """One call of the C entry point ``entry`` ("asw_bss_eval_sdr" or "asw_bss_eval_sources"), host memory standing in for
+    every pointer: what is refused is refused before the first launch.  ``null``: the name(s) of the pointers passed as
+    null.  -> (status, last error, workspace bytes asked for)."""
+    from acousticswarms_speech_amd import evalkit, native
+    L, full = native.lib(), entry == "asw_bss_eval_sources"
+    null = (null,) if isinstance(null, str) else tuple(null or ())
+    K = len(counts) if K is None else K
+    c = (ctypes.c_int32 * max(1, len(counts)))(*counts)
+    n = max(1, sum(max(0, v) for v in counts))
+    q = max(1, sum(v * v for v in counts)) if full else n
+    ref = (ctypes.c_float * (n * max(T, 1)))()
+    est = (ctypes.c_float * (max(R, 1) * n * max(T, 1)))()
+    outs = {name: (ctypes.c_double * (max(R, 1) * q))() for name in (("sdr", "sir", "sar") if full else ("sdr",))}
+    status = (ctypes.c_int32 * max(1, len(counts)))()
+    need = getattr(L, entry + "_workspace_bytes")(c, K, R, T, flen, *((all_pairs,) if full else ()))
+    if sdr_only_size:
+        need = evalkit.bss_sources_workspace_bytes(counts, R, T, flen, bool(all_pairs), sdr_only=True)
+    ws = (ctypes.c_double * (need // 8 + 2))()
+    ptr = {"ref": ref, "est": est, "counts": c, "status": status, "ws": ws, **outs}
+    arg = {k: (None if k in null else ctypes.cast(v, ctypes.c_void_p)) for k, v in ptr.items()}
+    if arg["ws"] is not None:
+        arg["ws"] = ctypes.c_void_p(arg["ws"].value + ws_shift)
+    mode = (all_pairs,) if full else ()
+    rc = getattr(L, entry)(arg["ref"], arg["est"], arg["counts"], K, R, T, flen, *mode, *(arg[name] for name in outs),
+                           arg["status"], arg["ws"], need + ws_delta, None)
+    return rc, L.asw_last_error().decode(), need
+
+
+class Once:
+    """A JointModel whose forward pass runs once: the records made from it differ in the metric only."""
+
+    def __init__(self, jm):
+        self.jm, self.out = jm, None
+
+    def setup(self, **kw):
+        if self.out is None:
+            self.jm.setup(**kw)
+
+    def __call__(self, mix):
+        if self.out is None:
+            self.out = self.jm(mix)
+        return self.out

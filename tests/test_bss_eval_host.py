@@ -2,6 +2,7 @@
 to the host statement for items the device marks, and the refusals of the C entry point (all of which happen before the
 first launch)."""
 import ctypes
+import functools
 import re
 
 import numpy as np
@@ -11,13 +12,9 @@ import torch
 from acousticswarms_speech_amd import evalkit, native
 
 from tests import bss_eval_cases as cases
+from tests.bss_sources_cases import c_bytes as _c_bytes, c_call, stand_in as _stand_in
 
 MB = 1 << 20
-
-
-def _c_bytes(counts, R, T, flen):
-    c = (ctypes.c_int32 * max(1, len(counts)))(*counts)
-    return native.lib().asw_bss_eval_sdr_workspace_bytes(c, len(counts), R, T, flen)
 
 
 def test_workspace_formula_equals_the_library():
@@ -115,22 +112,6 @@ def test_host_default_is_untouched_by_the_option():
     np.testing.assert_array_equal(a[0], evalkit.bss_eval_sdr(gt, inp))
 
 
-def _stand_in(marked, seen):
-    """An op with the device op's signature on CPU tensors: the host statement per item, status 1 and NaN rows for the
-    items of ``marked`` (indices within the call)."""
-    def op(ref, est, counts, flen):
-        seen.append((tuple(ref.shape), tuple(est.shape), list(counts), flen))
-        R, N, _T = est.shape
-        sdr, status, n0 = np.zeros((R, N)), np.zeros(len(counts), dtype=np.int32), 0
-        for k, S in enumerate(counts):
-            for r in range(R):
-                sdr[r, n0:n0 + S] = np.nan if k in marked else evalkit.bss_eval_sdr(ref[n0:n0 + S].numpy(), est[r, n0:n0 + S].numpy(), flen) if S else 0
-            status[k] = int(k in marked)
-            n0 += S
-        return torch.from_numpy(sdr), torch.from_numpy(status)
-    return op
-
-
 def test_marked_items_are_recomputed_on_the_host():
     refs, ests = cases.make_batch(5, [2, 1, 0, 3], 400)
     want = [np.stack([evalkit.bss_eval_sdr(r, e[s], 16) for s in range(2)]) if r.shape[0] else np.zeros((2, 0))
@@ -170,24 +151,7 @@ def test_batch_shape_errors():
 
 
 # ---- the C entry point refuses on the host, before the first launch: host memory stands in for every pointer ---------
-def _call(counts=(2, 1), R=2, T=100, flen=8, null=None, ws_delta=0, ws_shift=0, K=None):
-    L = native.lib()
-    K = len(counts) if K is None else K
-    c = (ctypes.c_int32 * max(1, len(counts)))(*counts)
-    n = max(1, sum(max(0, v) for v in counts))
-    ref = (ctypes.c_float * (n * max(T, 1)))()
-    est = (ctypes.c_float * (max(R, 1) * n * max(T, 1)))()
-    sdr = (ctypes.c_double * (max(R, 1) * n))()
-    status = (ctypes.c_int32 * max(1, len(counts)))()
-    need = L.asw_bss_eval_sdr_workspace_bytes(c, K, R, T, flen)
-    ws = (ctypes.c_double * (need // 8 + 2))()
-    ptr = {"ref": ref, "est": est, "counts": c, "sdr": sdr, "status": status, "ws": ws}
-    arg = {k: (None if k == null else ctypes.cast(v, ctypes.c_void_p)) for k, v in ptr.items()}
-    if arg["ws"] is not None:
-        arg["ws"] = ctypes.c_void_p(arg["ws"].value + ws_shift)
-    rc = L.asw_bss_eval_sdr(arg["ref"], arg["est"], arg["counts"], K, R, T, flen, arg["sdr"], arg["status"], arg["ws"],
-                            need + ws_delta, None)
-    return rc, L.asw_last_error().decode(), need
+_call = functools.partial(c_call, "asw_bss_eval_sdr")
 
 
 @pytest.mark.parametrize("kw,message", [

@@ -3,6 +3,7 @@
 workspace formula and the packing rule in both modes, the refusals of the C entry point (all before the first launch),
 the Python layer's errors, the route back to the host for items the device marks, and the records."""
 import ctypes
+import functools
 import itertools
 import re
 
@@ -14,6 +15,7 @@ from acousticswarms_speech_amd import evalkit, native
 
 from tests import bss_eval_cases as cases
 from tests import bss_sources_cases as sc
+from tests.bss_sources_cases import c_bytes as _c_bytes, stand_in as _stand_in
 
 SMALL = [c for c in sc.MATCHED if c not in sc.WORKING]
 
@@ -157,16 +159,6 @@ def test_enumeration_equals_assignment_up_to_six():
 
 
 # ---- workspace and packing ----------------------------------------------------------------------------------------------
-def _c_bytes(counts, R, T, flen, all_pairs):
-    c = (ctypes.c_int32 * max(1, len(counts)))(*counts)
-    return native.lib().asw_bss_eval_sources_workspace_bytes(c, len(counts), R, T, flen, int(all_pairs))
-
-
-def _c_sdr_bytes(counts, R, T, flen):
-    c = (ctypes.c_int32 * max(1, len(counts)))(*counts)
-    return native.lib().asw_bss_eval_sdr_workspace_bytes(c, len(counts), R, T, flen)
-
-
 def test_workspace_formula_equals_the_library():
     rng = np.random.default_rng(41)
     shapes = [([5], 2, 48000, 512), ([2], 2, 16000, 512), ([1], 1, 64, 64), ([0, 2, 0], 2, 257, 21), ([3, 1, 2], 3, 4099, 43),
@@ -182,7 +174,7 @@ def test_workspace_formula_equals_the_library():
             assert evalkit.bss_sources_workspace_bytes(counts, R, T, flen, all_pairs, sdr_only=True) <= got
         # matched and SDR only: the size of the SDR entry, by its formula and by the library
         only = evalkit.bss_sources_workspace_bytes(counts, R, T, flen, False, sdr_only=True)
-        assert only == evalkit.bss_workspace_bytes(counts, R, T, flen) == _c_sdr_bytes(counts, R, T, flen)
+        assert only == evalkit.bss_workspace_bytes(counts, R, T, flen) == _c_bytes(counts, R, T, flen)
         if all(S <= 1 for S in counts):                                        # one talker: all pairs is the one pair
             assert evalkit.bss_sources_workspace_bytes(counts, R, T, flen, True) == \
                 evalkit.bss_sources_workspace_bytes(counts, R, T, flen, False)
@@ -226,27 +218,7 @@ def test_packing_default_is_todays_and_all_pairs_keeps_the_properties():
 
 
 # ---- the C entry point refuses on the host, before the first launch: host memory stands in for every pointer ---------
-def _call(counts=(2, 1), R=2, T=100, flen=8, all_pairs=0, null=(), ws_delta=0, ws_shift=0, K=None, sdr_only_size=False):
-    L = native.lib()
-    K = len(counts) if K is None else K
-    c = (ctypes.c_int32 * max(1, len(counts)))(*counts)
-    n = max(1, sum(max(0, v) for v in counts))
-    q = max(1, sum(v * v for v in counts))
-    ref = (ctypes.c_float * (n * max(T, 1)))()
-    est = (ctypes.c_float * (max(R, 1) * n * max(T, 1)))()
-    outs = {name: (ctypes.c_double * (max(R, 1) * q))() for name in ("sdr", "sir", "sar")}
-    status = (ctypes.c_int32 * max(1, len(counts)))()
-    need = L.asw_bss_eval_sources_workspace_bytes(c, K, R, T, flen, all_pairs)
-    if sdr_only_size:
-        need = evalkit.bss_sources_workspace_bytes(counts, R, T, flen, bool(all_pairs), sdr_only=True)
-    ws = (ctypes.c_double * (need // 8 + 2))()
-    ptr = {"ref": ref, "est": est, "counts": c, "status": status, "ws": ws, **outs}
-    arg = {k: (None if k in null else ctypes.cast(v, ctypes.c_void_p)) for k, v in ptr.items()}
-    if arg["ws"] is not None:
-        arg["ws"] = ctypes.c_void_p(arg["ws"].value + ws_shift)
-    rc = L.asw_bss_eval_sources(arg["ref"], arg["est"], arg["counts"], K, R, T, flen, all_pairs, arg["sdr"], arg["sir"],
-                                arg["sar"], arg["status"], arg["ws"], need + ws_delta, None)
-    return rc, L.asw_last_error().decode(), need
+_call = functools.partial(sc.c_call, "asw_bss_eval_sources")
 
 
 @pytest.mark.parametrize("all_pairs", [0, 1])
@@ -290,30 +262,6 @@ def test_c_empty_batch_launches_nothing():
 
 
 # ---- the Python layer ---------------------------------------------------------------------------------------------------
-def _stand_in(marked, seen):
-    """An op with the device op's signature on CPU tensors: the host statement per item, status 1 and NaN for the items
-    of ``marked`` (indices within the call)."""
-    def op(ref, est, counts, flen, all_pairs):
-        seen.append((tuple(ref.shape), tuple(est.shape), list(counts), flen, all_pairs))
-        R, N, _T = est.shape
-        ncol = sum(S * S for S in counts) if all_pairs else N
-        vals, status, n0, c0 = np.zeros((3, R, ncol)), np.zeros(len(counts), dtype=np.int32), 0, 0
-        for k, S in enumerate(counts):
-            width = S * S if all_pairs else S
-            for r in range(R if S else 0):
-                r_k, e_k = ref[n0:n0 + S].numpy(), est[r, n0:n0 + S].numpy()
-                if k in marked:
-                    vals[:, r, c0:c0 + width] = np.nan
-                elif all_pairs:
-                    vals[:, r, c0:c0 + width] = np.stack(evalkit.bss_eval_matrices(r_k, e_k, flen)).reshape(3, width)
-                else:
-                    vals[:, r, c0:c0 + width] = evalkit.bss_eval_sources(r_k, e_k, flen)[:3]
-            status[k] = int(k in marked)
-            n0, c0 = n0 + S, c0 + width
-        return tuple(torch.from_numpy(v) for v in vals) + (torch.from_numpy(status),)
-    return op
-
-
 def _want(refs, ests, flen, permute):
     out = []
     for r, e in zip(refs, ests):

@@ -17,6 +17,7 @@ import torch
 
 from acousticswarms_speech_amd import evalkit, native
 from tests import bss_eval_cases as cases
+from tests.bss_sources_cases import Once as _Once
 
 pytestmark = pytest.mark.gpu
 
@@ -205,22 +206,6 @@ def test_compute_metrics_device_against_host():
     dev = evalkit.compute_metrics(inp, est, gt, metrics="device")
     _check("compute_metrics", np.stack([dev[0], dev[1]]), np.stack([host[0], host[1]]))
     assert dev[2] == host[2] and dev[3] == host[3]                     # SI-SDR does not change
-
-
-class _Once:
-    """A JointModel whose forward pass runs once: the two records below differ in the metric only."""
-
-    def __init__(self, jm):
-        self.jm, self.out = jm, None
-
-    def setup(self, **kw):
-        if self.out is None:
-            self.jm.setup(**kw)
-
-    def __call__(self, mix):
-        if self.out is None:
-            self.out = self.jm(mix)
-        return self.out
 
 
 def test_record_device_against_host():

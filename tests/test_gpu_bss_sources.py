@@ -20,6 +20,7 @@ import torch
 
 from acousticswarms_speech_amd import evalkit, native
 from tests import bss_sources_cases as sc
+from tests.bss_sources_cases import Once as _Once
 
 pytestmark = pytest.mark.gpu
 
@@ -150,6 +151,20 @@ def test_sdr_bytes_with_and_without_sir_and_sar(all_pairs):
         assert old.cpu().numpy().tobytes() == sdr0 and status.cpu().numpy().tobytes() == st0
 
 
+def test_both_ops_give_the_same_sdr_and_status_bytes():
+    """The two registered ops are one adapter: on the same inputs ``bss_eval_sdr`` (null sir / sar, the smaller workspace)
+    and matched ``bss_eval_sources`` answer the same ``sdr`` and ``status``, byte for byte."""
+    refs, ests = sc.cases.make_batch(19, [2, 0, 3, 1], 257)
+    ref, est, counts = sc.pack(refs, ests)
+    assert est.shape[0] == 2
+    d_ref, d_est = torch.from_numpy(ref).to(DEV), torch.from_numpy(est).to(DEV)
+    sdr, status = native.torch_ops().bss_eval_sdr(d_ref, d_est, counts, 21)
+    full, _sir, _sar, full_status = native.torch_ops().bss_eval_sources(d_ref, d_est, counts, 21, False)
+    assert tuple(sdr.shape) == (2, 6) and status.cpu().tolist() == [0, 0, 0, 0]
+    assert sdr.cpu().numpy().tobytes() == full.cpu().numpy().tobytes()
+    assert status.cpu().numpy().tobytes() == full_status.cpu().numpy().tobytes()
+
+
 def _degenerate():
     refs, ests = sc.cases.make_batch(16, [2, 3, 1, 2], 600)
     refs, ests = [r.copy() for r in refs], [e.copy() for e in ests]
@@ -243,22 +258,6 @@ def test_compute_metrics_device_against_host():
     _check("compute_metrics", np.stack([np.stack([dev[0], dev[1]]), np.stack(dev[4][:2]), np.stack(dev[4][2:])]),
            np.stack([np.stack([host[0], host[1]]), np.stack(host[4][:2]), np.stack(host[4][2:])]))
     assert dev[2] == host[2] and dev[3] == host[3]
-
-
-class _Once:
-    """A JointModel whose forward pass runs once: the two records below differ in the metric only."""
-
-    def __init__(self, jm):
-        self.jm, self.out = jm, None
-
-    def setup(self, **kw):
-        if self.out is None:
-            self.jm.setup(**kw)
-
-    def __call__(self, mix):
-        if self.out is None:
-            self.out = self.jm(mix)
-        return self.out
 
 
 def test_record_device_against_host():
