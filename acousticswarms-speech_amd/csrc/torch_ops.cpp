@@ -797,6 +797,43 @@ std::tuple<Tensor, Tensor> cross_sisdr(const Tensor& est, const Tensor& ref, at:
   return {out, status};
 }
 
+// ---- a recording as overlapping blocks (longform.py) ------------------------------------------------------------------
+// -> [K, M, T]: block k is mix[:, starts[k] : starts[k] + T], zero past the end of the recording
+Tensor frame_blocks(const Tensor& mix, at::IntArrayRef starts, int64_t T) {
+  need(mix, "mix", at::kFloat, 2);
+  const int M = checked_int(mix.size(0), "M"), Ttot = checked_int(mix.size(1), "Ttot"), t = checked_int(T, "T");
+  const int K = checked_int(static_cast<int64_t>(starts.size()), "K");
+  TORCH_CHECK(t >= 1, "frame_blocks: T=", T);
+  const Counts a = checked_counts(starts, "starts");
+  Tensor out = at::empty({K, M, t}, mix.options());
+  if (K == 0 || M == 0) return out;
+  Launch l(mix);
+  check_status(asw_frame_blocks(mix.data_ptr<float>(), M, Ttot, a.v.data(), K, t, out.data_ptr<float>(), l.stream),
+               "asw_frame_blocks");
+  return out;
+}
+
+// -> [S, Ttot]: the normalised overlap-add of the rows; row_of is the [K, S] table, row-major (S = len(row_of) / K)
+Tensor stitch_blocks(const Tensor& rows, const Tensor& taper, at::IntArrayRef starts, at::IntArrayRef row_of, int64_t Ttot) {
+  need(rows, "rows", at::kFloat, 2);
+  need(taper, "taper", at::kDouble, 1);
+  same_device(rows, taper, "rows and taper");
+  const int N = checked_int(rows.size(0), "N"), T = checked_int(rows.size(1), "T"), tt = checked_int(Ttot, "Ttot");
+  const int K = checked_int(static_cast<int64_t>(starts.size()), "K");
+  TORCH_CHECK(taper.size(0) == T, "taper must be [T] = [", T, "], got [", taper.size(0), "]");
+  TORCH_CHECK(K >= 1 && row_of.size() % K == 0, "row_of must hold K x S entries: ", row_of.size(), " for K = ", K);
+  TORCH_CHECK(tt >= 0, "stitch_blocks: Ttot=", Ttot);
+  const int S = checked_int(static_cast<int64_t>(row_of.size()) / K, "S");
+  const Counts a = checked_counts(starts, "starts"), r = checked_counts(row_of, "row_of");
+  Tensor out = at::empty({S, tt}, rows.options());
+  if (S == 0 || tt == 0) return out;
+  Launch l(rows);
+  check_status(asw_stitch_blocks(rows.data_ptr<float>(), N, taper.data_ptr<double>(), a.v.data(), r.v.data(), K, S, T, tt,
+                                 out.data_ptr<float>(), l.stream),
+               "asw_stitch_blocks");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(asw, m) {
@@ -842,6 +879,8 @@ TORCH_LIBRARY(asw, m) {
   m.def("sep_infer_batch(int model, Tensor mix, Tensor offsets, int[] counts) -> Tensor");
   m.def("sep_forward(int model, Tensor mix, int n_speakers, int n_mics, int max_speakers) -> Tensor");
   m.def("sep_forward_counts(int model, Tensor mix, int[] counts, int n_mics, int max_speakers) -> Tensor");
+  m.def("frame_blocks(Tensor mix, int[] starts, int T) -> Tensor");
+  m.def("stitch_blocks(Tensor rows, Tensor taper, int[] starts, int[] row_of, int Ttot) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(asw, CUDA, m) {
@@ -875,4 +914,6 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("sep_infer_batch", &sep_infer_batch);
   m.impl("sep_forward", &sep_forward);
   m.impl("sep_forward_counts", &sep_forward_counts);
+  m.impl("frame_blocks", &frame_blocks);
+  m.impl("stitch_blocks", &stitch_blocks);
 }

@@ -16,6 +16,7 @@ import time
 
 import numpy as np
 
+from .longform import LINK_RADIUS
 from .mic_array import MicArray, run_search
 from .modes import MODE_NAMES, check_modes
 
@@ -257,6 +258,75 @@ class JointModel(object):
         if self.sep_model is None:
             raise RuntimeError("separate_batch needs a separation model (sep_model=None)")
         return self.sep_model.infer_batch(mixes, [[p[0].sample_offset for p in patches] for patches in patch_lists])
+
+    def forward_long(self, mix_data, block=48000, hop=None, localize="every", link_radius=LINK_RADIUS):
+        """Localise and separate a recording of any length on the array of ``setup()``: mix_data [M, Ttot] is cut into
+        blocks of ``block`` samples every ``hop`` (default block - block // 8; ``longform.block_starts``), the blocks
+        are searched, every block separates its talkers, and the tracks are joined by the normalised overlap-add of
+        ``longform.stitch_f64`` on the device (``SepModel.separate_blocks``: one upload, one read-back).
+
+        ``localize="every"``: every block is searched (``shard.localize_batch``, the blocks sharing their network
+        launches), the detections are linked into tracks by position (``longform.link_tracks``, ``link_radius`` metres),
+        and a block separates the talkers found in it, at the sample offsets
+        ``forward`` would separate them at; a track fades out over the seam into a block it was not found in.
+        ``localize="first"``: block 0 alone is searched and its talkers are separated in every block.
+
+        -> dict: ``audio`` float32 [n_tracks, Ttot]; ``present`` bool [n_tracks, K]; ``detection`` int64 [n_tracks, K],
+        the talker of block k that is the track (its row in that block's search result; -1 when absent);
+        ``positions``: {"per_block": float64 [n_tracks, K, 3], the centre in every block the track is present in (NaN
+        elsewhere; with "first", block 0's centre throughout), "mean": [n_tracks, 3]}; ``starts`` int64 [K]; ``blocks``:
+        the search results, one dict per searched block as ``localize_batch(..., details=True)`` returns them.
+
+        Needs a HIP separation model and a single rank (``RuntimeError`` otherwise, as ``separate=True``)."""
+        import torch
+        from . import longform
+        from .batching import result_record
+        from .sep import rounded_offsets
+        if localize not in ("every", "first"):
+            raise ValueError(f'localize must be "every" or "first", got {localize!r}')
+        if self.sep_model is None or not hasattr(self.sep_model, "separate_blocks"):
+            raise RuntimeError("forward_long needs a separation model (JointModel(sep_model=None))")
+        import torch.distributed as dist
+        if (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1) \
+                or getattr(self.spot_model, "world", 1) > 1:
+            raise RuntimeError("forward_long runs on one rank only: the audio is not gathered across ranks")
+        assert self.previous_config is not None, \
+            "Microphone positions and spk range were not provided, did you forget to call .setup()?"
+        mix = torch.as_tensor(mix_data).to(dtype=torch.float32)
+        if mix.dim() != 2:
+            raise ValueError("the recording must be [M, Ttot]")
+        (M, Ttot), T = (int(v) for v in mix.shape), int(block)
+        hop = T - T // 8 if hop is None else int(hop)
+        starts = longform.block_starts(Ttot, T, hop)
+        K = len(starts)
+        host = mix.cpu().numpy()
+        if localize == "first":
+            first = torch.from_numpy(longform.frame_f64(host, starts[:1], T, np.float32)[0])
+            self.times = [0, 0, 0, 0, 0]
+            patches, _audio_loc, _d0, _d1, spot_times = self.localize_by_separation(first)
+            self._mix_dev = self._mix_src = None
+            results = [result_record(patches, spot_times, list(self.times), True, (M, T))]
+            n = len(patches)
+            offsets = [rounded_offsets(list(results[0]["offsets"]), M - 1)] * K
+            det_of = np.tile(np.arange(n, dtype=np.int64), (K, 1))
+            per_block = np.repeat(results[0]["centres"].reshape(n, 1, 3), K, axis=1)
+        else:
+            from .shard import localize_batch
+            frames = longform.frame_f64(host, starts, T, np.float32)
+            results = localize_batch(self, [torch.from_numpy(f) for f in frames], details=True)
+            offsets = [rounded_offsets(list(r["offsets"]), M - 1) for r in results]
+            det_of, per_block = longform.link_tracks([r["centres"] for r in results], float(link_radius))
+        n_tracks = det_of.shape[1]
+        if n_tracks == 0:
+            audio = np.empty((0, Ttot), dtype=np.float32)
+        else:
+            from . import native
+            sep = self.sep_model
+            audio = native.to_host(sep.separate_blocks(mix.to(sep.device).contiguous(), starts, T, T - hop, offsets,
+                                                       longform.rows_of(det_of, [o.shape[0] for o in offsets])))
+        return {"audio": audio, "present": (det_of >= 0).T, "detection": det_of.T.copy(),
+                "positions": {"per_block": per_block, "mean": np.nanmean(per_block, axis=1).reshape(n_tracks, 3)},
+                "starts": starts, "blocks": results}
 
     def to(self, device=None):
         if device is not None:

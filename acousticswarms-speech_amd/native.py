@@ -18,7 +18,8 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["asw_common.cpp", "convgemm.hip", "resconv.hip", "pipegemm.hip", "resstack.hip", "downconv.hip", "prep_kernels.hip",
            "misc_kernels.hip", "attention.hip", "srp_kernels.hip",
            "pruner_kernels.hip", "geometry_kernels.hip", "cluster_kernels.hip",
-           "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip", "bss_kernels.hip", "eval_kernels.hip"]
+           "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip", "bss_kernels.hip", "eval_kernels.hip",
+           "longform_kernels.hip"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
 # (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out; eval_kernels.hip
 # rounds a * ref before it subtracts, as hostdsp.si_sdr does)
@@ -305,6 +306,9 @@ SIGNATURES = {
                                  c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
     "asw_lattice_nms_workspace_bytes": (c_int64, [c_int, c_int]),
     "asw_lattice_nms": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "asw_frame_blocks": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "asw_stitch_blocks": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_void_p]),
 }
 
 _lib = None

@@ -466,6 +466,38 @@ def inter_attention_groups(qkv, counts, nhead, out=None):
     return ctx
 
 
+def _host_i32(values):
+    import ctypes
+    flat = [int(v) for v in values]
+    return (ctypes.c_int32 * max(1, len(flat)))(*flat)
+
+
+def frame_blocks(mix, starts, T, out=None):
+    """mix [M,Ttot] -> the blocks [K,M,T] that start at ``starts`` (host integers), zero past the end
+    (``longform.frame_f64``).  ``out``: write into this tensor (tests)."""
+    M, Ttot = mix.shape
+    K = len(starts)
+    blocks = torch.empty((K, M, int(T)), dtype=torch.float32, device=mix.device) if out is None else out
+    assert blocks.shape == (K, M, int(T))
+    check(lib().asw_frame_blocks(ptr(_f32(mix)), M, Ttot, _host_i32(starts), K, int(T), ptr(_f32(blocks)), current_stream()))
+    return blocks
+
+
+def stitch_blocks(rows, taper, starts, row_of, Ttot, out=None):
+    """The normalised overlap-add of ``longform.stitch_f64``: rows [N,T] float32, taper [T] float64 (device), starts [K] and
+    row_of [K][S] host integers -> [S,Ttot] float32.  ``out``: write into this tensor (tests)."""
+    N, T = rows.shape
+    K = len(starts)
+    S = len(row_of[0])
+    assert len(row_of) == K and all(len(r) == S for r in row_of)
+    assert taper.is_cuda and taper.dtype == torch.float64 and taper.is_contiguous() and taper.shape == (T,)
+    res = torch.empty((S, int(Ttot)), dtype=torch.float32, device=rows.device) if out is None else out
+    assert res.shape == (S, int(Ttot))
+    check(lib().asw_stitch_blocks(ptr(_f32(rows)), N, ptr(taper), _host_i32(starts), _host_i32(v for r in row_of for v in r), K, S,
+                                  T, int(Ttot), ptr(_f32(res)), current_stream()))
+    return res
+
+
 def f16x3_overflow_count(reset=True) -> int:
     """Threads of f16x3 launches that produced an activation beyond the fp16 range since the last
     reset (asw_f16x3_overflow_count); 0 means no later GEMM clipped its input."""

@@ -136,6 +136,53 @@ class SepModel(DeviceModel):
                 pos += c
         return out
 
+    # ---- a recording of any length (longform.py) ----------------
+    def separate_blocks(self, mix_dev, starts, T, V, offsets, row_of):
+        """The blocks of a resident recording separated and stitched where they are: mix_dev [M,Ttot] float32 cuda,
+        ``starts`` [K] (``longform.block_starts``), ``offsets``: K rounded int32 arrays [n_k, M-1], the talkers of every
+        block, ``row_of`` [K, S] the row of track s among the rows of all blocks, block after block (-1: absent)
+        -> [S, Ttot] float32 cuda.  Per range of ``pack_items`` one ``frame_blocks`` and one ``infer_batch_device``, so at
+        most MAX_SEQUENCES blocks are framed at a time; then one ``stitch_blocks`` with the taper of overlap V."""
+        import torch
+        from . import longform
+        ops = native.torch_ops()
+        counts = [int(o.shape[0]) for o in offsets]
+        starts = [int(a) for a in starts]
+        parts = []
+        for first, last in pack_items(counts):
+            if sum(counts[first:last]) == 0:
+                continue
+            blocks = ops.frame_blocks(mix_dev, starts[first:last], int(T))
+            parts.append(self.infer_batch_device(
+                blocks, native.to_device(np.concatenate(offsets[first:last], axis=0), mix_dev.device), counts[first:last]))
+        rows = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return ops.stitch_blocks(rows, native.to_device(longform.taper(T, V), mix_dev.device), starts,
+                                 [int(r) for r in np.asarray(row_of).reshape(-1)], int(mix_dev.shape[1]))
+
+    def infer_long(self, input_channels, sample_list, hop=None, block=48000) -> np.ndarray:
+        """``infer_sample`` on a recording of any length: input_channels (M x Ttot), sample_list (S x (M-1)), the same
+        talkers in every block -> ndarray [S, Ttot] float32.  The recording is cut into blocks of ``block`` samples every
+        ``hop`` (default block - block // 8; ``longform.block_starts``, ``ValueError`` for an overlap outside
+        1 .. block // 2), each block is separated like a clip of its own, and the blocks are joined by the normalised
+        overlap-add of ``longform.stitch_f64``.  One upload of the mixture, one read-back of the result; framing,
+        networks and stitching stay on the device (``separate_blocks``)."""
+        import torch
+        from . import longform
+        mix = torch.as_tensor(input_channels)
+        if mix.dim() != 2:
+            raise ValueError("the recording must be [M, Ttot]")
+        Ttot, T = int(mix.shape[1]), int(block)
+        hop = T - T // 8 if hop is None else int(hop)
+        starts = longform.block_starts(Ttot, T, hop)
+        offs = rounded_offsets(sample_list, mix.shape[0] - 1)
+        K, S = len(starts), offs.shape[0]
+        pack_items([S] * K)                                   # more talkers than one call takes raise before the upload
+        if S == 0:
+            return np.empty((0, Ttot), dtype=np.float32)
+        self._need()
+        mix_d = mix.to(self.device, dtype=torch.float32).contiguous()
+        return native.to_host(self.separate_blocks(mix_d, starts, T, T - hop, [offs] * K, np.arange(K * S).reshape(K, S)))
+
     # ---- reference call surface ---------------------------------------------------
     def infer(self, input_channels, patch_list) -> np.ndarray:
         """:492-494."""

@@ -999,6 +999,28 @@ int64_t asw_lattice_nms_workspace_bytes(int N, int P);
 int asw_lattice_nms(const int32_t* cells, int N, int P, const double* scores, int radius, void* workspace,
                     int64_t workspace_bytes, int32_t* best, int32_t* degree, void* stream);
 
+/* ---- a recording of any length as overlapping blocks (longform.py) --------------------------
+ * starts and row_of are HOST tables, read before the call returns; every other pointer is device memory.  Both calls
+ * launch on `stream` and synchronise nothing; every refusal (null pointer, a shape outside M <= 65535 and
+ * T, Ttot <= 2^30, a table entry out of range) happens before the first launch.
+ *
+ * asw_frame_blocks: out[k][m][j] = mix[m][starts[k] + j] for j < T, 0 where starts[k] + j >= Ttot (longform.frame_f64).
+ * mix [M][Ttot], out [K][M][T]; 0 <= starts[k] < Ttot, in any order.
+ *
+ * asw_stitch_blocks: the normalised overlap-add of longform.stitch_f64,
+ *   out[s][t] = sum_k taper[t - starts[k]] x_k[s][t - starts[k]] / sum_k taper[t - starts[k]]
+ * over the blocks k with starts[k] <= t < starts[k] + T, in ascending k, accumulated in float64 and rounded once to
+ * float32.  rows [N][T] float32; x_k[s] is row row_of[k*S + s] of it, zeros when that entry is -1 (the track is absent
+ * from the block: its weight still counts in the denominator).  taper float64 [T], strictly positive (longform.taper;
+ * not checked: a zero denominator gives a non-finite sample, never an access out of bounds).  out [S][Ttot]; each
+ * sample is written once, by one thread, without atomics.  starts: starts[0] = 0, ascending, at most T apart (no gap)
+ * and starts[K-1] + T >= Ttot; row_of entries in -1 .. N-1.  The tables travel as kernel arguments; tables beyond one
+ * launch's share are cut into launches that each own a range of the output (a run of blocks and of tracks), for any S
+ * and K; only starts of which more than 15 blocks cover one sample are refused. */
+int asw_frame_blocks(const float* mix, int M, int Ttot, const int32_t* starts, int K, int T, float* out, void* stream);
+int asw_stitch_blocks(const float* rows, int N, const double* taper, const int32_t* starts, const int32_t* row_of, int K,
+                      int S, int T, int Ttot, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
