@@ -224,6 +224,29 @@ inline int up_feed_tiles(const std::vector<ResLayer>& res, int K, int T, bool gl
   return asw_resstack_tiles(T, K, (int)n, dil, glu && j0 == 0);
 }
 
+// ---- the parts of a residual-stack launch description (asw_resstack_args), one helper per part
+inline void bind_layer(asw_reslayer_desc& d, const ResLayer& r) {
+  d.Wf_hi = r.wt.fhi; d.Wf_lo = r.wt.flo; d.w_shift = r.wt.shift;
+  d.bias = r.bias.p; d.ln_gamma = r.g.p; d.ln_beta = r.b.p; d.dil = r.dil;
+}
+// GroupNorm + GLU on load: the same five fields in asw_resstack_args and asw_convgemm_args
+template <typename Args>
+inline void bind_glu(Args& a, const GluSrc& g) {
+  a.glu_raw = g.raw; a.glu_mr = g.mr; a.glu_gamma = g.gamma; a.glu_beta = g.beta; a.glu_out = g.side_out;
+}
+// the source-fed form: no x, the composed weight in layer 0's place
+inline void bind_src_feed(asw_resstack_args& a, const SrcFeed& f) {
+  a.src_hi = f.hi; a.src_lo = f.lo;
+  a.layer[0].Wf_hi = f.comp->fhi; a.layer[0].Wf_lo = f.comp->flo; a.layer[0].w_shift = f.comp->shift;
+  a.pre_hi = f.pre->fhi; a.pre_lo = f.pre->flo; a.pre_shift = f.pre->shift;
+}
+// UpFeed: the rows go to the next block's transposed convolution; the stack's output is not written
+inline void bind_up_feed(asw_resstack_args& a, const UpFeed& u) {
+  a.out = nullptr;
+  a.up_hi = u.w->fhi; a.up_lo = u.w->flo; a.up_shift = u.w->shift; a.up_bias = u.bias; a.up_skip = u.skip;
+  a.up_out = u.out; a.up_stats = u.stats;
+}
+
 inline int run_res(const std::vector<ResLayer>& res, int prec, int B, int T, int ch, int K, float* x, float* p, float* q,
             float** final_out, hipStream_t s, const GluSrc* glu = nullptr, const SrcFeed* feed = nullptr, UpFeed* up = nullptr) {
   // ping-pong: layer 0 reads x (kept intact), later layers alternate p/q
@@ -241,24 +264,12 @@ inline int run_res(const std::vector<ResLayer>& res, int prec, int B, int T, int
       a.x = ((glu || feed) && j == 0) ? nullptr : in;
       a.out = outb;
       a.B = B; a.T = T; a.C = ch; a.taps = K; a.n_layers = (int)n; a.precision = prec; a.ln_eps = 1e-5f;
-      for (size_t i = 0; i < n; ++i) {
-        const ResLayer& r = res[j + i];
-        a.layer[i].Wf_hi = r.wt.fhi; a.layer[i].Wf_lo = r.wt.flo; a.layer[i].w_shift = r.wt.shift;
-        a.layer[i].bias = r.bias.p; a.layer[i].ln_gamma = r.g.p; a.layer[i].ln_beta = r.b.p; a.layer[i].dil = r.dil;
-      }
-      if (glu && j == 0) {
-        a.glu_raw = glu->raw; a.glu_mr = glu->mr; a.glu_gamma = glu->gamma; a.glu_beta = glu->beta; a.glu_out = glu->side_out;
-      }
-      if (feed && j == 0) {
-        a.src_hi = feed->hi; a.src_lo = feed->lo;
-        a.layer[0].Wf_hi = feed->comp->fhi; a.layer[0].Wf_lo = feed->comp->flo; a.layer[0].w_shift = feed->comp->shift;
-        a.pre_hi = feed->pre->fhi; a.pre_lo = feed->pre->flo; a.pre_shift = feed->pre->shift;
-      }
+      for (size_t i = 0; i < n; ++i) bind_layer(a.layer[i], res[j + i]);
+      if (glu && j == 0) bind_glu(a, *glu);
+      if (feed && j == 0) bind_src_feed(a, *feed);
       if (up && j + n == res.size()) {
-        // the last launch hands its rows to the next block's transposed convolution; the stack's output is not written
-        a.out = nullptr;
-        a.up_hi = up->w->fhi; a.up_lo = up->w->flo; a.up_shift = up->w->shift; a.up_bias = up->bias; a.up_skip = up->skip;
-        a.up_out = up->out; a.up_stats = up->stats;
+        // the last launch hands its rows to the next block's transposed convolution
+        bind_up_feed(a, *up);
         up->tiles = up_feed_tiles(res, K, T, glu != nullptr);
         if (up->tiles < 0) return up->tiles;
         outb = nullptr;
@@ -275,9 +286,7 @@ inline int run_res(const std::vector<ResLayer>& res, int prec, int B, int T, int
   for (size_t j = 0; j < res.size(); ++j) {
     asw_convgemm_args a = {};
     a.A = in; res[j].wt.bind(a, prec); a.bias = res[j].bias.p; a.resid = in;
-    if (glu && j == 0) {
-      a.glu_raw = glu->raw; a.glu_mr = glu->mr; a.glu_gamma = glu->gamma; a.glu_beta = glu->beta; a.glu_out = glu->side_out;
-    }
+    if (glu && j == 0) bind_glu(a, *glu);
     a.ln_gamma = res[j].g.p; a.ln_beta = res[j].b.p; a.out = outb;
     a.B = B; a.M_out = T; a.N = ch; a.Cin = ch; a.taps = K; a.stride = 1; a.dil = res[j].dil;
     a.pad = (res[j].dil * (K - 1) + 1) / 2;

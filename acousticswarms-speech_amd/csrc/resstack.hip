@@ -39,6 +39,11 @@ using namespace asw_mfma;
 
 constexpr int C = 64;
 constexpr int MAXL = 3;
+// The one tile shape: NW waves, each owning TM 32-row fragments x all 64 channels (two waves per SIMD), weights
+// prefetched QD k-steps ahead.
+constexpr int NW = 4, TM = 2, QD = 4;
+constexpr int NTHR = 64 * NW, SROWS = NTHR / 16;
+constexpr int R0 = 32 * NW * TM;         // rows layer 0 computes
 
 struct LayerDev {
   const half8* Wh;
@@ -51,16 +56,6 @@ struct LayerDev {
   int nfrag;                             // 32-row fragments this layer computes
   float scale;                           // 2^-w_shift
 };
-
-#ifdef ASW_PHASE_TIMING
-// Diagnostic build only (tests/micro/resstack_phases.py): cycles wave 0 of every workgroup spends per phase, summed
-// over workgroups: [0] staging, [1] layer-0 k-loop, [2] layer-0 epilogue + hand-over, [3] layer-1 k-loop,
-// [4] layer-1 epilogue + stores, [5] workgroups.
-__device__ unsigned long long g_rs_cycles[6] = {0, 0, 0, 0, 0, 0};
-#define RS_MARK(var) const unsigned long long var = __builtin_readcyclecounter()
-#else
-#define RS_MARK(var)
-#endif
 
 struct KArgs {
   const float* x;
@@ -93,6 +88,41 @@ struct UpArgs {
 };
 struct KArgsUp : KArgs { UpArgs u; };    // the kernel argument of the UpFeed instantiations
 
+// Diagnostic build only (-DASW_PHASE_TIMING, tests/micro/resstack_phases.py): cycles wave 0 of every workgroup spends
+// per phase, summed over workgroups: [0] staging, [1] layer-0 k-loop, [2] layer-0 epilogue + hand-over, [3] layer-1
+// k-loop, [4] layer-1 epilogue + stores, [5] workgroups.  Stamps: 0 start, 1 staged, 2 + 2 li after layer li's
+// k-loop, 3 + 2 li after layer li.
+#ifdef ASW_PHASE_TIMING
+__device__ unsigned long long g_rs_cycles[6] = {0, 0, 0, 0, 0, 0};
+struct PhaseClock {
+  unsigned long long t[2 * MAXL + 2];
+  __device__ __forceinline__ void mark(int i) { t[i] = __builtin_readcyclecounter(); }
+  __device__ __forceinline__ void mark_after(int i, float sink) {
+    asm volatile("" ::"v"(sink));                           // the stamp waits for the MFMAs
+    mark(i);
+  }
+  template <int NL>
+  __device__ __forceinline__ void report() const {
+    if (threadIdx.x != 0 || NL > 2) return;
+    atomicAdd(&g_rs_cycles[0], t[1] - t[0]);
+    atomicAdd(&g_rs_cycles[1], t[2] - t[1]);
+    if (NL == 2) {
+      atomicAdd(&g_rs_cycles[2], t[3] - t[2]);
+      atomicAdd(&g_rs_cycles[3], t[4] - t[3]);
+    }
+    atomicAdd(&g_rs_cycles[4], t[2 * NL + 1] - t[2 * NL]);
+    atomicAdd(&g_rs_cycles[5], 1ull);
+  }
+};
+#else
+struct PhaseClock {
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void mark_after(int, float) {}
+  template <int NL>
+  __device__ __forceinline__ void report() const {}
+};
+#endif
+
 // One 16-byte row of a source plane through its buffer descriptor: rows outside [0, T) read as zeros.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t src_rsrc(const half8* base, long rows) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<half8*>(base), 0, (int)(rows * 16), 0x00020000);
@@ -101,6 +131,466 @@ __device__ __forceinline__ half8 src_load(__amdgpu_buffer_rsrc_t r, int row) {
   return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(r, row >= 0 ? row * 16 : (int)0x80000000, 0, 0));
 }
 
+// ------------------------------------------------------------------ the row map
+// The three kinds of row of a workgroup's tile, contiguous or polyphase (POLY: PH phases of R0 / PH rows of j each,
+// a fragment inside one phase), and every conversion between them:
+//   image row     a row of the LDS image (layer 0's input, later each layer's output in its place)
+//   fragment row  row (wave * TM + i) * 32 + (lane & 31) of the R0 rows a layer computes
+//   sequence row  a row t of the [T][64] tensors in memory
+template <bool POLY, int PH>
+struct RowMap {
+  static constexpr int BMJ = R0 / PH;                   // polyphase: rows of j per phase
+  static_assert(BMJ % 32 == 0, "a row fragment must stay inside one phase");
+  int T, taps, dil0, pad0, jb, pb, m0, BM, n_img, halo0;
+
+  __device__ __forceinline__ RowMap(int tile, const KArgs& p) : T(p.T), taps(p.taps), dil0(p.L[0].dil), pad0(p.L[0].pad) {
+    const int n_pb = POLY ? (dil0 + PH - 1) / PH : 1;
+    jb = POLY ? tile / n_pb : 0;
+    pb = POLY ? tile - jb * n_pb : 0;
+    m0 = tile * p.BM;
+    BM = p.BM;
+    n_img = POLY ? PH * rj() : R0 + 2 * pad0;
+    halo0 = p.L[0].halo;
+  }
+  __device__ __forceinline__ int rj() const { return BMJ + taps - 1; }          // polyphase: image rows per phase
+
+  // ---- image row -> the sequence row it is staged from, and whether that row exists
+  __device__ __forceinline__ ImgSrc staged_from(int irow) const {
+    int g;
+    bool ok = irow < n_img;
+    if (!POLY) {
+      g = m0 - halo0 - pad0 + irow;
+    } else {
+      const int ph = pb * PH + irow / rj();
+      const int jj = jb * BMJ + irow % rj() - (taps - 1) / 2;
+      g = dil0 * jj + ph;
+      ok = ok && ph < dil0 && jj >= 0;
+    }
+    return {g, ok && g >= 0 && g < T};
+  }
+  // (GLU on load) is sequence row g one of the rows this tile delivers
+  __device__ __forceinline__ bool delivers(int g) const { return g >= m0 && g < m0 + BM; }
+
+  // ---- fragment row -> image row at tap 0; image rows between two taps; from tap 0 to the centre tap (the residual)
+  __device__ __forceinline__ int image_row(int frow) const { return POLY ? (frow / BMJ) * rj() + frow % BMJ : frow; }
+  __device__ __forceinline__ int tap_rows(const LayerDev& Ld) const { return POLY ? 1 : Ld.dil; }
+  __device__ __forceinline__ int centre_rows(const LayerDev& Ld, bool first) const { return POLY ? (taps - 1) / 2 : first ? pad0 : Ld.pad; }
+
+  // ---- fragment row -> sequence row
+  // a layer with `halo` rows still to come after it (contiguous tiles only): is the row inside the sequence
+  __device__ __forceinline__ bool handed_on(int frow, int halo) const {
+    const int t = m0 - halo + frow;
+    return t >= 0 && t < T;
+  }
+  // the last layer (`ok`: a row this tile delivers)
+  __device__ __forceinline__ int phase(int frow) const { return pb * PH + frow / BMJ; }
+  __device__ __forceinline__ int seq_row(int frow) const { return POLY ? dil0 * (jb * BMJ + frow % BMJ) + phase(frow) : m0 + frow; }
+  __device__ __forceinline__ ImgSrc delivered(int frow) const {
+    const int t = seq_row(frow);
+    return {t, (POLY ? phase(frow) < dil0 : frow < BM) && t < T};
+  }
+  // sequence rows between two rows of a fragment; the delivered rows of the fragment that starts at fragment row f0
+  // are a prefix of it: their number, not yet clamped to [0, 32]
+  __device__ __forceinline__ int row_step() const { return POLY ? dil0 : 1; }
+  __device__ __forceinline__ int run_rows(int f0) const {
+    if (!POLY) return min(BM, T - m0) - f0;
+    const int t0 = seq_row(f0);
+    return (phase(f0) < dil0 && t0 < T) ? (T - 1 - t0) / dil0 + 1 : 0;
+  }
+};
+
+// this lane's row of its wave's fragment i, as a fragment row
+__device__ __forceinline__ int frag_row(int wid, int i, int lane) { return (wid * TM + i) * 32 + (lane & 31); }
+
+// This wave's fragments that exist in a layer, f(i) for i < nf.  Written out, not a loop over i: each phase is
+// optimised on its own before it is inlined, its channel walks unrolled by then, and from a loop the per-channel table
+// and image addresses of all fragments were hoisted in front of the first one (+8 VGPRs, the single-pass kernels' fourth
+// wave per SIMD).
+template <typename F>
+__device__ __forceinline__ void for_each_fragment(int nf, const F& f) {
+  static_assert(TM == 2, "one line per fragment");
+  if (0 < nf) f(0);
+  if (1 < nf) f(1);
+}
+
+// ------------------------------------------------------------------ the channel walk
+// A lane (half h = lane >> 5) holds sixteen groups of four consecutive channels of its row: group q of the 32-channel
+// block cb is registers 4 q .. 4 q + 3 of acc[cb] and channels c0 .. c0 + 3.  f(cb, q, c0), in register order.
+template <typename F>
+__device__ __forceinline__ void for_each_group(int h, const F& f) {
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) f(cb, q, cb * 32 + q * 8 + h * 4);
+}
+__device__ __forceinline__ float4 group4(const floatx16& a, int q) { return make_float4(a[q * 4 + 0], a[q * 4 + 1], a[q * 4 + 2], a[q * 4 + 3]); }
+
+// ------------------------------------------------------------------ the phases
+// per-layer vectors -> LDS: tab[NL][bias | gamma | beta][64]
+template <int NL>
+__device__ __forceinline__ void load_layer_vectors(const KArgs& p, float* tab, int tid) {
+  for (int i = tid; i < NL * 3 * 16; i += NTHR) {
+    const int li = i / 48, w = (i - li * 48) / 16, c4 = i & 15;
+    const float* src = w == 0 ? p.L[li].bias : w == 1 ? p.L[li].gamma : p.L[li].beta;
+    reinterpret_cast<float4*>(tab)[i] = *reinterpret_cast<const float4*>(src + c4 * 4);
+  }
+}
+
+// stage + split the input rows of layer 0 (16 threads per row, 8 rows per thread in flight)
+template <bool GLU, int NTERM, typename Map>
+__device__ __forceinline__ void stage_rows(const KArgs& p, const Map& map, int b, char* img, int tid) {
+  const int T = map.T;
+  const __amdgpu_buffer_rsrc_t rX = GLU ? act_rsrc(p.glu_raw + (long)b * T * 2 * C, (long)T * 2 * C)
+                                        : act_rsrc(p.x + (long)b * T * C, (long)T * C);
+  const int srow = tid >> 4, sc4 = tid & 15;
+  const int R_img = map.n_img;
+  GluCoef gc;
+  if (GLU) {
+    gc.stats(p.glu_mr, b);
+    gc.affine(p.glu_gamma, p.glu_beta, C, sc4 * 4);
+  }
+  // (This loop stays here instead of calling stage_image of f16x3_tile.h, which resconv16 and downconv64 use: through
+  // the shared routine the GLU variant of the fused pair measured 0.7 % slower, 11.11 -> 11.21 ms per bench step.)
+  // the whole image is requested before the first row is converted: one exposed memory latency per tile (with 8
+  // rows per thread in flight the three rounds of a 262-row image took 17 % of a workgroup's time)
+  constexpr int SU = GLU ? 9 : 18;
+  for (int r0 = 0; r0 < R_img; r0 += SROWS * SU) {
+    float4 buf[SU];
+    float4 gate[GLU ? SU : 1];
+    bool okr[GLU ? SU : 1];
+#pragma unroll
+    for (int u = 0; u < SU; ++u) {
+      const ImgSrc f = map.staged_from(r0 + u * SROWS + srow);
+      if (GLU) {
+        buf[u] = act_load4(rX, (long)f.g * 2 * C + sc4 * 4, f.ok);
+        gate[u] = act_load4(rX, (long)f.g * 2 * C + C + sc4 * 4, f.ok);
+        okr[u] = f.ok;
+        // (each row's two loads go out as soon as their address is there: left alone, the scheduler computed all nine
+        // addresses first and the GLU pair measured 0.65 % slower, 10.92 -> 10.99 ms per bench step)
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+        buf[u] = act_load4(rX, (long)f.g * C + sc4 * 4, f.ok);
+      }
+    }
+    if (GLU) {
+#pragma unroll
+      for (int u = 0; u < SU; ++u) {
+        const float4 o = gn_glu4(buf[u], gate[u], gc, okr[u]);
+        buf[u] = o;
+        // the normalised tensor is also a skip connection: each tile writes the rows of its own output range once
+        if (p.glu_out && okr[u]) {
+          const int g = map.staged_from(r0 + u * SROWS + srow).g;
+          if (map.delivers(g)) *reinterpret_cast<float4*>(p.glu_out + ((long)b * T + g) * C + sc4 * 4) = o;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < SU; ++u) {
+      const int row = r0 + u * SROWS + srow;
+      if (row < R_img) {
+        half4 hi, lo;
+        split4t<NTERM>(buf[u], hi, lo);
+        *reinterpret_cast<half4*>(img + row * RS + IMG_HI + sc4 * 8) = hi;
+        *reinterpret_cast<half4*>(img + row * RS + IMG_LO + sc4 * 8) = lo;      // (the residual reads it in every mode)
+      }
+    }
+  }
+}
+
+// SRC: layer 0 on the source planes, up to and including its residual; also brings the per-layer vectors to LDS.
+// (Every wave owns TM whole fragments here: nfrag == NW * TM, checked by the host.)
+// Lane (row r, half h) holds, for k-step ks, the 8 source channels of row r + tap, tap = 2 ks + h: one 16-byte
+// load per plane.  Tap 7 does not exist -- its weights are zero -- but its rows are read and are finite (data or
+// the descriptor's zeros).  Everything is requested before the first MFMA: one exposed latency per tile.
+template <int NL, typename Map>
+__device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, int b, float* tab, int tid, floatx16 (&acc)[TM][2]) {
+  const LayerDev& Ld = p.L[0];
+  const int T = map.T, lane = tid & 63, wid = tid >> 6, h = lane >> 5;
+  const __amdgpu_buffer_rsrc_t rH = src_rsrc(p.src_h + (long)b * T, T), rL = src_rsrc(p.src_l + (long)b * T, T);
+  const int g0 = map.staged_from(frag_row(wid, 0, lane)).g;                     // global row of this lane's row at tap 0
+  half8 xh[4][TM], xl[4][TM], rh[TM], rl[TM];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      xh[ks][i] = src_load(rH, g0 + i * 32 + 2 * ks + h);
+      xl[ks][i] = src_load(rL, g0 + i * 32 + 2 * ks + h);
+    }
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {                        // the residual's rows (centre tap); the half h == 1 meets zero weights
+    rh[i] = src_load(rH, g0 + i * 32 + map.centre_rows(Ld, true));
+    rl[i] = src_load(rL, g0 + i * 32 + map.centre_rows(Ld, true));
+  }
+  // weight stream: k-steps 0..3 of the composed weight, then the 1x1 weight as "k-step 4"; two slots
+  half8 wh[2][2], wl[2][2];
+  auto wload = [&](auto kgc, int slot) {
+    constexpr int kg = decltype(kgc)::value;
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      if constexpr (kg < 4) frag_load<3>(Ld.Wh, Ld.Wl, (long)kg * 2 + cb, lane, wh[slot][cb], wl[slot][cb]);
+      else frag_load<3>(p.Pre_h, p.Pre_l, (long)cb, lane, wh[slot][cb], wl[slot][cb]);
+    }
+  };
+  wload(std::integral_constant<int, 0>{}, 0);
+  wload(std::integral_constant<int, 1>{}, 1);
+  load_layer_vectors<NL>(p, tab, tid);                  // (here: after layer 0's operand loads are out, under the same wait)
+  __syncthreads();
+  auto kstep = [&](auto ksc) {
+    constexpr int ks = decltype(ksc)::value;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) mma3<3, true>(acc[i][cb], xh[ks][i], xl[ks][i], wh[ks & 1][cb], wl[ks & 1][cb]);
+    if constexpr (ks + 2 <= 4) wload(std::integral_constant<int, ks + 2>{}, ks & 1);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  kstep(std::integral_constant<int, 0>{});
+  kstep(std::integral_constant<int, 1>{});
+  kstep(std::integral_constant<int, 2>{});
+  kstep(std::integral_constant<int, 3>{});
+  // + bias, ReLU -- brought to the units of the 1x1 weight (both weights carry a power-of-two pre-scale, so the
+  // rescaling is exact) -- then the residual x0 = Wpre~ u~ accumulated on top: no second accumulator set
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    for_each_group(h, [&](int cb, int q, int c0) __attribute__((always_inline)) {
+      const float4 bi = *reinterpret_cast<const float4*>(tab + c0);
+      const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][cb][q * 4 + j] = fmaxf(acc[i][cb][q * 4 + j] * Ld.scale + bv[j], 0.f) * p.pre_up;
+    });
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) mma3<3, true>(acc[i][cb], rh[i], rl[i], wh[0][cb], wl[0][cb]);
+  }
+}
+
+// the convolution of one layer from the image: this wave's first nf (<= TM) fragments, one k-loop instantiation per
+// count (wave-uniform choice; nf <= 0: none)
+template <int NTERM, typename Map>
+__device__ __forceinline__ void conv_layer(const KArgs& p, const LayerDev& Ld, const Map& map, const char* img, int nf, int lane,
+                                           int wid, floatx16 (&acc)[TM][2]) {
+  const int taps = map.taps, h = lane >> 5;
+  const int tapstep = map.tap_rows(Ld) * RS;
+  auto run = [&](auto nfc) {
+    constexpr int NF = decltype(nfc)::value;
+    int xb[NF];
+    floatx16 a[NF][2];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      xb[i] = (map.image_row((wid * TM + i) * 32) + (lane & 31)) * RS + h * 16;
+      a[i][0] = acc[i][0];
+      a[i][1] = acc[i][1];
+    }
+    kloop<NF, 2, QD, NTERM>(
+        a, taps, [&](int tap, int i) __attribute__((always_inline)) { return img + xb[i] + tap * tapstep; }, Ld.Wh, Ld.Wl,
+        [](int kg, int cb) __attribute__((always_inline)) { return (long)kg * 2 + cb; }, lane);
+#pragma unroll
+    for (int i = 0; i < NF; ++i) { acc[i][0] = a[i][0]; acc[i][1] = a[i][1]; }
+  };
+  if (nf >= TM) run(std::integral_constant<int, TM>{});
+  else if (nf == 1) run(std::integral_constant<int, 1>{});
+}
+
+// the epilogue in registers: + bias, ReLU, + residual (the layer's own input, from the image), LayerNorm.
+// IN_ACC (the source-fed layer 0): bias, ReLU and residual are in the accumulators already.
+template <bool IN_ACC, bool FUSED_VAR, typename Map>
+__device__ __forceinline__ void finish_rows(const KArgs& p, const LayerDev& Ld, const Map& map, const char* img, const float* tb,
+                                            bool first, int nf, int lane, int wid, floatx16 (&acc)[TM][2]) {
+  const int h = lane >> 5;
+  const int cpad = map.centre_rows(Ld, first);                 // image row of the residual = tap-0 row + centre tap
+  for_each_fragment(nf, [&](int i) __attribute__((always_inline)) {
+    const char* rrow = img + (map.image_row(frag_row(wid, i, lane)) + cpad) * RS;
+    float s = 0.f;
+    for_each_group(h, [&](int cb, int q, int c0) __attribute__((always_inline)) {
+      const float4 bi = *reinterpret_cast<const float4*>(tb + c0);
+      const half4 rh = *reinterpret_cast<const half4*>(rrow + IMG_HI + c0 * 2);
+      const half4 rl = *reinterpret_cast<const half4*>(rrow + IMG_LO + c0 * 2);
+      const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float v;
+        if constexpr (IN_ACC) {
+          v = acc[i][cb][q * 4 + j] * p.pre_down;
+        } else {
+          v = fmaxf(acc[i][cb][q * 4 + j] * Ld.scale + bv[j], 0.f);
+          v += (float)rh[j] + (float)rl[j];
+        }
+        acc[i][cb][q * 4 + j] = v;
+        s += v;
+      }
+    });
+    s += __shfl_xor(s, 32, 64);
+    const float mean = s * (1.0f / C);
+    float d = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float cx = acc[i][cb][r] - mean;
+        // (Said term by term, not left to contraction, so that every form keeps the bits it has always produced: the
+        // compiler used to round each product and then add -- packed multiplies -- except in the UpFeed
+        // instantiations, where it fused the first 26 terms into multiply-adds and rounded the last 6 products.)
+        if (FUSED_VAR && cb * 16 + r < 26) {
+          d = __builtin_fmaf(cx, cx, d);
+        } else {
+#pragma clang fp contract(off)
+          d += cx * cx;
+        }
+      }
+    d += __shfl_xor(d, 32, 64);
+    const float rstd = 1.0f / sqrtf(d * (1.0f / C) + p.eps);
+    for_each_group(h, [&](int cb, int q, int c0) __attribute__((always_inline)) {
+      const float4 g4 = *reinterpret_cast<const float4*>(tb + 64 + c0);
+      const float4 b4 = *reinterpret_cast<const float4*>(tb + 128 + c0);
+      const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, be[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][cb][q * 4 + j] = (acc[i][cb][q * 4 + j] - mean) * rstd * gv[j] + be[j];
+    });
+  });
+}
+
+// the next layer's input replaces this layer's in the image: rows outside the sequence are its zero padding
+template <int NTERM, typename Map>
+__device__ __forceinline__ void hand_over(const LayerDev& Ld, const Map& map, char* img, int nf, int lane, int wid,
+                                          const floatx16 (&acc)[TM][2]) {
+  for_each_fragment(nf, [&](int i) __attribute__((always_inline)) {
+    const int frow = frag_row(wid, i, lane);
+    const bool inside = map.handed_on(frow, Ld.halo);
+    char* wrow = img + frow * RS;
+    for_each_group(lane >> 5, [&](int cb, int q, int c0) __attribute__((always_inline)) {
+      float4 v = group4(acc[i][cb], q);
+      if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);
+      half4 hi, lo;
+      split4t<NTERM>(v, hi, lo);
+      *reinterpret_cast<half4*>(wrow + IMG_HI + c0 * 2) = hi;
+      *reinterpret_cast<half4*>(wrow + IMG_LO + c0 * 2) = lo;
+    });
+  });
+}
+
+// UpFeed.  The GEMM runs with the activation as the MFMA A operand (the same registers serve either side:
+// lane = row, 8 k per lane half), so a result block has its output CHANNEL on the lane and 16 rows in registers:
+// one store instruction writes two whole 128-byte lines, and a lane's 16 values share a GroupNorm group.
+template <int NTERM, typename Map>
+__device__ __forceinline__ void up_feed(const KArgs& p, const UpArgs& u, const LayerDev& Ld, const Map& map, int b, int tile,
+                                        char* smem, int tid, const floatx16 (&acc)[TM][2]) {
+  const int T = map.T, lane = tid & 63, wid = tid >> 6, h = lane >> 5;
+  const __amdgpu_buffer_rsrc_t rS = act_rsrc(u.skip + (long)b * T * C, (long)T * C);
+  const int tstep = map.row_step();                     // sequence rows between two rows of a fragment
+  const int widu = __builtin_amdgcn_readfirstlane(wid); // (the row bookkeeping and the store bases stay scalar)
+  half8 xh[TM][4], xl[TM][4];
+  int t0[TM], nv[TM];                                   // sequence row of a fragment's row 0; its rows that exist (a prefix)
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int f0 = (widu * TM + i) * 32;
+    t0[i] = map.seq_row(f0);
+    const int lim = map.run_rows(f0);
+    nv[i] = i < Ld.nfrag - widu * TM ? min(max(lim, 0), 32) : 0;
+    const bool ok = (lane & 31) < nv[i];
+    const long e0 = ((long)t0[i] + (long)(lane & 31) * tstep) * C + h * 4;
+    float4 sk[8];
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) sk[c8] = act_load4(rS, e0 + c8 * 8, ok);
+    for_each_group(h, [&](int cb, int q, int) __attribute__((always_inline)) {
+      const float4 s4 = sk[cb * 4 + q];
+      const float4 v = make_float4(acc[i][cb][q * 4 + 0] + s4.x, acc[i][cb][q * 4 + 1] + s4.y,
+                                   acc[i][cb][q * 4 + 2] + s4.z, acc[i][cb][q * 4 + 3] + s4.w);
+      half4 hi, lo;
+      split4t<NTERM>(v, hi, lo);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        xh[i][cb * 2 + (q >> 1)][(q & 1) * 4 + j] = hi[j];
+        xl[i][cb * 2 + (q >> 1)][(q & 1) * 4 + j] = lo[j];
+      }
+    });
+  }
+  float st0 = 0.f, sq0 = 0.f, st1 = 0.f, sq1 = 0.f;
+  // Stores go through one buffer descriptor per fragment that covers exactly its rows that exist: the address is one
+  // 32-bit offset, and a row past the end (of the sequence, or of this tile's share) is dropped by the bounds
+  // check instead of by a branch.
+  __amdgpu_buffer_rsrc_t rO[TM];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+    rO[i] = __builtin_amdgcn_make_buffer_rsrc(u.out + ((long)b * T + t0[i]) * UPN, 0,
+                                              nv[i] > 0 ? ((nv[i] - 1) * tstep + 1) * UPN * 4 : 0, 0x00020000);
+  const int voff = (4 * h * tstep * UPN + (lane & 31)) * 4; // this lane's part of a store address: its first row, its channel
+  const int rstep = tstep * UPN * 4;
+  half8 wh[2][2], wl[2][2];
+  auto wload = [&](int ks, int nb2, int slot) __attribute__((always_inline)) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) frag_load<NTERM>(u.Wh, u.Wl, (long)ks * (UPN / 32) + nb2 * 2 + e, lane, wh[slot][e], wl[slot][e]);
+  };
+  wload(0, 0, 0);
+#pragma unroll 1
+  for (int nb2 = 0; nb2 < UPN / 64; ++nb2) {            // two 32-channel blocks at a time: 0, 2 the value half, 1, 3 the gate half
+    floatx16 y[TM][2];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) y[i][e][r] = 0.f;
+    const float bv[2] = {u.bias[nb2 * 64 + (lane & 31)], u.bias[nb2 * 64 + 32 + (lane & 31)]};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      // the next k-step's weights (after the last one: the next pair's first, the last pair fetching its own again)
+      if (ks < 3) wload(ks + 1, nb2, (ks + 1) & 1);
+      else wload(0, nb2 + 1 < UPN / 64 ? nb2 + 1 : nb2, 0);
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) mma3<NTERM, false>(y[i][e], xh[i][ks], xl[i][ks], wh[ks & 1][e], wl[ks & 1][e]);
+    }
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const bool whole = nv[i] == 32;                   // (wave-uniform) every row of the fragment exists
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = y[i][e][r] * u.scale + bv[e];
+          // (the whole offset in the vector operand: that is the one the bounds check compares)
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rO[i],
+                                                voff + ((r & 3) + 8 * (r >> 2)) * rstep + (nb2 * 64 + e * 32) * 4, 0, 0);
+          const float m = (whole || acc_row(r, h) < nv[i]) ? v : 0.f;
+          s1 += m;
+          s2 += m * m;
+        }
+    }
+    if (nb2 & 1) { st1 += s1; sq1 += s2; } else { st0 += s1; sq0 += s2; }
+  }
+  // GroupNorm partial sums of this tile: lanes, then waves, in a fixed order; one slot per (item, tile), no atomics
+  st0 = wave_sum(st0); sq0 = wave_sum(sq0); st1 = wave_sum(st1); sq1 = wave_sum(sq1);
+  __syncthreads();                                      // every wave is done with the image
+  float* red = reinterpret_cast<float*>(smem);
+  if (lane == 0) { red[wid * 4 + 0] = st0; red[wid * 4 + 1] = sq0; red[wid * 4 + 2] = st1; red[wid * 4 + 3] = sq1; }
+  __syncthreads();
+  if (tid < 4) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) s += red[w * 4 + tid];
+    u.stats[((long)b * p.ntile + tile) * 4 + tid] = s;
+  }
+}
+
+// the stack's output: the rows of this tile that it delivers, one float4 per group
+template <typename Map>
+__device__ __forceinline__ void store_rows(const KArgs& p, const Map& map, int b, int nf, int lane, int wid,
+                                           const floatx16 (&acc)[TM][2]) {
+  float* __restrict__ ob = p.out + (long)b * map.T * C;
+  for_each_fragment(nf, [&](int i) __attribute__((always_inline)) {
+    const ImgSrc o = map.delivered(frag_row(wid, i, lane));
+    if (o.ok) {
+      float* orow = ob + (long)o.g * C;
+      for_each_group(lane >> 5, [&](int cb, int q, int c0) __attribute__((always_inline)) {
+        *reinterpret_cast<float4*>(orow + c0) = group4(acc[i][cb], q);
+      });
+    }
+  });
+}
+
+// ------------------------------------------------------------------ the kernel
 // NL fused layers (contiguous row tiles) or one layer on polyphase row sets (POLY, NL == 1).
 // NW waves, each owning TM 32-row fragments x all 64 channels.
 //
@@ -118,17 +608,12 @@ __device__ __forceinline__ half8 src_load(__amdgpu_buffer_rsrc_t r, int row) {
 // folds into the packed weight, asw_up_feed_kperm).  So the last layer adds the skip rows, splits the sum, runs
 // W_up (x + skip) + bias for the 256 output channels from registers and writes the raw rows and their GroupNorm
 // partial sums (UpArgs).  x is never stored: one write and one read of it and one launch less.
-template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int NTERM, int QD, bool SRC = false, bool UP = false>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(TM >= 4 ? 1 : 2)))
+template <int NL, int PH, bool POLY, bool GLU, int NTERM, bool SRC = false, bool UP = false>
+__global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2)))
 void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
   static_assert(!UP || (!SRC && NTERM == 3), "UpFeed: f16x3, never source-fed");
   static_assert(!POLY || NL == 1, "polyphase row sets: single layers only");
   static_assert(!SRC || (!POLY && !GLU && NTERM == 3), "source-fed layer 0: contiguous tiles, f16x3");
-  static_assert(QD == 2 || QD == 4, "weight prefetch depth in k-steps");
-  constexpr int NTHR = 64 * NW, SROWS = NTHR / 16;
-  constexpr int R0 = 32 * NW * TM;                      // rows layer 0 computes
-  constexpr int BMJ = R0 / PH;                          // polyphase: rows of j per phase
-  static_assert(BMJ % 32 == 0, "a row fragment must stay inside one phase");
 
   extern __shared__ __align__(16) char smem[];
   char* img = smem;
@@ -138,103 +623,22 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
   int idx;
   if (!xcd_tile_run(p.B * p.ntile, idx)) return;        // XCD-aware order: a contiguous run of (item, row tile) pairs
   const int b = idx / p.ntile, tile = idx - b * p.ntile;
-  const int T = p.T, taps = p.taps;
-  const int dil0 = p.L[0].dil, pad0 = p.L[0].pad;
-  const int n_pb = POLY ? (dil0 + PH - 1) / PH : 1;
-  const int jb = POLY ? tile / n_pb : 0, pb = POLY ? tile - jb * n_pb : 0;
-  const int m0 = tile * p.BM;
-  const int RJ = BMJ + taps - 1;                        // polyphase: image rows per phase
-  const int R_img = POLY ? PH * RJ : R0 + 2 * pad0;
+  const RowMap<POLY, PH> map(tile, p);
 
-  RS_MARK(t_start);
-  // ---- per-layer vectors -> LDS
-  if constexpr (!SRC) {                  // (SRC: after layer 0's operand loads are out, under the same wait)
-    for (int i = tid; i < NL * 3 * 16; i += NTHR) {
-      const int li = i / 48, w = (i - li * 48) / 16, c4 = i & 15;
-      const float* src = w == 0 ? p.L[li].bias : w == 1 ? p.L[li].gamma : p.L[li].beta;
-      reinterpret_cast<float4*>(tab)[i] = *reinterpret_cast<const float4*>(src + c4 * 4);
-    }
+  PhaseClock clk;
+  clk.mark(0);
+  if constexpr (!SRC) {                  // (SRC: source_layer0 loads the vectors and has nothing to stage)
+    load_layer_vectors<NL>(p, tab, tid);
+    stage_rows<GLU, NTERM>(p, map, b, img, tid);
+    __syncthreads();
   }
-  // ---- stage + split the input rows of layer 0 (16 threads per row, 8 rows per thread in flight)
-  if constexpr (!SRC) {
-    const __amdgpu_buffer_rsrc_t rX = GLU ? act_rsrc(p.glu_raw + (long)b * T * 2 * C, (long)T * 2 * C)
-                                          : act_rsrc(p.x + (long)b * T * C, (long)T * C);
-    const int srow = tid >> 4, sc4 = tid & 15;
-    GluCoef gc;
-    if (GLU) {
-      gc.stats(p.glu_mr, b);
-      gc.affine(p.glu_gamma, p.glu_beta, C, sc4 * 4);
-    }
-    // (This loop stays here instead of calling stage_image of f16x3_tile.h, which resconv16 and downconv64 use: through
-    // the shared routine the GLU variant of the fused pair measured 0.7 % slower, 11.11 -> 11.21 ms per bench step.)
-    // the whole image is requested before the first row is converted: one exposed memory latency per tile (with 8
-    // rows per thread in flight the three rounds of a 262-row image took 17 % of a workgroup's time)
-    constexpr int SU = GLU ? 9 : 18;
-    for (int r0 = 0; r0 < R_img; r0 += SROWS * SU) {
-      float4 buf[SU];
-      float4 gate[GLU ? SU : 1];
-      bool okr[GLU ? SU : 1];
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int row = r0 + u * SROWS + srow;
-        int g;
-        bool ok = row < R_img;
-        if (!POLY) {
-          g = m0 - p.L[0].halo - pad0 + row;
-        } else {
-          const int ph = pb * PH + row / RJ;
-          const int jj = jb * BMJ + row % RJ - (taps - 1) / 2;
-          g = dil0 * jj + ph;
-          ok = ok && ph < dil0 && jj >= 0;
-        }
-        ok = ok && g >= 0 && g < T;
-        if (GLU) {
-          buf[u] = act_load4(rX, (long)g * 2 * C + sc4 * 4, ok);
-          gate[u] = act_load4(rX, (long)g * 2 * C + C + sc4 * 4, ok);
-          okr[u] = ok;
-        } else {
-          buf[u] = act_load4(rX, (long)g * C + sc4 * 4, ok);
-        }
-      }
-      if (GLU) {
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const float4 o = gn_glu4(buf[u], gate[u], gc, okr[u]);
-          buf[u] = o;
-          // the normalised tensor is also a skip connection: each tile writes the rows of its own output range once
-          if (p.glu_out && okr[u]) {
-            const int g = m0 - p.L[0].halo - pad0 + r0 + u * SROWS + srow;
-            if (g >= m0 && g < m0 + p.BM)
-              *reinterpret_cast<float4*>(p.glu_out + ((long)b * T + g) * C + sc4 * 4) = o;
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int row = r0 + u * SROWS + srow;
-        if (row < R_img) {
-          half4 hi, lo;
-          split4t<NTERM>(buf[u], hi, lo);
-          *reinterpret_cast<half4*>(img + row * RS + IMG_HI + sc4 * 8) = hi;
-          *reinterpret_cast<half4*>(img + row * RS + IMG_LO + sc4 * 8) = lo;      // (the residual reads it in every mode)
-        }
-      }
-    }
-  }
-  if constexpr (!SRC) __syncthreads();
-  RS_MARK(t_staged);
-#ifdef ASW_PHASE_TIMING
-  unsigned long long t_marks[2 * MAXL + 1];
-  t_marks[0] = t_staged;
-#endif
+  clk.mark(1);
 
-  const int h = lane >> 5;
   floatx16 acc[TM][2];
   auto layer = [&](auto lic) {
     constexpr int li = decltype(lic)::value;
-    constexpr bool last = li == NL - 1;
+    constexpr bool fed = SRC && li == 0;
     const LayerDev& Ld = p.L[li];
-    const int tapstep = (POLY ? 1 : Ld.dil) * RS;
     const int nf = Ld.nfrag - wid * TM;                 // fragments of this wave that exist in this layer (<= 0: none)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -242,389 +646,72 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][cb][r] = 0.f;        // (all of acc defined on every path: it stays in registers)
-    // image row of output row `trow` at tap 0
-    auto img_row = [&](int trow) { return POLY ? (trow / BMJ) * RJ + trow % BMJ : trow; };
-    // this wave's first nf (<= TM) fragments: one k-loop instantiation per count (wave-uniform choice)
-    auto run = [&](auto nfc) {
-      constexpr int NF = decltype(nfc)::value;
-      int xb[NF];
-      floatx16 a[NF][2];
-#pragma unroll
-      for (int i = 0; i < NF; ++i) {
-        xb[i] = (img_row((wid * TM + i) * 32) + (lane & 31)) * RS + h * 16;
-        a[i][0] = acc[i][0];
-        a[i][1] = acc[i][1];
-      }
-      kloop<NF, 2, QD, NTERM>(
-          a, taps, [&](int tap, int i) __attribute__((always_inline)) { return img + xb[i] + tap * tapstep; }, Ld.Wh, Ld.Wl,
-          [](int kg, int cb) __attribute__((always_inline)) { return (long)kg * 2 + cb; }, lane);
-#pragma unroll
-      for (int i = 0; i < NF; ++i) { acc[i][0] = a[i][0]; acc[i][1] = a[i][1]; }
-    };
-    if constexpr (SRC && li == 0) {
-      // Layer 0 on the source planes (every wave owns TM whole fragments here: nfrag == NW * TM, checked by the host).
-      // Lane (row r, half h) holds, for k-step ks, the 8 source channels of row r + tap, tap = 2 ks + h: one 16-byte
-      // load per plane.  Tap 7 does not exist -- its weights are zero -- but its rows are read and are finite (data or
-      // the descriptor's zeros).  Everything is requested before the first MFMA: one exposed latency per tile.
-      const __amdgpu_buffer_rsrc_t rH = src_rsrc(p.src_h + (long)b * T, T), rL = src_rsrc(p.src_l + (long)b * T, T);
-      const int g0 = m0 - Ld.halo - Ld.pad + wid * TM * 32 + (lane & 31);       // global row of this lane's row at tap 0
-      half8 xh[4][TM], xl[4][TM], rh[TM], rl[TM];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          xh[ks][i] = src_load(rH, g0 + i * 32 + 2 * ks + h);
-          xl[ks][i] = src_load(rL, g0 + i * 32 + 2 * ks + h);
-        }
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {                    // the residual's rows (centre tap); the half h == 1 meets zero weights
-        rh[i] = src_load(rH, g0 + i * 32 + Ld.pad);
-        rl[i] = src_load(rL, g0 + i * 32 + Ld.pad);
-      }
-      // weight stream: k-steps 0..3 of the composed weight, then the 1x1 weight as "k-step 4"; two slots
-      half8 wh[2][2], wl[2][2];
-      auto wload = [&](auto kgc, int slot) {
-        constexpr int kg = decltype(kgc)::value;
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          if constexpr (kg < 4) frag_load<3>(Ld.Wh, Ld.Wl, (long)kg * 2 + cb, lane, wh[slot][cb], wl[slot][cb]);
-          else frag_load<3>(p.Pre_h, p.Pre_l, (long)cb, lane, wh[slot][cb], wl[slot][cb]);
-        }
-      };
-      wload(std::integral_constant<int, 0>{}, 0);
-      wload(std::integral_constant<int, 1>{}, 1);
-      for (int i = tid; i < NL * 3 * 16; i += NTHR) {   // per-layer vectors -> LDS
-        const int lj = i / 48, w = (i - lj * 48) / 16, c4 = i & 15;
-        const float* src = w == 0 ? p.L[lj].bias : w == 1 ? p.L[lj].gamma : p.L[lj].beta;
-        reinterpret_cast<float4*>(tab)[i] = *reinterpret_cast<const float4*>(src + c4 * 4);
-      }
-      __syncthreads();
-      auto kstep = [&](auto ksc) {
-        constexpr int ks = decltype(ksc)::value;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) mma3<3, true>(acc[i][cb], xh[ks][i], xl[ks][i], wh[ks & 1][cb], wl[ks & 1][cb]);
-        if constexpr (ks + 2 <= 4) wload(std::integral_constant<int, ks + 2>{}, ks & 1);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      kstep(std::integral_constant<int, 0>{});
-      kstep(std::integral_constant<int, 1>{});
-      kstep(std::integral_constant<int, 2>{});
-      kstep(std::integral_constant<int, 3>{});
-      // + bias, ReLU -- brought to the units of the 1x1 weight (both weights carry a power-of-two pre-scale, so the
-      // rescaling is exact) -- then the residual x0 = Wpre~ u~ accumulated on top: no second accumulator set
-      const float* tb0 = tab;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float4 bi = *reinterpret_cast<const float4*>(tb0 + cb * 32 + q * 8 + h * 4);
-            const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              acc[i][cb][q * 4 + j] = fmaxf(acc[i][cb][q * 4 + j] * Ld.scale + bv[j], 0.f) * p.pre_up;
-          }
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) mma3<3, true>(acc[i][cb], rh[i], rl[i], wh[0][cb], wl[0][cb]);
-      }
-    } else {
-    if (nf >= TM) run(std::integral_constant<int, TM>{});
-    else if constexpr (TM > 1) {
-      if (nf == 1) run(std::integral_constant<int, 1>{});
-      if constexpr (TM > 2) {
-        if (nf == 2) run(std::integral_constant<int, 2>{});
-        if (nf == 3) run(std::integral_constant<int, 3>{});
-      }
-    }
-    }
-#ifdef ASW_PHASE_TIMING
-    {
-      float sink = acc[0][0][0];
-      asm volatile("" ::"v"(sink));                     // the stamp waits for the MFMAs
-      t_marks[2 * li + 1] = __builtin_readcyclecounter();
-    }
-#endif
-    // ---- epilogue in registers: + bias, ReLU, + residual (the layer's own input, from the image), LayerNorm
-    const float* tb = tab + li * 192;
-    const int cpad = POLY ? (taps - 1) / 2 : Ld.pad;    // image row of the residual = tap-0 row + centre tap
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      if (i < nf) {
-        const int trow = (wid * TM + i) * 32 + (lane & 31);
-        const char* rrow = img + (img_row(trow) + cpad) * RS;
-        float s = 0.f;
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int c0 = cb * 32 + q * 8 + h * 4;
-            const float4 bi = *reinterpret_cast<const float4*>(tb + c0);
-            const half4 rh = *reinterpret_cast<const half4*>(rrow + IMG_HI + c0 * 2);
-            const half4 rl = *reinterpret_cast<const half4*>(rrow + IMG_LO + c0 * 2);
-            const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float v;
-              if constexpr (SRC && li == 0) {
-                v = acc[i][cb][q * 4 + j] * p.pre_down;          // bias, ReLU and residual are in the accumulators
-              } else {
-                v = fmaxf(acc[i][cb][q * 4 + j] * Ld.scale + bv[j], 0.f);
-                v += (float)rh[j] + (float)rl[j];
-              }
-              acc[i][cb][q * 4 + j] = v;
-              s += v;
-            }
-          }
-        s += __shfl_xor(s, 32, 64);
-        const float mean = s * (1.0f / C);
-        float d = 0.f;
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { const float cx = acc[i][cb][r] - mean; d += cx * cx; }
-        d += __shfl_xor(d, 32, 64);
-        const float rstd = 1.0f / sqrtf(d * (1.0f / C) + p.eps);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int c0 = cb * 32 + q * 8 + h * 4;
-            const float4 g4 = *reinterpret_cast<const float4*>(tb + 64 + c0);
-            const float4 b4 = *reinterpret_cast<const float4*>(tb + 128 + c0);
-            const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, be[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][cb][q * 4 + j] = (acc[i][cb][q * 4 + j] - mean) * rstd * gv[j] + be[j];
-          }
-      }
-    }
-    if constexpr (!last) {
-      // the next layer's input replaces this layer's in the image: rows outside the sequence are its zero padding
-      if constexpr (!(SRC && li == 0)) __syncthreads(); // every wave is done reading the old image
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        if (i < nf) {
-          const int trow = (wid * TM + i) * 32 + (lane & 31);
-          const int t = m0 - Ld.halo + trow;
-          const bool inside = t >= 0 && t < T;
-          char* wrow = img + trow * RS;
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int c0 = cb * 32 + q * 8 + h * 4;
-              float4 v = make_float4(acc[i][cb][q * 4 + 0], acc[i][cb][q * 4 + 1], acc[i][cb][q * 4 + 2], acc[i][cb][q * 4 + 3]);
-              if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);
-              half4 hi, lo;
-              split4t<NTERM>(v, hi, lo);
-              *reinterpret_cast<half4*>(wrow + IMG_HI + c0 * 2) = hi;
-              *reinterpret_cast<half4*>(wrow + IMG_LO + c0 * 2) = lo;
-            }
-        }
-      }
+    if constexpr (fed) source_layer0<NL>(p, map, b, tab, tid, acc);
+    else conv_layer<NTERM>(p, Ld, map, img, nf, lane, wid, acc);
+    clk.mark_after(2 + 2 * li, acc[0][0][0]);
+    finish_rows<fed, UP>(p, Ld, map, img, tab + li * 192, li == 0, nf, lane, wid, acc);
+    if constexpr (li < NL - 1) {
+      if constexpr (!fed) __syncthreads();              // every wave is done reading the old image
+      hand_over<NTERM>(Ld, map, img, nf, lane, wid, acc);
       __syncthreads();
     } else if constexpr (UP) {
-      const UpArgs& u = p.u;
-      // ---- UpFeed.  The GEMM runs with the activation as the MFMA A operand (the same registers serve either side:
-      // lane = row, 8 k per lane half), so a result block has its output CHANNEL on the lane and 16 rows in registers:
-      // one store instruction writes two whole 128-byte lines, and a lane's 16 values share a GroupNorm group.
-      const __amdgpu_buffer_rsrc_t rS = act_rsrc(u.skip + (long)b * T * C, (long)T * C);
-      const int tstep = POLY ? dil0 : 1;                // sequence rows between two rows of a fragment
-      const int widu = __builtin_amdgcn_readfirstlane(wid);     // (the row bookkeeping and the store bases stay scalar)
-      half8 xh[TM][4], xl[TM][4];
-      int t0[TM], nv[TM];                               // sequence row of a fragment's row 0; its rows that exist (a prefix)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int f0 = (widu * TM + i) * 32;
-        int lim;
-        if (!POLY) {
-          t0[i] = m0 + f0;
-          lim = min(p.BM, T - m0) - f0;
-        } else {
-          const int ph = pb * PH + f0 / BMJ;
-          t0[i] = dil0 * (jb * BMJ + f0 % BMJ) + ph;
-          lim = (ph < dil0 && t0[i] < T) ? (T - 1 - t0[i]) / dil0 + 1 : 0;
-        }
-        nv[i] = i < Ld.nfrag - widu * TM ? min(max(lim, 0), 32) : 0;
-        const bool ok = (lane & 31) < nv[i];
-        const long e0 = ((long)t0[i] + (long)(lane & 31) * tstep) * C + h * 4;
-        float4 sk[8];
-#pragma unroll
-        for (int c8 = 0; c8 < 8; ++c8) sk[c8] = act_load4(rS, e0 + c8 * 8, ok);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float4 s4 = sk[cb * 4 + q];
-            const float4 v = make_float4(acc[i][cb][q * 4 + 0] + s4.x, acc[i][cb][q * 4 + 1] + s4.y,
-                                         acc[i][cb][q * 4 + 2] + s4.z, acc[i][cb][q * 4 + 3] + s4.w);
-            half4 hi, lo;
-            split4t<NTERM>(v, hi, lo);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              xh[i][cb * 2 + (q >> 1)][(q & 1) * 4 + j] = hi[j];
-              xl[i][cb * 2 + (q >> 1)][(q & 1) * 4 + j] = lo[j];
-            }
-          }
-      }
-      float st0 = 0.f, sq0 = 0.f, st1 = 0.f, sq1 = 0.f;
-      // Stores go through one buffer descriptor per fragment that covers exactly its rows that exist: the address is one
-      // 32-bit offset, and a row past the end (of the sequence, or of this tile's share) is dropped by the bounds
-      // check instead of by a branch.
-      __amdgpu_buffer_rsrc_t rO[TM];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        rO[i] = __builtin_amdgcn_make_buffer_rsrc(u.out + ((long)b * T + t0[i]) * UPN, 0,
-                                                  nv[i] > 0 ? ((nv[i] - 1) * tstep + 1) * UPN * 4 : 0, 0x00020000);
-      const int voff = (4 * h * tstep * UPN + (lane & 31)) * 4; // this lane's part of a store address: its first row, its channel
-      const int rstep = tstep * UPN * 4;
-      half8 wh[2][2], wl[2][2];
-      auto wload = [&](int ks, int nb2, int slot) __attribute__((always_inline)) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) frag_load<NTERM>(u.Wh, u.Wl, (long)ks * (UPN / 32) + nb2 * 2 + e, lane, wh[slot][e], wl[slot][e]);
-      };
-      wload(0, 0, 0);
-#pragma unroll 1
-      for (int nb2 = 0; nb2 < UPN / 64; ++nb2) {        // two 32-channel blocks at a time: 0, 2 the value half, 1, 3 the gate half
-        floatx16 y[TM][2];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) y[i][e][r] = 0.f;
-        const float bv[2] = {u.bias[nb2 * 64 + (lane & 31)], u.bias[nb2 * 64 + 32 + (lane & 31)]};
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          // the next k-step's weights (after the last one: the next pair's first, the last pair fetching its own again)
-          if (ks < 3) wload(ks + 1, nb2, (ks + 1) & 1);
-          else wload(0, nb2 + 1 < UPN / 64 ? nb2 + 1 : nb2, 0);
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) mma3<NTERM, false>(y[i][e], xh[i][ks], xl[i][ks], wh[ks & 1][e], wl[ks & 1][e]);
-        }
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const bool whole = nv[i] == 32;               // (wave-uniform) every row of the fragment exists
-#pragma unroll
-          for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float v = y[i][e][r] * u.scale + bv[e];
-              // (the whole offset in the vector operand: that is the one the bounds check compares)
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rO[i],
-                                                    voff + ((r & 3) + 8 * (r >> 2)) * rstep + (nb2 * 64 + e * 32) * 4, 0, 0);
-              const float m = (whole || acc_row(r, h) < nv[i]) ? v : 0.f;
-              s1 += m;
-              s2 += m * m;
-            }
-        }
-        if (nb2 & 1) { st1 += s1; sq1 += s2; } else { st0 += s1; sq0 += s2; }
-      }
-      // GroupNorm partial sums of this tile: lanes, then waves, in a fixed order; one slot per (item, tile), no atomics
-      st0 = wave_sum(st0); sq0 = wave_sum(sq0); st1 = wave_sum(st1); sq1 = wave_sum(sq1);
-      __syncthreads();                                  // every wave is done with the image
-      float* red = reinterpret_cast<float*>(smem);
-      if (lane == 0) { red[wid * 4 + 0] = st0; red[wid * 4 + 1] = sq0; red[wid * 4 + 2] = st1; red[wid * 4 + 3] = sq1; }
-      __syncthreads();
-      if (tid < 4) {
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) s += red[w * 4 + tid];
-        u.stats[((long)b * p.ntile + tile) * 4 + tid] = s;
-      }
+      up_feed<NTERM>(p, p.u, Ld, map, b, tile, smem, tid, acc);
     } else {
-      float* __restrict__ ob = p.out + (long)b * T * C;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        if (i < nf) {
-          const int trow = (wid * TM + i) * 32 + (lane & 31);
-          int t;
-          bool ok;
-          if (!POLY) {
-            t = m0 + trow;
-            ok = trow < p.BM && t < T;
-          } else {
-            const int ph = pb * PH + trow / BMJ;
-            t = dil0 * (jb * BMJ + trow % BMJ) + ph;
-            ok = ph < dil0 && t < T;
-          }
-          if (ok) {
-            float* orow = ob + (long)t * C;
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const int c0 = cb * 32 + q * 8 + h * 4;
-                *reinterpret_cast<float4*>(orow + c0) =
-                    make_float4(acc[i][cb][q * 4 + 0], acc[i][cb][q * 4 + 1], acc[i][cb][q * 4 + 2], acc[i][cb][q * 4 + 3]);
-              }
-          }
-        }
-      }
+      store_rows(p, map, b, nf, lane, wid, acc);
     }
+    clk.mark(3 + 2 * li);
   };
   layer(std::integral_constant<int, 0>{});
-#ifdef ASW_PHASE_TIMING
-  t_marks[2] = __builtin_readcyclecounter();
-#endif
   if constexpr (NL > 1) layer(std::integral_constant<int, 1>{});
   if constexpr (NL > 2) layer(std::integral_constant<int, 2>{});
-#ifdef ASW_PHASE_TIMING
-  if (threadIdx.x == 0 && NL <= 2) {
-    const unsigned long long t_end = __builtin_readcyclecounter();
-    atomicAdd(&g_rs_cycles[0], t_staged - t_start);
-    atomicAdd(&g_rs_cycles[1], t_marks[1] - t_marks[0]);
-    if (NL == 1) {
-      atomicAdd(&g_rs_cycles[4], t_end - t_marks[1]);
-    } else {
-      atomicAdd(&g_rs_cycles[2], t_marks[2] - t_marks[1]);
-      atomicAdd(&g_rs_cycles[3], t_marks[3] - t_marks[2]);
-      atomicAdd(&g_rs_cycles[4], t_end - t_marks[3]);
-    }
-    atomicAdd(&g_rs_cycles[5], 1ull);
-  }
-#endif
+  clk.report<NL>();
 }
 
-template <int NL, int NW, int TM, int PH, bool POLY, bool GLU, int QD, bool SRC = false>
-int launch_stack(const KArgs& k, const UpArgs* up, int precision, size_t smem, double flops, const char* tag, hipStream_t s) {
-  char nm[128], detail[48] = "";
-  snprintf(nm, sizeof nm, "resstack64<%s,%dx%d%s%s%s%s>", tag, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
-           GLU ? ",glu" : "", SRC ? ",src" : "", up ? ",up" : "");
-  if (asw::prof_detail()) snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
-  if constexpr (!SRC) {
-    if (up) {
-      // algorithmic bytes: the stack's input and the skip rows read once, the raw rows written once
-      KArgsUp ku;
-      static_cast<KArgs&>(ku) = k;
-      ku.u = *up;
-      return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, false, true>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, false, true>>(
-          1, dim3(xcd_grid_run(k.B * k.ntile)), dim3(64 * NW), smem, 160 * 1024, nm, detail,
-          flops + 2.0 * k.B * (double)k.T * C * UPN, (double)k.B * k.T * 4 * ((GLU ? 3 : 2) * C + UPN), s, ku);
-    }
-  }
-  if constexpr (SRC) {
-    // f16x3 only; algorithmic bytes: the two source planes read once, the output written once
-    return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, true>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD, true>>(
-        1, dim3(xcd_grid_run(k.B * k.ntile)), dim3(64 * NW), smem, 160 * 1024, nm, detail, flops,
-        (double)k.B * k.T * (32 + C * 4), s, k);
-  } else {
+// ------------------------------------------------------------------ launch
+template <bool GLU, bool SRC, bool UP>
+double stack_bytes(const KArgs& k) {
+  const double rows = (double)k.B * k.T;
+  // f16x3 only; algorithmic bytes: the two source planes read once, the output written once
+  if (SRC) return rows * (32 + C * 4);
+  // algorithmic bytes: the stack's input and the skip rows read once, the raw rows written once
+  if (UP) return rows * 4 * ((GLU ? 3 : 2) * C + UPN);
   // algorithmic bytes: the stack's input read once, its output written once
-  return asw::launch_pair<resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 1, QD>, resstack64_kernel<NL, NW, TM, PH, POLY, GLU, 3, QD>>(
-      precision, dim3(xcd_grid_run(k.B * k.ntile)), dim3(64 * NW), smem, 160 * 1024, nm, detail, flops,
-      (double)k.B * k.T * C * 4 * (GLU ? 3 : 2), s, k);
+  return rows * C * 4 * (GLU ? 3 : 2);
+}
+
+// One form of the kernel: its single-pass and its f16x3 instantiation (SRC and UP are f16x3 only: the host has
+// checked the precision).
+template <int NL, int PH, bool POLY, bool GLU, bool SRC, bool UP>
+int launch_stack(const KArgs& k, const UpArgs* up, int precision, size_t smem, double flops, hipStream_t s) {
+  char nm[128], detail[48] = "";
+  snprintf(nm, sizeof nm, "resstack64<%d,%dx%d%s%s%s%s>", NL, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
+           GLU ? ",glu" : "", SRC ? ",src" : "", UP ? ",up" : "");
+  if (asw::prof_detail()) snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
+  std::conditional_t<UP, KArgsUp, KArgs> ka;
+  static_cast<KArgs&>(ka) = k;
+  if constexpr (UP) {
+    ka.u = *up;
+    flops += 2.0 * k.B * (double)k.T * C * UPN;
   }
+  return asw::launch_pair<resstack64_kernel<NL, PH, POLY, GLU, (SRC || UP) ? 3 : 1, SRC, UP>, resstack64_kernel<NL, PH, POLY, GLU, 3, SRC, UP>>(
+      precision, dim3(xcd_grid_run(k.B * k.ntile)), dim3(NTHR), smem, 160 * 1024, nm, detail, flops, stack_bytes<GLU, SRC, UP>(k), s, ka);
+}
+
+// the staged forms of a tiling: GroupNorm + GLU on load (contiguous tiles only) or not, UpFeed or not
+template <int NL, int PH, bool POLY>
+int launch_staged(const KArgs& k, const UpArgs* up, bool glu, int precision, size_t smem, double flops, hipStream_t s) {
+  if constexpr (!POLY) {
+    if (glu) return up ? launch_stack<NL, PH, POLY, true, false, true>(k, up, precision, smem, flops, s)
+                       : launch_stack<NL, PH, POLY, true, false, false>(k, up, precision, smem, flops, s);
+  }
+  return up ? launch_stack<NL, PH, POLY, false, false, true>(k, up, precision, smem, flops, s)
+            : launch_stack<NL, PH, POLY, false, false, false>(k, up, precision, smem, flops, s);
 }
 
 // The row tiling of a launch whose layer 0 computes R0 rows (asw_resstack_tiles reports ntile to a caller that sizes
 // the UpFeed statistics).
 struct TilePlan { bool poly; int PH, BM, ntile; };
-TilePlan plan_tiles(int T, int n_layers, int dil0, int halo0, bool glu, int R0) {
+TilePlan plan_tiles(int T, int n_layers, int dil0, int halo0, bool glu) {
   // one layer of large dilation: polyphase row sets while every phase still fills its share of the tile
   const int rpp = T / dil0;                              // rows per phase
   if (n_layers == 1 && dil0 >= 7 && rpp >= 48 && !glu) {
@@ -636,11 +723,9 @@ TilePlan plan_tiles(int T, int n_layers, int dil0, int halo0, bool glu, int R0) 
   return {false, 1, BM, BM > 0 ? asw::cdiv(T, BM) : 0};
 }
 
-template <int NW, int TM>
 int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, double flops, hipStream_t s) {
-  constexpr int R0 = 32 * NW * TM;
   const int dil0 = k.L[0].dil;
-  const TilePlan tp = plan_tiles(a.T, a.n_layers, dil0, k.L[0].halo, glu, R0);
+  const TilePlan tp = plan_tiles(a.T, a.n_layers, dil0, k.L[0].halo, glu);
   k.BM = tp.BM;
   k.ntile = tp.ntile;
   if (tp.poly) {
@@ -650,9 +735,9 @@ int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, d
     k.img_rows = PH * (BMJ + a.taps - 1);
     const size_t smem = (size_t)k.img_rows * RS + 3 * 64 * sizeof(float);
     switch (PH) {
-      case 1: return launch_stack<1, NW, TM, 1, true, false, 4>(k, up, a.precision, smem, flops, "1", s);
-      case 2: return launch_stack<1, NW, TM, 2, true, false, 4>(k, up, a.precision, smem, flops, "1", s);
-      default: return launch_stack<1, NW, TM, 4, true, false, 4>(k, up, a.precision, smem, flops, "1", s);
+      case 1: return launch_staged<1, 1, true>(k, up, false, a.precision, smem, flops, s);
+      case 2: return launch_staged<1, 2, true>(k, up, false, a.precision, smem, flops, s);
+      default: return launch_staged<1, 4, true>(k, up, false, a.precision, smem, flops, s);
     }
   }
   ASW_CHECK_ARG(k.BM >= R0 / 2, "resstack: the later layers' halo (%d rows per side) leaves %d of %d rows; fuse fewer layers",
@@ -669,15 +754,12 @@ int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, d
                 rows, dil0, a.taps);
   if (k.src_h) {
     ASW_CHECK_ARG(k.L[0].nfrag == NW * TM, "resstack: source-fed layer 0 computes %d of %d fragments", k.L[0].nfrag, NW * TM);
-    return launch_stack<2, NW, TM, 1, false, false, 4, true>(k, nullptr, a.precision, smem, flops, "2", s);
+    return launch_stack<2, 1, false, false, true, false>(k, nullptr, a.precision, smem, flops, s);
   }
   switch (a.n_layers) {
-    case 1: return glu ? launch_stack<1, NW, TM, 1, false, true, 4>(k, up, a.precision, smem, flops, "1", s)
-                       : launch_stack<1, NW, TM, 1, false, false, 4>(k, up, a.precision, smem, flops, "1", s);
-    case 2: return glu ? launch_stack<2, NW, TM, 1, false, true, 4>(k, up, a.precision, smem, flops, "2", s)
-                       : launch_stack<2, NW, TM, 1, false, false, 4>(k, up, a.precision, smem, flops, "2", s);
-    default: return glu ? launch_stack<3, NW, TM, 1, false, true, 4>(k, up, a.precision, smem, flops, "3", s)
-                        : launch_stack<3, NW, TM, 1, false, false, 4>(k, up, a.precision, smem, flops, "3", s);
+    case 1: return launch_staged<1, 1, false>(k, up, glu, a.precision, smem, flops, s);
+    case 2: return launch_staged<2, 1, false>(k, up, glu, a.precision, smem, flops, s);
+    default: return launch_staged<3, 1, false>(k, up, glu, a.precision, smem, flops, s);
   }
 }
 
@@ -718,8 +800,8 @@ extern "C" int asw_resstack_tiles(int T, int taps, int n_layers, const int32_t* 
   ASW_CHECK_ARG(T > 0 && taps >= 3 && taps % 2 == 1 && n_layers >= 1 && n_layers <= MAXL && dil, "resstack_tiles: bad argument");
   int halo0 = 0;
   for (int i = 1; i < n_layers; ++i) halo0 += dil[i] * (taps - 1) / 2;
-  const TilePlan t = plan_tiles(T, n_layers, dil[0], halo0, glu != 0, 256);
-  ASW_CHECK_ARG(t.BM >= 128, "resstack_tiles: the later layers' halo (%d rows per side) is too wide", halo0);
+  const TilePlan t = plan_tiles(T, n_layers, dil[0], halo0, glu != 0);
+  ASW_CHECK_ARG(t.BM >= R0 / 2, "resstack_tiles: the later layers' halo (%d rows per side) is too wide", halo0);
   return t.ntile;
 }
 
@@ -769,5 +851,5 @@ extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream)
     up.bias = a.up_bias; up.skip = a.up_skip; up.out = a.up_out; up.stats = a.up_stats;
     up.scale = ldexpf(1.0f, -a.up_shift);
   }
-  return dispatch<4, 2>(a, k, a.up_hi ? &up : nullptr, glu, flops, s);   // 4 waves x 2 row fragments: 256 rows computed by layer 0
+  return dispatch(a, k, a.up_hi ? &up : nullptr, glu, flops, s);   // 4 waves x 2 row fragments: 256 rows computed by layer 0
 }

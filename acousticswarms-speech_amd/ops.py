@@ -71,21 +71,17 @@ def convgemm(A, Wt, M_out, N, Cin, taps=1, stride=1, dil=1, pad=0, bias=None, re
     return out, stats
 
 
-def resstack(x, layers, taps=7, precision="f16x3", eps=1e-5, glu=None, out=None, glu_out=None):
-    """A stack of 1..3 64-channel residual layers in one launch (include/asw_hip.h:asw_resstack64_f16x3).
-    layers: [(Wt [64][taps*64], bias, gamma, beta, dil), ...]; x [B][T][64] or None with glu = (raw, mr, gamma, beta)."""
-    src = x if glu is None else glu[0]
-    B, T = src.shape[0], src.shape[1]
-    if out is None:
-        out = torch.empty((B, T, 64), dtype=torch.float32, device=src.device)
+def _resstack_args(B, T, layers, taps, precision, eps, x=None, glu=None, glu_out=None, k0=None):
+    """The ResStackArgs of a launch, without its outputs, and the tensors it points into (to be kept alive until the
+    launch has run).  layers: [(Wt [64][taps*64], bias, gamma, beta, dil), ...]; k0: the K of layer 0 where it is not
+    taps * 64 (the source-fed form's composed weight)."""
     a = ResStackArgs()
     a.x = _f32(x).data_ptr() if x is not None else None
-    a.out = out.data_ptr()
     a.B, a.T, a.C, a.taps, a.n_layers = B, T, 64, taps, len(layers)
     a.precision, a.ln_eps = (1 if precision == "f16x3" else 2), eps
     keep = []
     for i, (Wt, bias, gamma, beta, dil) in enumerate(layers):
-        fh, fl, sh = pack_fragments_f16(_f32(Wt), 64, taps * 64)
+        fh, fl, sh = pack_fragments_f16(_f32(Wt), 64, k0 if (i == 0 and k0) else taps * 64)
         keep.append((fh, fl))
         d = a.layer[i]
         d.Wf_hi, d.Wf_lo, d.w_shift, d.dil = fh.data_ptr(), fl.data_ptr(), sh, dil
@@ -94,8 +90,24 @@ def resstack(x, layers, taps=7, precision="f16x3", eps=1e-5, glu=None, out=None,
         a.glu_raw, a.glu_mr, a.glu_gamma, a.glu_beta = (_f32(t).data_ptr() for t in glu)
         if glu_out is not None:
             a.glu_out = _f32(glu_out).data_ptr()
+    return a, keep
+
+
+def _resstack_launch(a):
     check(lib().asw_resstack64_f16x3(byref(a), current_stream()))
     torch.cuda.current_stream().synchronize()
+
+
+def resstack(x, layers, taps=7, precision="f16x3", eps=1e-5, glu=None, out=None, glu_out=None):
+    """A stack of 1..3 64-channel residual layers in one launch (include/asw_hip.h:asw_resstack64_f16x3).
+    layers: [(Wt [64][taps*64], bias, gamma, beta, dil), ...]; x [B][T][64] or None with glu = (raw, mr, gamma, beta)."""
+    src = x if glu is None else glu[0]
+    B, T = src.shape[0], src.shape[1]
+    if out is None:
+        out = torch.empty((B, T, 64), dtype=torch.float32, device=src.device)
+    a, keep = _resstack_args(B, T, layers, taps, precision, eps, x=x, glu=glu, glu_out=glu_out)
+    a.out = out.data_ptr()
+    _resstack_launch(a)
     return out
 
 
@@ -107,18 +119,7 @@ def resstack_up(x, layers, up_wt, up_bias, skip, taps=7, eps=1e-5, glu=None):
     src = x if glu is None else glu[0]
     B, T = src.shape[0], src.shape[1]
     dev = src.device
-    a = ResStackArgs()
-    a.x = _f32(x).data_ptr() if x is not None else None
-    a.B, a.T, a.C, a.taps, a.n_layers, a.precision, a.ln_eps = B, T, 64, taps, len(layers), 1, eps
-    keep = []
-    for i, (Wt, bias, gamma, beta, dil) in enumerate(layers):
-        fh, fl, sh = pack_fragments_f16(_f32(Wt), 64, taps * 64)
-        keep.append((fh, fl))
-        d = a.layer[i]
-        d.Wf_hi, d.Wf_lo, d.w_shift, d.dil = fh.data_ptr(), fl.data_ptr(), sh, dil
-        d.bias, d.ln_gamma, d.ln_beta = _f32(bias).data_ptr(), _f32(gamma).data_ptr(), _f32(beta).data_ptr()
-    if glu is not None:
-        a.glu_raw, a.glu_mr, a.glu_gamma, a.glu_beta = (_f32(t).data_ptr() for t in glu)
+    a, keep = _resstack_args(B, T, layers, taps, "f16x3", eps, x=x, glu=glu)
     dils = (ctypes.c_int32 * 3)(*([l[4] for l in layers] + [1] * (3 - len(layers))))
     tiles = lib().asw_resstack_tiles(T, taps, len(layers), dils, int(glu is not None))
     check(min(tiles, 0))
@@ -127,8 +128,7 @@ def resstack_up(x, layers, up_wt, up_bias, skip, taps=7, eps=1e-5, glu=None):
     stats = torch.full((B, tiles, 4), float("nan"), dtype=torch.float32, device=dev)
     a.up_hi, a.up_lo, a.up_shift = uh.data_ptr(), ul.data_ptr(), ush
     a.up_bias, a.up_skip, a.up_out, a.up_stats = _f32(up_bias).data_ptr(), _f32(skip).data_ptr(), raw.data_ptr(), stats.data_ptr()
-    check(lib().asw_resstack64_f16x3(byref(a), current_stream()))
-    torch.cuda.current_stream().synchronize()
+    _resstack_launch(a)
     return raw, stats
 
 
@@ -150,21 +150,14 @@ def resstack_src(src_hi, src_lo, pre_w, pre_b, layers, taps=7, eps=1e-5, out=Non
     check(lib().asw_compose_source_weights(ctypes.c_void_p(wc.ctypes.data), ctypes.c_void_p(wp.ctypes.data),
                                            ctypes.c_void_p(bp.ctypes.data), M, taps, ctypes.c_void_p(comp.ctypes.data),
                                            ctypes.c_void_p(pre16.ctypes.data)))
-    a = ResStackArgs()
+    # layer 0 runs on the composed weight; the later layers on their own, k-major
+    dev_layers = [(torch.from_numpy(comp).to(dev) if i == 0 else pack_conv_weight(l[0]).to(dev),) + tuple(l[1:])
+                  for i, l in enumerate(layers)]
+    a, keep = _resstack_args(B, T, dev_layers, taps, "f16x3", eps, k0=64)
     a.out = out.data_ptr()
-    a.B, a.T, a.C, a.taps, a.n_layers, a.precision, a.ln_eps = B, T, 64, taps, len(layers), 1, eps
-    keep = []
-    for i, (w, bias, gamma, beta, dil) in enumerate(layers):
-        Wt = torch.from_numpy(comp).to(dev) if i == 0 else pack_conv_weight(w).to(dev)
-        fh, fl, sh = pack_fragments_f16(Wt, 64, Wt.shape[1])
-        keep.append((fh, fl))
-        d = a.layer[i]
-        d.Wf_hi, d.Wf_lo, d.w_shift, d.dil = fh.data_ptr(), fl.data_ptr(), sh, dil
-        d.bias, d.ln_gamma, d.ln_beta = _f32(bias).data_ptr(), _f32(gamma).data_ptr(), _f32(beta).data_ptr()
     ph, pl, psh = pack_fragments_f16(torch.from_numpy(pre16).to(dev), 64, 16)
     a.src_hi, a.src_lo, a.pre_hi, a.pre_lo, a.pre_shift = src_hi.data_ptr(), src_lo.data_ptr(), ph.data_ptr(), pl.data_ptr(), psh
-    check(lib().asw_resstack64_f16x3(byref(a), current_stream()))
-    torch.cuda.current_stream().synchronize()
+    _resstack_launch(a)
     return out
 
 

@@ -45,6 +45,12 @@ CASES = {
     "contiguous": (300, (1,), False),
     "pair": (500, (1, 7), False),
     "pair-glu": (500, (1, 7), True),
+    # the other two polyphase widths (the row bookkeeping of all three goes through one row map, csrc/resstack.hip):
+    # 48 rows per phase, the smallest length that still takes the polyphase form: four phases per tile, a short last
+    # phase, rows past the end
+    "poly4": (2357, (49,), False),
+    # 224 rows per phase, the smallest length with one phase per tile
+    "poly1": (10987, (49,), False),
 }
 _CACHE = {}
 
@@ -111,7 +117,8 @@ def _fused(args):
 @pytest.mark.parametrize("name", list(CASES))
 def test_fused_launch_vs_separate_launches_and_float64(name):
     """Relative L2 against float64 measured on the MI355X, fused / separate: poly 2.113e-07 / 2.113e-07, contiguous
-    2.134e-07 / 2.141e-07, pair 2.472e-07 / 2.471e-07, pair-glu 2.526e-07 / 2.522e-07; the finalised statistics differ
+    2.134e-07 / 2.141e-07, pair 2.472e-07 / 2.471e-07, pair-glu 2.526e-07 / 2.522e-07, poly4 2.105e-07 / 2.105e-07,
+    poly1 2.124e-07 / 2.123e-07; the finalised statistics differ
     from the separate path's by at most 1.2e-07 relative."""
     args, want, raw_sep, mr_sep = _case(name)
     raw, st, mr = _fused(args)
