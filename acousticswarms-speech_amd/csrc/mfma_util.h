@@ -68,8 +68,11 @@ __device__ __forceinline__ void split4(const float4 x, half4& hi, half4& lo) {
 // Single-pass f16 mode (precision 2: one MFMA per product, the hi halves only): the hi half is rounded to
 // nearest instead of truncated -- with no lo half to catch the remainder, truncation would bias every
 // product low by ~2^-12.  lo is still produced (the C = 64 residual layer reads its residual from the image).
+// The plain conversion turns |x| >= 65520 into inf (and the remainder x - inf into NaN), so x is clamped to the fp16
+// range first (one v_med3_f32 per element): finite overflow saturates at +-65504 here as it does in split4.
+__device__ __forceinline__ _Float16 rn_sat(float x) { return (_Float16)__builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
 __device__ __forceinline__ void split4_rn(const float4 x, half4& hi, half4& lo) {
-  const _Float16 h0 = (_Float16)x.x, h1 = (_Float16)x.y, h2 = (_Float16)x.z, h3 = (_Float16)x.w;
+  const _Float16 h0 = rn_sat(x.x), h1 = rn_sat(x.y), h2 = rn_sat(x.z), h3 = rn_sat(x.w);
   const fp16x2 l01 = __builtin_amdgcn_cvt_pkrtz(x.x - (float)h0, x.y - (float)h1);
   const fp16x2 l23 = __builtin_amdgcn_cvt_pkrtz(x.z - (float)h2, x.w - (float)h3);
   hi = half4{h0, h1, h2, h3};

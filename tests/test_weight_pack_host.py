@@ -6,20 +6,7 @@ import numpy as np
 import pytest
 
 from acousticswarms_speech_amd.native import lib
-
-
-def split_np(w):
-    """shift = 11 - exponent of max|w| (frexp), clamped to +-24, 0 for all-zero weights; scale, clamp to the fp16
-    range; hi = float16(c), lo = float16(c - float32(hi)), as uint16 bit patterns."""
-    w = np.asarray(w, dtype=np.float32).ravel()
-    mx = np.float32(np.max(np.abs(w)))
-    shift = 0
-    if mx > 0:
-        shift = int(np.clip(11 - int(np.frexp(mx)[1]), -24, 24))
-    c = np.clip(w * np.float32(2.0 ** shift), np.float32(-65504.0), np.float32(65504.0)).astype(np.float32)
-    hi = c.astype(np.float16)
-    lo = (c - hi.astype(np.float32)).astype(np.float16)
-    return hi.view(np.uint16), lo.view(np.uint16), shift
+from tests.f16_model import split_np      # the numpy statement of the split (shared with the kernels' CPU model)
 
 
 def pack_np(w, N, K):
