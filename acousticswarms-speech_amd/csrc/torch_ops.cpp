@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -834,6 +835,70 @@ Tensor stitch_blocks(const Tensor& rows, const Tensor& taper, at::IntArrayRef st
   return out;
 }
 
+// ---- STFT, inverse STFT and the oracle mask baselines (oracle_masks.py) -------------------------------------------------
+// -> complex128 [R, 1025, F], F = ceil(N / 1024) + 1 (oracle_masks.stft_f64)
+Tensor stft(const Tensor& x) {
+  need(x, "x", at::kFloat, 2);
+  const int R = checked_int(x.size(0), "R"), N = checked_int(x.size(1), "N");
+  TORCH_CHECK(R <= 65535, "stft: ", R, " rows (at most 65535)");
+  TORCH_CHECK(N >= 2048 && N <= (1 << 25), "stft: N = ", N, " outside 2048..2^25");
+  const int64_t F = (N + 1023) / 1024 + 1;
+  Tensor z = at::empty({R, 1025, F}, x.options().dtype(at::kComplexDouble));
+  if (R == 0) return z;
+  Launch l(x);
+  check_status(asw_stft(x.data_ptr<float>(), R, N, reinterpret_cast<double*>(z.data_ptr()), l.stream), "asw_stft");
+  return z;
+}
+
+// -> float64 [R, n]: the first n samples of the inverse STFT of z [R, 1025, F] (oracle_masks.istft_f64)
+Tensor istft(const Tensor& z, int64_t n) {
+  need(z, "z", at::kComplexDouble, 3);
+  const int R = checked_int(z.size(0), "R"), F = checked_int(z.size(2), "F"), N = checked_int(n, "n");
+  TORCH_CHECK(z.size(1) == 1025, "z must be [R, 1025, F], got [R, ", z.size(1), ", F]");
+  TORCH_CHECK(R <= 65535 && F >= 2 && F <= (1 << 15) + 1, "istft: R = ", R, " (at most 65535) or F = ", F, " outside 2..32769");
+  TORCH_CHECK(N >= 0 && N <= (F - 1) * 1024, "istft: n = ", N, " outside 0..", (F - 1) * 1024, ", what ", F, " frames cover");
+  Tensor out = at::empty({R, N}, z.options().dtype(at::kDouble));
+  if (R == 0 || N == 0) return out;
+  const size_t ws_bytes = asw_istft_workspace_bytes(R, F);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_istft_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, z.options().dtype(at::kDouble));
+  Launch l(z);
+  check_status(asw_istft(reinterpret_cast<const double*>(z.data_ptr()), R, F, N, out.data_ptr<double>(), ws.data_ptr(), ws_bytes,
+                         l.stream),
+               "asw_istft");
+  return out;
+}
+
+// -> float64 [sum counts, T]: the ideal ratio ("irm") or ideal binary ("ibm") mask estimates of K items, item k one row
+// of mix [K, T], the next counts[k] rows of ref [sum counts, T] and lengths[k] <= T samples; an output row is zero from
+// lengths[k] on (oracle_masks.irm_f64 / ibm_f64 per item).  Both lists are read on the host.
+Tensor oracle_masks(const Tensor& mix, const Tensor& ref, at::IntArrayRef counts, at::IntArrayRef lengths, std::string kind,
+                    double alpha, double theta) {
+  need(mix, "mix", at::kFloat, 2);
+  need(ref, "ref", at::kFloat, 2);
+  same_device(mix, ref, "mix and ref");
+  const int K = checked_int(mix.size(0), "K"), T = checked_int(mix.size(1), "T");
+  TORCH_CHECK(kind == "irm" || kind == "ibm", "oracle_masks: kind must be \"irm\" or \"ibm\", got \"", kind, "\"");
+  TORCH_CHECK(K <= 65535, "oracle_masks: ", K, " items (at most 65535)");
+  TORCH_CHECK(static_cast<int64_t>(counts.size()) == K && static_cast<int64_t>(lengths.size()) == K, "mix holds ", K,
+              " items, counts ", counts.size(), ", lengths ", lengths.size());
+  TORCH_CHECK(ref.size(1) == T, "mix [K, ", T, "] and ref [NR, ", ref.size(1), "] differ in length");
+  TORCH_CHECK(alpha == alpha && theta == theta, "oracle_masks: alpha or theta is not a number");
+  const Counts c = checked_counts(counts, "counts", 0, 64), n = checked_counts(lengths, "lengths", 2048, T);
+  TORCH_CHECK(c.sum == ref.size(0), "counts sum to ", c.sum, ", ref has ", ref.size(0), " rows");
+  Tensor out = at::empty({c.sum, T}, mix.options().dtype(at::kDouble));
+  if (K == 0 || c.sum == 0) return out;
+  const size_t ws_bytes = asw_oracle_masks_workspace_bytes(c.v.data(), n.v.data(), K);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_oracle_masks_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, mix.options().dtype(at::kDouble));
+  Launch l(mix);
+  check_status(asw_oracle_masks(mix.data_ptr<float>(), ref.data_ptr<float>(), c.v.data(), n.v.data(), K, T,
+                                kind == "irm" ? ASW_ORACLE_IRM : ASW_ORACLE_IBM, alpha, theta, out.data_ptr<double>(), ws.data_ptr(),
+                                ws_bytes, l.stream),
+               "asw_oracle_masks");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(asw, m) {
@@ -881,6 +946,10 @@ TORCH_LIBRARY(asw, m) {
   m.def("sep_forward_counts(int model, Tensor mix, int[] counts, int n_mics, int max_speakers) -> Tensor");
   m.def("frame_blocks(Tensor mix, int[] starts, int T) -> Tensor");
   m.def("stitch_blocks(Tensor rows, Tensor taper, int[] starts, int[] row_of, int Ttot) -> Tensor");
+  m.def("stft(Tensor x) -> Tensor");
+  m.def("istft(Tensor z, int n) -> Tensor");
+  m.def("oracle_masks(Tensor mix, Tensor ref, int[] counts, int[] lengths, str kind, float alpha=1.0, float theta=0.5) -> "
+        "Tensor");
 }
 
 TORCH_LIBRARY_IMPL(asw, CUDA, m) {
@@ -916,4 +985,7 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("sep_forward_counts", &sep_forward_counts);
   m.impl("frame_blocks", &frame_blocks);
   m.impl("stitch_blocks", &stitch_blocks);
+  m.impl("stft", &stft);
+  m.impl("istft", &istft);
+  m.impl("oracle_masks", &oracle_masks);
 }

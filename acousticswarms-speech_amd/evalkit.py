@@ -491,40 +491,124 @@ def cross_sisdr_batch(est_list, ref_list, device=None, op=None):
     return out, sorted(recomputed)
 
 
-def compute_metrics(input_signal, est_signal, gt, metrics="host", bss="sdr"):
+# ---- oracle mask baselines on the device (csrc/stft_kernels.hip: asw_oracle_masks) ---------------
+ORACLES = ("irm", "ibm")                # the reference's two baselines (sep/helpers/irm.py, ibm.py)
+
+
+def check_oracle(oracle):
+    """``oracle`` as a tuple of baseline names without repeats, in the order given; an unknown name raises."""
+    names = (oracle,) if isinstance(oracle, str) else tuple(oracle)
+    for name in names:
+        if name not in ORACLES:
+            raise ValueError(f"oracle baselines must be among {ORACLES}, got {name!r}")
+    return tuple(dict.fromkeys(names))
+
+
+def oracle_masks_batch(refs, mixes, kind, alpha: float = 1.0, theta: float = 0.5, device=None, op=None):
+    """``oracle_masks.irm_f64`` / ``ibm_f64`` (``kind`` "irm" / "ibm") of many items on the device.  ``refs[k]`` is
+    [S_k, N_k], ``mixes[k]`` is [N_k]; counts and lengths may differ from item to item.  The rows are rounded to
+    float32 (exact for wav and network output) and the items of one length go out in ONE ``torch.ops.asw.oracle_masks``
+    call (at most 65535 items each), as ``cross_sisdr_batch`` groups.  -> list of [S_k, N_k] float64 arrays in item
+    order; an item without references gives a [0, N_k] array and is not sent.  ``theta`` counts for "ibm" only.  ``op``
+    replaces the device op (a stand-in on CPU tensors in the host tests); without it a missing library or GPU is a
+    ``RuntimeError``."""
+    import torch
+    from .oracle_masks import NFFT, check_kind
+    check_kind(kind)
+    if len(refs) != len(mixes):
+        raise ValueError(f"{len(mixes)} mixtures for {len(refs)} reference sets")
+    if not refs:
+        return []
+    refs = [np.ascontiguousarray(r, dtype=np.float32) for r in refs]
+    mixes = [np.ascontiguousarray(m, dtype=np.float32) for m in mixes]
+    by_length = {}
+    for k, (r, m) in enumerate(zip(refs, mixes)):
+        if r.ndim != 2 or m.ndim != 1 or r.shape[1] != m.shape[0]:
+            raise ValueError(f"item {k}: references {r.shape} and mixture {m.shape} are not [S, N] and [N]")
+        if r.shape[0] > XS_MAX_REF:
+            raise ValueError(f"item {k}: {r.shape[0]} references (at most {XS_MAX_REF})")
+        if m.shape[0] < NFFT:
+            raise ValueError(f"item {k}: {m.shape[0]} samples are fewer than the window of {NFFT}")
+        if r.shape[0] > 0:
+            by_length.setdefault(m.shape[0], []).append(k)
+    out = [np.zeros(r.shape) for r in refs]
+    if not by_length:
+        return out
+    op, dev = _device_op("oracle_masks", device, op)
+    for N, members in by_length.items():
+        for first in range(0, len(members), XS_MAX_ITEMS):
+            ks = members[first:first + XS_MAX_ITEMS]
+            mix = torch.from_numpy(np.stack([mixes[k] for k in ks])).to(dev)
+            ref = torch.from_numpy(np.concatenate([refs[k] for k in ks], axis=0)).to(dev)
+            rows = op(mix, ref, [refs[k].shape[0] for k in ks], [N] * len(ks), kind, float(alpha), float(theta)).cpu().numpy()
+            pos = 0
+            for k in ks:
+                S = refs[k].shape[0]
+                out[k] = np.array(rows[pos:pos + S], dtype=np.float64)
+                pos += S
+    return out
+
+
+def oracle_estimates(gt, mix_row, oracle, metrics="host", op=None):
+    """{name: [S, N] float32} for the baselines of ``oracle``: the mask estimates of every ground truth of one sample
+    (references ``gt`` [S, N] in ground-truth order, mixture ``mix_row`` [N]) from the statements (``metrics="host"``) or
+    from one ``oracle_masks_batch`` call per baseline, rounded to float32 -- what every scoring op here reads."""
+    from .oracle_masks import masks_f64
+    if metrics == "host":
+        return {name: masks_f64(gt, mix_row, name).astype(np.float32) for name in oracle}
+    return {name: oracle_masks_batch([gt], [mix_row], name, op=op)[0].astype(np.float32) for name in oracle}
+
+
+def compute_metrics(input_signal, est_signal, gt, metrics="host", bss="sdr", oracle=(), oracle_est=None):
     """(input_sdr, output_sdr, input_sisdr, output_sisdr) per matched talker, as
     sep/eval/get_items.py:46-70 with permute=False: BSS-eval SDR and SI-SDR of the unprocessed
     reference-microphone signal and of the separated output against the ground truth.
     ``metrics="device"`` takes the two BSS-eval SDRs from one ``bss_eval_sdr_device`` call (R = 2: the
     unprocessed set and the separated set); the signals are read as float32 there.  ``bss="all"`` appends a fifth
     entry, ``(input_sir, output_sir, input_sar, output_sar)``, from ``bss_eval_sources`` (host) or one
-    ``bss_eval_sources_device`` call (device), which then gives the two SDRs as well."""
+    ``bss_eval_sources_device`` call (device), which then gives the two SDRs as well.
+    ``oracle``: baseline names (``ORACLES``); a last entry is then appended, {name: (sdr, sisdr)} -- the BSS-eval SDR and
+    the SI-SDR of the baseline's estimates against ``gt``, row for row.  ``oracle_est`` holds the estimates {name: [n, T]},
+    one row per row of ``gt`` (``record_from_result`` picks them from the masks of the sample's whole ground truth);
+    without it they are ``oracle_estimates(gt, input_signal[0], ...)``.  On the device the baselines' rows join the same
+    BSS call as further estimate sets."""
     check_metrics(metrics)
     check_bss(bss)
+    oracle = check_oracle(oracle)
     gt = np.asarray(gt, dtype=np.float64)
     inp = np.asarray(input_signal, dtype=np.float64)
     est = np.asarray(est_signal, dtype=np.float64)
+    if oracle and oracle_est is None:
+        oracle_est = oracle_estimates(gt, inp[0], oracle, metrics)
+    extra = [np.asarray(oracle_est[name], dtype=np.float64) for name in oracle]
     input_sisdr = [si_sdr(inp[i], gt[i]) for i in range(gt.shape[0])]
     output_sisdr = [si_sdr(est[i], gt[i]) for i in range(gt.shape[0])]
     if metrics == "host":
-        sdr, sir, sar = (np.stack(v) for v in zip(bss_eval_sources(gt, inp)[:3], bss_eval_sources(gt, est)[:3]))
+        sdr, sir, sar = (np.stack(v) for v in zip(*(bss_eval_sources(gt, rows)[:3] for rows in (inp, est, *extra))))
     elif bss == "all":
-        sdr, sir, sar, _perm = bss_eval_sources_device(gt, np.stack([inp, est]))
+        sdr, sir, sar, _perm = bss_eval_sources_device(gt, np.stack([inp, est, *extra]))
     else:
-        sdr = bss_eval_sdr_device(gt, np.stack([inp, est]))
+        sdr = bss_eval_sdr_device(gt, np.stack([inp, est, *extra]))
     out = (sdr[0], sdr[1], input_sisdr, output_sisdr)
-    return out + ((sir[0], sir[1], sar[0], sar[1]),) if bss == "all" else out
+    if bss == "all":
+        out += ((sir[0], sir[1], sar[0], sar[1]),)
+    if oracle:
+        out += ({name: (sdr[2 + q], [si_sdr(rows[i], gt[i]) for i in range(gt.shape[0])])
+                 for q, (name, rows) in enumerate(zip(oracle, extra))},)
+    return out
 
 
 # ---- one sample --------------------------------------------------------------------------------
-def evaluate_sample(model, metadata, mix, gt, metrics="host", bss="sdr"):
+def evaluate_sample(model, metadata, mix, gt, metrics="host", bss="sdr", oracle=()):
     """Run ``model`` (a ``JointModel``) on one sample and build the reference's result record
     (sep/eval/eval_model.py:129-236).  Returns (record, tp, fp, fn).  ``metrics``: "host" or "device", where the
     record's two BSS-eval SDR fields come from (``compute_metrics``).  ``bss``: "sdr" (the record as it was) or "all"
-    (``sir_in_mir``, ``sir_mir``, ``sar_in_mir``, ``sar_mir`` added to every matched talker's entry)."""
+    (``sir_in_mir``, ``sir_mir``, ``sar_in_mir``, ``sar_mir`` added to every matched talker's entry).  ``oracle``: the
+    oracle mask baselines to score next to the output, as in ``record_from_result``; () leaves the record as it was."""
     check_metrics(metrics)
     check_bss(bss)
-    return record_from_result(metadata, mix, gt, search_result(model, metadata, mix), metrics, bss=bss)
+    oracle = check_oracle(oracle)
+    return record_from_result(metadata, mix, gt, search_result(model, metadata, mix), metrics, bss=bss, oracle=oracle)
 
 
 def search_result(model, metadata, mix):
@@ -550,7 +634,7 @@ def _separated(result):
     return result["audio_loc"] if audio is None else np.asarray(audio)
 
 
-def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, bss="sdr"):
+def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, bss="sdr", oracle=()):
     """The second step of ``evaluate_sample``: the reference's result record (sep/eval/eval_model.py:129-236) from what
     the search returned (``search_result``, or a dict of ``shard.localize_batch(..., details=True)``).  Returns
     (record, tp, fp, fn).  Without ``scores`` every SI-SDR is ``hostdsp.si_sdr`` on the host and ``metrics`` says where
@@ -560,9 +644,16 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, b
     ``"bss"``, the BSS-eval SDRs of the unprocessed and of the separated set, one row of ``matched`` values each.
     ``bss="all"`` adds four fields to every matched talker's entry: ``sir_in_mir`` / ``sar_in_mir`` of the unprocessed
     set and ``sir_mir`` / ``sar_mir`` of the separated set, the raw values and no differences (one talker has SIR +inf on
-    both sides); ``scores["bss"]`` then holds their four rows too, after the two SDR rows and in the fields' order."""
+    both sides); ``scores["bss"]`` then holds their four rows too, after the two SDR rows and in the fields' order.
+    ``oracle``: names among ``ORACLES``.  For "irm" every matched talker's entry gains ``si_snri_irm`` -- the SI-SDR of the
+    ideal ratio mask's estimate for that ground truth, minus ``si_snr_in`` -- and ``si_snri_mir_irm`` -- its BSS-eval SDR
+    minus ``si_snr_in_mir``; "ibm" likewise.  The masks are those of ``mix[0]`` with the sample's whole ground truth as
+    references, in ground-truth order (``oracle_estimates``: the statements for ``metrics="host"``, the device
+    otherwise), rounded to float32 and scored as the separated output is; ``scores["oracle"]`` holds them ready-made as
+    {name: (sdr row, sisdr row)} of ``matched`` values.  With () the record is what it was."""
     check_metrics(metrics)
     check_bss(bss)
+    oracle = check_oracle(oracle)
     _mics, mic_positions, _voices, gt_pos, offsets_gt, roi = preprocess_metadata(metadata)
     est_pos, audio_loc, sep_audio = result["centres"], result["audio_loc"], _separated(result)
     n_out = len(est_pos)
@@ -579,8 +670,9 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, b
     unmatched = list(range(n_out))
     # cols: per matched pair the SDR of the unprocessed and of the separated set, their SI-SDRs, the SI-SDR of the
     # localisation stage and, with bss="all", the four SIR / SAR values in the order of the fields below
-    cols = []
+    cols, oracle_cols = [], {}
     if perm and scores is not None:
+        oracle_cols = scores.get("oracle") or {}
         M, loc0 = scores["sisdr"], 1 + (n_out if result.get("audio") is not None else 0)
         cols = [*scores["bss"][:2], [float(M[0, s]) for _o, s in perm], [float(M[1 + o, s]) for o, s in perm],
                 [float(M[loc0 + o, s]) for o, s in perm], *scores["bss"][2:]]
@@ -589,9 +681,11 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, b
         # decoder when attached), localisation-stage output, ground truth, unprocessed mic 0
         pa = np.array(perm)
         ref_sig = np.repeat(mix[0:1].astype(np.float64), len(perm), axis=0)
-        m = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics, bss)
+        picked = {name: rows[pa[:, 1]] for name, rows in oracle_estimates(gt, mix[0], oracle, metrics).items()}
+        m = compute_metrics(ref_sig, sep_audio[pa[:, 0]], gt[pa[:, 1]], metrics, bss, oracle, picked)
         loc_sisdr = [si_sdr(audio_loc[o].astype(np.float64), gt[s].astype(np.float64)) for o, s in perm]
         cols = [*m[:4], loc_sisdr, *(m[4] if bss == "all" else ())]
+        oracle_cols = m[-1] if oracle else {}
     for i, (out_id, s) in enumerate(perm):
         unmatched.remove(out_id)
         in_sdr, out_sdr, in_sisdr, out_sisdr, loc_sisdr, *extra = (c[i] for c in cols)
@@ -604,14 +698,16 @@ def record_from_result(metadata, mix, gt, result, metrics="host", scores=None, b
             "si_snri": out_sisdr - in_sisdr,
             "si_snr_in_old": in_sisdr,
             "si_snri_old": loc_sisdr - in_sisdr,
-            **{k: float(v) for k, v in zip(("sir_in_mir", "sir_mir", "sar_in_mir", "sar_mir"), extra)}})
+            **{k: float(v) for k, v in zip(("sir_in_mir", "sir_mir", "sar_in_mir", "sar_mir"), extra)},
+            **{f"si_snri{kind}_{name}": float(oracle_cols[name][q][i] - base)
+               for name in oracle for q, kind, base in ((1, "", in_sisdr), (0, "_mir", in_sdr))}})
     for rid in unmatched:
         rec["false_positive"].append({"pos": est_pos[rid].tolist(),
                                       "sample": np.asarray(result["audio_offsets"][rid]).tolist()})
     return rec, tp, fp, fn
 
 
-def records_from_results(samples, results, metrics="host", ops=None, stats=None, bss="sdr"):
+def records_from_results(samples, results, metrics="host", ops=None, stats=None, bss="sdr", oracle=()):
     """The records of a batch: ``samples[k]`` = (metadata, mix, gt) as ``get_items`` reads them, ``results[k]`` what the
     search returned for it (``search_result`` / ``shard.localize_batch(..., details=True)``).  -> [(record, tp, fp, fn)]
     in sample order.  ``metrics="host"``: ``record_from_result`` per sample, the host statements throughout.
@@ -624,21 +720,34 @@ def records_from_results(samples, results, metrics="host", ops=None, stats=None,
          with ``bss="all"`` ONE ``bss_eval_sources_batch`` call in its place (the BSS stand-in of ``ops`` then has that
          op's signature).
     ``ops``: stand-ins (cross op, BSS op) for the two device ops (host tests).  ``stats``: a dict that receives the
-    seconds of the steps (``"sisdr_s"``, ``"match_s"``, ``"bss_s"``)."""
+    seconds of the steps (``"sisdr_s"``, ``"match_s"``, ``"bss_s"``).
+    ``oracle``: baseline names as in ``record_from_result``.  On the device ONE ``oracle_masks_batch`` call per baseline
+    comes first and covers every sample; its rows, rounded to float32, are appended to the estimate rows of step 1 (one
+    per ground truth) and, picked by the matching, to the estimate sets of step 3 (R = 2 + the baselines): the number of
+    device calls grows by the oracle calls only.  ``ops`` may then carry a third stand-in, for the oracle op, and
+    ``stats`` receives ``"oracle_s"`` too."""
     import time
     check_metrics(metrics)
     check_bss(bss)
+    oracle = check_oracle(oracle)
     if len(samples) != len(results):
         raise ValueError(f"{len(results)} results for {len(samples)} samples")
     if metrics == "host":
-        return [record_from_result(meta, mix, gt, res, "host", bss=bss) for (meta, mix, gt), res in zip(samples, results)]
-    cross_op, bss_op = ops if ops is not None else (None, None)
+        return [record_from_result(meta, mix, gt, res, "host", bss=bss, oracle=oracle)
+                for (meta, mix, gt), res in zip(samples, results)]
+    cross_op, bss_op, *more_ops = ops if ops is not None else (None, None)
+    t_start = time.perf_counter()
+    masks = {name: [rows.astype(np.float32) for rows in
+                    oracle_masks_batch([gt for _meta, _mix, gt in samples], [mix[0] for _meta, mix, _gt in samples], name,
+                                       op=more_ops[0] if more_ops else None)] for name in oracle}
     t0 = time.perf_counter()
-    est_rows = []
-    for (_meta, mix, _gt), res in zip(samples, results):
+    est_rows, oracle_row0 = [], []
+    for k, ((_meta, mix, _gt), res) in enumerate(zip(samples, results)):
         rows = [np.asarray(mix[0:1], dtype=np.float32), np.asarray(_separated(res), dtype=np.float32)]
         if res.get("audio") is not None:
             rows.append(np.asarray(res["audio_loc"], dtype=np.float32))
+        oracle_row0.append(sum(r.reshape(-1, mix.shape[1]).shape[0] for r in rows))
+        rows += [masks[name][k] for name in oracle]
         est_rows.append(np.concatenate([r.reshape(-1, mix.shape[1]) for r in rows], axis=0))
     mats, _ = cross_sisdr_batch(est_rows, [gt for _meta, _mix, gt in samples], op=cross_op)
     t1 = time.perf_counter()
@@ -655,17 +764,26 @@ def records_from_results(samples, results, metrics="host", ops=None, stats=None,
         (_meta, mix, gt), pa = samples[k], np.array(perms[k])
         ref_sig = np.repeat(np.asarray(mix[0:1], dtype=np.float32), len(pa), axis=0)
         refs.append(np.asarray(gt)[pa[:, 1]])
-        sets.append(np.stack([ref_sig, np.asarray(_separated(results[k]), dtype=np.float32)[pa[:, 0]]]))
+        sets.append(np.stack([ref_sig, np.asarray(_separated(results[k]), dtype=np.float32)[pa[:, 0]],
+                              *(masks[name][k][pa[:, 1]] for name in oracle)]))
     if bss == "all":
         vals, _ = bss_eval_sources_batch(refs, sets, op=bss_op)
-        scored = {k: (*sdr, *sir, *sar) for k, (sdr, sir, sar, _perm) in zip(matched, vals)}
+        scored = {k: (*sdr[:2], *sir[:2], *sar[:2]) for k, (sdr, sir, sar, _perm) in zip(matched, vals)}
+        sdrs = {k: sdr for k, (sdr, _sir, _sar, _perm) in zip(matched, vals)}
     else:
         vals, _ = bss_eval_sdr_batch(refs, sets, op=bss_op)
-        scored = {k: tuple(sdr) for k, sdr in zip(matched, vals)}
+        scored = {k: tuple(sdr[:2]) for k, sdr in zip(matched, vals)}
+        sdrs = dict(zip(matched, vals))
+    # per baseline the SDR row of its estimate set and the diagonal entries of its block of the SI-SDR matrix
+    oracle_scores = {k: {name: (sdrs[k][2 + q], [float(mats[k][oracle_row0[k] + q * len(samples[k][2]) + s, s])
+                                                 for _o, s in perms[k]]) for q, name in enumerate(oracle)} for k in matched}
     if stats is not None:
         stats.update(sisdr_s=t1 - t0, match_s=t2 - t1, bss_s=time.perf_counter() - t2)
+        if oracle:
+            stats.update(oracle_s=t0 - t_start)
     return [record_from_result(meta, mix, gt, res, "device",
-                               {"sisdr": mats[k], "perm": perms[k], "bss": scored.get(k)}, bss=bss)
+                               {"sisdr": mats[k], "perm": perms[k], "bss": scored.get(k), "oracle": oracle_scores.get(k)},
+                               bss=bss, oracle=oracle)
             for k, ((meta, mix, gt), res) in enumerate(zip(samples, results))]
 
 
@@ -684,9 +802,10 @@ def group_samples(shapes, batch):
 
 
 def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", batch=1, concurrent=2, stats=None,
-                     bss="sdr"):
+                     bss="sdr", oracle=()):
     """Every sample directory of ``dataset_dir``; writes ``result_<sample>.json`` like the
-    reference and returns overall (tp, fp, fn, precision, recall).  ``metrics`` and ``bss`` as in ``evaluate_sample``.
+    reference and returns overall (tp, fp, fn, precision, recall).  ``metrics``, ``bss`` and ``oracle`` as in
+    ``evaluate_sample``.
 
     ``batch=1``: one ``evaluate_sample`` per directory.  ``batch=N``: the directories in sorted order, consecutive
     samples of equal (M, T) in calls of at most N (``group_samples``); a call is ONE
@@ -696,10 +815,13 @@ def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", ba
     import time
     check_metrics(metrics)
     check_bss(bss)
+    oracle = check_oracle(oracle)
     if batch < 1:
         raise ValueError(f"batch = {batch} < 1")
     tot = np.zeros(3, dtype=np.int64)
     spent = {"read_s": 0.0, "search_s": 0.0, "sisdr_s": 0.0, "match_s": 0.0, "bss_s": 0.0, "record_s": 0.0, "write_s": 0.0}
+    if oracle:
+        spent["oracle_s"] = 0.0
 
     def write(name, rec, tp, fp, fn):
         tot[:] += (tp, fp, fn)
@@ -724,7 +846,7 @@ def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", ba
                                  separate=model.sep_model is not None, details=True, concurrent=concurrent)
         t1 = time.perf_counter()
         step = {}
-        records = records_from_results(samples, results, metrics, stats=step, bss=bss)
+        records = records_from_results(samples, results, metrics, stats=step, bss=bss, oracle=oracle)
         spent["search_s"] += t1 - t0
         spent["record_s"] += time.perf_counter() - t1
         for key, value in step.items():
@@ -741,7 +863,7 @@ def evaluate_dataset(model, dataset_dir, results_folder=None, metrics="host", ba
             t0 = time.perf_counter()                         # evaluate_sample, its two steps timed apart
             result = search_result(model, metadata, mix)
             t1 = time.perf_counter()
-            rec, tp, fp, fn = record_from_result(metadata, mix, gt, result, metrics, bss=bss)
+            rec, tp, fp, fn = record_from_result(metadata, mix, gt, result, metrics, bss=bss, oracle=oracle)
             spent["search_s"] += t1 - t0
             spent["record_s"] += time.perf_counter() - t1
             write(name, rec, tp, fp, fn)

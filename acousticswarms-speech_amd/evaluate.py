@@ -2,6 +2,7 @@
 
     python -m acousticswarms_speech_amd.evaluate DATASET --spot_experiment_dir D --sep_experiment_dir D
         [--results_folder F] [--spot_batch_size 128] [--batch N] [--metrics host|device] [--bss sdr|all]
+        [--oracle irm,ibm]
         [--precision f16x3|f16x3_safe|f32] [--geometry host|device] [--use_cuda] [--cached_init]
 
 Loads both networks with ``experiment.load_model_from_exp``, moves them to the GPU, builds the ``JointModel`` and runs
@@ -10,6 +11,15 @@ Loads both networks with ``experiment.load_model_from_exp``, moves them to the G
 import argparse
 
 PRECISIONS = ("f16x3", "f16x3_safe", "f32")
+
+
+def oracle_names(text):
+    """``--oracle irm,ibm`` -> ("irm", "ibm"); an unknown name is an argparse error."""
+    from .evalkit import check_oracle
+    try:
+        return check_oracle(tuple(n.strip() for n in text.split(",") if n.strip()))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def build_parser():
@@ -33,6 +43,8 @@ def build_parser():
                    help="Where the BSS-eval SDR (and with --batch > 1 the SI-SDR matrices) are computed")
     p.add_argument("--bss", choices=("sdr", "all"), default="sdr",
                    help="BSS-eval fields of the record: the SDR alone, or SIR and SAR of both sets too")
+    p.add_argument("--oracle", type=oracle_names, default=(),
+                   help="Oracle mask baselines to score next to the output, comma-separated: irm, ibm")
     p.add_argument("--precision", choices=PRECISIONS, default="f32", help="Arithmetic of both networks")
     p.add_argument("--geometry", choices=("host", "device"), default="host", help="Where the array geometry is built")
     return p
@@ -50,7 +62,7 @@ def main(argv=None):
     sep = load_model_from_exp(args.sep_experiment_dir, precision=args.precision)
     model = JointModel(spot, sep, device=device, geometry=args.geometry).to(device)
     tot = evalkit.evaluate_dataset(model, args.dataset, args.results_folder, metrics=args.metrics, batch=args.batch,
-                                   bss=args.bss)
+                                   bss=args.bss, oracle=args.oracle)
     print("Overall tp: {}, fp: {}, fn: {}".format(tot["tp"], tot["fp"], tot["fn"]))
     print("Overall Precision: {} Recall: {}".format(tot["precision"], tot["recall"]))
     return tot

@@ -491,6 +491,59 @@ def stitch_blocks(rows, taper, starts, row_of, Ttot, out=None):
     return res
 
 
+def _ws_f64(nbytes, device):
+    return torch.empty(((int(nbytes) + 7) // 8,), dtype=torch.float64, device=device)
+
+
+def stft(x, out=None):
+    """x [R,N] float32 -> complex128 [R,1025,F], the STFT of ``oracle_masks.stft_f64``.  ``out``: write into this
+    tensor (tests)."""
+    from .oracle_masks import NBINS, frame_count
+    R, N = x.shape
+    F = frame_count(N)
+    z = torch.empty((R, NBINS, F), dtype=torch.complex128, device=x.device) if out is None else out
+    assert z.shape == (R, NBINS, F) and z.dtype == torch.complex128 and z.is_cuda and z.is_contiguous()
+    check(lib().asw_stft(ptr(_f32(x)), R, N, ptr(z), current_stream()))
+    return z
+
+
+def istft(z, N, out=None):
+    """z [R,1025,F] complex128 -> [R,N] float64, the inverse STFT of ``oracle_masks.istft_f64``.  ``out``: write into
+    this tensor (tests)."""
+    R, _nb, F = z.shape
+    assert z.is_cuda and z.dtype == torch.complex128 and z.is_contiguous() and _nb == 1025
+    res = torch.empty((R, int(N)), dtype=torch.float64, device=z.device) if out is None else out
+    assert res.shape == (R, int(N)) and res.dtype == torch.float64 and res.is_cuda and res.is_contiguous()
+    nbytes = lib().asw_istft_workspace_bytes(R, F)
+    if nbytes == 0:
+        check(-1)
+    ws = _ws_f64(nbytes, z.device)
+    check(lib().asw_istft(ptr(z), R, F, int(N), ptr(res), ptr(ws), nbytes, current_stream()))
+    return res
+
+
+ORACLE_KINDS = {"irm": 0, "ibm": 1}            # ASW_ORACLE_IRM, ASW_ORACLE_IBM
+
+
+def oracle_masks(mix, ref, counts, lengths, kind, alpha=1.0, theta=0.5, out=None):
+    """The oracle mask estimates of K items in one call (``oracle_masks.irm_f64`` / ``ibm_f64`` per item): mix [K,T] and
+    ref [sum counts,T] float32, ``counts`` and ``lengths`` host integers -> [sum counts,T] float64, row j of item k zero
+    beyond lengths[k].  ``out``: write into this tensor (tests)."""
+    K, T = mix.shape
+    assert len(counts) == K and len(lengths) == K and ref.shape == (sum(int(c) for c in counts), T)
+    res = torch.empty((ref.shape[0], T), dtype=torch.float64, device=mix.device) if out is None else out
+    assert res.shape == (ref.shape[0], T) and res.dtype == torch.float64 and res.is_cuda and res.is_contiguous()
+    c, n = _host_i32(counts), _host_i32(lengths)
+    nbytes = lib().asw_oracle_masks_workspace_bytes(c, n, K)
+    if nbytes == 0:
+        check(-1)
+    ws = _ws_f64(nbytes, mix.device)
+    check(lib().asw_oracle_masks(ptr(_f32(mix)), ptr(_f32(ref)) if ref.shape[0] else None, c, n, K, T, ORACLE_KINDS[kind],
+                                 float(alpha), float(theta), ptr(res) if ref.shape[0] else None, ptr(ws), nbytes,
+                                 current_stream()))
+    return res
+
+
 def f16x3_overflow_count(reset=True) -> int:
     """Threads of f16x3 launches that produced an activation beyond the fp16 range since the last
     reset (asw_f16x3_overflow_count); 0 means no later GEMM clipped its input."""

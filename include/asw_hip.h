@@ -1021,6 +1021,56 @@ int asw_frame_blocks(const float* mix, int M, int Ttot, const int32_t* starts, i
 int asw_stitch_blocks(const float* rows, int N, const double* taper, const int32_t* starts, const int32_t* row_of, int K,
                       int S, int T, int Ttot, float* out, void* stream);
 
+/* ---- STFT, inverse STFT and the oracle mask baselines (oracle_masks.py) ---------------------
+ * The transform pair of scipy.signal.stft(x, nperseg=2048) / scipy.signal.istft(Z) with every other argument at its
+ * default, in float64: periodic Hann window w[n] = 0.5 - 0.5 cos(2 pi n / 2048), hop 1024, 1025 one-sided bins, the
+ * signal extended by 1024 zeros on each side and zero-padded to a whole hop, F = ceil(N / 1024) + 1 frames, every
+ * spectrum divided by sum(w); backwards the one-sided inverse transform (the imaginary parts of bins 0 and 1024 do not
+ * count) times w sum(w), overlap-added, divided by the overlap-added w^2 -- a table of 1024 values, periodic in the hop,
+ * as every kept sample lies in exactly two frames -- and trimmed by 1024 samples at both ends.  The statements are
+ * oracle_masks.stft_f64 and istft_f64; only the order of the sums inside a transform differs from them.
+ *   A workgroup owns one frame: the 2048 windowed samples as 1024 complex values, a 1024-point radix-2 Stockham
+ *   transform between two LDS buffers (self-sorting), and a split pass into the 1025 bins; the inverse runs the three
+ *   steps backwards.  Twiddles and windows come from a float64 table that the host builds once per device (one
+ *   hipMalloc and one blocking copy of 57 KB at the first call on that device; never freed).  The overlap-add has one
+ *   writer per output sample, which gathers its two frames: no atomics, two calls give identical bytes.
+ * Every pointer is device memory unless it says HOST; calls launch on `stream` and synchronise nothing; every refusal
+ * happens on the host before the first launch.  Lengths below 2048 are refused (scipy would shrink the window).
+ *
+ * asw_stft: x float32 [R][N] -> z complex128 [R][1025][F] (re, im interleaved; 16-byte aligned), F = ceil(N/1024) + 1.
+ *   0 <= R <= 65535, 2048 <= N <= 2^25; R = 0 succeeds and touches nothing.
+ * asw_istft: z complex128 [R][1025][F] -> out float64 [R][N], the first N samples of the inverse, 0 <= N <= 1024 (F - 1),
+ *   F >= 2.  workspace: asw_istft_workspace_bytes(R, F) bytes, 16-byte aligned (the windowed time frames, 2048 doubles
+ *   per row and frame, behind one small table that a host-to-device copy on the stream fills).
+ *
+ * asw_oracle_masks: the ideal ratio mask (kind ASW_ORACLE_IRM) or ideal binary mask (ASW_ORACLE_IBM) estimates of K
+ * items in one launch sequence (oracle_masks.irm_f64 / ibm_f64 per item).  Item k is one mixture row, S_k =
+ * counts_host[k] reference rows and a length N_k = lengths_host[k]; both lists are HOST arrays read before the call
+ * returns.  mix float32 [K][stride], ref float32 [sum S_k][stride] with item k owning the next S_k rows, out float64
+ * [sum S_k][stride] in the same row order: out row j of item k holds the N_k samples of the estimate for reference j,
+ * then zeros up to the stride; samples of mix and ref beyond N_k are never read.  With X the STFT of the mixture and S_j
+ * those of the references, eps = 2^-52:
+ *   IRM  mask_j = |S_j|^alpha / (eps + sum_k |S_k|^alpha), the sum in reference order starting from eps;
+ *   IBM  r_j = |S_j|^alpha / (eps + |X|^alpha), mask_j = 1 where r_j >= theta, else 0;
+ *   the estimate is the inverse STFT of X mask_j.  alpha == 1 takes |.| as it is, any other alpha goes through pow.
+ *   First launch, a workgroup per (frame, item): it transforms the mixture's frame and keeps the spectrum in LDS, for
+ *   the IRM transforms every reference once to sum the denominator, then transforms reference after reference (again),
+ *   forms the mask, and inverse-transforms X mask_j; the windowed time frames go to the workspace, no spectrum does.
+ *   Second launch: the overlap-add, normalisation and trim, one thread per output sample.
+ * workspace: asw_oracle_masks_workspace_bytes(counts_host, lengths_host, K) bytes, 16-byte aligned; a multiple of 8; 0
+ * with the error message set for arguments this call would refuse.  Refused: a null pointer with work to do, K < 0 or
+ * K > 65535, S_k < 0 or S_k > 64, N_k < 2048 or N_k > 2^25 or N_k > stride, a kind that is neither, alpha or theta not
+ * a number, a short or misaligned workspace.  K = 0 succeeds and touches nothing; an item with S_k = 0 rides along. */
+#define ASW_ORACLE_IRM 0
+#define ASW_ORACLE_IBM 1
+int asw_stft(const float* x, int R, int N, double* z, void* stream);
+size_t asw_istft_workspace_bytes(int R, int F);
+int asw_istft(const double* z, int R, int F, int N, double* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t asw_oracle_masks_workspace_bytes(const int32_t* counts_host, const int32_t* lengths_host, int K);
+int asw_oracle_masks(const float* mix, const float* ref, const int32_t* counts_host, const int32_t* lengths_host, int K,
+                     int stride, int kind, double alpha, double theta, double* out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
