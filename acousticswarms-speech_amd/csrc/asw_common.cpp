@@ -97,7 +97,7 @@ extern "C" int asw_pack_up_feed_f16(const float* Wt, int N, int K, uint16_t* hi,
   return rc;
 }
 
-// ---- residue-image A feed: the schedule of pipe_mainloop_res, enumerated on the host ----
+// ---- residue-image A feed: the residue walk of pipe_mainloop, enumerated on the host ----
 namespace asw {
 bool residue_feed_on() {                  // like ASW_NO_RESSTACK: set to anything, "0" included, means off
   static const bool off = getenv("ASW_NO_RESIDUE_FEED") != nullptr;

@@ -48,7 +48,7 @@ struct SmemAttr {
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- residue-image A feed (include/asw_hip.h: asw_residue_schedule).  The formulae of the schedule, written once:
-// the host enumeration (asw_common.cpp) and the device loop (pipe_mainloop_res, pipegemm.hip) both go through them.
+// the host enumeration (asw_common.cpp) and the device loop (pipe_mainloop, pipegemm.hip) both go through them.
 #ifdef __HIPCC__
 #define ASW_HOST_DEVICE __host__ __device__
 #else
@@ -67,12 +67,20 @@ inline bool residue_feed_applies(int taps, int stride, int dil, int Cin, int BK,
   return dil == 1 && stride >= 2 && taps > stride && BK > 0 && BK % 16 == 0 && Cin > 0 && Cin % BK == 0 && !skip;
 }
 bool residue_feed_on();                                    // false when ASW_NO_RESIDUE_FEED is set, to any value (read once)
-// what the pipelined tiles ask before they take the feed: their ring has ASW_RESIDUE_MAX_SHIFT rows beyond BM per image,
-// and their element offsets are 32-bit (a tile reaches at most BM + 64 rows past a_len)
+// What every launch of a pipelined tile (pipegemm.hip) asks beside a_len < 2^29: the element offsets of its A operand
+// (ResidueA, f16x3_tile.h) are 32-bit.  Past a_len a tile forms offsets of up to BM + ASW_RESIDUE_MAX_SHIFT + NT / KV
+// (= 64) frames of `stride` rows, and the chunk walk adds up to taps * dil rows for the tap: with each product below
+// 2^20 the sum stays below 2^30.  A convolution beyond these goes to the two-barrier 256 x 256 tile (64-bit offsets);
+// the mask path, which has no other kernel, refuses it.  No model comes near them.
+inline bool pipe_offsets_ok(const asw_convgemm_args& a) {
+  return (int64_t)a.stride * a.a_row_stride < (1 << 20) && (int64_t)a.pad * a.a_row_stride < (1 << 20) &&
+         (int64_t)a.taps * a.dil * a.a_row_stride < (1 << 20);
+}
+// what the pipelined tiles ask before they take the residue walk: their ring has ASW_RESIDUE_MAX_SHIFT rows beyond BM
+// per image (every other shape, or every shape under ASW_NO_RESIDUE_FEED, takes the chunk walk)
 inline bool residue_feed_ok(const asw_convgemm_args& a, int BK) {
   return residue_feed_on() && residue_feed_applies(a.taps, a.stride, a.dil, a.Cin, BK, a.A2 != nullptr) &&
-         (a.taps - 1) / a.stride <= ASW_RESIDUE_MAX_SHIFT && a.a_len < ((int64_t)1 << 29) &&
-         (int64_t)a.stride * a.a_row_stride < (1 << 20) && (int64_t)a.pad * a.a_row_stride < (1 << 20);
+         (a.taps - 1) / a.stride <= ASW_RESIDUE_MAX_SHIFT;
 }
 
 #ifdef __HIPCC__

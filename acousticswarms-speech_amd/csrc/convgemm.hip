@@ -457,7 +457,8 @@ extern "C" int asw_convgemm_f32(const asw_convgemm_args* args, void* stream) {
       const int t = wide_tile_kind(a.B, a.M_out, a.N, a.taps * a.Cin);
       // (192-row tiles, i.e. a single row tile per item and a long K, stay on the two-barrier kernel:
       // with so little reuse of a weight fragment the global B path loses, 296 vs 322 TFLOP/s)
-      if (a.Wf_hi && a.Wf_lo && t == 2 && (a.taps * a.Cin) % 16 == 0 && a.N % 32 == 0) return asw::pipe_gemm(a, s);   // pipegemm.hip
+      if (a.Wf_hi && a.Wf_lo && t == 2 && (a.taps * a.Cin) % 16 == 0 && a.N % 32 == 0 && asw::pipe_offsets_ok(a))
+        return asw::pipe_gemm(a, s);                                                                  // pipegemm.hip
       if (t == 3) return launch_variant<GemmTile<192, 256, 2, 4, true>>(a, s);
       if (t == 2) return launch_variant<GemmTile<256, 256, 2, 4, true>>(a, s);
       return launch_variant<GemmTile<128, 128, 2, 2, true>>(a, s);

@@ -1,7 +1,7 @@
 // f16x3_tile.h -- the building blocks the split-fp16 ("f16x3") matrix kernels share (convgemm.hip, pipegemm.hip,
 // resconv.hip, resstack.hip, downconv.hip): the three-term product, the fragment-order weight load, the halo-image row layout with its staging
-// loop, the pinned transposed k-loop, the chunked and the residue-image A operand of the row-major GEMMs and the XCD-aware
-// tile orders.
+// loop, the pinned transposed k-loop, the A operands of the row-major GEMMs (ChunkedA of the two-barrier kernel, ResidueA
+// of the pipelined tiles, one deposit) and the XCD-aware tile orders.
 // Everything is inlined into its caller; a kernel experiment changes one of these instead of a copy per kernel.
 #pragma once
 #include "mfma_util.h"
@@ -173,11 +173,30 @@ __device__ __forceinline__ void kloop(floatx16 (&acc)[NF][CB], int taps, const X
   }
 }
 
-// ------------------------------------------------------------------ chunked A operand (row-major f16 GEMMs)
+// ------------------------------------------------------------------ A operands of the row-major f16 GEMMs
+// Both feeds hold a tile's fp32 rows as float4 v of thread tid = element tid + v * NT of a [ROWS][BK / 4] image, and
+// deposit them split to fp16 hi / lo in rows of LDH = BK + 8 halves.  ROWS bounds the image: only the last float4 of a
+// thread can fall outside it.
+template <int NTERM, int ROWS, int BK, int NT, int NV>
+__device__ __forceinline__ void deposit_rows(const float4 (&ra)[NV], int tid, _Float16* Ah, _Float16* Al) {
+  constexpr int KV = BK / 4, LDH = BK + 8;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int idx = tid + v * NT;
+    const int row = idx / KV, cv = idx - row * KV;
+    if ((v + 1) * NT <= ROWS * KV || idx < ROWS * KV) {
+      half4 hi, lo;
+      split4t<NTERM>(ra[v], hi, lo);
+      *reinterpret_cast<half4*>(Ah + row * LDH + cv * 4) = hi;
+      if (NTERM == 3) *reinterpret_cast<half4*>(Al + row * LDH + cv * 4) = lo;
+    }
+  }
+}
+
+// ---- chunked A operand (convgemm16_kernel)
 // The fp32 activation rows of a BM-row tile, walked in chunks of BK channels of one tap by NT threads: fetched to
 // registers through the buffer descriptor (padding and rows past the end read as zeros; A2F adds the skip operand on
-// load -- a compile-time variant, no runtime "load or zero" branch), then split and deposited as fp16 hi / lo rows of
-// LDH = BK + 8 halves.  Shared by convgemm16_kernel and pipe_mainloop.
+// load -- a compile-time variant, no runtime "load or zero" branch), then split and deposited.
 template <int BM, int BK, int NT, bool A2F>
 struct ChunkedA {
   static constexpr int KV = BK / 4;                // float4 per row
@@ -225,82 +244,83 @@ struct ChunkedA {
   }
   template <int NTERM>
   __device__ __forceinline__ void deposit(_Float16* Ah, _Float16* Al) const {
-#pragma unroll
-    for (int v = 0; v < A_VEC; ++v) {
-      const int idx = tid + v * NT;
-      const int row = idx / KV, cv = idx - row * KV;
-      if (idx < BM * KV) {
-        half4 hi, lo;
-        split4t<NTERM>(ra[v], hi, lo);
-        *reinterpret_cast<half4*>(Ah + row * LDH + cv * 4) = hi;
-        if (NTERM == 3) *reinterpret_cast<half4*>(Al + row * LDH + cv * 4) = lo;
-      }
-    }
+    deposit_rows<NTERM, BM, BK, NT>(ra, tid, Ah, Al);
   }
 };
 
-// ------------------------------------------------------------------ residue-image A operand (strided convolutions)
-// ChunkedA fetches, splits and deposits the BM rows of every (tap, chunk).  With taps > stride, tap j of frame f and
-// tap j + stride of frame f - 1 are the same input row: a 33-tap stride-16 tile handles every row 2.05 times.  Here a
-// stage is the image of ONE residue r = tap mod stride and one BK-channel chunk c: image row i is input row
-// (m0 + i) * stride - pad + r, and tap r + q * stride of tile row i reads image row i + q (asw::ResidueFeed,
-// include/asw_hip.h: asw_residue_schedule).  An image has BM + (taps - 1 - r) / stride rows; the ring stage is sized
-// for ROWS = BM + ASW_RESIDUE_MAX_SHIFT.  The BM rows every image has are FULL float4 per thread, as in ChunkedA; the
-// rows beyond them are one more float4 in the first threads only (the other lanes' loads are disabled: no traffic).
-// Loads stay on the buffer descriptor: padding, rows past a_len and disabled lanes read as zeros and no index can fault.
-// No skip operand (A2F only occurs with one tap), dil == 1.
-// Unlike ChunkedA, rows of frames past M_out ARE fetched where a valid frame reads them through a shift (only rows
-// from M_out + ASW_RESIDUE_MAX_SHIFT on are left zero), so the phantom frames of a ragged tile accumulate real data:
+// ---- residue-image A operand (the pipelined tiles of pipegemm.hip: every stage of their main loop is one image)
+// An image is the BM + shift input rows that ONE residue r = tap mod W of the walk and one BK-channel chunk c need:
+// image row i is input row (m0 + i) * stride - pad + r * dil, and tap r + q * W of tile row i reads image row i + q
+// (asw::ResidueFeed, include/asw_hip.h: asw_residue_schedule).  Two walks:
+//  * SHIFTS == 0, W = taps, the chunk walk: one tap per image, every (tap, chunk) fetched, split and deposited for
+//    its BM rows, as ChunkedA does;
+//  * SHIFTS == ASW_RESIDUE_MAX_SHIFT, W = stride, the residue walk (asw::residue_feed_ok; dil == 1): with
+//    taps > stride, tap j of frame f and tap j + stride of frame f - 1 are the same input row -- a 33-tap stride-16
+//    tile handles every row 2.05 times in the chunk walk, once here.  An image has BM + (taps - 1 - r) / stride rows.
+// The ring stage is sized for ROWS = BM + SHIFTS.  The BM rows every image has are FULL float4 per thread; the rows
+// beyond them are one more float4 in the first threads only (the other lanes' loads are disabled: no traffic).
+// Loads stay on the buffer descriptor: padding, rows past a_len and disabled lanes read as zeros and no index can
+// fault.  A2F adds the skip operand on load (a second descriptor, compile-time, as in ChunkedA).
+// Rows of frames past M_out ARE fetched where a valid frame reads them through a shift (only rows from
+// M_out + SHIFTS on are left zero), so the phantom frames of a ragged tile accumulate real data in the residue walk:
 // the caller clears their accumulators after the K loop.
-template <int BM, int BK, int NT>
+template <int BM, int BK, int NT, bool A2F, int SH>
 struct ResidueA {
   static constexpr int KV = BK / 4;                // float4 per row
   static constexpr int LDH = BK + 8;               // halves per staged row
-  static constexpr int ROWS = BM + ASW_RESIDUE_MAX_SHIFT;
+  static constexpr int SHIFTS = SH, ROWS = BM + SHIFTS;
+  // the k-step of a stage after which the stage loop deposits the next image: the middle of a one-tap stage, the end
+  // of the first tap where more taps follow -- where each walk was measured, and the one place where the loop's
+  // schedule differs between the walks
+  static constexpr int DEPOSIT_AFTER = SH ? BK / 16 - 1 : BK / 32 - 1;
   static constexpr int FULL = BM * KV / NT;
   static constexpr int A_VEC = (ROWS * KV + NT - 1) / NT;
-  static_assert(BM * KV % NT == 0 && A_VEC == FULL + 1, "BM rows split evenly; the shifted rows fit one more float4");
+  static_assert(BM * KV % NT == 0 && A_VEC == FULL + (SHIFTS > 0), "BM rows split evenly; the shifted rows fit one more float4");
   float4 ra[A_VEC];
   // The staging addresses are ONE per-thread element offset plus uniform terms (float4 v of a thread is NT / KV rows
   // below float4 v - 1): an offset and a flag per float4, as ChunkedA keeps them, cost the three-term mask path its
-  // last VGPRs and eight bytes of scratch.  32-bit: offsets stay below a_len + (BM + shift) rows, a_len < 2^29.
+  // last VGPRs and eight bytes of scratch.  32-bit: offsets stay below a_len + (BM + shift) rows + the tap term,
+  // a_len < 2^29 (asw::pipe_offsets_ok bounds the terms at every launch).
   int a_base;                                      // element offset of (image row tid / KV, residue 0, c 0) + column
   int blk_step;                                    // NT / KV rows
   int row_lim;                                     // image rows from here on serve phantom frames only: left zero
-  int row_step;
-  __amdgpu_buffer_rsrc_t rA;
+  int row_step;                                    // from a residue's image to the next one's
+  __amdgpu_buffer_rsrc_t rA, rA2;
   const int& tid;                                  // (by reference: see ChunkedA)
 
+  // the walk of a launch: the residue walk steps by the stride, the chunk walk is its case of one tap per image
+  static __device__ __forceinline__ asw::ResidueFeed walk(const asw_convgemm_args& p) {
+    return asw::ResidueFeed{p.taps, SHIFTS ? p.stride : p.taps, p.Cin / BK};
+  }
   __device__ __forceinline__ ResidueA(const asw_convgemm_args& p, int b, int m0, const int& tid) : tid(tid) {
     const int row = tid / KV, cv = tid - row * KV;
     a_base = (int)(((long)(m0 + row) * p.stride - p.pad) * p.a_row_stride) + cv * 4;
     blk_step = (NT / KV) * p.stride * (int)p.a_row_stride;
-    row_lim = p.M_out + ASW_RESIDUE_MAX_SHIFT - m0;
-    row_step = (int)p.a_row_stride;
+    row_lim = p.M_out + SHIFTS - m0;
+    row_step = p.dil * (int)p.a_row_stride;
     rA = act_rsrc(p.A + (long)b * p.a_batch_stride, p.a_len);
+    rA2 = act_rsrc((A2F ? p.A2 : p.A) + (long)b * p.a_batch_stride, p.a_len);
   }
-  // image of residue r, chunk c; `shifts` = its rows beyond BM
+  // image of residue r, chunk c; `shifts` = its rows beyond BM (-BM: no row at all, every lane disabled)
   __device__ __forceinline__ void load(int r, int c, int shifts) {
     const int koff = r * row_step + c * BK;
     const int rows = min(BM + shifts, row_lim);
 #pragma unroll
-    for (int v = 0; v < A_VEC; ++v)                     // padding / past-the-end offsets read as zeros
-      ra[v] = act_load4(rA, a_base + v * blk_step + koff, tid / KV + v * (NT / KV) < rows);
+    for (int v = 0; v < A_VEC; ++v) {                   // padding / past-the-end offsets read as zeros
+      const int e = a_base + v * blk_step + koff;
+      const bool ok = tid / KV + v * (NT / KV) < rows;
+      float4 x = act_load4(rA, e, ok);
+      if (A2F) {
+        const float4 y = act_load4(rA2, e, ok);
+        x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+      }
+      ra[v] = x;
+    }
   }
   // (rows an image does not have are deposited as the zeros their disabled loads returned: no tap reads them)
   template <int NTERM>
   __device__ __forceinline__ void deposit(_Float16* Ah, _Float16* Al) const {
-#pragma unroll
-    for (int v = 0; v < A_VEC; ++v) {
-      const int idx = tid + v * NT;
-      const int row = idx / KV, cv = idx - row * KV;
-      if (v < FULL || idx < ROWS * KV) {
-        half4 hi, lo;
-        split4t<NTERM>(ra[v], hi, lo);
-        *reinterpret_cast<half4*>(Ah + row * LDH + cv * 4) = hi;
-        if (NTERM == 3) *reinterpret_cast<half4*>(Al + row * LDH + cv * 4) = lo;
-      }
-    }
+    deposit_rows<NTERM, ROWS, BK, NT>(ra, tid, Ah, Al);
   }
 };
 
@@ -309,7 +329,7 @@ struct ResidueA {
 // the 8 XCDs, each with its own L2).  Both orders pad the grid so that every XCD gets the same number of slots;
 // padded slots exit.
 //
-// "Groups of 8" (convgemm16, pipe_mainloop): slot s = L / 8 of one XCD walks the column tiles of a row tile first:
+// "Groups of 8" (convgemm16, pipe_mainloop of pipegemm.hip): slot s = L / 8 of one XCD walks the column tiles of a row tile first:
 // the ncol workgroups that read the same activation rows run back to back on ONE L2, so those rows come from HBM
 // once instead of once per column tile.  The (batch item, row tile) pairs are dealt to the XCDs in groups of 8, so
 // every XCD gets the same share whatever the number of row tiles per item.

@@ -1,7 +1,7 @@
 // gemm_epilogue.h -- what the row-major GEMM kernels of convgemm.hip, pipegemm.hip and resconv.hip share.
 //
 // Epilogue: the accumulators of one 32-row slab are written to LDS (C/D map:
-// col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)), then each wave owns whole
+// col = lane&31, row = acc_row(r, lane>>5), mfma_util.h), then each wave owns whole
 // rows: + residual, * gate tensor, LayerNorm over the row (two-pass, wave shuffles),
 // GroupNorm partial sums, coalesced row stores.
 #pragma once
@@ -86,7 +86,7 @@ floatx16 (&acc)[BM / WM / 32][BN / WN / 32], const asw_convgemm_args& p,
       const float bv = p.bias ? p.bias[n0 + col] : 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = wm * 32 + acc_row(r, lane >> 5);
         float v = acc[tm][tn][r] * acc_scale + bv;
         if (p.relu == 1) v = fmaxf(v, 0.f);
         else if (p.relu == 2) v = v / (1.0f + expf(-v));             // Swish (Conformer feed-forward)

@@ -1,6 +1,7 @@
 // pipegemm.hip -- the pipelined 256-column f16x3 GEMM (convgemm16p) and the mask path built on its main loop, reached
 // from the dispatcher of convgemm.hip through asw::pipe_gemm and from asw_mask_path_f16x3.  Layout and arithmetic
-// are described at the head of convgemm.hip, the epilogue in gemm_epilogue.h.
+// are described at the head of convgemm.hip, the epilogue in gemm_epilogue.h.  ONE main loop (pipe_mainloop) walks the
+// stages of a ResidueA feed (f16x3_tile.h) in both of its walks; the mask path kernel is that loop plus named phases.
 #include <type_traits>
 
 #include "gemm_epilogue.h"
@@ -11,133 +12,55 @@ using namespace asw_mfma;
 // ------------------------------------------------------------------ pipelined wide-tile GEMM
 // The 8-wave 256-column tiles (mask encoder, strided / transposed convolutions, big linears) as a
 // software pipeline with ONE barrier per 32-wide chunk instead of two (cycle counters on the
-// two-barrier kernel above, mask-encoder shape: per chunk wave 0 spent 1150 cycles depositing the
+// two-barrier kernel of convgemm.hip, mask-encoder shape: per chunk wave 0 spent 1150 cycles depositing the
 // next chunk with every MFMA pipe of the workgroup idle, tests/micro/phase_timing.py):
 //  * B never touches LDS: the weights are pre-packed in MFMA-fragment order (asw_pack_fragments_f16,
 //    the layout of the residual kernel), each wave pulls its two column fragments per k-step with
 //    coalesced 1 KiB loads, QDB k-steps ahead of their use (L2-resident: one column tile of the
 //    largest matrix is 2.1 MB);
 //  * A (fp32 activations) is split to fp16 hi / lo while it is deposited, into a two-stage LDS ring:
-//    the rows of chunk k+1 are fetched before, and deposited after, the MFMAs of chunk k, so the
+//    the rows of image k+1 are fetched before, and deposited after, the MFMAs of image k, so the
 //    deposit of one wave overlaps the MFMAs of the others and only the ring hand-over needs a barrier.
-// Same tiling (wave tile BM/2 x 64), same epilogue, same XCD-aware tile order as the kernel above.
+// Same tiling (wave tile BM/2 x 64), same epilogue, same XCD-aware tile order as the two-barrier kernel.
 // Measured (T = 48 000, batch 64): mask encoder 312 -> 332 TFLOP/s, strided / transposed convolutions
-// +3-6 %.  64-wide chunks (half the barriers, 147 KB ring) spill and lose: 304.
+// +3-6 %.  64-wide chunks (half the barriers, 147 KB ring) spill and lose: 304 -- BK is the constant 32 here.
+constexpr int BN = 256, WN = 4, LDC = BN + 4;
+constexpr int BK = 32, KS = BK / 16;             // a chunk of one tap is KS k-steps (16 K each)
+constexpr int QDB = 2;                           // B fragments in flight, in k-steps
+static_assert(KS == QDB, "a tap is QDB k-steps: the B buffer of a k-step is its index within the tap");
+
+// the A feed of a tile: the residue walk where asw::residue_feed_ok says so at the launch site (RES), else the chunk walk
+template <int BM, int WM, bool A2F, bool RES>
+using PipeFeed = ResidueA<BM, BK, 64 * WM * WN, A2F, RES ? ASW_RESIDUE_MAX_SHIFT : 0>;
+// bytes of the two-stage A ring: hi + lo image of Feed::ROWS rows per stage
+template <typename Feed>
+constexpr size_t pipe_ring_bytes() { return (size_t)2 * 2 * Feed::ROWS * Feed::LDH * sizeof(_Float16); }
+
 // Main loop of one 256-column tile: picks the tile of this workgroup (false: none, the whole workgroup
 // leaves), runs the K loop and returns the accumulators (wave (wm, wn) of WM x 4 holds rows
 // wm*BM/WM + 32*i.., columns wn*64 + 32*j..).  Ends on a barrier: the ring is free for the epilogue.
 // WM = 2: eight waves on a 256-row tile, one workgroup per CU.  WM = 1: four waves on a 128-row tile with the
 // SAME wave tile (128 x 64), two independent workgroups per CU -- one's epilogue under the other's main loop.
-template <int BM, bool A2F, int BK, int NTERM = 3, int WM = 2>
+//
+// The loop walks STAGES.  A stage is one LDS image of the feed -- one (residue, chunk) -- plus the taps that read it
+// (tap r + q * W at row shift q); ONE barrier per stage; the next image is fetched at the top of the stage and
+// deposited DEP k-steps into it.  Chunk walk (W = taps): one tap per image, stage r * cpb + c is chunk kc of the tap-major
+// K order and its k-steps are kc * KS + ks.  Residue walk (W = stride, strided convolutions with taps > stride): every
+// input row deposited once per tile instead of once per tap.  Mask encoder (33 taps, stride 16): 32 deposits and
+// barriers per tile instead of 66, 4 k-steps (6 for residue 0) between barriers instead of 2.  The fragment index of a
+// k-step is the same in both walks, only the order of the visit differs; every tap contributes KS == QDB k-steps, so
+// the B slot of a k-step is static.
+// Frames past M_out: an image row serves up to three frames, so the phantom frames of a ragged tile have
+// accumulated real rows in the residue walk.  That is undone HERE, by clearing their accumulators after the loop -- the
+// state the chunk walk's disabled loads leave, where the clearing changes nothing -- and not in the epilogues: outputs,
+// GroupNorm partial sums, the mask path's bypass gating, decoder contraction and range guard all see zeros.
+template <int BM, typename Feed, int NTERM, int WM>
 __device__ __forceinline__ bool pipe_mainloop(const asw_convgemm_args& p, float* smem, floatx16 (&acc)[BM / WM / 32][2],
                                               dim3& tile_out, int& ncol_out) {
-  constexpr int BN = 256, WN = 4, NT = 64 * WM * WN;
-  constexpr int QDB = 2;                           // B fragments in flight, in k-steps
-  constexpr int LDH = BK + 8;
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int STAGE = 2 * BM * LDH;              // halves per ring stage (hi image + lo image)
-
-  _Float16* ring = reinterpret_cast<_Float16*>(smem);
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int ncol = p.N / BN, nrt = (p.M_out + BM - 1) / BM;
-  uint3 tl;
-  if (!xcd_tile_groups(p.B, nrt, ncol, tl)) return false;     // XCD-aware order, groups of 8
-  const dim3 tile(tl.x, tl.y, tl.z);
-  tile_out = tile;
-  ncol_out = ncol;
-  const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
-  const int nk = p.taps * (p.Cin / BK);
-  const half8* __restrict__ Wh = reinterpret_cast<const half8*>(p.Wf_hi);
-  const half8* __restrict__ Wl = reinterpret_cast<const half8*>(p.Wf_lo);
-  const int NTF = p.N / 32;                        // column fragments across N
-  const int nt0 = n0 / 32 + wn * TN;
-
-  ChunkedA<BM, BK, NT, A2F> A(p, b, m0, tid);
-  auto deposit = [&](int stage) {
-    _Float16* Ah = ring + stage * STAGE;
-    A.template deposit<NTERM>(Ah, Ah + BM * LDH);
-  };
-  auto bload = [&](int kg, half8 (&bh)[TN], half8 (&bl)[TN]) {          // kg = global k-step (16 K each)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) frag_load<NTERM>(Wh, Wl, (long)kg * NTF + nt0 + j, lane, bh[j], bl[j]);
-  };
-
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int a_off = (wm * (BM / WM) + (lane & 31)) * LDH + (lane >> 5) * 8;
-  half8 qh[QDB][TN], ql[QDB][TN];                  // B fragments of the next QDB k-steps
-  const int nks = nk * (BK / 16);                  // k-steps in all
-#pragma unroll
-  for (int q = 0; q < QDB; ++q) bload(q, qh[q], ql[q]);
-  A.load(0);
-  deposit(0);
-  __syncthreads();
-  constexpr int KS = BK / 16;
-  static_assert(KS % QDB == 0, "the B ring is one chunk deep");
-  // One chunk; PAR = chunk parity, compile-time so that ring stage and B buffer indices are static
-  // (the loop below is unrolled by two).
-  auto chunk = [&](int kc, auto par) {
-    constexpr int PAR = decltype(par)::value;
-    if (kc + 1 < nk) A.load(kc + 1);               // in flight under the MFMAs of this chunk
-    const _Float16* Ah = ring + PAR * STAGE;
-    const _Float16* Al = Ah + BM * LDH;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      half8 ah[TM], al[TM];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        ah[i] = *reinterpret_cast<const half8*>(Ah + a_off + i * 32 * LDH + ks * 16);
-        if (NTERM == 3) al[i] = *reinterpret_cast<const half8*>(Al + a_off + i * 32 * LDH + ks * 16);
-      }
-      const int q = (PAR * KS + ks) % QDB;         // B register buffer of this k-step
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma3<NTERM>(acc[i][j], ah[i], al[i], qh[q][j], ql[q][j]);
-      const int kg = kc * KS + ks + QDB;           // same slot, QDB k-steps ahead
-      if (kg < nks) bload(kg, qh[q], ql[q]);
-      // deposit of the next chunk between the k-steps: its conversions and LDS writes issue in the
-      // shadow of this wave's own MFMAs (the other stage was last read one chunk ago, before the
-      // previous barrier)
-      if (ks == KS / 2 - 1 && kc + 1 < nk) deposit(PAR ^ 1);
-    }
-    __syncthreads();
-  };
-  for (int kc = 0; kc < nk; kc += 2) {
-    chunk(kc, std::integral_constant<int, 0>{});
-    if (kc + 1 < nk) chunk(kc + 1, std::integral_constant<int, 1>{});
-  }
-  return true;
-}
-
-// The same main loop over the stages of the residue-image feed (ResidueA, f16x3_tile.h; asw::residue_feed_ok decides
-// at the launch sites): strided convolutions with taps > stride deposit every input row once per tile instead of
-// once per tap.  A stage is the image of one (residue, chunk); ONE barrier per stage; the next image is fetched at
-// the top of the stage and deposited after the first tap's k-steps; the image's other taps (row shift q) follow
-// before the barrier.  Mask encoder (33 taps, stride 16): 32 deposits and barriers per tile instead of 66, 4 k-steps
-// (6 for residue 0) between barriers instead of 2.  The fragment index of a k-step is what it is in pipe_mainloop,
-// only the order of the visit differs; every tap contributes KS == QDB k-steps, so the B slot of a k-step is static.
-// Frames past M_out: an image row serves up to three frames, so the phantom frames of a ragged tile have
-// accumulated real rows.  That is undone HERE, by clearing their accumulators after the loop -- the state ChunkedA's
-// a_ok leaves -- and not in the epilogues: outputs, GroupNorm partial sums, the mask path's bypass gating, decoder
-// contraction and range guard all see zeros as they did.
-template <int BM, int BK, int NTERM = 3, int WM = 2>
-__device__ __forceinline__ bool pipe_mainloop_res(const asw_convgemm_args& p, float* smem, floatx16 (&acc)[BM / WM / 32][2],
-                                                  dim3& tile_out, int& ncol_out) {
-  constexpr int BN = 256, WN = 4, NT = 64 * WM * WN;
-  constexpr int QDB = 2, KS = BK / 16;
-  static_assert(KS == QDB, "a tap is QDB k-steps: the B buffer of a k-step is its index within the tap");
-  using Feed = ResidueA<BM, BK, NT>;
   constexpr int LDH = Feed::LDH, ROWS = Feed::ROWS;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
   constexpr int STAGE = 2 * ROWS * LDH;            // halves per ring stage (hi image + lo image)
+  constexpr int DEP = Feed::DEPOSIT_AFTER;         // the k-step of a stage after which the next image is deposited
 
   _Float16* ring = reinterpret_cast<_Float16*>(smem);
 
@@ -150,9 +73,9 @@ __device__ __forceinline__ bool pipe_mainloop_res(const asw_convgemm_args& p, fl
   tile_out = tile;
   ncol_out = ncol;
   const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
-  const asw::ResidueFeed rf{p.taps, p.stride, p.Cin / BK};
+  const asw::ResidueFeed rf = Feed::walk(p);
   const int nst = rf.stages();
-  const int tap_ks = p.stride * rf.cpb * KS;       // k-steps from a tap to the next tap of the same image
+  const int tap_ks = rf.stride * rf.cpb * KS;      // k-steps from a tap to the next tap of the same image
   const half8* __restrict__ Wh = reinterpret_cast<const half8*>(p.Wf_hi);
   const half8* __restrict__ Wl = reinterpret_cast<const half8*>(p.Wf_lo);
   const int NTF = p.N / 32;                        // column fragments across N
@@ -196,9 +119,9 @@ __device__ __forceinline__ bool pipe_mainloop_res(const asw_convgemm_args& p, fl
     const _Float16* Ah = ring + PAR * STAGE;
     const _Float16* Al = Ah + ROWS * LDH;
 #pragma unroll
-    for (int q = 0; q <= ASW_RESIDUE_MAX_SHIFT; ++q) {
-      if (q == 0 || q <= sh) {                     // tap r + q * stride: tile row i reads image row i + q
-        const bool last = q == sh;
+    for (int q = 0; q <= Feed::SHIFTS; ++q) {
+      if (q == 0 || q <= sh) {                     // tap r + q * W: tile row i reads image row i + q
+        const bool last = q == Feed::SHIFTS || q == sh;
         // the fragments QDB k-steps ahead: the same k-steps of the image's next tap, or of the next image's first
         const int kb = rf.kstep(rf.tap(r, q), c, KS);
         const int kn = !last ? kb + tap_ks : more ? rf.kstep(rf.tap(rn, 0), cn, KS) : kb;
@@ -215,10 +138,15 @@ __device__ __forceinline__ bool pipe_mainloop_res(const asw_convgemm_args& p, fl
 #pragma unroll
             for (int j = 0; j < TN; ++j) mma3<NTERM>(acc[i][j], ah[i], al[i], qh[ks][j], ql[ks][j]);
           bload(kn + ks, qh[ks], ql[ks]);
+          // deposit of the next image between the k-steps: its conversions and LDS writes issue in the shadow of
+          // this wave's own MFMAs (the other stage was last read one stage ago, before the previous barrier).
+          // Eight waves: unconditional like the loads (after the last stage: zeros into the stage nobody reads again);
+          // under `if (more)` hipcc sinks the A loads of a one-tap stage down to this block and waits for them on the
+          // spot (plain 256-row tile 3.51 -> 3.92 ms per step, mask path 17.17 -> 17.57).  Four waves: the second
+          // workgroup of the CU hides that wait, and the extra deposit in front of the epilogue of a tile of 8-16
+          // stages costs more (3.58 -> 3.66).  (A switch on the TILE, WM; the feeds differ in DEP alone.)
+          if (q == 0 && ks == DEP && (more || WM == 2)) deposit(PAR ^ 1);
         }
-        // deposit of the next image after the first tap: its conversions and LDS writes issue in the shadow of
-        // this wave's own MFMAs (the other stage was last read one stage ago, before the previous barrier)
-        if (q == 0 && more) deposit(PAR ^ 1);
       }
     }
     __syncthreads();
@@ -233,8 +161,7 @@ __device__ __forceinline__ bool pipe_mainloop_res(const asw_convgemm_args& p, fl
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = wm * (BM / WM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (m0 + row >= p.M_out) {
+        if (m0 + wm * (BM / WM) + i * 32 + acc_row(e, lane >> 5) >= p.M_out) {
 #pragma unroll
           for (int j = 0; j < TN; ++j) acc[i][j][e] = 0.f;
         }
@@ -243,20 +170,14 @@ __device__ __forceinline__ bool pipe_mainloop_res(const asw_convgemm_args& p, fl
   return true;
 }
 
-template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int NTERM = 3, int WM = 2, bool RES = false>
+template <int BM, bool STATS, bool MUL, bool A2F, int NTERM, int WM, bool RES>
 __global__ __launch_bounds__(256 * WM) __attribute__((amdgpu_waves_per_eu(2)))
 void convgemm16p_kernel(const asw_convgemm_args p) {
-  constexpr int BN = 256, WN = 4;
-  static_assert(!(RES && A2F), "the residue-image feed has no skip operand");
   extern __shared__ __align__(16) float smem[];
   floatx16 acc[BM / WM / 32][2];
   dim3 tile;
   int ncol;
-  if constexpr (RES) {
-    if (!pipe_mainloop_res<BM, BK, NTERM, WM>(p, smem, acc, tile, ncol)) return;
-  } else {
-    if (!pipe_mainloop<BM, A2F, BK, NTERM, WM>(p, smem, acc, tile, ncol)) return;
-  }
+  if (!pipe_mainloop<BM, PipeFeed<BM, WM, A2F, RES>, NTERM, WM>(p, smem, acc, tile, ncol)) return;
   epilogue<BM, BN, WM, WN, false, STATS, false, MUL>(acc, p, smem, __builtin_ldexpf(1.0f, -p.w_shift),
                                                      RowsContig{(int)tile.x * BM, p.M_out}, tile, ncol);
 }
@@ -265,50 +186,32 @@ void convgemm16p_kernel(const asw_convgemm_args p) {
 // reference_bypass, mask_encoder and the output_decoder taps (network.py:327-349,397-405) without the
 // 2048-channel latents ever reaching memory:
 //   taps[f][j] = sum_e relu(mask_enc(x)[f][e] + b_e) * relu(bypass(ref)[f][e] + c_e) * D[e][j]
-// The main loop is the pipelined GEMM above (mask encoder, K = taps*Cin).  Epilogue, per 256 x 256 tile:
-//  A. each wave computes the bypass tile of its own 32 x 32 accumulator blocks with nine more MFMAs
-//     (K = 33 padded to 48; the frames of the reference channel are read straight from global memory
-//     in A-fragment order) and gates the accumulators in registers;
-//  B. the gated latent goes through an LDS slab, 128 rows at a time, and comes back in A-fragment
-//     order for the decoder contraction over the tile's 256 latent channels: eight waves = four
-//     32-row blocks x two 32-tap blocks, 48 MFMAs each.  The result is a PARTIAL tap product (this
-//     column tile's share of the sum over e); the overlap-add kernel adds the N/256 partials.
+// The main loop is the pipelined GEMM above (mask encoder, K = taps*Cin).  Epilogue, per 256 x 256 tile, in the
+// phases below: A. bypass tile and gating in registers (mask_gate); B. the gated latent through an LDS slab, 128 rows
+// at a time (mask_slab_store), back in A-fragment order for the decoder contraction (mask_contract) and out as a
+// PARTIAL tap product (mask_store_taps: this column tile's share of the sum over e; the overlap-add kernel adds the
+// N/256 partials).
 // Per candidate (T = 48 000) this writes 8 x 3008 x 33 floats instead of writing the bypass latent,
 // reading it, writing the gated latent and reading that again (4 x 24.6 MB).
 //
 // SCALED (asw_mask_path_f16x3_scaled, the f16x3_safe mode): the gated latent is the one un-normalised tensor that is
 // split to fp16 inside a kernel, and split4 saturates at 65504.  This variant gives every latent row of a pass (one
-// frame, the tile's 256 channels) a power-of-two scale of its own: with 2^e <= max|row| < 2^(e+1) the row is
-// multiplied by 2^(MASK_BINADE - e) before the split, which puts its largest magnitude into [2^12, 2^13) whatever it
-// was -- up as well as down, so small rows keep their lo halves out of the fp16 subnormals too -- and the frame's taps
-// by 2^(e - MASK_BINADE) after the contraction.  Both steps are exact (v_ldexp_f32), so the kernel is exactly
-// homogeneous per frame: scaling a frame's latent by 2^k scales its taps by 2^k, bit for bit.  A lane owns one slab
-// row in A-fragment order: the row maximum is a pre-pass over its own 128 values and one exchange with lane ^ 32; an
-// output register belongs to another row than the lane's A row, so the exponents come back through a bpermute.  A
-// row of zeros (or of fp32 subnormals) keeps scale 1.  The range guard counts non-finite latents only.
+// frame, the tile's 256 channels) a power-of-two scale of its own (mask_row_scale) before the split and takes it off
+// the frame's taps after the contraction.  Both steps are exact (v_ldexp_f32), so the kernel is exactly
+// homogeneous per frame: scaling a frame's latent by 2^k scales its taps by 2^k, bit for bit.
 constexpr int MASK_BINADE = 12;
-template <int BM, int KSB, int NTERM = 3, bool RES = false, bool SCALED = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
-void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
-  constexpr int BN = 256, WN = 4, TM = BM / 64, TN = 2, LDC = BN + 4, BK = 32;
-  static_assert(BM == 256, "slab passes are written for 2 x 128 rows");
-  extern __shared__ __align__(16) float smem[];
-  floatx16 acc[TM][TN];
-  dim3 tile;
-  int ncol;
-  if constexpr (RES) {
-    if (!pipe_mainloop_res<BM, BK, NTERM>(p, smem, acc, tile, ncol)) return;
-  } else {
-    if (!pipe_mainloop<BM, false, BK, NTERM>(p, smem, acc, tile, ncol)) return;
-  }
-  const int tid = threadIdx.x, lane = tid & 63;
-  // (SCALED: the wave index as a scalar, which frees the vector registers the extra pass needs -- no scratch)
-  const int wid = SCALED ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
-  const float acc_scale = __builtin_ldexpf(1.0f, -p.w_shift);
-  const float byp_scale = __builtin_ldexpf(1.0f, -mf.byp_shift), dec_scale = __builtin_ldexpf(1.0f, -mf.dec_shift);
-  // ---- A: bypass tile + gating, in registers
+constexpr int MASK_KSB = 3;                      // k-steps of the bypass kernel: 33 taps padded to 48
+
+// Phase A: each wave computes the bypass tile of its own 32 x 32 accumulator blocks with nine more MFMAs (K = 33 padded
+// to 48; the frames of the reference channel are read straight from global memory in A-fragment order) and gates
+// the accumulators in registers.  The latent is split to fp16 halves in mask_contract: same range guard as a latent
+// written for a later GEMM (SCALED: every row is brought into range first, a finite magnitude is no error; the row
+// maxima of mask_row_scale find the rest).
+template <int TM, int KSB, int NTERM, bool SCALED>
+__device__ __forceinline__ void mask_gate(floatx16 (&acc)[TM][2], const asw_convgemm_args& p, const asw_maskpath_args& mf,
+                                          int b, int m0, int n0, int lane, int wm, int wn) {
+  constexpr int TN = 2;
+  const float acc_scale = __builtin_ldexpf(1.0f, -p.w_shift), byp_scale = __builtin_ldexpf(1.0f, -mf.byp_shift);
   const __amdgpu_buffer_rsrc_t rR = act_rsrc(mf.ref + (long)b * mf.ref_batch_stride, mf.ref_len);
   const half8* __restrict__ Bh = reinterpret_cast<const half8*>(mf.byp_hi);
   const half8* __restrict__ Bl = reinterpret_cast<const half8*>(mf.byp_lo);
@@ -324,7 +227,7 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
     for (int ks = 0; ks < KSB; ++ks) frag_load<NTERM>(Bh, Bl, (long)ks * NTF + nt, lane, wh[ks], wl[ks]);
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
-      const int f = m0 + wm * (BM / 2) + tm * 32 + (lane & 31);
+      const int f = m0 + wm * (TM * 32) + tm * 32 + (lane & 31);
       const bool ok = f < p.M_out;
       floatx16 bp;
 #pragma unroll
@@ -347,108 +250,162 @@ void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
         acc[tm][tn][r] = v;
       }
     }
+    // one column block after the other (only loads may move up across this line): with both blocks' bypass tiles
+    // scheduled together the three-term kernels, which sit at the 256 VGPRs of two waves per SIMD, spill (248 bytes
+    // of scratch without it)
+    if (tn == 0) __builtin_amdgcn_sched_barrier(0x20);
   }
-  // the latent is split to fp16 halves below: same range guard as a latent written for a later GEMM
-  // (SCALED: every row is brought into range first, a finite magnitude is no error; the row maxima below find the rest)
   if (!SCALED && !(amax <= 65504.f)) atomicAdd(&g_f16x3_overflow, 1u);
-  // ---- B: decoder contraction through the slab, rows [pass*128, pass*128 + 128) of the tile per pass
-  float* Ct = smem;
+}
+
+// Phase B, slab store: the 128 rows of this wave row's gated accumulators into the slab
+template <int TM>
+__device__ __forceinline__ void mask_slab_store(float* Ct, const floatx16 (&acc)[TM][2], int lane, int wn) {
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+      const int col = wn * 64 + tn * 32 + (lane & 31);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) Ct[(tm * 32 + acc_row(r, lane >> 5)) * LDC + col] = acc[tm][tn][r];
+    }
+}
+
+// Phase B, row scale of SCALED.  A lane owns one slab row in A-fragment order (`src`: its 128 values of the 256): with
+// 2^e <= max|row| < 2^(e+1) the row is split as row * 2^rsh, rsh = MASK_BINADE - e, which puts its largest magnitude into
+// [2^12, 2^13) whatever it was -- up as well as down, so small rows keep their lo halves out of the fp16 subnormals
+// too.  The row maximum is a pre-pass over the lane's own values and one exchange with lane ^ 32.  A row of zeros (or
+// of fp32 subnormals) keeps scale 1.  The range guard counts non-finite latents only.
+__device__ __forceinline__ int mask_row_scale(const float* src) {
+  // magnitudes order like their bit patterns, and a NaN (which fmaxf would drop) sorts above every number
+  unsigned mb = 0;
+  auto mag = [](float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; };
+#pragma unroll 4
+  for (int ks = 0; ks < BN / 16; ++ks) {
+    const float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
+    const float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
+    mb = max(max(max(mb, mag(x0.x)), max(mag(x0.y), mag(x0.z))), max(max(mag(x0.w), mag(x1.x)), mag(x1.y)));
+    mb = max(mb, max(mag(x1.z), mag(x1.w)));
+  }
+  const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);   // the other half of the row: lane ^ 32
+  const int ef = (int)(max(sw[0], sw[1]) >> 23);                            // biased exponent of the row maximum
+  if (ef == 255) atomicAdd(&g_f16x3_overflow, 1u);                          // range guard: inf or NaN in the latent
+  return (ef == 0 || ef == 255) ? 0 : MASK_BINADE + 127 - ef;
+}
+
+// Phase B, decoder contraction over the tile's 256 latent channels: eight waves = four 32-row blocks x two 32-tap
+// blocks (tt), 48 MFMAs each; the lane's row comes back from the slab in A-fragment order, times 2^rsh if SCALED
+template <int NTERM, bool SCALED>
+__device__ __forceinline__ floatx16 mask_contract(const float* src, int rsh, const asw_maskpath_args& mf, int n0, int tt, int lane) {
   const half8* __restrict__ Dh = reinterpret_cast<const half8*>(mf.dec_hi);
   const half8* __restrict__ Dl = reinterpret_cast<const half8*>(mf.dec_lo);
+  floatx16 tp;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) tp[r] = 0.f;
+#pragma unroll 4
+  for (int ks = 0; ks < BN / 16; ++ks) {
+    float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
+    float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
+    if constexpr (SCALED) {
+      x0 = make_float4(__builtin_ldexpf(x0.x, rsh), __builtin_ldexpf(x0.y, rsh), __builtin_ldexpf(x0.z, rsh), __builtin_ldexpf(x0.w, rsh));
+      x1 = make_float4(__builtin_ldexpf(x1.x, rsh), __builtin_ldexpf(x1.y, rsh), __builtin_ldexpf(x1.z, rsh), __builtin_ldexpf(x1.w, rsh));
+    }
+    half8 dh, dl;
+    frag_load<NTERM>(Dh, Dl, (long)(n0 / 16 + ks) * 2 + tt, lane, dh, dl);
+    half4 h0, l0, h1, l1;
+    split4t<NTERM>(x0, h0, l0);
+    split4t<NTERM>(x1, h1, l1);
+    const half8 ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+    const half8 al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+    mma3<NTERM>(tp, ah, al, dh, dl);
+  }
+  return tp;
+}
+
+// Phase B, tap store of the block whose first frame is f0.  SCALED: register r holds row acc_row(r, lane >> 5) of the
+// block, another row than the lane's A row, so that row's exponent comes back through a bpermute and its scale is
+// undone first (every lane takes part in the exchange, whatever it stores below)
+template <bool SCALED>
+__device__ __forceinline__ void mask_store_taps(floatx16 tp, int rsh, const asw_maskpath_args& mf, float* __restrict__ outp,
+                                                int f0, int M_out, int tt, int lane) {
+  if constexpr (SCALED) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tp[r] = __builtin_ldexpf(tp[r], -__shfl(rsh, acc_row(r, lane >> 5), 64));
+  }
+  const float dec_scale = __builtin_ldexpf(1.0f, -mf.dec_shift);
+  const int j = tt * 32 + (lane & 31);
+  if (j < mf.dec_taps) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int f = f0 + acc_row(r, lane >> 5);
+      if (f < M_out) outp[(long)f * 64 + j] = tp[r] * dec_scale;
+    }
+  }
+}
+
+template <int BM, int KSB, int NTERM, bool RES, bool SCALED>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
+void maskpath16p_kernel(const asw_convgemm_args p, const asw_maskpath_args mf) {
+  constexpr int TM = BM / 64;
+  static_assert(BM == 256, "slab passes are written for 2 x 128 rows");
+  extern __shared__ __align__(16) float smem[];
+  floatx16 acc[TM][2];
+  dim3 tile;
+  int ncol;
+  if (!pipe_mainloop<BM, PipeFeed<BM, 2, false, RES>, NTERM, 2>(p, smem, acc, tile, ncol)) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // (the wave index as a scalar: wm, ft and tt live across every phase, and as vector registers they are the ones
+  // that go to scratch)
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wid / WN, wn = wid % WN;
+  const int b = tile.z, m0 = tile.x * BM, n0 = tile.y * BN;
+  mask_gate<TM, KSB, NTERM, SCALED>(acc, p, mf, b, m0, n0, lane, wm, wn);
+  // rows [pass*128, pass*128 + 128) of the tile per pass
+  float* Ct = smem;
   const int ft = wid & 3, tt = wid >> 2;                       // 32-row block, 32-tap block of this wave
   float* __restrict__ outp = mf.taps + ((long)tile.y * p.B + b) * p.M_out * 64;
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
     if (pass) __syncthreads();                                 // (pass 0: the main loop ended on a barrier)
-    if (wm == pass) {
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-          const int col = wn * 64 + tn * 32 + (lane & 31);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            Ct[row * LDC + col] = acc[tm][tn][r];
-          }
-        }
-    }
+    if (wm == pass) mask_slab_store<TM>(Ct, acc, lane, wn);
     __syncthreads();
-    floatx16 tp;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tp[r] = 0.f;
     const float* src = Ct + (ft * 32 + (lane & 31)) * LDC + (lane >> 5) * 8;
     int rsh = 0;                                               // SCALED: this lane's row is split as row * 2^rsh
-    if constexpr (SCALED) {
-      // magnitudes order like their bit patterns, and a NaN (which fmaxf would drop) sorts above every number
-      unsigned mb = 0;
-      auto mag = [](float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; };
-#pragma unroll 4
-      for (int ks = 0; ks < BN / 16; ++ks) {
-        const float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
-        const float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
-        mb = max(max(max(mb, mag(x0.x)), max(mag(x0.y), mag(x0.z))), max(max(mag(x0.w), mag(x1.x)), mag(x1.y)));
-        mb = max(mb, max(mag(x1.z), mag(x1.w)));
-      }
-      const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);   // the other half of the row: lane ^ 32
-      const int ef = (int)(max(sw[0], sw[1]) >> 23);                            // biased exponent of the row maximum
-      rsh = (ef == 0 || ef == 255) ? 0 : MASK_BINADE + 127 - ef;
-      if (ef == 255) atomicAdd(&g_f16x3_overflow, 1u);                          // range guard: inf or NaN in the latent
-    }
-#pragma unroll 4
-    for (int ks = 0; ks < BN / 16; ++ks) {
-      float4 x0 = *reinterpret_cast<const float4*>(src + ks * 16);
-      float4 x1 = *reinterpret_cast<const float4*>(src + ks * 16 + 4);
-      if constexpr (SCALED) {
-        x0 = make_float4(__builtin_ldexpf(x0.x, rsh), __builtin_ldexpf(x0.y, rsh), __builtin_ldexpf(x0.z, rsh), __builtin_ldexpf(x0.w, rsh));
-        x1 = make_float4(__builtin_ldexpf(x1.x, rsh), __builtin_ldexpf(x1.y, rsh), __builtin_ldexpf(x1.z, rsh), __builtin_ldexpf(x1.w, rsh));
-      }
-      half8 dh, dl;
-      frag_load<NTERM>(Dh, Dl, (long)(n0 / 16 + ks) * 2 + tt, lane, dh, dl);
-      half4 h0, l0, h1, l1;
-      split4t<NTERM>(x0, h0, l0);
-      split4t<NTERM>(x1, h1, l1);
-      const half8 ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-      const half8 al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-      mma3<NTERM>(tp, ah, al, dh, dl);
-    }
-    if constexpr (SCALED) {
-      // register r holds row (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of the block: undo that row's scale (every lane
-      // takes part in the exchange, whatever it stores below)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        tp[r] = __builtin_ldexpf(tp[r], -__shfl(rsh, (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), 64));
-    }
-    const int j = tt * 32 + (lane & 31);
-    if (j < mf.dec_taps) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int f = m0 + pass * 128 + ft * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (f < p.M_out) outp[(long)f * 64 + j] = tp[r] * dec_scale;
-      }
-    }
+    if constexpr (SCALED) rsh = mask_row_scale(src);
+    const floatx16 tp = mask_contract<NTERM, SCALED>(src, rsh, mf, n0, tt, lane);
+    mask_store_taps<SCALED>(tp, rsh, mf, outp, m0 + pass * 128 + ft * 32, p.M_out, tt, lane);
   }
 }
 
-// bytes of the two-stage A ring: hi + lo image of BM rows per stage, or of ResidueA's BM + ASW_RESIDUE_MAX_SHIFT
-template <int BM, int BK, bool RES>
-constexpr size_t pipe_ring_bytes() {
-  return (size_t)2 * 2 * (BM + (RES ? ASW_RESIDUE_MAX_SHIFT : 0)) * (BK + 8) * sizeof(_Float16);
+// mask encoder + bypass + decoder taps; the encoder's rows through the residue walk where it applies
+template <bool RES, bool SCALED>
+int launch_mask(const asw_convgemm_args& a, const asw_maskpath_args& m, hipStream_t s) {
+  constexpr int BM = 256, KSB = MASK_KSB;
+  constexpr size_t ring = pipe_ring_bytes<PipeFeed<BM, 2, false, true>>();     // (the larger of the two feeds' rings)
+  constexpr size_t slab = (size_t)128 * LDC * sizeof(float);
+  constexpr size_t smem = ring > slab ? ring : slab;
+  static_assert(smem <= 160 * 1024, "LDS budget");
+  const dim3 grid(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN));
+  const double flops = 2.0 * a.B * (double)a.M_out * a.N * ((double)a.taps * a.Cin + m.byp_taps + m.dec_taps);
+  const asw::ShapeTag tag(a, 's', a.stride, RES ? " res" : "");     // the detailed profile says which feed ran
+  return asw::launch_pair<maskpath16p_kernel<BM, KSB, SCALED ? 3 : 1, RES, SCALED>, maskpath16p_kernel<BM, KSB, 3, RES, SCALED>>(
+      a.precision, grid, dim3(512), smem, smem, SCALED ? "maskpath16ps<256,256,32>" : "maskpath16p<256,256,32>", tag.s, flops,
+      0.0, s, a, m);
 }
 
 int launch_mask_path(const asw_maskpath_args* args, void* stream, bool scaled = false) {
   ASW_CHECK_ARG(args, "mask_path: null argument block");
   const asw_maskpath_args& m = *args;
   asw_convgemm_args a = m.enc;
-  hipStream_t s = asw::as_stream(stream);
-  constexpr int BM = 256, BN = 256, BK = 32, KSB = 3;
   ASW_CHECK_ARG(a.A && a.Wf_hi && a.Wf_lo && m.ref && m.byp_hi && m.byp_lo && m.dec_hi && m.dec_lo && m.taps,
                 "mask_path: null pointer (fragment-order weights are required)");
   ASW_CHECK_ARG(a.B > 0 && a.M_out > 0 && a.N % BN == 0 && a.Cin % BK == 0 && a.taps > 0 && a.stride > 0,
                 "mask_path: shape (N %% 256 == 0, Cin %% 32 == 0)");
+  ASW_CHECK_ARG(a.a_len > 0 && a.a_len < ((int64_t)1 << 29) && asw::pipe_offsets_ok(a),
+                "mask_path: input rows beyond the 32-bit offsets of the pipelined tile");
   ASW_CHECK_ARG(a.A2 == nullptr && a.mul == nullptr && a.resid == nullptr && a.ln_gamma == nullptr && a.stats == nullptr,
                 "mask_path: the encoder block takes A, weights and bias only");
-  ASW_CHECK_ARG(m.byp_k == 16 * KSB, "mask_path: bypass kernel padded to %d taps, %d given", 16 * KSB, m.byp_k);
+  ASW_CHECK_ARG(m.byp_k == 16 * MASK_KSB, "mask_path: bypass kernel padded to %d taps, %d given", 16 * MASK_KSB, m.byp_k);
   ASW_CHECK_ARG(m.dec_taps > 0 && m.dec_taps <= 64 && m.ref_hop > 0 && m.ref_hop % 4 == 0 && m.ref_len > 0,
                 "mask_path: decoder taps 1..64, reference hop a multiple of 4 samples");
   ASW_CHECK_ARG((reinterpret_cast<uintptr_t>(m.ref) & 15) == 0 && m.ref_batch_stride % 4 == 0,
@@ -456,41 +413,22 @@ int launch_mask_path(const asw_maskpath_args* args, void* stream, bool scaled = 
   ASW_CHECK_ARG(a.precision == 1 || a.precision == 2, "mask_path: precision 1 (f16x3) or 2 (single-pass f16)");
   ASW_CHECK_ARG(!scaled || a.precision == 1, "mask_path: the per-frame scale exists for precision 1 (f16x3) only");
   a.relu = 1;
-  constexpr size_t ring = pipe_ring_bytes<BM, BK, true>();     // (the larger of the two feeds' rings)
-  constexpr size_t slab = (size_t)128 * (BN + 4) * sizeof(float);
-  constexpr size_t smem = ring > slab ? ring : slab;
-  static_assert(pipe_ring_bytes<BM, BK, false>() <= ring && smem <= 160 * 1024, "LDS budget");
-  const dim3 grid(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN));
-  const double flops = 2.0 * a.B * (double)a.M_out * a.N * ((double)a.taps * a.Cin + m.byp_taps + m.dec_taps);
   const bool res = asw::residue_feed_ok(a, BK);
-  const asw::ShapeTag tag(a, 's', a.stride, res ? " res" : "");     // the detailed profile says which feed ran
-  // mask encoder + bypass + decoder taps; the encoder's rows through the residue-image feed where it applies
-  if (scaled) {
-    constexpr const char* name = "maskpath16ps<256,256,32>";
-    if (res)
-      return asw::launch_pair<maskpath16p_kernel<BM, KSB, 3, true, true>, maskpath16p_kernel<BM, KSB, 3, true, true>>(
-          a.precision, grid, dim3(512), smem, smem, name, tag.s, flops, 0.0, s, a, m);
-    return asw::launch_pair<maskpath16p_kernel<BM, KSB, 3, false, true>, maskpath16p_kernel<BM, KSB, 3, false, true>>(
-        a.precision, grid, dim3(512), smem, smem, name, tag.s, flops, 0.0, s, a, m);
-  }
-  if (res)
-    return asw::launch_pair<maskpath16p_kernel<BM, KSB, 1, true>, maskpath16p_kernel<BM, KSB, 3, true>>(
-        a.precision, grid, dim3(512), smem, smem, "maskpath16p<256,256,32>", tag.s, flops, 0.0, s, a, m);
-  return asw::launch_pair<maskpath16p_kernel<BM, KSB, 1>, maskpath16p_kernel<BM, KSB, 3>>(
-      a.precision, grid, dim3(512), smem, smem, "maskpath16p<256,256,32>", tag.s, flops, 0.0, s, a, m);
+  const auto launch = scaled ? (res ? launch_mask<true, true> : launch_mask<false, true>)
+                             : (res ? launch_mask<true, false> : launch_mask<false, false>);
+  return launch(a, m, asw::as_stream(stream));
 }
 
-template <int BM, bool STATS, bool MUL, bool A2F, int BK = 32, int WM = 2, bool RES = false>
+template <int BM, bool STATS, bool MUL, bool A2F, int WM, bool RES>
 int launch_pipe(const asw_convgemm_args& a, hipStream_t s) {
-  constexpr int BN = 256;
-  constexpr size_t ring = pipe_ring_bytes<BM, BK, RES>();
-  constexpr size_t slab = (size_t)(WM * 32) * (BN + 4) * sizeof(float);
+  constexpr size_t ring = pipe_ring_bytes<PipeFeed<BM, WM, A2F, RES>>();
+  constexpr size_t slab = (size_t)(WM * 32) * LDC * sizeof(float);
   constexpr size_t smem = ring > slab ? ring : slab;
   static_assert(smem <= 160 * 1024, "LDS budget");
   static_assert(BM == 128 * WM, "wave tile 128 x 64");
   ASW_CHECK_ARG(A2F == (a.A2 != nullptr), "convgemm: skip operand variant mismatch");
-  ASW_CHECK_ARG(a.Cin % BK == 0 && a.N % BN == 0, "convgemm: pipelined tile needs Cin %% BK == 0 and N %% 256 == 0");
-  return asw::launch_pair<convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 1, WM, RES>, convgemm16p_kernel<BM, STATS, MUL, A2F, BK, 3, WM, RES>>(
+  ASW_CHECK_ARG(a.Cin % BK == 0 && a.N % BN == 0, "convgemm: pipelined tile needs Cin %% 32 == 0 and N %% 256 == 0");
+  return asw::launch_pair<convgemm16p_kernel<BM, STATS, MUL, A2F, 1, WM, RES>, convgemm16p_kernel<BM, STATS, MUL, A2F, 3, WM, RES>>(
       a.precision, dim3(xcd_grid_groups((long)asw::cdiv(a.M_out, BM) * a.B, a.N / BN)), dim3(256 * WM), smem, smem,
       asw::prof_name(MUL ? "convgemm16pm" : "convgemm16p", BM, BN, BK, false, STATS),
       asw::ShapeTag(a, 's', a.stride, RES ? " res" : "").s,
@@ -503,8 +441,8 @@ struct PipeTile {                        // pipelined 256-column kernel: convgem
   static int run(const asw_convgemm_args& a, hipStream_t s) {
     // strided convolutions with taps > stride: every input row deposited once per tile (plain and statistics forms)
     if constexpr (!MUL && !A2F)
-      if (asw::residue_feed_ok(a, 32)) return launch_pipe<BM, STATS, MUL, A2F, 32, WM, true>(a, s);
-    return launch_pipe<BM, STATS, MUL, A2F, 32, WM>(a, s);
+      if (asw::residue_feed_ok(a, BK)) return launch_pipe<BM, STATS, MUL, A2F, WM, true>(a, s);
+    return launch_pipe<BM, STATS, MUL, A2F, WM, false>(a, s);
   }
 };
 
@@ -513,7 +451,7 @@ struct PipeTile {                        // pipelined 256-column kernel: convgem
 namespace asw {
 int pipegemm_f16x3_overflow(int reset, unsigned int* count) { return f16x3_overflow_read(reset, count); }
 
-// The wide f16x3 tile with fragment-order weights (the caller has checked both).
+// The wide f16x3 tile with fragment-order weights (the caller has checked both, and asw::pipe_offsets_ok).
 int pipe_gemm(const asw_convgemm_args& a, hipStream_t s) {
   // Short K (the decoder's transposed convolutions): two independent 4-wave workgroups of 128 rows per CU, same
   // wave tile -- one drains its tile while the other computes (K = 512: 234 -> 260 TFLOP/s, K = 256: 186 -> 193;

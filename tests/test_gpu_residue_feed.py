@@ -1,6 +1,8 @@
-"""The residue-image A feed of the pipelined f16x3 tiles (ResidueA, csrc/f16x3_tile.h; pipe_mainloop_res,
-csrc/pipegemm.hip): strided convolutions with taps > stride deposit every input row once per tile and run all the taps
-that read it from one LDS image.  Mask path and strided convolutions against torch float64 on the CPU of the same fp32
+"""The A feed of the pipelined f16x3 tiles (ResidueA, csrc/f16x3_tile.h; pipe_mainloop, csrc/pipegemm.hip: one stage
+loop, two walks).  On the residue walk, strided convolutions with taps > stride deposit every input row once per tile and
+run all the taps that read it from one LDS image; every other shape, and every shape under ASW_NO_RESIDUE_FEED, takes
+the chunk walk of the same loop, one tap per image -- with the skip operand, the gate tensor or a dilation, which the
+residue walk never sees.  Mask path and convolutions against torch float64 on the CPU of the same fp32
 inputs, at the bar tests/test_gpu_kernels.py holds these kernels to (relative l2 error < 3e-6; single-pass f16 mode:
 2e-3, its bar in tests/test_gpu_f16x3.py), full and ragged tiles, both feeds (ASW_NO_RESIDUE_FEED=1 in a child process).
 
@@ -57,13 +59,13 @@ def _launch_names(fn):
     return out, list(json.loads(buf.value.decode()))
 
 
-def _assert_feed(names, prefix):
+def _assert_feed(names, prefix, applies=True):
     """The detailed launch name says which feed ran: "... s<stride> res]" on the residue-image feed, "... s<stride>]"
-    on the chunk-per-tap one.  Every shape here is one the residue feed applies to, so it must have run unless the
-    process was started with ASW_NO_RESIDUE_FEED, and then it must not have."""
+    on the chunk-per-tap one.  Where the residue feed applies to the shape it must have run unless the process was
+    started with ASW_NO_RESIDUE_FEED, and then it must not have; where it does not apply it must not have run."""
     mine = [n for n in names if n.startswith(prefix)]
     assert mine, names
-    want_res = "ASW_NO_RESIDUE_FEED" not in os.environ
+    want_res = applies and "ASW_NO_RESIDUE_FEED" not in os.environ
     for n in mine:
         assert n.endswith(" res]") == want_res, (n, want_res)
 
@@ -114,48 +116,74 @@ def _run_mask(name, precision):
             "overflow": ops.f16x3_overflow_count(reset=True)}
 
 
-# ---------------------------------------------------------------- strided convolutions
+# ---------------------------------------------------------------- convolutions
 # C, N, taps, stride, M_out, B, distinct items, stats, expected launch-name prefix (None: whatever the shape reaches)
+# and what the shapes of the chunk walk alone add ({}: nothing): dil, skip (a second input added on load), gate (a tensor
+# the output is multiplied by)
 CONV = {
-    "k7s4_M296_B2": (128, 256, 7, 4, 296, 2, 2, True, None),
-    "k5s4_M270_B2": (128, 256, 5, 4, 270, 2, 2, True, None),
-    "k5s2_M300_B2": (128, 256, 5, 2, 300, 2, 2, True, None),
+    "k7s4_M296_B2": (128, 256, 7, 4, 296, 2, 2, True, None, {}),
+    "k5s4_M270_B2": (128, 256, 5, 4, 270, 2, 2, True, None, {}),
+    "k5s2_M300_B2": (128, 256, 5, 2, 300, 2, 2, True, None, {}),
     # the shapes that reach the pipelined tiles: two row tiles per item, the second ragged (244 frames of 256)
-    "k7s4_M500_B256": (128, 256, 7, 4, 500, 256, 4, True, "convgemm16p<256,256,32,stats>"),
-    "k7s4_M500_B256_plain": (128, 256, 7, 4, 500, 256, 4, False, "convgemm16p<256,256,32,plain>"),   # range guard live
-    "k5s4_M500_B256": (128, 256, 5, 4, 500, 256, 4, True, "convgemm16p<256,256,32,stats>"),
-    "k5s2_M500_B256": (128, 256, 5, 2, 500, 256, 4, True, "convgemm16p<256,256,32,stats>"),         # three taps on one image
-    "k7s4_C64_M500_B256": (64, 256, 7, 4, 500, 256, 4, True, "convgemm16p<128,256,32,stats>"),      # K <= 512: 4-wave tile
+    "k7s4_M500_B256": (128, 256, 7, 4, 500, 256, 4, True, "convgemm16p<256,256,32,stats>", {}),
+    "k7s4_M500_B256_plain": (128, 256, 7, 4, 500, 256, 4, False, "convgemm16p<256,256,32,plain>", {}),   # range guard live
+    "k5s4_M500_B256": (128, 256, 5, 4, 500, 256, 4, True, "convgemm16p<256,256,32,stats>", {}),
+    "k5s2_M500_B256": (128, 256, 5, 2, 500, 256, 4, True, "convgemm16p<256,256,32,stats>", {}),         # three taps on one image
+    "k7s4_C64_M500_B256": (64, 256, 7, 4, 500, 256, 4, True, "convgemm16p<128,256,32,stats>", {}),      # K <= 512: 4-wave tile
+    # the chunk walk where the residue walk never applies (the last 128- or 256-row tile ragged as above): the decoder's
+    # transposed convolution (one tap, skip operand, statistics), the gated linear, a dilated stride-1 convolution
+    "k1_skip_C256_M500_B256": (256, 256, 1, 1, 500, 256, 4, True, "convgemm16p<128,256,32,stats>", dict(skip=True)),
+    "k1_gate_C1024_M500_B256": (1024, 256, 1, 1, 500, 256, 4, False, "convgemm16pm<256,256,32,plain>", dict(gate=True)),
+    "k3d2_M500_B256": (128, 256, 3, 1, 500, 256, 4, True, "convgemm16p<128,256,32,stats>", dict(dil=2)),
 }
+
+
+def _conv_row(name):
+    *row, extra = CONV[name]
+    return (*row, dict(dict(dil=1, skip=False, gate=False), **extra))
+
+
 _conv_ref = {}
 
 
 def _conv_reference(name):
     if name not in _conv_ref:
-        C, N, K, s, M, B, nd, stats, _ = CONV[name]
-        T = (M - 1) * s + 1 + (K - 1) - 2 * (K // 2)        # the shortest input with M output frames
+        C, N, K, s, M, B, nd, stats, _, o = _conv_row(name)
+        pad = o["dil"] * (K // 2)
+        T = (M - 1) * s + 1 + o["dil"] * (K - 1) - 2 * pad  # the shortest input with M output frames
         T += s - 1                                          # ... and the longest: rows past the last tap exist
         x = _rand(nd, C, T, seed=60)
         w = _rand(N, C, K, seed=61, scale=1 / math.sqrt(C * K))
         b = _rand(N, seed=62, scale=0.1)
-        want = F.conv1d(x.double(), w.double(), b.double(), stride=s, padding=K // 2).transpose(1, 2).contiguous()
+        x2 = _rand(nd, C, T, seed=63) if o["skip"] else None
+        gate = _rand(nd, M, N, seed=64) if o["gate"] else None
+        xin = x.double() + x2.double() if o["skip"] else x.double()
+        want = F.conv1d(xin, w.double(), b.double(), stride=s, padding=pad, dilation=o["dil"]).transpose(1, 2).contiguous()
         assert want.shape == (nd, M, N)
-        _conv_ref[name] = dict(x=x, w=w, b=b, want=want)
+        if o["gate"]:
+            want = want * gate.double()
+        _conv_ref[name] = dict(x=x, w=w, b=b, x2=x2, gate=gate, pad=pad, want=want)
     return _conv_ref[name]
 
 
 def _run_conv(name, precision):
     from acousticswarms_speech_amd import ops
-    C, N, K, s, M, B, nd, stats, prefix = CONV[name]
+    C, N, K, s, M, B, nd, stats, prefix, o = _conv_row(name)
     r = _conv_reference(name)
-    xc = r["x"].transpose(1, 2).contiguous().repeat(B // nd, 1, 1).cuda()       # item b = distinct item b % nd
+
+    def items(t):                                           # item b = distinct item b % nd
+        return None if t is None else t.cuda().repeat(B // nd, 1, 1)
+    xc = items(r["x"].transpose(1, 2).contiguous())
+    x2c = items(None if r["x2"] is None else r["x2"].transpose(1, 2).contiguous())
+    gc = items(r["gate"])
     wt = ops.pack_conv_weight(r["w"]).cuda()
     ops.f16x3_overflow_count(reset=True)
-    (out, st), names = _launch_names(lambda: ops.convgemm(xc, wt, M, N, C, taps=K, stride=s, pad=K // 2, bias=r["b"].cuda(),
+    (out, st), names = _launch_names(lambda: ops.convgemm(xc, wt, M, N, C, taps=K, stride=s, dil=o["dil"], pad=r["pad"],
+                                                           bias=r["b"].cuda(), A2=x2c, mul=gc,
                                                            stats_chan_mod=N if stats else 0, precision=precision))
     if prefix is not None:
         assert any(n.startswith(prefix) for n in names), names
-        _assert_feed(names, prefix)
+        _assert_feed(names, prefix, applies=K > s >= 2)
     want = r["want"].cuda()
     diff = out.view(B // nd, nd, M, N).double() - want
     fig = {"rel": float(diff.norm() / (want.norm() * math.sqrt(B // nd))), "overflow": ops.f16x3_overflow_count(reset=True)}
@@ -204,7 +232,8 @@ def _all_f16x3():
 
 
 def test_both_feeds_inside_the_bar():
-    """Every shape once more on the chunk-per-tap feed (ASW_NO_RESIDUE_FEED=1 is read once per process: a fresh child).
+    """Every shape once more on the chunk-per-tap feed (ASW_NO_RESIDUE_FEED=1 is read once per process: a fresh child;
+    it takes under 3 s on an MI355X with the float64 references of all eleven rows, the limit of 300 s is for a cold start).
     The two feeds add the K terms in different orders, so they are not compared bit for bit; each is held to the bar."""
     env = dict(os.environ, ASW_NO_RESIDUE_FEED="1")
     p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=300)
