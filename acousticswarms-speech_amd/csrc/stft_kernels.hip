@@ -12,6 +12,7 @@
 // The house rules of eval_kernels.hip hold: grids over host-built tables, no atomics, no cross-lane operations, no
 // device-side assert, one writer per address, every sum in one fixed order.
 #include "asw_common.h"
+#include "fft1024.h"
 
 #include <cmath>
 #include <cstdint>
@@ -20,8 +21,7 @@
 
 namespace {
 
-constexpr int NFFT = 2048, HOP = 1024, NB = 1025, NH = 1024;   // NH: the complex transform's length
-constexpr int THREADS = 256;
+using namespace asw::fft;              // NFFT, HOP, NB, NH, THREADS; Lds, fft1024, the split and merge steps (fft1024.h)
 constexpr int MAX_K = 65535, MAX_S = 64, MAX_ROWS = 65535;
 constexpr int MAX_T = 1 << 25;
 constexpr long MAX_GRID = 1L << 30;
@@ -47,10 +47,7 @@ int device_tables(const double** out) {
   if (!g_tables.tab[dev]) {
     std::vector<double> h(N_TAB);
     const double pi = 3.14159265358979323846;
-    for (int t = 0; t < NH; ++t) {
-      h[O_TW + 2 * t] = std::cos(2.0 * pi * t / NFFT);
-      h[O_TW + 2 * t + 1] = -std::sin(2.0 * pi * t / NFFT);
-    }
+    fill_twiddles(&h[O_TW]);
     double wsum = 0.0;
     for (int n = 0; n < NFFT; ++n) {
       h[O_WIN + n] = 0.5 - 0.5 * std::cos(2.0 * pi * n / NFFT);
@@ -82,34 +79,6 @@ struct Item {                          // one (mixture row, reference rows) grou
 };
 
 // ---- device pieces -----------------------------------------------------------------------------------------------
-struct Lds {
-  double re[2][NH], im[2][NH];
-};
-
-// The 1024-point transform of (re[0], im[0]) in place: ten radix-2 Stockham passes, buffer 0 -> 1 -> 0 ...; INV takes the
-// conjugate twiddles (no scaling).  Enters and leaves through a barrier.
-template <bool INV>
-__device__ __forceinline__ void fft1024(Lds& L, const double* __restrict__ tw, int tid) {
-  int src = 0;
-#pragma unroll 1
-  for (int ns = 1; ns < NH; ns <<= 1) {
-    __syncthreads();
-    const int step = NH / ns;
-    for (int j = tid; j < NH / 2; j += THREADS) {
-      const int k = j & (ns - 1);
-      const double c = tw[2 * (k * step)], s0 = tw[2 * (k * step) + 1];
-      const double s = INV ? -s0 : s0;
-      const double ar = L.re[src][j], ai = L.im[src][j], xr = L.re[src][j + NH / 2], xi = L.im[src][j + NH / 2];
-      const double br = xr * c - xi * s, bi = xr * s + xi * c;
-      const int j0 = ((j - k) << 1) + k;
-      L.re[src ^ 1][j0] = ar + br, L.im[src ^ 1][j0] = ai + bi;
-      L.re[src ^ 1][j0 + ns] = ar - br, L.im[src ^ 1][j0 + ns] = ai - bi;
-    }
-    src ^= 1;
-  }
-  __syncthreads();
-}
-
 // frame f of a row of N float32 samples, windowed, into buffer 0: padded sample p = 1024 f + n is x[p - 1024] or 0
 __device__ __forceinline__ void load_frame(Lds& L, const float* __restrict__ row, int N, int f, const double* __restrict__ win,
                                            int tid) {
@@ -119,41 +88,6 @@ __device__ __forceinline__ void load_frame(Lds& L, const float* __restrict__ row
     const double a = t >= 0 && t < N ? (double)row[t] : 0.0, b = t + 1 >= 0 && t + 1 < N ? (double)row[t + 1] : 0.0;
     L.re[0][m] = a * win[2 * m], L.im[0][m] = b * win[2 * m + 1];
   }
-}
-
-struct Cx { double r, i; };
-
-// The one-sided bins k and 1024 - k (0 < k <= 512) of the real frame from the half-length transform Z in buffer 0:
-// X[k] = E + W^k O, X[1024-k] = conj(E - W^k O) with E, O the transforms of the even and odd samples, divided by sum(w)
-__device__ __forceinline__ void split_pair(const Lds& L, const double* __restrict__ tw, int k, double wsum, Cx& xk, Cx& xm) {
-  const int km = NH - k;
-  const double ar = L.re[0][k], ai = L.im[0][k], br = L.re[0][km], bi = L.im[0][km];
-  const double er = 0.5 * (ar + br), ei = 0.5 * (ai - bi), orr = 0.5 * (ai + bi), oi = -0.5 * (ar - br);
-  const double c = tw[2 * k], s = tw[2 * k + 1];
-  const double tr = orr * c - oi * s, ti = orr * s + oi * c;
-  xk = Cx{(er + tr) / wsum, (ei + ti) / wsum};
-  xm = Cx{(er - tr) / wsum, -(ei - ti) / wsum};
-}
-// bins 0 and 1024: both real
-__device__ __forceinline__ void split_ends(const Lds& L, double wsum, Cx& x0, Cx& xn) {
-  const double ar = L.re[0][0], ai = L.im[0][0];
-  x0 = Cx{(ar + ai) / wsum, 0.0};
-  xn = Cx{(ar - ai) / wsum, 0.0};
-}
-
-// The reverse: Z'[k] = E + i O and Z'[1024-k] = conj(E) + i conj(O) from the bins Y[k], Y[1024-k], written to buffer 0
-// with the 1/1024 of the inverse transform folded in
-__device__ __forceinline__ void merge_pair(Lds& L, const double* __restrict__ tw, int k, Cx yk, Cx ym) {
-  const int km = NH - k;
-  const double er = 0.5 * (yk.r + ym.r), ei = 0.5 * (yk.i - ym.i), tr = 0.5 * (yk.r - ym.r), ti = 0.5 * (yk.i + ym.i);
-  const double c = tw[2 * k], s = -tw[2 * k + 1];                       // W^-k
-  const double orr = tr * c - ti * s, oi = tr * s + ti * c;
-  const double sc = 1.0 / NH;
-  L.re[0][k] = (er - oi) * sc, L.im[0][k] = (ei + orr) * sc;
-  L.re[0][km] = (er + oi) * sc, L.im[0][km] = (orr - ei) * sc;
-}
-__device__ __forceinline__ void merge_ends(Lds& L, double y0, double yn) {        // the imaginary parts do not count
-  L.re[0][0] = 0.5 * (y0 + yn) * (1.0 / NH), L.im[0][0] = 0.5 * (y0 - yn) * (1.0 / NH);
 }
 
 // the time frame in buffer 0 (after the inverse transform), times w * sum(w), to its slot of the workspace

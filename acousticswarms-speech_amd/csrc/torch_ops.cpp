@@ -899,6 +899,74 @@ Tensor oracle_masks(const Tensor& mix, const Tensor& ref, at::IntArrayRef counts
   return out;
 }
 
+// ---- room simulator (roomsim.py) ----------------------------------------------------------------------------------------
+void need_host_f64(const Tensor& t, const char* name, std::initializer_list<int64_t> shape) {
+  TORCH_CHECK(t.is_cpu(), name, " must be a host (cpu) tensor: the library reads it before the call returns");
+  TORCH_CHECK(t.scalar_type() == at::kDouble, name, " must be float64, got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.sizes() == at::IntArrayRef(shape.begin(), shape.size()), name, " has shape ", t.sizes(), ", expected ",
+              at::IntArrayRef(shape.begin(), shape.size()));
+}
+
+// -> float64 [sum counts, M, length] on the current HIP device: the image-source responses of K shoebox scenes
+// (roomsim.rir_f64).  rooms [K,3], absorption [K], src [sum counts,3] and mics [K,M,3] are HOST float64 tensors and the two
+// lists host integers, as the library validates all of them before its one launch; the op is registered for the CPU key.
+Tensor room_rir(const Tensor& rooms, const Tensor& absorption, at::IntArrayRef max_orders, const Tensor& src, const Tensor& mics,
+                at::IntArrayRef counts, double fs, int64_t length) {
+  const int K = checked_int(static_cast<int64_t>(counts.size()), "K");
+  TORCH_CHECK(K <= 65535, "room_rir: ", K, " scenes (at most 65535)");
+  TORCH_CHECK(mics.dim() == 3, "mics must be [K, M, 3], got ", mics.dim(), " dimensions");
+  const int M = checked_int(mics.size(1), "M");
+  TORCH_CHECK(M >= 1 && M <= 1024, "room_rir: M = ", M, " outside 1..1024");
+  TORCH_CHECK(length >= 1 && length <= (1 << 25), "room_rir: length = ", length, " outside 1..2^25");
+  TORCH_CHECK(static_cast<int64_t>(max_orders.size()) == K, "counts holds ", K, " scenes, max_orders ", max_orders.size());
+  const Counts c = checked_counts(counts, "counts", 0, 64), n = checked_counts(max_orders, "max_orders");
+  TORCH_CHECK(c.sum <= 65535, "room_rir: ", c.sum, " sources (at most 65535)");
+  need_host_f64(rooms, "rooms", {K, 3});
+  need_host_f64(absorption, "absorption", {K});
+  need_host_f64(src, "src", {c.sum, 3});
+  need_host_f64(mics, "mics", {K, M, 3});
+  const auto dev = c10::Device(c10::DeviceType::CUDA, c10::hip::current_device());
+  Tensor out = at::empty({c.sum, M, length}, at::TensorOptions().dtype(at::kDouble).device(dev));
+  const size_t ws_bytes = asw_room_rir_workspace_bytes(K, M, static_cast<int>(c.sum));
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_room_rir_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, out.options());
+  Launch l(out);
+  check_status(asw_room_rir(rooms.data_ptr<double>(), absorption.data_ptr<double>(), n.v.data(), src.data_ptr<double>(),
+                            mics.data_ptr<double>(), c.v.data(), K, M, fs, static_cast<int>(length), out.data_ptr<double>(),
+                            ws.data_ptr(), ws_bytes, l.stream),
+               "asw_room_rir");
+  return out;
+}
+
+// -> (premix float64 [sum counts, M, T], mix float64 [K, M, T]): dry [sum counts, T] float32 through rir [sum counts, M,
+// length] float64, and the sum over the sources of every scene in order (roomsim.convolve_f64)
+std::tuple<Tensor, Tensor> room_convolve(const Tensor& dry, const Tensor& rir, at::IntArrayRef counts) {
+  need(dry, "dry", at::kFloat, 2);
+  need(rir, "rir", at::kDouble, 3);
+  same_device(dry, rir, "dry and rir");
+  const int K = checked_int(static_cast<int64_t>(counts.size()), "K"), T = checked_int(dry.size(1), "T");
+  const int M = checked_int(rir.size(1), "M"), length = checked_int(rir.size(2), "length");
+  TORCH_CHECK(K <= 65535, "room_convolve: ", K, " scenes (at most 65535)");
+  const Counts c = checked_counts(counts, "counts", 0, 64);
+  TORCH_CHECK(c.sum == dry.size(0) && c.sum == rir.size(0), "counts sum to ", c.sum, ", dry has ", dry.size(0), " rows and rir ",
+              rir.size(0));
+  TORCH_CHECK(M >= 1 && M <= 1024, "room_convolve: M = ", M, " outside 1..1024");
+  TORCH_CHECK(T >= 1 && T <= (1 << 25) && length >= 1 && length <= (1 << 25), "room_convolve: T = ", T, " or length = ", length,
+              " outside 1..2^25");
+  Tensor premix = at::empty({c.sum, M, T}, rir.options());
+  Tensor mix = at::empty({K, M, T}, rir.options());
+  if (K == 0) return {premix, mix};
+  const size_t ws_bytes = asw_room_convolve_workspace_bytes(c.v.data(), K, M, length, T);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_room_convolve_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, rir.options());
+  Launch l(dry);
+  check_status(asw_room_convolve(dry.data_ptr<float>(), rir.data_ptr<double>(), c.v.data(), K, M, length, T, premix.data_ptr<double>(),
+                                 mix.data_ptr<double>(), ws.data_ptr(), ws_bytes, l.stream),
+               "asw_room_convolve");
+  return {premix, mix};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(asw, m) {
@@ -950,6 +1018,9 @@ TORCH_LIBRARY(asw, m) {
   m.def("istft(Tensor z, int n) -> Tensor");
   m.def("oracle_masks(Tensor mix, Tensor ref, int[] counts, int[] lengths, str kind, float alpha=1.0, float theta=0.5) -> "
         "Tensor");
+  m.def("room_rir(Tensor rooms, Tensor absorption, int[] max_orders, Tensor src, Tensor mics, int[] counts, float fs, "
+        "int length) -> Tensor");
+  m.def("room_convolve(Tensor dry, Tensor rir, int[] counts) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(asw, CUDA, m) {
@@ -988,4 +1059,10 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("stft", &stft);
   m.impl("istft", &istft);
   m.impl("oracle_masks", &oracle_masks);
+  m.impl("room_convolve", &room_convolve);
+}
+
+// room_rir takes its geometry as host tensors (the library validates it on the host) and answers on the current device
+TORCH_LIBRARY_IMPL(asw, CPU, m) {
+  m.impl("room_rir", &room_rir);
 }

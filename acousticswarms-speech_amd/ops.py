@@ -544,6 +544,61 @@ def oracle_masks(mix, ref, counts, lengths, kind, alpha=1.0, theta=0.5, out=None
     return res
 
 
+def _host_f64(a, shape):
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    assert a.shape == tuple(shape), f"shape {a.shape}, expected {tuple(shape)}"
+    return a
+
+
+def room_rir(rooms, absorption, max_orders, src, mics, counts, fs, length, device=None, out=None):
+    """The image-source responses of K shoebox scenes in one call (``roomsim.rir_f64``): rooms [K,3], absorption [K],
+    src [sum counts,3] and mics [K,M,3] host float64 arrays, ``max_orders`` and ``counts`` host integers -> float64
+    [sum counts,M,length] on ``device`` (the current one by default).  ``out``: write into this tensor (tests)."""
+    K = len(counts)
+    NS = sum(int(c) for c in counts)
+    import numpy as np
+    M = np.shape(mics)[1]
+    rooms, absorption, src = _host_f64(rooms, (K, 3)), _host_f64(absorption, (K,)), _host_f64(src, (NS, 3))
+    mics = _host_f64(mics, (K, M, 3))
+    assert len(max_orders) == K
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if out is None else out.device
+    res = torch.empty((NS, M, int(length)), dtype=torch.float64, device=device) if out is None else out
+    assert res.shape == (NS, M, int(length)) and res.dtype == torch.float64 and res.is_cuda and res.is_contiguous()
+    nbytes = lib().asw_room_rir_workspace_bytes(K, M, NS)
+    if nbytes == 0:
+        check(-1)
+    with torch.cuda.device(res.device):
+        ws = _ws_f64(nbytes, res.device)
+        check(lib().asw_room_rir(rooms.ctypes.data, absorption.ctypes.data, _host_i32(max_orders), src.ctypes.data, mics.ctypes.data,
+                                 _host_i32(counts), K, M, float(fs), int(length), ptr(res), ptr(ws), nbytes, current_stream()))
+    return res
+
+
+def room_convolve(dry, rir, counts, out=None):
+    """dry [sum counts,T] float32 through rir [sum counts,M,length] float64 (``roomsim.convolve_f64``) -> (premix
+    [sum counts,M,T], mix [K,M,T]) float64, mix the sum of a scene's premix rows in source order.  ``out``: the pair of
+    tensors to write into (tests)."""
+    NS, T = dry.shape
+    _ns, M, length = rir.shape
+    K = len(counts)
+    assert _ns == NS == sum(int(c) for c in counts)
+    assert rir.is_cuda and rir.dtype == torch.float64 and rir.is_contiguous()
+    premix, mix = (torch.empty((NS, M, T), dtype=torch.float64, device=dry.device),
+                   torch.empty((K, M, T), dtype=torch.float64, device=dry.device)) if out is None else out
+    for t, shape in ((premix, (NS, M, T)), (mix, (K, M, T))):
+        assert t.shape == shape and t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()
+    c = _host_i32(counts)
+    nbytes = lib().asw_room_convolve_workspace_bytes(c, K, M, length, T)
+    if nbytes == 0:
+        check(-1)
+    ws = _ws_f64(nbytes, dry.device)
+    check(lib().asw_room_convolve(ptr(_f32(dry)) if NS else None, ptr(rir) if NS else None, c, K, M, length, T,
+                                  ptr(premix) if NS else None, ptr(mix), ptr(ws), nbytes, current_stream()))
+    return premix, mix
+
+
 def f16x3_overflow_count(reset=True) -> int:
     """Threads of f16x3 launches that produced an activation beyond the fp16 range since the last
     reset (asw_f16x3_overflow_count); 0 means no later GEMM clipped its input."""

@@ -4,7 +4,10 @@ pyroomacoustics and the Zenodo datasets are unavailable offline, so benchmarks
 and parity tests run on free-field (optionally first-order image-source)
 mixtures whose geometry follows the reference's dataset recipe
 (datasets/generate_dataset.py:341-376 desk + robots fanned from mic 0,
-:512-578 talker placement, :19-20 amplitudes).
+:512-578 talker placement, :19-20 amplitudes).  The scenes
+here stay what the benchmark and the parity tests were recorded on; shoebox
+rooms simulated by the image-source method, with the reference's recipe drawn
+exactly, are ``room_scenes.make_room_scene``.
 """
 from dataclasses import dataclass
 

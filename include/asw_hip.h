@@ -1071,6 +1071,47 @@ int asw_oracle_masks(const float* mix, const float* ref, const int32_t* counts_h
                      int stride, int kind, double alpha, double theta, double* out, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- Room simulator: image-source impulse responses and their convolution (roomsim.py) --------
+ * The shoebox simulation of the dataset generator in float64, many scenes per call.  Scene k is an axis-aligned box
+ * rooms[k] = (Lx, Ly, Lz) with one corner at the origin, one energy absorption a_k on all six walls (amplitude
+ * reflection r = sqrt(1 - a)), an image order N_k and S_k = counts[k] sources; the sources of all scenes are packed in
+ * scene order, every scene has M microphones.  The statements are roomsim.rir_f64 and roomsim.convolve_f64.
+ *
+ * asw_room_rir: rir float64 [sum S_k][M][length] (device), every sample written once.  Every other array is a HOST
+ *   array read before the call returns: rooms [K][3], absorption [K], max_orders [K], src [sum S_k][3], mics [K][M][3],
+ *   counts [K].  The images are the integer triples n with |nx| + |ny| + |nz| <= N in the order nx, ny, nz ascending;
+ *   along an axis image n lies at n L + s for even n and (n + 1) L - s for odd n.  With d = sqrt(dx dx + dy dy + dz dz)
+ *   summed in that order, t = d / 343 * fs, ip = floor(t) and f = t - ip, an image adds
+ *   r^(|nx|+|ny|+|nz|) / (4 pi d) * w[j] * sinc(j - 40 - f) to sample ip + j for j = 0..80, w[j] = 0.5 - 0.5 cos(2 pi j /
+ *   80); taps at or beyond `length` are dropped.  ip and f are those of the statement bit for bit (the file is compiled
+ *   without fused multiply-adds); sin, the r^n table of the host's pow and the order of the sum are the library's own.
+ *     A workgroup owns one (source, microphone) pair and 1024 samples; it walks the (nx, ny) columns, solves each for the
+ *     nz that can reach its samples, decides by the exact delay and adds the hits in image order.  No atomics.
+ *   workspace: asw_room_rir_workspace_bytes(K, M, sum S_k) bytes, 8-byte aligned (the host-built tables).
+ *   Refused: K outside 0..65535, M outside 1..1024, S_k outside 0..64, more than 65535 sources, length outside 1..2^25,
+ *   fs outside (0, 1e9], a side outside (0, 1e6], absorption outside (0, 1], an order outside 0..150, a source or
+ *   microphone not strictly inside its room, a source at a microphone's position, a null pointer with work to do, a
+ *   short or misaligned workspace.  K = 0 succeeds and touches nothing.
+ *
+ * asw_room_convolve: premix[s][m][t] = sum_k dry[s][t - k] rir[s][m][k] for t < T, and mix[k][m] the sum of the premix
+ *   rows of scene k in source order.  dry float32 [sum S_k][T], rir float64 [sum S_k][M][length], premix float64
+ *   [sum S_k][M][T], mix float64 [K][M][T], all device; counts HOST.  Uniformly partitioned overlap-save with hop 1024
+ *   and frame 2048 on the transform of the STFT: one launch each transforms the frames of dry and the zero-padded
+ *   1024-tap partitions of rir, a third accumulates X[s][b - p] H[s][m][p] over p ascending per (scene, microphone,
+ *   block), inverts and keeps the second half.  A scene with S_k = 0 gets a zero mix.
+ *   workspace: asw_room_convolve_workspace_bytes(counts, K, M, length, T) bytes, 16-byte aligned (the spectra: 16400
+ *   bytes per source and block of T plus per source, microphone and partition of length); 0 with the error message set
+ *   for arguments the call would refuse.  Refused: K outside 0..65535, M outside 1..1024, S_k outside 0..64, length or T
+ *   outside 1..2^25, more than 65535 (source, microphone) pairs, a null pointer with work to do, a short or misaligned
+ *   workspace. */
+size_t asw_room_rir_workspace_bytes(int K, int M, int n_src);
+int asw_room_rir(const double* rooms_host, const double* absorption_host, const int32_t* max_orders_host, const double* src_host,
+                 const double* mics_host, const int32_t* counts_host, int K, int M, double fs, int length, double* rir,
+                 void* workspace, size_t workspace_bytes, void* stream);
+size_t asw_room_convolve_workspace_bytes(const int32_t* counts_host, int K, int M, int length, int T);
+int asw_room_convolve(const float* dry, const double* rir, const int32_t* counts_host, int K, int M, int length, int T,
+                      double* premix, double* mix, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
