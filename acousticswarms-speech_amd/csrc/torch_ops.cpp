@@ -967,6 +967,75 @@ std::tuple<Tensor, Tensor> room_convolve(const Tensor& dry, const Tensor& rir, a
   return {premix, mix};
 }
 
+// ---- training batches (train_data.py) -------------------------------------------------------------------------------
+// -> float64 [rows, T] on the current HIP device: power-law noise rows (train_data.colored_noise_f64).  The keys and row
+// indices are host integers, so the op has no tensor argument and is registered for every backend.
+Tensor colored_noise(at::IntArrayRef row_keys, at::IntArrayRef row_ids, int64_t T, double exponent, int64_t max_rows_per_pass) {
+  const int rows = checked_int(static_cast<int64_t>(row_keys.size()), "rows");
+  TORCH_CHECK(static_cast<int64_t>(row_ids.size()) == rows, "row_keys holds ", rows, " rows, row_ids ", row_ids.size());
+  const Counts ids = checked_counts(row_ids, "row_ids", 0, INT32_MAX);
+  const std::vector<int64_t> keys(row_keys.begin(), row_keys.end());
+  const auto dev = c10::Device(c10::DeviceType::CUDA, c10::hip::current_device());
+  Tensor out = at::empty({rows, T}, at::TensorOptions().dtype(at::kDouble).device(dev));
+  const size_t ws_bytes = asw_colored_noise_workspace_bytes(rows, checked_int(T, "T"), checked_int(max_rows_per_pass, "max_rows_per_pass"));
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_colored_noise_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, out.options());
+  Launch l(out);
+  check_status(asw_colored_noise(keys.data(), ids.v.data(), rows, static_cast<int>(T), exponent, static_cast<int>(max_rows_per_pass),
+                                 out.data_ptr<double>(), ws.data_ptr(), ws_bytes, l.stream),
+               "asw_colored_noise");
+  return out;
+}
+
+// -> [items, S_max * M, T] float32 (float64 when out_f64): mix [K, M, T] rolled per item and talker block and perturbed
+// (train_data.train_batch_f64).  shifts is the flattened [items, S_max, M] table; pink [items, S_max * M, T] float64 or None
+Tensor train_batch(const Tensor& mix, at::IntArrayRef item_mix, at::IntArrayRef shifts, int64_t S_max, at::IntArrayRef counts,
+                   at::ArrayRef<double> pink_level, at::ArrayRef<double> white_level, at::IntArrayRef white_key,
+                   const c10::optional<Tensor>& pink, bool out_f64) {
+  need(mix, "mix", at::kFloat, 3);
+  const int K = checked_int(mix.size(0), "K"), M = checked_int(mix.size(1), "M"), T = checked_int(mix.size(2), "T");
+  const int items = checked_int(static_cast<int64_t>(item_mix.size()), "items"), S = checked_int(S_max, "S_max");
+  TORCH_CHECK(S >= 1 && M >= 1, "train_batch: S_max = ", S, " or M = ", M, " below 1");
+  TORCH_CHECK(static_cast<int64_t>(counts.size()) == items && static_cast<int64_t>(pink_level.size()) == items &&
+                  static_cast<int64_t>(white_level.size()) == items && static_cast<int64_t>(white_key.size()) == items,
+              "train_batch: item_mix holds ", items, " items, the other tables do not");
+  TORCH_CHECK(static_cast<int64_t>(shifts.size()) == static_cast<int64_t>(items) * S * M, "train_batch: shifts holds ", shifts.size(),
+              " entries, expected items * S_max * M = ", static_cast<int64_t>(items) * S * M);
+  const Counts im = checked_counts(item_mix, "item_mix"), sh = checked_counts(shifts, "shifts"), cn = checked_counts(counts, "counts", 0, S);
+  const std::vector<int64_t> keys(white_key.begin(), white_key.end());
+  if (pink.has_value()) {
+    need(*pink, "pink", at::kDouble, 3);
+    same_device(mix, *pink, "mix and pink");
+    TORCH_CHECK(pink->size(0) == items && pink->size(1) == static_cast<int64_t>(S) * M && pink->size(2) == T,
+                "pink must be [items, S_max * M, T]");
+  }
+  Tensor out = at::empty({items, static_cast<int64_t>(S) * M, T}, mix.options().dtype(out_f64 ? at::kDouble : at::kFloat));
+  if (items == 0) return out;
+  const size_t ws_bytes = asw_train_batch_workspace_bytes(items, S, M);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_train_batch_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, mix.options().dtype(at::kDouble));
+  Launch l(mix);
+  check_status(asw_train_batch(mix.data_ptr<float>(), K, M, T, items, S, im.v.data(), sh.v.data(), cn.v.data(), pink_level.data(),
+                               white_level.data(), keys.data(), pink.has_value() ? pink->data_ptr<double>() : nullptr, out.data_ptr(),
+                               out_f64 ? 1 : 0, ws.data_ptr(), ws_bytes, l.stream),
+               "asw_train_batch");
+  return out;
+}
+
+// -> float64 [N, 4]: mean |e - g|, -SNR, -SI-SDR and max |g| of every row (train_data.row_losses_f64)
+Tensor train_losses(const Tensor& est, const Tensor& gt) {
+  need(est, "est", at::kFloat, 2);
+  need(gt, "gt", at::kFloat, 2);
+  same_device(est, gt, "est and gt");
+  TORCH_CHECK(est.sizes() == gt.sizes(), "est and gt must have one shape");
+  const int N = checked_int(est.size(0), "N"), T = checked_int(est.size(1), "T");
+  Tensor out = at::empty({N, 4}, est.options().dtype(at::kDouble));
+  if (N == 0) return out;
+  Launch l(est);
+  check_status(asw_train_losses(est.data_ptr<float>(), gt.data_ptr<float>(), N, T, out.data_ptr<double>(), l.stream), "asw_train_losses");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(asw, m) {
@@ -1021,6 +1090,10 @@ TORCH_LIBRARY(asw, m) {
   m.def("room_rir(Tensor rooms, Tensor absorption, int[] max_orders, Tensor src, Tensor mics, int[] counts, float fs, "
         "int length) -> Tensor");
   m.def("room_convolve(Tensor dry, Tensor rir, int[] counts) -> (Tensor, Tensor)");
+  m.def("colored_noise(int[] row_keys, int[] row_ids, int T, float exponent=1.0, int max_rows_per_pass=0) -> Tensor");
+  m.def("train_batch(Tensor mix, int[] item_mix, int[] shifts, int S_max, int[] counts, float[] pink_level, float[] white_level, "
+        "int[] white_key, Tensor? pink=None, bool out_f64=False) -> Tensor");
+  m.def("train_losses(Tensor est, Tensor gt) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(asw, CUDA, m) {
@@ -1060,9 +1133,16 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("istft", &istft);
   m.impl("oracle_masks", &oracle_masks);
   m.impl("room_convolve", &room_convolve);
+  m.impl("train_batch", &train_batch);
+  m.impl("train_losses", &train_losses);
 }
 
 // room_rir takes its geometry as host tensors (the library validates it on the host) and answers on the current device
 TORCH_LIBRARY_IMPL(asw, CPU, m) {
   m.impl("room_rir", &room_rir);
+}
+
+// colored_noise takes host integers only and answers on the current device
+TORCH_LIBRARY_IMPL(asw, CompositeExplicitAutograd, m) {
+  m.impl("colored_noise", &colored_noise);
 }

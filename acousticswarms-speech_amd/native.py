@@ -19,7 +19,7 @@ SOURCES = ["asw_common.cpp", "convgemm.hip", "resconv.hip", "pipegemm.hip", "res
            "misc_kernels.hip", "attention.hip", "srp_kernels.hip",
            "pruner_kernels.hip", "geometry_kernels.hip", "cluster_kernels.hip",
            "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip", "bss_kernels.hip", "eval_kernels.hip",
-           "longform_kernels.hip", "stft_kernels.hip", "room_kernels.hip"]
+           "longform_kernels.hip", "stft_kernels.hip", "room_kernels.hip", "augment_kernels.hip"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
 # (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out; eval_kernels.hip
 # rounds a * ref before it subtracts, as hostdsp.si_sdr does; room_kernels.hip must floor every image delay as
@@ -322,6 +322,12 @@ SIGNATURES = {
     "asw_room_convolve_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "asw_room_convolve": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),
+    "asw_colored_noise_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "asw_colored_noise": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "asw_train_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "asw_train_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "asw_train_losses": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -599,6 +599,83 @@ def room_convolve(dry, rir, counts, out=None):
     return premix, mix
 
 
+def _host_i64(values):
+    import ctypes
+    flat = [((int(v) + 2 ** 63) % 2 ** 64) - 2 ** 63 for v in values]         # 64-bit keys, as signed words
+    return (ctypes.c_int64 * max(1, len(flat)))(*flat)
+
+
+def _host_f64_list(values):
+    import ctypes
+    flat = [float(v) for v in values]
+    return (ctypes.c_double * max(1, len(flat)))(*flat)
+
+
+def colored_noise(key, rows, T, exponent=1.0, max_rows_per_pass=0, device=None, out=None):
+    """Power-law noise rows (``train_data.colored_noise_f64``) -> float64 [rows,T] on ``device``.  ``key``: one integer for
+    every row, or one per row; ``rows``: a count (rows 0..rows-1 of the key) or the list of row indices.  Rows are
+    processed ``max_rows_per_pass`` at a time (0: what fits 256 MiB of workspace); the bytes do not depend on it.
+    ``out``: write into this tensor (tests)."""
+    ids = list(range(rows)) if isinstance(rows, int) else [int(r) for r in rows]
+    keys = [int(key)] * len(ids) if isinstance(key, int) else [int(k) for k in key]
+    assert len(keys) == len(ids)
+    n = len(ids)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if out is None else out.device
+    res = torch.empty((n, int(T)), dtype=torch.float64, device=device) if out is None else out
+    assert res.shape == (n, int(T)) and res.dtype == torch.float64 and res.is_cuda and res.is_contiguous()
+    nbytes = lib().asw_colored_noise_workspace_bytes(n, int(T), int(max_rows_per_pass))
+    if nbytes == 0:
+        check(-1)
+    with torch.cuda.device(res.device):
+        ws = _ws_f64(nbytes, res.device)
+        check(lib().asw_colored_noise(_host_i64(keys), _host_i32(ids), n, int(T), float(exponent), int(max_rows_per_pass), ptr(res),
+                                      ptr(ws), nbytes, current_stream()))
+    return res
+
+
+def train_batch(mix, item_mix, shifts, counts, pink_level, white_level, white_key, pink=None, dtype=torch.float32, out=None):
+    """mix [K,M,T] float32 -> [I,S_max*M,T]: block s of item i is mixture ``item_mix[i]`` rolled by ``shifts[i][s]`` (host
+    integers [I][S_max][M]) for s < ``counts[i]`` and zero beyond, plus ``white_level[i]`` times inline Philox normals
+    under ``white_key[i]`` plus ``pink_level[i]`` times ``pink`` [I,S_max*M,T] float64 (``colored_noise``; may be None when
+    every pink level is zero), summed in float64 and rounded once (``train_data.train_batch_f64``).  ``dtype``:
+    torch.float32, or torch.float64 for the unrounded sum (tests).  ``out``: write into this tensor (tests)."""
+    import numpy as np
+    K, M, T = mix.shape
+    sh = np.ascontiguousarray(np.asarray(shifts, dtype=np.int32))
+    n_items = len(item_mix)
+    assert sh.ndim == 3 and sh.shape[0] == n_items and sh.shape[2] == M, f"shifts {sh.shape}: expected [{n_items}][S_max][{M}]"
+    S = sh.shape[1]
+    assert len(counts) == len(pink_level) == len(white_level) == len(white_key) == n_items
+    assert dtype in (torch.float32, torch.float64)
+    if pink is not None:
+        assert pink.shape == (n_items, S * M, T) and pink.dtype == torch.float64 and pink.is_contiguous() and pink.device == mix.device
+    res = torch.empty((n_items, S * M, T), dtype=dtype, device=mix.device) if out is None else out
+    assert res.shape == (n_items, S * M, T) and res.dtype == dtype and res.is_cuda and res.is_contiguous()
+    nbytes = lib().asw_train_batch_workspace_bytes(n_items, S, M)
+    if nbytes == 0:
+        check(-1)
+    with torch.cuda.device(mix.device):
+        ws = _ws_f64(nbytes, mix.device)
+        check(lib().asw_train_batch(ptr(_f32(mix)), K, M, T, n_items, S, _host_i32(item_mix), sh.ctypes.data, _host_i32(counts),
+                                    _host_f64_list(pink_level), _host_f64_list(white_level), _host_i64(white_key), ptr(pink), ptr(res),
+                                    int(dtype == torch.float64), ptr(ws), nbytes, current_stream()))
+    return res
+
+
+def train_losses(est, gt, out=None):
+    """est, gt [N,T] float32 -> float64 [N,4]: mean |e - g|, the negative SNR, the negative SI-SDR and max |g| of every
+    row (``train_data.row_losses_f64``); ``train_data.loss_from_rows`` combines them into the scalar of a loss name.
+    ``out``: write into this tensor (tests)."""
+    N, T = est.shape
+    assert gt.shape == est.shape and gt.device == est.device
+    res = torch.empty((N, 4), dtype=torch.float64, device=est.device) if out is None else out
+    assert res.shape == (N, 4) and res.dtype == torch.float64 and res.is_cuda and res.is_contiguous()
+    with torch.cuda.device(est.device):
+        check(lib().asw_train_losses(ptr(_f32(est)), ptr(_f32(gt)), N, T, ptr(res), current_stream()))
+    return res
+
+
 def f16x3_overflow_count(reset=True) -> int:
     """Threads of f16x3 launches that produced an activation beyond the fp16 range since the last
     reset (asw_f16x3_overflow_count); 0 means no later GEMM clipped its input."""

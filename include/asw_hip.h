@@ -1112,6 +1112,48 @@ size_t asw_room_convolve_workspace_bytes(const int32_t* counts_host, int K, int 
 int asw_room_convolve(const float* dry, const double* rir, const int32_t* counts_host, int K, int M, int length, int T,
                       double* premix, double* mix, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Training batches: noise, rolled mixtures, loss terms (train_data.py) ------------------------
+ * float64 arithmetic, no atomics, every sum in a fixed order: two calls give identical bytes.  The statements are
+ * train_data.colored_noise_f64, train_batch_f64 and row_losses_f64.
+ *
+ * asw_colored_noise: out float64 [rows][T] (device), every sample written once.  Row r is the power-law noise
+ *   irfft(s, n = T) / sigma of the reference's powerlaw_psd_gaussian (fmin = 0), its two arrays of normals drawn by
+ *   Philox4x32-10 under the 64-bit key row_key[r] with the counter (bin, row_id[r], 0, 0): words 0:1 and 2:3 give two
+ *   uniforms (2 m + 1) / 2^53, m the top 52 bits, and Box-Muller the pair of normals.  row_key and row_id are HOST arrays
+ *   read before the call returns.  Any 2 <= T <= 524288: Bluestein's chirp transform over L = 1024 R >= 2 T - 1, the
+ *   L-point transform a four-step (R-point column transforms, twiddles, 1024-point row transforms); rows 2p and 2p + 1
+ *   share one complex transform as its real and imaginary part.  Rows are processed in passes of at most
+ *   max_rows_per_pass (0: as many as fit 256 MiB of workspace; otherwise at least 2, odd values round down); the bytes do
+ *   not depend on it.
+ *   workspace: asw_colored_noise_workspace_bytes(rows, T, max_rows_per_pass) bytes, 16-byte aligned; 0 with the error
+ *   message set for arguments the call would refuse.  Refused: rows outside 0..2^20, T outside 2..524288, exponent outside
+ *   0..8, max_rows_per_pass negative or 1, a null pointer with work to do, a short or misaligned workspace.
+ *
+ * asw_train_batch: out [items][S_max * M][T], float32 or (out_f64 != 0) float64, device.  Row c = s M + m of item i is
+ *   x + white_level[i] w + pink_level[i] pink[i][c][t] summed in float64 in that order and rounded once, where x is
+ *   mix[item_mix[i]][m][(t - shifts[i][s][m]) mod T] for s < counts[i] and |shift| <= T and zero otherwise, and w is the
+ *   first normal of the Philox block (t, c, 1, 0) under white_key[i].  A level of zero leaves its term out, so that with
+ *   both zero the output is the rolled mixture bit for bit.  mix float32 [K][M][T] and pink float64 [items][S_max * M][T]
+ *   (may be null when every pink level is zero) are device arrays; item_mix, shifts, counts, the levels and white_key are
+ *   HOST arrays read before the call returns.
+ *   workspace: asw_train_batch_workspace_bytes(items, S_max, M) bytes, 8-byte aligned.
+ *   Refused: items or S_max * M beyond 65535, T outside 1..2^25, a count outside 0..S_max, an item_mix outside 0..K-1 on
+ *   an item with talkers, a level that is not finite, a non-zero pink level without pink, a null pointer with work to do.
+ *
+ * asw_train_losses: out float64 [N][4] = (mean |e - g|, -SNR, -SI-SDR, max |g|) of every row of est, gt float32 [N][T]
+ *   (device).  SNR and SI-SDR are those of asteroid's SingleSrcNegSDR: both rows zero-meaned, EPS = 1e-8 added to the
+ *   denominator and inside the logarithm.  One workgroup per row, three passes: the means, the centred sums, the residual
+ *   against the scaled target. */
+size_t asw_colored_noise_workspace_bytes(int rows, int T, int max_rows_per_pass);
+int asw_colored_noise(const int64_t* row_key_host, const int32_t* row_id_host, int rows, int T, double exponent, int max_rows_per_pass,
+                      double* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t asw_train_batch_workspace_bytes(int items, int S_max, int M);
+int asw_train_batch(const float* mix, int K, int M, int T, int items, int S_max, const int32_t* item_mix_host, const int32_t* shifts_host,
+                    const int32_t* counts_host, const double* pink_level_host, const double* white_level_host,
+                    const int64_t* white_key_host, const double* pink, void* out, int out_f64, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int asw_train_losses(const float* est, const float* gt, int N, int T, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
