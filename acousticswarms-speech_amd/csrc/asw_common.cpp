@@ -144,6 +144,7 @@ struct Rec { std::string name; double work, bytes; hipEvent_t e0, e1; };
 std::mutex g_mu;
 bool g_on = false;
 bool g_detail = false;
+bool g_form = true;
 std::vector<Rec> g_recs;
 std::vector<hipEvent_t> g_pool;
 hipEvent_t take_event() {
@@ -160,6 +161,7 @@ std::string prof_name(const char* base, int bm, int bn, int bk, bool ln, bool st
   return b;
 }
 bool prof_detail() { return g_detail; }
+bool prof_form() { return g_form; }
 ProfScope::ProfScope(hipStream_t s, const std::string& name, double work, double bytes) : slot(-1), stream(s) {
   if (!g_on) return;
   std::lock_guard<std::mutex> lk(g_mu);
@@ -180,7 +182,8 @@ extern "C" int asw_profile_enable(int on) {
   for (auto& r : asw::g_recs) { asw::g_pool.push_back(r.e0); asw::g_pool.push_back(r.e1); }
   asw::g_recs.clear();
   asw::g_on = on != 0;
-  asw::g_detail = on == 2;                 // 2: GEMM launch names carry their shape
+  asw::g_detail = on == 2 || on == 3;      // 2, 3: GEMM launch names carry their shape
+  asw::g_form = on != 2;                   // 2 alone leaves out the tiling form (prof_form)
   return ASW_OK;
 }
 

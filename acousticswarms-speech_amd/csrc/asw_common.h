@@ -109,6 +109,9 @@ __device__ __forceinline__ float gn_glu_value(float a, float g, float m0, float 
 namespace asw {
 std::string prof_name(const char* base, int bm, int bn, int bk, bool ln, bool stats);
 bool prof_detail();
+// Does a launch name say which of several bit-identical tilings ran (resstack64's ",carry")?  Not under
+// asw_profile_enable(2), whose names identify the arithmetic of a launch and nothing else.
+bool prof_form();
 // `work` = algorithmic FLOPs of the launch (GEMM-class kernels), `bytes` = algorithmic HBM bytes (the
 // memory-bound passes); either may be 0.
 struct ProfScope {

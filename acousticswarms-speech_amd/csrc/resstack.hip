@@ -19,7 +19,11 @@
 //    needs (output rows + the summed halos) once, layer i writes its output -- already split to fp16
 //    hi / lo -- over the LDS image it has just consumed, layer i + 1 reads it from there.  With
 //    R0 = 256 rows computed by layer 0 the pair (dilation 1, dilation 7; halo 3 + 21) produces
-//    256 - 42 = 214 finished rows per workgroup: 12 % more MFMA work, half the HBM round trips.
+//    256 - 42 = 214 finished rows from a tile that stands alone: half the HBM round trips.  The
+//    42 layer-0 rows two neighbouring tiles share are computed once all the same: a workgroup
+//    walks a run of consecutive tiles of an item and carries them from tile to tile, so every
+//    tile after a run's first finishes 256 rows (resstack64_carry_kernel; the three-layer stack
+//    and UpFeed keep the stand-alone tile and its recomputed halo).
 //
 // Large dilations (49) cannot be fused (the halo would be the tile); they run through the same
 // kernel as single layers on polyphase row sets (x[phase + dil * j] is a dilation-1 convolution in j),
@@ -29,6 +33,8 @@
 // 16 B pad (272 B: the 16-byte fragment reads of 32 consecutive rows are bank-conflict free).  Weights
 // never touch LDS: MFMA-fragment order (asw_pack_fragments_f16), one coalesced 1 KiB load per fragment,
 // QD k-steps ahead.
+#include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 #include "asw_common.h"
@@ -71,6 +77,7 @@ struct KArgs {
   const half8* Pre_l;
   float pre_up, pre_down;                // SRC: 2^pre_shift and its inverse
   int B, T, taps, ntile, BM, img_rows;
+  int nrun, run_q, run_long0;            // CARRY: runs per item; tiles of a short run; the first run with one tile more
   float eps;
   LayerDev L[MAXL];
 };
@@ -90,7 +97,7 @@ struct KArgsUp : KArgs { UpArgs u; };    // the kernel argument of the UpFeed in
 
 // Diagnostic build only (-DASW_PHASE_TIMING, tests/micro/resstack_phases.py): cycles wave 0 of every workgroup spends
 // per phase, summed over workgroups: [0] staging, [1] layer-0 k-loop, [2] layer-0 epilogue + hand-over, [3] layer-1
-// k-loop, [4] layer-1 epilogue + stores, [5] workgroups.  Stamps: 0 start, 1 staged, 2 + 2 li after layer li's
+// k-loop, [4] layer-1 epilogue + stores, [5] workgroups (the carried-halo kernel: tiles).  Stamps: 0 start, 1 staged, 2 + 2 li after layer li's
 // k-loop, 3 + 2 li after layer li.
 #ifdef ASW_PHASE_TIMING
 __device__ unsigned long long g_rs_cycles[6] = {0, 0, 0, 0, 0, 0};
@@ -137,11 +144,14 @@ __device__ __forceinline__ half8 src_load(__amdgpu_buffer_rsrc_t r, int row) {
 //   image row     a row of the LDS image (layer 0's input, later each layer's output in its place)
 //   fragment row  row (wave * TM + i) * 32 + (lane & 31) of the R0 rows a layer computes
 //   sequence row  a row t of the [T][64] tensors in memory
-template <bool POLY, int PH>
+template <bool POLY, int PH, bool CARRY = false>
 struct RowMap {
   static constexpr int BMJ = R0 / PH;                   // polyphase: rows of j per phase
   static_assert(BMJ % 32 == 0, "a row fragment must stay inside one phase");
   int T, taps, dil0, pad0, jb, pb, m0, BM, n_img, halo0;
+  // CARRY only:
+  int shift;                             // rows by which layer 0's rows lie later than m0 - halo0 (a steady tile)
+  int glu_lo, glu_hi;                    // (GLU on load) the sequence rows whose normalised form this tile writes out
 
   __device__ __forceinline__ RowMap(int tile, const KArgs& p) : T(p.T), taps(p.taps), dil0(p.L[0].dil), pad0(p.L[0].pad) {
     const int n_pb = POLY ? (dil0 + PH - 1) / PH : 1;
@@ -152,6 +162,22 @@ struct RowMap {
     n_img = POLY ? PH * rj() : R0 + 2 * pad0;
     halo0 = p.L[0].halo;
   }
+  // Tile `j` of a carried-halo run that starts at sequence row s (contiguous tiles, two layers).  The head tile (j == 0)
+  // is the tile above: layer 0 computes rows m0 - halo0 .. and BM = R0 - 2 halo0 rows are delivered.  A steady tile
+  // delivers R0 rows: its first 2 halo0 layer-0 rows are the previous tile's last, so layer 0 starts at m0 + halo0.
+  // The normalised input rows (GLU side output) go out with the layer-0 rows a tile computes, clipped to the run.
+  __device__ __forceinline__ RowMap(int s, int j, bool last, const KArgs& p) : T(p.T), taps(p.taps), dil0(p.L[0].dil), pad0(p.L[0].pad) {
+    static_assert(CARRY && !POLY, "carried halo: contiguous tiles");
+    const bool head = j == 0;
+    jb = pb = 0;
+    halo0 = p.L[0].halo;
+    m0 = head ? s : s + p.BM + (j - 1) * R0;
+    BM = head ? p.BM : R0;
+    n_img = R0 + 2 * pad0;
+    shift = head ? 0 : 2 * halo0;
+    glu_lo = head ? m0 : m0 + halo0;
+    glu_hi = last ? m0 + BM : m0 + BM + halo0;
+  }
   __device__ __forceinline__ int rj() const { return BMJ + taps - 1; }          // polyphase: image rows per phase
 
   // ---- image row -> the sequence row it is staged from, and whether that row exists
@@ -159,7 +185,7 @@ struct RowMap {
     int g;
     bool ok = irow < n_img;
     if (!POLY) {
-      g = m0 - halo0 - pad0 + irow;
+      g = m0 - halo0 - pad0 + (CARRY ? shift : 0) + irow;
     } else {
       const int ph = pb * PH + irow / rj();
       const int jj = jb * BMJ + irow % rj() - (taps - 1) / 2;
@@ -169,7 +195,7 @@ struct RowMap {
     return {g, ok && g >= 0 && g < T};
   }
   // (GLU on load) is sequence row g one of the rows this tile delivers
-  __device__ __forceinline__ bool delivers(int g) const { return g >= m0 && g < m0 + BM; }
+  __device__ __forceinline__ bool delivers(int g) const { return CARRY ? g >= glu_lo && g < glu_hi : g >= m0 && g < m0 + BM; }
 
   // ---- fragment row -> image row at tap 0; image rows between two taps; from tap 0 to the centre tap (the residual)
   __device__ __forceinline__ int image_row(int frow) const { return POLY ? (frow / BMJ) * rj() + frow % BMJ : frow; }
@@ -179,7 +205,7 @@ struct RowMap {
   // ---- fragment row -> sequence row
   // a layer with `halo` rows still to come after it (contiguous tiles only): is the row inside the sequence
   __device__ __forceinline__ bool handed_on(int frow, int halo) const {
-    const int t = m0 - halo + frow;
+    const int t = m0 - halo + (CARRY ? shift : 0) + frow;
     return t >= 0 && t < T;
   }
   // the last layer (`ok`: a row this tile delivers)
@@ -226,13 +252,24 @@ __device__ __forceinline__ void for_each_group(int h, const F& f) {
 __device__ __forceinline__ float4 group4(const floatx16& a, int q) { return make_float4(a[q * 4 + 0], a[q * 4 + 1], a[q * 4 + 2], a[q * 4 + 3]); }
 
 // ------------------------------------------------------------------ the phases
-// per-layer vectors -> LDS: tab[NL][bias | gamma | beta][64]
-template <int NL>
-__device__ __forceinline__ void load_layer_vectors(const KArgs& p, float* tab, int tid) {
+// The per-layer vectors in LDS, tab[NL][bias | gamma | beta][64], as float4 groups STRIDE bytes apart: one array behind
+// the image (STRIDE 16), or -- the carried-halo form, whose image leaves no room behind it -- group i in the 16 pad
+// bytes of image row i (STRIDE RS), which no staging, hand-over or fragment read touches.
+template <int STRIDE>
+struct Tab {
+  static_assert(STRIDE % 16 == 0, "float4 groups");
+  float* p;
+  __device__ __forceinline__ float4& at(int word) const { return *reinterpret_cast<float4*>(p + word * (STRIDE / 16)); }
+  __device__ __forceinline__ Tab layer(int li) const { return {p + li * 192 * (STRIDE / 16)}; }
+};
+
+// per-layer vectors -> LDS
+template <int NL, typename TabT>
+__device__ __forceinline__ void load_layer_vectors(const KArgs& p, TabT tab, int tid) {
   for (int i = tid; i < NL * 3 * 16; i += NTHR) {
     const int li = i / 48, w = (i - li * 48) / 16, c4 = i & 15;
     const float* src = w == 0 ? p.L[li].bias : w == 1 ? p.L[li].gamma : p.L[li].beta;
-    reinterpret_cast<float4*>(tab)[i] = *reinterpret_cast<const float4*>(src + c4 * 4);
+    tab.at(i * 4) = *reinterpret_cast<const float4*>(src + c4 * 4);
   }
 }
 
@@ -302,8 +339,11 @@ __device__ __forceinline__ void stage_rows(const KArgs& p, const Map& map, int b
 // Lane (row r, half h) holds, for k-step ks, the 8 source channels of row r + tap, tap = 2 ks + h: one 16-byte
 // load per plane.  Tap 7 does not exist -- its weights are zero -- but its rows are read and are finite (data or
 // the descriptor's zeros).  Everything is requested before the first MFMA: one exposed latency per tile.
-template <int NL, typename Map>
-__device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, int b, float* tab, int tid, floatx16 (&acc)[TM][2]) {
+// (load_tab: false on the later tiles of a carried-halo run, whose vectors are in LDS already; the barrier stays, and
+// there it also keeps the hand-over behind the previous tile's last reads of the image.)
+template <int NL, bool WOFS, typename Map, typename TabT>
+__device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, int b, TabT tab, bool load_tab, int wofs, int tid,
+                                              floatx16 (&acc)[TM][2]) {
   const LayerDev& Ld = p.L[0];
   const int T = map.T, lane = tid & 63, wid = tid >> 6, h = lane >> 5;
   const __amdgpu_buffer_rsrc_t rH = src_rsrc(p.src_h + (long)b * T, T), rL = src_rsrc(p.src_l + (long)b * T, T);
@@ -327,13 +367,13 @@ __device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, in
     constexpr int kg = decltype(kgc)::value;
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
-      if constexpr (kg < 4) frag_load<3>(Ld.Wh, Ld.Wl, (long)kg * 2 + cb, lane, wh[slot][cb], wl[slot][cb]);
-      else frag_load<3>(p.Pre_h, p.Pre_l, (long)cb, lane, wh[slot][cb], wl[slot][cb]);
+      if constexpr (kg < 4) frag_load<3>(Ld.Wh, Ld.Wl, (long)kg * 2 + cb + (WOFS ? wofs : 0), lane, wh[slot][cb], wl[slot][cb]);
+      else frag_load<3>(p.Pre_h, p.Pre_l, (long)cb + (WOFS ? wofs : 0), lane, wh[slot][cb], wl[slot][cb]);
     }
   };
   wload(std::integral_constant<int, 0>{}, 0);
   wload(std::integral_constant<int, 1>{}, 1);
-  load_layer_vectors<NL>(p, tab, tid);                  // (here: after layer 0's operand loads are out, under the same wait)
+  if (load_tab) load_layer_vectors<NL>(p, tab, tid);    // (here: after layer 0's operand loads are out, under the same wait)
   __syncthreads();
   auto kstep = [&](auto ksc) {
     constexpr int ks = decltype(ksc)::value;
@@ -353,7 +393,7 @@ __device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, in
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     for_each_group(h, [&](int cb, int q, int c0) __attribute__((always_inline)) {
-      const float4 bi = *reinterpret_cast<const float4*>(tab + c0);
+      const float4 bi = tab.at(c0);
       const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -365,10 +405,11 @@ __device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, in
 }
 
 // the convolution of one layer from the image: this wave's first nf (<= TM) fragments, one k-loop instantiation per
-// count (wave-uniform choice; nf <= 0: none)
-template <int NTERM, typename Map>
-__device__ __forceinline__ void conv_layer(const KArgs& p, const LayerDev& Ld, const Map& map, const char* img, int nf, int lane,
-                                           int wid, floatx16 (&acc)[TM][2]) {
+// count (wave-uniform choice; nf <= 0: none).  WOFS: wofs is added to every weight fragment's index (the carried-halo
+// kernel's opaque zero).
+template <int NTERM, bool WOFS, typename Map>
+__device__ __forceinline__ void conv_layer(const KArgs& p, const LayerDev& Ld, const Map& map, const char* img, int nf, int wofs,
+                                           int lane, int wid, floatx16 (&acc)[TM][2]) {
   const int taps = map.taps, h = lane >> 5;
   const int tapstep = map.tap_rows(Ld) * RS;
   auto run = [&](auto nfc) {
@@ -381,9 +422,14 @@ __device__ __forceinline__ void conv_layer(const KArgs& p, const LayerDev& Ld, c
       a[i][0] = acc[i][0];
       a[i][1] = acc[i][1];
     }
-    kloop<NF, 2, QD, NTERM>(
-        a, taps, [&](int tap, int i) __attribute__((always_inline)) { return img + xb[i] + tap * tapstep; }, Ld.Wh, Ld.Wl,
-        [](int kg, int cb) __attribute__((always_inline)) { return (long)kg * 2 + cb; }, lane);
+    if constexpr (WOFS)
+      kloop<NF, 2, QD, NTERM>(
+          a, taps, [&](int tap, int i) __attribute__((always_inline)) { return img + xb[i] + tap * tapstep; }, Ld.Wh, Ld.Wl,
+          [wofs](int kg, int cb) __attribute__((always_inline)) { return (long)kg * 2 + cb + wofs; }, lane);
+    else
+      kloop<NF, 2, QD, NTERM>(
+          a, taps, [&](int tap, int i) __attribute__((always_inline)) { return img + xb[i] + tap * tapstep; }, Ld.Wh, Ld.Wl,
+          [](int kg, int cb) __attribute__((always_inline)) { return (long)kg * 2 + cb; }, lane);
 #pragma unroll
     for (int i = 0; i < NF; ++i) { acc[i][0] = a[i][0]; acc[i][1] = a[i][1]; }
   };
@@ -393,8 +439,8 @@ __device__ __forceinline__ void conv_layer(const KArgs& p, const LayerDev& Ld, c
 
 // the epilogue in registers: + bias, ReLU, + residual (the layer's own input, from the image), LayerNorm.
 // IN_ACC (the source-fed layer 0): bias, ReLU and residual are in the accumulators already.
-template <bool IN_ACC, bool FUSED_VAR, typename Map>
-__device__ __forceinline__ void finish_rows(const KArgs& p, const LayerDev& Ld, const Map& map, const char* img, const float* tb,
+template <bool IN_ACC, bool FUSED_VAR, typename Map, typename TabT>
+__device__ __forceinline__ void finish_rows(const KArgs& p, const LayerDev& Ld, const Map& map, const char* img, const TabT tb,
                                             bool first, int nf, int lane, int wid, floatx16 (&acc)[TM][2]) {
   const int h = lane >> 5;
   const int cpad = map.centre_rows(Ld, first);                 // image row of the residual = tap-0 row + centre tap
@@ -402,7 +448,7 @@ __device__ __forceinline__ void finish_rows(const KArgs& p, const LayerDev& Ld, 
     const char* rrow = img + (map.image_row(frag_row(wid, i, lane)) + cpad) * RS;
     float s = 0.f;
     for_each_group(h, [&](int cb, int q, int c0) __attribute__((always_inline)) {
-      const float4 bi = *reinterpret_cast<const float4*>(tb + c0);
+      const float4 bi = tb.at(c0);
       const half4 rh = *reinterpret_cast<const half4*>(rrow + IMG_HI + c0 * 2);
       const half4 rl = *reinterpret_cast<const half4*>(rrow + IMG_LO + c0 * 2);
       const float bv[4] = {bi.x, bi.y, bi.z, bi.w};
@@ -440,8 +486,8 @@ __device__ __forceinline__ void finish_rows(const KArgs& p, const LayerDev& Ld, 
     d += __shfl_xor(d, 32, 64);
     const float rstd = 1.0f / sqrtf(d * (1.0f / C) + p.eps);
     for_each_group(h, [&](int cb, int q, int c0) __attribute__((always_inline)) {
-      const float4 g4 = *reinterpret_cast<const float4*>(tb + 64 + c0);
-      const float4 b4 = *reinterpret_cast<const float4*>(tb + 128 + c0);
+      const float4 g4 = tb.at(64 + c0);
+      const float4 b4 = tb.at(128 + c0);
       const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, be[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][cb][q * 4 + j] = (acc[i][cb][q * 4 + j] - mean) * rstd * gv[j] + be[j];
@@ -449,14 +495,15 @@ __device__ __forceinline__ void finish_rows(const KArgs& p, const LayerDev& Ld, 
   });
 }
 
-// the next layer's input replaces this layer's in the image: rows outside the sequence are its zero padding
+// the next layer's input replaces this layer's in the image, from image row `row0` on (0, or the carried rows of a
+// steady tile): rows outside the sequence are its zero padding
 template <int NTERM, typename Map>
-__device__ __forceinline__ void hand_over(const LayerDev& Ld, const Map& map, char* img, int nf, int lane, int wid,
+__device__ __forceinline__ void hand_over(const LayerDev& Ld, const Map& map, char* img, int row0, int nf, int lane, int wid,
                                           const floatx16 (&acc)[TM][2]) {
   for_each_fragment(nf, [&](int i) __attribute__((always_inline)) {
     const int frow = frag_row(wid, i, lane);
     const bool inside = map.handed_on(frow, Ld.halo);
-    char* wrow = img + frow * RS;
+    char* wrow = img + (row0 + frow) * RS;
     for_each_group(lane >> 5, [&](int cb, int q, int c0) __attribute__((always_inline)) {
       float4 v = group4(acc[i][cb], q);
       if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -617,7 +664,7 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
 
   extern __shared__ __align__(16) char smem[];
   char* img = smem;
-  float* tab = reinterpret_cast<float*>(smem + (size_t)p.img_rows * RS);       // [NL][bias | gamma | beta][64]
+  const Tab<16> tab = {reinterpret_cast<float*>(smem + (size_t)p.img_rows * RS)};    // [NL][bias | gamma | beta][64]
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int idx;
@@ -646,13 +693,13 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][cb][r] = 0.f;        // (all of acc defined on every path: it stays in registers)
-    if constexpr (fed) source_layer0<NL>(p, map, b, tab, tid, acc);
-    else conv_layer<NTERM>(p, Ld, map, img, nf, lane, wid, acc);
+    if constexpr (fed) source_layer0<NL, false>(p, map, b, tab, true, 0, tid, acc);
+    else conv_layer<NTERM, false>(p, Ld, map, img, nf, 0, lane, wid, acc);
     clk.mark_after(2 + 2 * li, acc[0][0][0]);
-    finish_rows<fed, UP>(p, Ld, map, img, tab + li * 192, li == 0, nf, lane, wid, acc);
+    finish_rows<fed, UP>(p, Ld, map, img, tab.layer(li), li == 0, nf, lane, wid, acc);
     if constexpr (li < NL - 1) {
       if constexpr (!fed) __syncthreads();              // every wave is done reading the old image
-      hand_over<NTERM>(Ld, map, img, nf, lane, wid, acc);
+      hand_over<NTERM>(Ld, map, img, 0, nf, lane, wid, acc);
       __syncthreads();
     } else if constexpr (UP) {
       up_feed<NTERM>(p, p.u, Ld, map, b, tile, smem, tid, acc);
@@ -667,6 +714,106 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
   clk.report<NL>();
 }
 
+// The carried-halo form of the fused pair (contiguous tiles, never UpFeed).  A workgroup owns a RUN of consecutive row
+// tiles of one item and walks them in time order.  The first tile of a run is the tile of the kernel above: R0 layer-0
+// rows, of which layer 1 can finish BM = R0 - 2 halo.  Every later tile finishes R0 rows: the 2 halo layer-0 rows in
+// front of its own are the previous tile's last -- split to fp16 hi / lo as hand_over left them -- and travel in
+// registers (CQ 16-byte pieces per thread) across the staging and layer 0 of the new tile, whose hand-over puts them in
+// front of the R0 new rows.  Both layers then run NW * TM whole fragments and no layer-0 row is computed twice inside
+// a run.  The image of layer 1 is R0 + 2 halo rows, which leaves no room behind it at two workgroups per CU: the
+// per-layer vectors live in the rows' pad bytes (Tab), loaded once per run.  A row's arithmetic does not depend on the
+// tile that computes it: the results are those of the kernel above bit for bit.
+constexpr int CQ = 3;                    // 16-byte pieces of carried rows per thread: 2 halo <= CQ * NTHR / 16 = 48 rows
+template <bool GLU, int NTERM, bool SRC>
+__global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2)))
+void resstack64_carry_kernel(const KArgs p) {
+  static_assert(!SRC || (!GLU && NTERM == 3), "source-fed layer 0: f16x3");
+  constexpr int NL = 2;
+  using Map = RowMap<false, 1, true>;
+
+  extern __shared__ __align__(16) char smem[];
+  char* img = smem;
+  const Tab<RS> tab = {reinterpret_cast<float*>(smem + IMG_LO + C * 2)};       // [NL][bias | gamma | beta][64] in the rows' pad bytes
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int idx;
+  if (!xcd_tile_run(p.B * p.nrun, idx)) return;         // XCD-aware order: a contiguous run of (item, run) pairs
+  const int b = idx / p.nrun, run = idx - b * p.nrun;
+  // the runs of an item (plan_runs): run_q tiles each, one more from run_long0 on; n tiles cover BM + (n - 1) R0 rows
+  const int s = run * (p.BM + (p.run_q - 1) * R0) + max(run - p.run_long0, 0) * R0;
+  const int n = p.run_q + (run >= p.run_long0 ? 1 : 0);
+  const int crows = 2 * p.L[0].halo;                    // rows carried from tile to tile
+
+  PhaseClock clk;
+  floatx16 acc[TM][2];
+  half8 carry[CQ];                                      // this thread's pieces of the carried rows
+#pragma unroll 1
+  for (int j = 0; j < n; ++j) {
+    const bool steady = j > 0;
+    const Map map(s, j, j == n - 1, p);
+    if (map.m0 >= p.T) break;                           // (the planner leaves no such tile)
+    // The weight addresses are made opaque tile by tile.  Left as loop invariants, the first QD k-steps of both
+    // layers' weights were loaded once in front of the loop and held across it: 256 VGPRs and scratch.
+    // (wofs: a zero the compiler cannot see through, uniform, added to every weight fragment's index.)
+    int wofs = 0;
+    asm volatile("" : "+v"(wofs));
+    wofs = __builtin_amdgcn_readfirstlane(wofs);
+
+    clk.mark(0);
+    if constexpr (!SRC) {                               // (SRC: source_layer0 loads the vectors and has nothing to stage)
+      if (steady) __syncthreads();                      // every wave is done with the previous tile's image
+      else load_layer_vectors<NL>(p, tab, tid);
+      stage_rows<GLU, NTERM>(p, map, b, img, tid);
+      __syncthreads();
+    }
+    clk.mark(1);
+
+    auto layer = [&](auto lic) __attribute__((always_inline)) {
+      constexpr int li = decltype(lic)::value;
+      constexpr bool fed = SRC && li == 0;
+      const LayerDev& Ld = p.L[li];
+      // fragments of this wave in this layer: all of them, but for layer 1 of the head tile
+      const int nf = (li == 0 || steady ? NW * TM : Ld.nfrag) - wid * TM;
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[i][cb][r] = 0.f;
+      if constexpr (fed) source_layer0<NL, true>(p, map, b, tab, !steady, wofs, tid, acc);
+      else conv_layer<NTERM, true>(p, Ld, map, img, nf, wofs, lane, wid, acc);
+      clk.mark_after(2 + 2 * li, acc[0][0][0]);
+      finish_rows<fed, false>(p, Ld, map, img, tab.layer(li), li == 0, nf, lane, wid, acc);
+      if constexpr (li == 0) {
+        if constexpr (!fed) __syncthreads();            // every wave is done reading the old image
+        hand_over<NTERM>(Ld, map, img, steady ? crows : 0, nf, lane, wid, acc);
+        if (steady) {                                   // the carried rows in front of the new ones
+#pragma unroll
+          for (int k = 0; k < CQ; ++k) {
+            const int c = tid + k * NTHR;
+            if (c < crows * 16) *reinterpret_cast<half8*>(img + (c >> 4) * RS + (c & 15) * 16) = carry[k];
+          }
+        }
+        __syncthreads();
+      } else {
+        store_rows(p, map, b, nf, lane, wid, acc);
+      }
+      clk.mark(3 + 2 * li);
+    };
+    layer(std::integral_constant<int, 0>{});
+    layer(std::integral_constant<int, 1>{});
+    clk.report<NL>();                                   // (diagnostic build: per tile)
+
+    if (j + 1 < n) {                                    // the next tile starts from the last `crows` layer-0 rows of this image
+#pragma unroll
+      for (int k = 0; k < CQ; ++k) {
+        const int c = tid + k * NTHR;
+        if (c < crows * 16) carry[k] = *reinterpret_cast<const half8*>(img + (map.BM + (c >> 4)) * RS + (c & 15) * 16);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ launch
 template <bool GLU, bool SRC, bool UP>
 double stack_bytes(const KArgs& k) {
@@ -679,22 +826,37 @@ double stack_bytes(const KArgs& k) {
   return rows * C * 4 * (GLU ? 3 : 2);
 }
 
+template <int NL, int PH, bool POLY, bool GLU, int NTERM, bool SRC, bool UP, bool CARRY>
+constexpr auto stack_kernel() {
+  if constexpr (CARRY) {
+    static_assert(NL == 2 && !POLY && !UP, "carried halo: the fused pair on contiguous tiles, not UpFeed");
+    return &resstack64_carry_kernel<GLU, NTERM, SRC>;
+  } else {
+    return &resstack64_kernel<NL, PH, POLY, GLU, NTERM, SRC, UP>;
+  }
+}
+
 // One form of the kernel: its single-pass and its f16x3 instantiation (SRC and UP are f16x3 only: the host has
 // checked the precision).
-template <int NL, int PH, bool POLY, bool GLU, bool SRC, bool UP>
+template <int NL, int PH, bool POLY, bool GLU, bool SRC, bool UP, bool CARRY = false>
 int launch_stack(const KArgs& k, const UpArgs* up, int precision, size_t smem, double flops, hipStream_t s) {
   char nm[128], detail[48] = "";
-  snprintf(nm, sizeof nm, "resstack64<%d,%dx%d%s%s%s%s>", NL, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
-           GLU ? ",glu" : "", SRC ? ",src" : "", UP ? ",up" : "");
-  if (asw::prof_detail()) snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
+  snprintf(nm, sizeof nm, "resstack64<%d,%dx%d%s%s%s%s%s>", NL, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
+           CARRY && asw::prof_form() ? ",carry" : "", GLU ? ",glu" : "", SRC ? ",src" : "", UP ? ",up" : "");
+  if (asw::prof_detail()) {
+    if (CARRY && asw::prof_form()) snprintf(detail, sizeof detail, "[B%d M%d d%d r%d]", k.B, k.T, k.L[0].dil, k.nrun);
+    else snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
+  }
   std::conditional_t<UP, KArgsUp, KArgs> ka;
   static_cast<KArgs&>(ka) = k;
   if constexpr (UP) {
     ka.u = *up;
     flops += 2.0 * k.B * (double)k.T * C * UPN;
   }
-  return asw::launch_pair<resstack64_kernel<NL, PH, POLY, GLU, (SRC || UP) ? 3 : 1, SRC, UP>, resstack64_kernel<NL, PH, POLY, GLU, 3, SRC, UP>>(
-      precision, dim3(xcd_grid_run(k.B * k.ntile)), dim3(NTHR), smem, 160 * 1024, nm, detail, flops, stack_bytes<GLU, SRC, UP>(k), s, ka);
+  return asw::launch_pair<stack_kernel<NL, PH, POLY, GLU, (SRC || UP) ? 3 : 1, SRC, UP, CARRY>(),
+                          stack_kernel<NL, PH, POLY, GLU, 3, SRC, UP, CARRY>()>(
+      precision, dim3(xcd_grid_run(k.B * (CARRY ? k.nrun : k.ntile))), dim3(NTHR), smem, 160 * 1024, nm, detail, flops,
+      stack_bytes<GLU, SRC, UP>(k), s, ka);
 }
 
 // the staged forms of a tiling: GroupNorm + GLU on load (contiguous tiles only) or not, UpFeed or not
@@ -723,6 +885,37 @@ TilePlan plan_tiles(int T, int n_layers, int dil0, int halo0, bool glu) {
   return {false, 1, BM, BM > 0 ? asw::cdiv(T, BM) : 0};
 }
 
+// The runs of the carried-halo form.  An item's rows are cut into `nrun` runs, each a head tile of BM rows followed by
+// steady tiles of R0 rows; the item's tiles are dealt to the runs as evenly as they go, the runs with one tile more
+// last, so that only the item's very last tile is ragged and none is empty.
+struct RunPlan { int nrun, q, long0; };  // runs per item; tiles of a short run; index of the first run with q + 1 tiles
+RunPlan plan_runs(int T, int BM, int want) {
+  const int nrun = std::max(1, std::min(want, asw::cdiv(T, BM)));
+  const int ntile = nrun + asw::cdiv(std::max(T - nrun * BM, 0), R0);
+  return {nrun, ntile / nrun, nrun - ntile % nrun};
+}
+// Runs per item when the caller leaves them to the library: about four workgroups per CU in the grid (two resident
+// rounds of two per CU) while B is small, and no run shorter than a head and a steady tile.
+int auto_runs(int T, int BM, int B, int n_cu) {
+  return std::max(1, std::min(asw::cdiv(4 * n_cu, B), T / (BM + R0)));
+}
+int device_cus() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 256;
+  return cus[dev];
+}
+// Does the fused pair take the carried-halo form: more than one tile of rows, the carried rows fit the registers that
+// hold them, and the image of a steady tile -- R0 + 2 halo rows for layer 1 -- admits two workgroups per CU.
+// ASW_RESSTACK_NO_CARRY=1 (or runs_per_item < 0) keeps the recomputed-halo tiling (A/B measurements).
+bool carry_applies(int T, int n_layers, int BM, int pad0, int halo0, bool up, int runs_per_item) {
+  static const bool off = getenv("ASW_RESSTACK_NO_CARRY") != nullptr;
+  const int rows = R0 + 2 * std::max(pad0, halo0);
+  return !off && runs_per_item >= 0 && n_layers == 2 && !up && T > BM && halo0 > 0 && 2 * halo0 * 16 <= CQ * NTHR &&
+         (size_t)rows * RS <= 80 * 1024 && rows >= 2 * 3 * 16;
+}
+
 int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, double flops, hipStream_t s) {
   const int dil0 = k.L[0].dil;
   const TilePlan tp = plan_tiles(a.T, a.n_layers, dil0, k.L[0].halo, glu);
@@ -747,6 +940,15 @@ int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, d
     k.L[i].nfrag = asw::cdiv(k.BM + 2 * k.L[i].halo, 32);
     const int r = 32 * k.L[i].nfrag + 2 * k.L[i].pad;
     rows = r > rows ? r : rows;
+  }
+  if (carry_applies(a.T, a.n_layers, k.BM, k.L[0].pad, k.L[0].halo, up != nullptr, a.runs_per_item)) {
+    const RunPlan rp = plan_runs(a.T, k.BM, a.runs_per_item > 0 ? a.runs_per_item : auto_runs(a.T, k.BM, a.B, device_cus()));
+    k.nrun = rp.nrun; k.run_q = rp.q; k.run_long0 = rp.long0;
+    k.img_rows = R0 + 2 * std::max(k.L[0].pad, k.L[0].halo);
+    const size_t lds = (size_t)k.img_rows * RS;          // (the per-layer vectors sit in the rows' pad bytes)
+    if (k.src_h) return launch_stack<2, 1, false, false, true, false, true>(k, nullptr, a.precision, lds, flops, s);
+    return glu ? launch_stack<2, 1, false, true, false, false, true>(k, nullptr, a.precision, lds, flops, s)
+               : launch_stack<2, 1, false, false, false, false, true>(k, nullptr, a.precision, lds, flops, s);
   }
   k.img_rows = rows;
   const size_t smem = (size_t)rows * RS + (size_t)a.n_layers * 3 * 64 * sizeof(float);
@@ -803,6 +1005,22 @@ extern "C" int asw_resstack_tiles(int T, int taps, int n_layers, const int32_t* 
   const TilePlan t = plan_tiles(T, n_layers, dil[0], halo0, glu != 0);
   ASW_CHECK_ARG(t.BM >= R0 / 2, "resstack_tiles: the later layers' halo (%d rows per side) is too wide", halo0);
   return t.ntile;
+}
+
+extern "C" int asw_resstack_runs(int T, int B, int taps, const int32_t* dil, int runs_per_item, int n_cu, int32_t* head_rows,
+                                 int32_t* steady_rows, int32_t* run_start, int32_t* run_tiles, int max_runs) {
+  ASW_CHECK_ARG(T > 0 && B > 0 && taps >= 3 && taps % 2 == 1 && dil && n_cu > 0 && max_runs >= 0, "resstack_runs: bad argument");
+  const int pad0 = dil[0] * (taps - 1) / 2, halo0 = dil[1] * (taps - 1) / 2, BM = R0 - 2 * halo0;
+  if (BM < R0 / 2 || !carry_applies(T, 2, BM, pad0, halo0, false, runs_per_item)) return 0;
+  const RunPlan rp = plan_runs(T, BM, runs_per_item > 0 ? runs_per_item : auto_runs(T, BM, B, n_cu));
+  if (head_rows) *head_rows = BM;
+  if (steady_rows) *steady_rows = R0;
+  for (int r = 0; r < rp.nrun && r < max_runs; ++r) {
+    // (as the kernel finds them)
+    if (run_start) run_start[r] = r * (BM + (rp.q - 1) * R0) + std::max(r - rp.long0, 0) * R0;
+    if (run_tiles) run_tiles[r] = rp.q + (r >= rp.long0 ? 1 : 0);
+  }
+  return rp.nrun;
 }
 
 extern "C" int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream) {

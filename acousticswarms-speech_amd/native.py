@@ -155,7 +155,7 @@ class ResStackArgs(Structure):
                 ("glu_raw", c_void_p), ("glu_mr", c_void_p), ("glu_gamma", c_void_p), ("glu_beta", c_void_p),
                 ("glu_out", c_void_p), ("src_hi", c_void_p), ("src_lo", c_void_p), ("pre_hi", c_void_p), ("pre_lo", c_void_p),
                 ("pre_shift", c_int32), ("up_hi", c_void_p), ("up_lo", c_void_p), ("up_shift", c_int32), ("up_bias", c_void_p),
-                ("up_skip", c_void_p), ("up_out", c_void_p), ("up_stats", c_void_p)]
+                ("up_skip", c_void_p), ("up_out", c_void_p), ("up_stats", c_void_p), ("runs_per_item", c_int32)]
 
 
 # name -> (restype, argtypes); must list every symbol declared in include/asw_hip.h
@@ -230,6 +230,8 @@ SIGNATURES = {
     "asw_mask_path_f16x3_scaled": (c_int, [POINTER(MaskPathArgs), c_void_p]),
     "asw_resstack64_f16x3": (c_int, [POINTER(ResStackArgs), c_void_p]),
     "asw_resstack_tiles": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_int]),
+    "asw_resstack_runs": (c_int, [c_int, c_int, c_int, POINTER(c_int32), c_int, c_int, POINTER(c_int32), POINTER(c_int32),
+                                  POINTER(c_int32), POINTER(c_int32), c_int]),
     "asw_up_feed_kperm": (c_int, [c_int]),
     "asw_pack_up_feed_f16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32)]),
     "asw_compose_source_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -98,15 +98,17 @@ def _resstack_launch(a):
     torch.cuda.current_stream().synchronize()
 
 
-def resstack(x, layers, taps=7, precision="f16x3", eps=1e-5, glu=None, out=None, glu_out=None):
+def resstack(x, layers, taps=7, precision="f16x3", eps=1e-5, glu=None, out=None, glu_out=None, runs_per_item=0):
     """A stack of 1..3 64-channel residual layers in one launch (include/asw_hip.h:asw_resstack64_f16x3).
-    layers: [(Wt [64][taps*64], bias, gamma, beta, dil), ...]; x [B][T][64] or None with glu = (raw, mr, gamma, beta)."""
+    layers: [(Wt [64][taps*64], bias, gamma, beta, dil), ...]; x [B][T][64] or None with glu = (raw, mr, gamma, beta).
+    runs_per_item: asw_resstack_args.runs_per_item (the fused pair's carried-halo form; < 0 switches it off)."""
     src = x if glu is None else glu[0]
     B, T = src.shape[0], src.shape[1]
     if out is None:
         out = torch.empty((B, T, 64), dtype=torch.float32, device=src.device)
     a, keep = _resstack_args(B, T, layers, taps, precision, eps, x=x, glu=glu, glu_out=glu_out)
     a.out = out.data_ptr()
+    a.runs_per_item = runs_per_item
     _resstack_launch(a)
     return out
 
@@ -132,7 +134,7 @@ def resstack_up(x, layers, up_wt, up_bias, skip, taps=7, eps=1e-5, glu=None):
     return raw, stats
 
 
-def resstack_src(src_hi, src_lo, pre_w, pre_b, layers, taps=7, eps=1e-5, out=None):
+def resstack_src(src_hi, src_lo, pre_w, pre_b, layers, taps=7, eps=1e-5, out=None, runs_per_item=0):
     """The fused pair with its first layer fed by the 8-channel source of the 1x1 convolution (pre_w [64][M], pre_b [64])
     in front of it (include/asw_hip.h:asw_resstack_args.src_hi).  src_hi / src_lo: the planes of shift_norm_src;
     layers: [(conv weight [64][64][taps] torch layout, bias, gamma, beta, dil)] * 2."""
@@ -157,6 +159,7 @@ def resstack_src(src_hi, src_lo, pre_w, pre_b, layers, taps=7, eps=1e-5, out=Non
     a.out = out.data_ptr()
     ph, pl, psh = pack_fragments_f16(torch.from_numpy(pre16).to(dev), 64, 16)
     a.src_hi, a.src_lo, a.pre_hi, a.pre_lo, a.pre_shift = src_hi.data_ptr(), src_lo.data_ptr(), ph.data_ptr(), pl.data_ptr(), psh
+    a.runs_per_item = runs_per_item
     _resstack_launch(a)
     return out
 

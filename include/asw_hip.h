@@ -35,7 +35,10 @@ const char* asw_last_error(void);
 int asw_abi_version(void);
 
 /* Optional launch profiler: while enabled, every GEMM-class launch is bracketed by HIP
- * events on its own stream.  asw_profile_enable(on) also clears earlier records;
+ * events on its own stream.  asw_profile_enable(on) also clears earlier records
+ * (on = 2: launch names carry their shape, "name[B.. M.. ..]", and stand for the arithmetic of
+ * the launch alone; on = 3: the shape and, as with on = 1, the tiling form where several
+ * compute the same bits, such as resstack64's ",carry");
  * asw_profile_report() waits for the recorded events and writes a JSON object
  * {"kernel<tile>": {"launches": n, "ms": total, "work": flops}, ...} into buf. */
 int asw_profile_enable(int on);
@@ -508,8 +511,23 @@ typedef struct asw_resstack_args {
   const float* up_skip;
   float* up_out;
   float* up_stats;
+  /* The fused pair (n_layers == 2, not UpFeed) on more than one tile of rows runs in its carried-halo form: a
+   * workgroup walks a run of consecutive row tiles of one item and hands the layer-0 rows two neighbouring tiles share
+   * from tile to tile instead of computing them twice (same results, bit for bit).  Runs per item: 0 = chosen by the
+   * library from B, T and the device's CU count; > 0 = this many (clamped to the tiles there are); < 0 = the
+   * recomputed-halo tiling, as does ASW_RESSTACK_NO_CARRY=1 in the environment.  Launch names carry ",carry",
+   * e.g. resstack64<2,4x2,carry,glu>, and with asw_profile_enable(3) the runs per item, "[B.. M.. d.. r<runs>]";
+   * asw_profile_enable(2) shows the launch under the name of the recomputed-halo form, whose bits it computes. */
+  int32_t runs_per_item;
 } asw_resstack_args;
 int asw_resstack64_f16x3(const asw_resstack_args* args, void* stream);
+/* Host helper: the runs asw_resstack64_f16x3 cuts an item into for the fused pair of dilations dil[2] with these T, B,
+ * taps and runs_per_item on a device of n_cu compute units.  Returns the runs per item (0: the launch does not take the
+ * carried-halo form; negative asw_status on a bad argument) and, for the first max_runs of them, the first row and the
+ * number of tiles of each run.  The first tile of a run delivers *head_rows rows, every later one *steady_rows; the
+ * last tile of the last run ends at or after T. */
+int asw_resstack_runs(int T, int B, int taps, const int32_t* dil, int runs_per_item, int n_cu, int32_t* head_rows,
+                      int32_t* steady_rows, int32_t* run_start, int32_t* run_tiles, int max_runs);
 /* Row tiles per batch item of the asw_resstack64_f16x3 launch with these T, taps, n_layers, dilations dil[n_layers] and
  * GroupNorm + GLU on load or not: the number of UpFeed statistics slots per item.  Negative asw_status on a bad argument. */
 int asw_resstack_tiles(int T, int taps, int n_layers, const int32_t* dil, int glu);
