@@ -22,8 +22,8 @@
 //    256 - 42 = 214 finished rows from a tile that stands alone: half the HBM round trips.  The
 //    42 layer-0 rows two neighbouring tiles share are computed once all the same: a workgroup
 //    walks a run of consecutive tiles of an item and carries them from tile to tile, so every
-//    tile after a run's first finishes 256 rows (resstack64_carry_kernel; the three-layer stack
-//    and UpFeed keep the stand-alone tile and its recomputed halo).
+//    tile after a run's first finishes 256 rows (resstack64_carry_kernel, the pair's one kernel:
+//    runs of one tile are the stand-alone tiling; three layers and UpFeed keep resstack64_kernel).
 //
 // Large dilations (49) cannot be fused (the halo would be the tile); they run through the same
 // kernel as single layers on polyphase row sets (x[phase + dil * j] is a dilation-1 convolution in j),
@@ -34,7 +34,7 @@
 // never touch LDS: MFMA-fragment order (asw_pack_fragments_f16), one coalesced 1 KiB load per fragment,
 // QD k-steps ahead.
 #include <algorithm>
-#include <cstdlib>
+#include <climits>
 #include <type_traits>
 
 #include "asw_common.h"
@@ -50,6 +50,15 @@ constexpr int MAXL = 3;
 constexpr int NW = 4, TM = 2, QD = 4;
 constexpr int NTHR = 64 * NW, SROWS = NTHR / 16;
 constexpr int R0 = 32 * NW * TM;         // rows layer 0 computes
+
+// The runs of the fused pair.  An item's rows are cut into `nrun` runs, each a head tile of BM rows followed by steady
+// tiles of R0 rows (n tiles cover BM + (n - 1) R0 rows); the item's tiles are dealt to the runs as evenly as they go,
+// the runs with one tile more last, so that only the item's very last tile is ragged and none is empty.
+struct RunPlan {
+  int nrun, q, long0;                    // runs per item; tiles of a short run; index of the first run with q + 1 tiles
+  ASW_HOST_DEVICE int tiles(int run) const { return q + (run >= long0 ? 1 : 0); }
+  ASW_HOST_DEVICE int start(int run, int BM) const { return run * (BM + (q - 1) * R0) + (run - long0 > 0 ? run - long0 : 0) * R0; }
+};
 
 struct LayerDev {
   const half8* Wh;
@@ -77,7 +86,7 @@ struct KArgs {
   const half8* Pre_l;
   float pre_up, pre_down;                // SRC: 2^pre_shift and its inverse
   int B, T, taps, ntile, BM, img_rows;
-  int nrun, run_q, run_long0;            // CARRY: runs per item; tiles of a short run; the first run with one tile more
+  RunPlan runs;                          // the fused pair: the runs of an item
   float eps;
   LayerDev L[MAXL];
 };
@@ -340,8 +349,8 @@ __device__ __forceinline__ void stage_rows(const KArgs& p, const Map& map, int b
 // load per plane.  Tap 7 does not exist -- its weights are zero -- but its rows are read and are finite (data or
 // the descriptor's zeros).  Everything is requested before the first MFMA: one exposed latency per tile.
 // (load_tab: false on the later tiles of a carried-halo run, whose vectors are in LDS already; the barrier stays, and
-// there it also keeps the hand-over behind the previous tile's last reads of the image.)
-template <int NL, bool WOFS, typename Map, typename TabT>
+// there it also keeps the hand-over behind the previous tile's last reads of the image.  wofs: as in conv_layer.)
+template <int NL, typename Map, typename TabT>
 __device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, int b, TabT tab, bool load_tab, int wofs, int tid,
                                               floatx16 (&acc)[TM][2]) {
   const LayerDev& Ld = p.L[0];
@@ -367,8 +376,8 @@ __device__ __forceinline__ void source_layer0(const KArgs& p, const Map& map, in
     constexpr int kg = decltype(kgc)::value;
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
-      if constexpr (kg < 4) frag_load<3>(Ld.Wh, Ld.Wl, (long)kg * 2 + cb + (WOFS ? wofs : 0), lane, wh[slot][cb], wl[slot][cb]);
-      else frag_load<3>(p.Pre_h, p.Pre_l, (long)cb + (WOFS ? wofs : 0), lane, wh[slot][cb], wl[slot][cb]);
+      if constexpr (kg < 4) frag_load<3>(Ld.Wh, Ld.Wl, (long)kg * 2 + cb + wofs, lane, wh[slot][cb], wl[slot][cb]);
+      else frag_load<3>(p.Pre_h, p.Pre_l, (long)cb + wofs, lane, wh[slot][cb], wl[slot][cb]);
     }
   };
   wload(std::integral_constant<int, 0>{}, 0);
@@ -639,14 +648,8 @@ __device__ __forceinline__ void store_rows(const KArgs& p, const Map& map, int b
 
 // ------------------------------------------------------------------ the kernel
 // NL fused layers (contiguous row tiles) or one layer on polyphase row sets (POLY, NL == 1).
-// NW waves, each owning TM 32-row fragments x all 64 channels.
-//
-// SRC: layer 0's input x0 is itself a 1x1 convolution of an 8-channel source u~ = (u_0 .. u_6, 1) (zero outside the
-// sequence), x0[t] = Wpre~ u~[t], which nothing non-linear separates from layer 0's convolution.  Layer 0 then runs
-// on u~ with the composed weights Wc_k Wpre~ (k index = tap * 8 + channel: 4 k-steps of two taps each instead of
-// taps x 4), its B operand loaded straight from the two fp16 planes of u~ -- a fragment is 32 consecutive 16-byte
-// rows -- with no LDS image and no staging pass; the residual x0 is one more k-step with Wpre~ (K = 8 padded to 16)
-// accumulated onto the ReLU'd accumulators.  x0 is never materialised.
+// NW waves, each owning TM 32-row fragments x all 64 channels.  The pair comes here as UpFeed only: without it, it is
+// resstack64_carry_kernel's.
 //
 // UP ("UpFeed", f16x3): the stack is the last of a decoder block and the next block is a 64 -> 64 channel stride-2
 // transposed convolution.  That convolution is a one-tap GEMM over channels of (x + skip), and a finished LayerNorm
@@ -655,12 +658,12 @@ __device__ __forceinline__ void store_rows(const KArgs& p, const Map& map, int b
 // folds into the packed weight, asw_up_feed_kperm).  So the last layer adds the skip rows, splits the sum, runs
 // W_up (x + skip) + bias for the 256 output channels from registers and writes the raw rows and their GroupNorm
 // partial sums (UpArgs).  x is never stored: one write and one read of it and one launch less.
-template <int NL, int PH, bool POLY, bool GLU, int NTERM, bool SRC = false, bool UP = false>
+template <int NL, int PH, bool POLY, bool GLU, int NTERM, bool UP = false>
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2)))
 void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
-  static_assert(!UP || (!SRC && NTERM == 3), "UpFeed: f16x3, never source-fed");
+  static_assert(!UP || NTERM == 3, "UpFeed: f16x3");
   static_assert(!POLY || NL == 1, "polyphase row sets: single layers only");
-  static_assert(!SRC || (!POLY && !GLU && NTERM == 3), "source-fed layer 0: contiguous tiles, f16x3");
+  static_assert(NL != 2 || UP, "the pair without UpFeed: resstack64_carry_kernel");
 
   extern __shared__ __align__(16) char smem[];
   char* img = smem;
@@ -674,17 +677,14 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
 
   PhaseClock clk;
   clk.mark(0);
-  if constexpr (!SRC) {                  // (SRC: source_layer0 loads the vectors and has nothing to stage)
-    load_layer_vectors<NL>(p, tab, tid);
-    stage_rows<GLU, NTERM>(p, map, b, img, tid);
-    __syncthreads();
-  }
+  load_layer_vectors<NL>(p, tab, tid);
+  stage_rows<GLU, NTERM>(p, map, b, img, tid);
+  __syncthreads();
   clk.mark(1);
 
   floatx16 acc[TM][2];
   auto layer = [&](auto lic) {
     constexpr int li = decltype(lic)::value;
-    constexpr bool fed = SRC && li == 0;
     const LayerDev& Ld = p.L[li];
     const int nf = Ld.nfrag - wid * TM;                 // fragments of this wave that exist in this layer (<= 0: none)
 #pragma unroll
@@ -693,12 +693,11 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][cb][r] = 0.f;        // (all of acc defined on every path: it stays in registers)
-    if constexpr (fed) source_layer0<NL, false>(p, map, b, tab, true, 0, tid, acc);
-    else conv_layer<NTERM, false>(p, Ld, map, img, nf, 0, lane, wid, acc);
+    conv_layer<NTERM, false>(p, Ld, map, img, nf, 0, lane, wid, acc);
     clk.mark_after(2 + 2 * li, acc[0][0][0]);
-    finish_rows<fed, UP>(p, Ld, map, img, tab.layer(li), li == 0, nf, lane, wid, acc);
+    finish_rows<false, UP>(p, Ld, map, img, tab.layer(li), li == 0, nf, lane, wid, acc);
     if constexpr (li < NL - 1) {
-      if constexpr (!fed) __syncthreads();              // every wave is done reading the old image
+      __syncthreads();                                  // every wave is done reading the old image
       hand_over<NTERM>(Ld, map, img, 0, nf, lane, wid, acc);
       __syncthreads();
     } else if constexpr (UP) {
@@ -714,7 +713,7 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
   clk.report<NL>();
 }
 
-// The carried-halo form of the fused pair (contiguous tiles, never UpFeed).  A workgroup owns a RUN of consecutive row
+// The fused pair (contiguous tiles, never UpFeed), its halo carried.  A workgroup owns a RUN (RunPlan) of consecutive row
 // tiles of one item and walks them in time order.  The first tile of a run is the tile of the kernel above: R0 layer-0
 // rows, of which layer 1 can finish BM = R0 - 2 halo.  Every later tile finishes R0 rows: the 2 halo layer-0 rows in
 // front of its own are the previous tile's last -- split to fp16 hi / lo as hand_over left them -- and travel in
@@ -722,13 +721,22 @@ void resstack64_kernel(const std::conditional_t<UP, KArgsUp, KArgs> p) {
 // front of the R0 new rows.  Both layers then run NW * TM whole fragments and no layer-0 row is computed twice inside
 // a run.  The image of layer 1 is R0 + 2 halo rows, which leaves no room behind it at two workgroups per CU: the
 // per-layer vectors live in the rows' pad bytes (Tab), loaded once per run.  A row's arithmetic does not depend on the
-// tile that computes it: the results are those of the kernel above bit for bit.
+// tile that computes it: a plan of one tile per run IS the recomputed-halo tiling (the host's, on request or where
+// nothing can be carried; the image is then the rows a head tile needs) and gives the same results bit for bit.
+//
+// SRC: layer 0's input x0 is itself a 1x1 convolution of an 8-channel source u~ = (u_0 .. u_6, 1) (zero outside the
+// sequence), x0[t] = Wpre~ u~[t], which nothing non-linear separates from layer 0's convolution.  Layer 0 then runs
+// on u~ with the composed weights Wc_k Wpre~ (k index = tap * 8 + channel: 4 k-steps of two taps each instead of
+// taps x 4), its B operand loaded straight from the two fp16 planes of u~ -- a fragment is 32 consecutive 16-byte
+// rows -- with no LDS image and no staging pass; the residual x0 is one more k-step with Wpre~ (K = 8 padded to 16)
+// accumulated onto the ReLU'd accumulators.  x0 is never materialised.
 constexpr int CQ = 3;                    // 16-byte pieces of carried rows per thread: 2 halo <= CQ * NTHR / 16 = 48 rows
 template <bool GLU, int NTERM, bool SRC>
 __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(2)))
 void resstack64_carry_kernel(const KArgs p) {
   static_assert(!SRC || (!GLU && NTERM == 3), "source-fed layer 0: f16x3");
   constexpr int NL = 2;
+  static_assert(R0 >= NL * 3 * 16, "one float4 group of the per-layer vectors per image row");
   using Map = RowMap<false, 1, true>;
 
   extern __shared__ __align__(16) char smem[];
@@ -737,11 +745,9 @@ void resstack64_carry_kernel(const KArgs p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int idx;
-  if (!xcd_tile_run(p.B * p.nrun, idx)) return;         // XCD-aware order: a contiguous run of (item, run) pairs
-  const int b = idx / p.nrun, run = idx - b * p.nrun;
-  // the runs of an item (plan_runs): run_q tiles each, one more from run_long0 on; n tiles cover BM + (n - 1) R0 rows
-  const int s = run * (p.BM + (p.run_q - 1) * R0) + max(run - p.run_long0, 0) * R0;
-  const int n = p.run_q + (run >= p.run_long0 ? 1 : 0);
+  if (!xcd_tile_run(p.B * p.runs.nrun, idx)) return;    // XCD-aware order: a contiguous run of (item, run) pairs
+  const int b = idx / p.runs.nrun, run = idx - b * p.runs.nrun;
+  const int s = p.runs.start(run, p.BM), n = p.runs.tiles(run);
   const int crows = 2 * p.L[0].halo;                    // rows carried from tile to tile
 
   PhaseClock clk;
@@ -780,7 +786,7 @@ void resstack64_carry_kernel(const KArgs p) {
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][cb][r] = 0.f;
-      if constexpr (fed) source_layer0<NL, true>(p, map, b, tab, !steady, wofs, tid, acc);
+      if constexpr (fed) source_layer0<NL>(p, map, b, tab, !steady, wofs, tid, acc);
       else conv_layer<NTERM, true>(p, Ld, map, img, nf, wofs, lane, wid, acc);
       clk.mark_after(2 + 2 * li, acc[0][0][0]);
       finish_rows<fed, false>(p, Ld, map, img, tab.layer(li), li == 0, nf, lane, wid, acc);
@@ -826,25 +832,23 @@ double stack_bytes(const KArgs& k) {
   return rows * C * 4 * (GLU ? 3 : 2);
 }
 
-template <int NL, int PH, bool POLY, bool GLU, int NTERM, bool SRC, bool UP, bool CARRY>
+template <int NL, int PH, bool POLY, bool GLU, int NTERM, bool SRC, bool UP>
 constexpr auto stack_kernel() {
-  if constexpr (CARRY) {
-    static_assert(NL == 2 && !POLY && !UP, "carried halo: the fused pair on contiguous tiles, not UpFeed");
-    return &resstack64_carry_kernel<GLU, NTERM, SRC>;
-  } else {
-    return &resstack64_kernel<NL, PH, POLY, GLU, NTERM, SRC, UP>;
-  }
+  static_assert(!SRC || (NL == 2 && !UP), "source-fed layer 0: the pair without UpFeed");
+  if constexpr (NL == 2 && !UP) return &resstack64_carry_kernel<GLU, NTERM, SRC>;
+  else return &resstack64_kernel<NL, PH, POLY, GLU, NTERM, UP>;
 }
 
 // One form of the kernel: its single-pass and its f16x3 instantiation (SRC and UP are f16x3 only: the host has
-// checked the precision).
-template <int NL, int PH, bool POLY, bool GLU, bool SRC, bool UP, bool CARRY = false>
-int launch_stack(const KArgs& k, const UpArgs* up, int precision, size_t smem, double flops, hipStream_t s) {
+// checked the precision).  carry (the pair without UpFeed): the plan hands rows from tile to tile, and the name says so.
+template <int NL, int PH, bool POLY, bool GLU, bool SRC, bool UP>
+int launch_stack(const KArgs& k, const UpArgs* up, int precision, size_t smem, double flops, hipStream_t s, bool carry = false) {
+  const bool say_carry = carry && asw::prof_form();
   char nm[128], detail[48] = "";
   snprintf(nm, sizeof nm, "resstack64<%d,%dx%d%s%s%s%s%s>", NL, NW, TM, POLY ? (PH == 1 ? ",poly1" : PH == 2 ? ",poly2" : ",poly4") : "",
-           CARRY && asw::prof_form() ? ",carry" : "", GLU ? ",glu" : "", SRC ? ",src" : "", UP ? ",up" : "");
+           say_carry ? ",carry" : "", GLU ? ",glu" : "", SRC ? ",src" : "", UP ? ",up" : "");
   if (asw::prof_detail()) {
-    if (CARRY && asw::prof_form()) snprintf(detail, sizeof detail, "[B%d M%d d%d r%d]", k.B, k.T, k.L[0].dil, k.nrun);
+    if (say_carry) snprintf(detail, sizeof detail, "[B%d M%d d%d r%d]", k.B, k.T, k.L[0].dil, k.runs.nrun);
     else snprintf(detail, sizeof detail, "[B%d M%d d%d]", k.B, k.T, k.L[0].dil);
   }
   std::conditional_t<UP, KArgsUp, KArgs> ka;
@@ -853,21 +857,27 @@ int launch_stack(const KArgs& k, const UpArgs* up, int precision, size_t smem, d
     ka.u = *up;
     flops += 2.0 * k.B * (double)k.T * C * UPN;
   }
-  return asw::launch_pair<stack_kernel<NL, PH, POLY, GLU, (SRC || UP) ? 3 : 1, SRC, UP, CARRY>(),
-                          stack_kernel<NL, PH, POLY, GLU, 3, SRC, UP, CARRY>()>(
-      precision, dim3(xcd_grid_run(k.B * (CARRY ? k.nrun : k.ntile))), dim3(NTHR), smem, 160 * 1024, nm, detail, flops,
-      stack_bytes<GLU, SRC, UP>(k), s, ka);
+  return asw::launch_pair<stack_kernel<NL, PH, POLY, GLU, (SRC || UP) ? 3 : 1, SRC, UP>(),
+                          stack_kernel<NL, PH, POLY, GLU, 3, SRC, UP>()>(
+      precision, dim3(xcd_grid_run(k.B * (NL == 2 && !UP ? k.runs.nrun : k.ntile))), dim3(NTHR), smem, 160 * 1024, nm, detail,
+      flops, stack_bytes<GLU, SRC, UP>(k), s, ka);                // (the pair without UpFeed: a workgroup per run, not per tile)
 }
 
-// the staged forms of a tiling: GroupNorm + GLU on load (contiguous tiles only) or not, UpFeed or not
+// the staged forms of a tiling: GroupNorm + GLU on load (contiguous tiles only) or not, UpFeed or not (the pair comes
+// here as UpFeed only: dispatch)
 template <int NL, int PH, bool POLY>
 int launch_staged(const KArgs& k, const UpArgs* up, bool glu, int precision, size_t smem, double flops, hipStream_t s) {
+  auto form = [&](auto gluc) {
+    constexpr bool GLU = decltype(gluc)::value;
+    if constexpr (NL != 2) {
+      if (!up) return launch_stack<NL, PH, POLY, GLU, false, false>(k, up, precision, smem, flops, s);
+    }
+    return launch_stack<NL, PH, POLY, GLU, false, true>(k, up, precision, smem, flops, s);
+  };
   if constexpr (!POLY) {
-    if (glu) return up ? launch_stack<NL, PH, POLY, true, false, true>(k, up, precision, smem, flops, s)
-                       : launch_stack<NL, PH, POLY, true, false, false>(k, up, precision, smem, flops, s);
+    if (glu) return form(std::true_type{});
   }
-  return up ? launch_stack<NL, PH, POLY, false, false, true>(k, up, precision, smem, flops, s)
-            : launch_stack<NL, PH, POLY, false, false, false>(k, up, precision, smem, flops, s);
+  return form(std::false_type{});
 }
 
 // The row tiling of a launch whose layer 0 computes R0 rows (asw_resstack_tiles reports ntile to a caller that sizes
@@ -885,10 +895,8 @@ TilePlan plan_tiles(int T, int n_layers, int dil0, int halo0, bool glu) {
   return {false, 1, BM, BM > 0 ? asw::cdiv(T, BM) : 0};
 }
 
-// The runs of the carried-halo form.  An item's rows are cut into `nrun` runs, each a head tile of BM rows followed by
-// steady tiles of R0 rows; the item's tiles are dealt to the runs as evenly as they go, the runs with one tile more
-// last, so that only the item's very last tile is ragged and none is empty.
-struct RunPlan { int nrun, q, long0; };  // runs per item; tiles of a short run; index of the first run with q + 1 tiles
+// The runs of an item of T rows (RunPlan) when `want` are asked for: never more than the item has head tiles.  INT_MAX
+// (dispatch, where nothing is carried) makes every tile a run of its own, at run * BM: the recomputed-halo tiling.
 RunPlan plan_runs(int T, int BM, int want) {
   const int nrun = std::max(1, std::min(want, asw::cdiv(T, BM)));
   const int ntile = nrun + asw::cdiv(std::max(T - nrun * BM, 0), R0);
@@ -906,14 +914,12 @@ int device_cus() {
   if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 256;
   return cus[dev];
 }
-// Does the fused pair take the carried-halo form: more than one tile of rows, the carried rows fit the registers that
-// hold them, and the image of a steady tile -- R0 + 2 halo rows for layer 1 -- admits two workgroups per CU.
-// ASW_RESSTACK_NO_CARRY=1 (or runs_per_item < 0) keeps the recomputed-halo tiling (A/B measurements).
-bool carry_applies(int T, int n_layers, int BM, int pad0, int halo0, bool up, int runs_per_item) {
-  static const bool off = getenv("ASW_RESSTACK_NO_CARRY") != nullptr;
+// Does the fused pair (without UpFeed) carry its halo: it is not asked to recompute it (runs_per_item < 0), there is
+// more than one tile of rows, the carried rows fit the registers that hold them, and the image of a steady tile --
+// R0 + 2 halo rows for layer 1 -- admits two workgroups per CU.
+bool carry_applies(int T, int BM, int pad0, int halo0, int runs_per_item) {
   const int rows = R0 + 2 * std::max(pad0, halo0);
-  return !off && runs_per_item >= 0 && n_layers == 2 && !up && T > BM && halo0 > 0 && 2 * halo0 * 16 <= CQ * NTHR &&
-         (size_t)rows * RS <= 80 * 1024 && rows >= 2 * 3 * 16;
+  return runs_per_item >= 0 && T > BM && halo0 > 0 && 2 * halo0 * 16 <= CQ * NTHR && (size_t)rows * RS <= 80 * 1024;
 }
 
 int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, double flops, hipStream_t s) {
@@ -922,8 +928,7 @@ int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, d
   k.BM = tp.BM;
   k.ntile = tp.ntile;
   if (tp.poly) {
-    const int PH = tp.PH;
-    const int BMJ = R0 / PH;
+    const int PH = tp.PH, BMJ = R0 / PH;
     k.L[0].nfrag = NW * TM;
     k.img_rows = PH * (BMJ + a.taps - 1);
     const size_t smem = (size_t)k.img_rows * RS + 3 * 64 * sizeof(float);
@@ -935,28 +940,23 @@ int dispatch(const asw_resstack_args& a, KArgs& k, const UpArgs* up, bool glu, d
   }
   ASW_CHECK_ARG(k.BM >= R0 / 2, "resstack: the later layers' halo (%d rows per side) leaves %d of %d rows; fuse fewer layers",
                 k.L[0].halo, k.BM, R0);
-  int rows = 0;
+  int rows = 0;                                          // of the image of a tile that stands alone
   for (int i = 0; i < a.n_layers; ++i) {
     k.L[i].nfrag = asw::cdiv(k.BM + 2 * k.L[i].halo, 32);
     const int r = 32 * k.L[i].nfrag + 2 * k.L[i].pad;
     rows = r > rows ? r : rows;
   }
-  if (carry_applies(a.T, a.n_layers, k.BM, k.L[0].pad, k.L[0].halo, up != nullptr, a.runs_per_item)) {
-    const RunPlan rp = plan_runs(a.T, k.BM, a.runs_per_item > 0 ? a.runs_per_item : auto_runs(a.T, k.BM, a.B, device_cus()));
-    k.nrun = rp.nrun; k.run_q = rp.q; k.run_long0 = rp.long0;
-    k.img_rows = R0 + 2 * std::max(k.L[0].pad, k.L[0].halo);
-    const size_t lds = (size_t)k.img_rows * RS;          // (the per-layer vectors sit in the rows' pad bytes)
-    if (k.src_h) return launch_stack<2, 1, false, false, true, false, true>(k, nullptr, a.precision, lds, flops, s);
-    return glu ? launch_stack<2, 1, false, true, false, false, true>(k, nullptr, a.precision, lds, flops, s)
-               : launch_stack<2, 1, false, false, false, false, true>(k, nullptr, a.precision, lds, flops, s);
-  }
-  k.img_rows = rows;
-  const size_t smem = (size_t)rows * RS + (size_t)a.n_layers * 3 * 64 * sizeof(float);
+  const bool pair = a.n_layers == 2 && !up;              // runs of tiles, the per-layer vectors in the rows' pad bytes
+  const bool carry = pair && carry_applies(a.T, k.BM, k.L[0].pad, k.L[0].halo, a.runs_per_item);
+  k.img_rows = carry ? R0 + 2 * std::max(k.L[0].pad, k.L[0].halo) : rows;
+  const size_t smem = (size_t)k.img_rows * RS + (pair ? 0 : (size_t)a.n_layers * 3 * 64 * sizeof(float));
   ASW_CHECK_ARG(smem <= 160 * 1024, "resstack: image of %d rows exceeds LDS (dilation %d x %d taps too wide for a contiguous tile)",
-                rows, dil0, a.taps);
-  if (k.src_h) {
-    ASW_CHECK_ARG(k.L[0].nfrag == NW * TM, "resstack: source-fed layer 0 computes %d of %d fragments", k.L[0].nfrag, NW * TM);
-    return launch_stack<2, 1, false, false, true, false>(k, nullptr, a.precision, smem, flops, s);
+                k.img_rows, dil0, a.taps);
+  if (pair) {
+    k.runs = plan_runs(a.T, k.BM, !carry ? INT_MAX : a.runs_per_item > 0 ? a.runs_per_item : auto_runs(a.T, k.BM, a.B, device_cus()));
+    if (k.src_h) return launch_stack<2, 1, false, false, true, false>(k, nullptr, a.precision, smem, flops, s, carry);
+    return glu ? launch_stack<2, 1, false, true, false, false>(k, nullptr, a.precision, smem, flops, s, carry)
+               : launch_stack<2, 1, false, false, false, false>(k, nullptr, a.precision, smem, flops, s, carry);
   }
   switch (a.n_layers) {
     case 1: return launch_staged<1, 1, false>(k, up, glu, a.precision, smem, flops, s);
@@ -1011,14 +1011,13 @@ extern "C" int asw_resstack_runs(int T, int B, int taps, const int32_t* dil, int
                                  int32_t* steady_rows, int32_t* run_start, int32_t* run_tiles, int max_runs) {
   ASW_CHECK_ARG(T > 0 && B > 0 && taps >= 3 && taps % 2 == 1 && dil && n_cu > 0 && max_runs >= 0, "resstack_runs: bad argument");
   const int pad0 = dil[0] * (taps - 1) / 2, halo0 = dil[1] * (taps - 1) / 2, BM = R0 - 2 * halo0;
-  if (BM < R0 / 2 || !carry_applies(T, 2, BM, pad0, halo0, false, runs_per_item)) return 0;
+  if (BM < R0 / 2 || !carry_applies(T, BM, pad0, halo0, runs_per_item)) return 0;
   const RunPlan rp = plan_runs(T, BM, runs_per_item > 0 ? runs_per_item : auto_runs(T, BM, B, n_cu));
   if (head_rows) *head_rows = BM;
   if (steady_rows) *steady_rows = R0;
   for (int r = 0; r < rp.nrun && r < max_runs; ++r) {
-    // (as the kernel finds them)
-    if (run_start) run_start[r] = r * (BM + (rp.q - 1) * R0) + std::max(r - rp.long0, 0) * R0;
-    if (run_tiles) run_tiles[r] = rp.q + (r >= rp.long0 ? 1 : 0);
+    if (run_start) run_start[r] = rp.start(r, BM);
+    if (run_tiles) run_tiles[r] = rp.tiles(r);
   }
   return rp.nrun;
 }

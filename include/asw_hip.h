@@ -515,7 +515,8 @@ typedef struct asw_resstack_args {
    * workgroup walks a run of consecutive row tiles of one item and hands the layer-0 rows two neighbouring tiles share
    * from tile to tile instead of computing them twice (same results, bit for bit).  Runs per item: 0 = chosen by the
    * library from B, T and the device's CU count; > 0 = this many (clamped to the tiles there are); < 0 = the
-   * recomputed-halo tiling, as does ASW_RESSTACK_NO_CARRY=1 in the environment.  Launch names carry ",carry",
+   * recomputed-halo tiling: every tile a run of its own, by the same kernel (also where nothing can be carried: one
+   * tile of rows, or more shared rows than the registers hold).  Launch names of a carrying plan carry ",carry",
    * e.g. resstack64<2,4x2,carry,glu>, and with asw_profile_enable(3) the runs per item, "[B.. M.. d.. r<runs>]";
    * asw_profile_enable(2) shows the launch under the name of the recomputed-halo form, whose bits it computes. */
   int32_t runs_per_item;

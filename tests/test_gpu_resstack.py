@@ -5,6 +5,8 @@ registers.  References: the torch fp32 statement of DilatedResidualLayer / Dilat
 Bar: relative L2 <= 2e-5 against torch fp32 (the f16x3 bar of tests/test_gpu_f16x3.py), <= 3e-6 against the
 per-layer HIP path (same arithmetic; only summation order and the residual's hi + lo read differ).
 Needs an MI355X."""
+import ctypes
+import json
 import math
 import os
 
@@ -67,13 +69,36 @@ def _dev_layers(ops, layers):
     return [(ops.pack_conv_weight(w).cuda(), b.cuda(), g.cuda(), be.cuda(), d) for w, b, g, be, d in layers]
 
 
+def _profiled(fn):
+    """launch names while fn() runs, with their shapes and the tiling form (profile mode 3)"""
+    from acousticswarms_speech_amd import native
+    L = native.lib()
+    L.asw_profile_enable(3)
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        buf = ctypes.create_string_buffer(1 << 16)
+        native.check(L.asw_profile_report(buf, len(buf)))
+    finally:
+        L.asw_profile_enable(0)
+    return out, list(json.loads(buf.value.decode()))
+
+
+def _one_tile_per_run(names):
+    """the fused pair ran, and under the name of the recomputed-halo tiling: nothing was carried"""
+    return any(n.startswith("resstack64<2,4x2") for n in names) and not any("carry" in n for n in names)
+
+
 @pytest.mark.parametrize("dils,K,T", [((1,), 7, 1000), ((1,), 7, 37), ((7,), 7, 777), ((49,), 7, 900), ((49,), 7, 100),
                                       ((49,), 7, 4900), ((49,), 7, 3000), ((49,), 7, 13000), ((7,), 7, 3000),
                                       ((1, 7), 7, 1000), ((1, 7), 7, 214), ((1, 7), 7, 215), ((1, 7), 7, 5), ((1, 7), 7, 3010),
-                                      ((1, 2, 4), 5, 1500), ((1, 2), 5, 233), ((2, 4), 5, 700), ((1, 7, 49), 7, 600)])
+                                      ((1, 2, 4), 5, 1500), ((1, 2), 5, 233), ((2, 4), 5, 700), ((1, 7, 49), 7, 600),
+                                      ((1, 9), 7, 405)])
 def test_resstack_vs_torch_and_per_layer_kernels(dils, K, T):
     """single layers (contiguous and polyphase), the spot pair (1, 7), the separation network's (1, 2, 4) with
-    5 taps; ragged lengths around the tile size (214 finished rows per workgroup for the pair)."""
+    5 taps; ragged lengths around the tile size (214 finished rows per workgroup for the pair).  The pair (1, 9) shares
+    2 x 27 = 54 layer-0 rows between tiles, more than the 48 the carrying registers hold: one tile of 202 rows per run
+    in an image of 278 rows, here two full tiles and one row."""
     from acousticswarms_speech_amd import ops
     B = 3
     x = _rand(B, C, T, seed=3)
@@ -87,7 +112,8 @@ def test_resstack_vs_torch_and_per_layer_kernels(dils, K, T):
         mid = ops.resstack(xc, _dev_layers(ops, layers[:2]), taps=K)
         got = ops.resstack(mid, _dev_layers(ops, layers[2:]), taps=K)
     else:
-        got = ops.resstack(xc, _dev_layers(ops, layers), taps=K)
+        got, names = _profiled(lambda: ops.resstack(xc, _dev_layers(ops, layers), taps=K))
+        assert dils != (1, 9) or _one_tile_per_run(names), names
     r = _rel(got.cpu(), want)
     r2 = _rel(got.cpu(), _hip_layers(ops, xc, layers, K).cpu())
     _log(f"resstack dils={dils} K={K} T={T}: rel vs torch {r:.3e}, vs per-layer HIP {r2:.3e}")
@@ -125,19 +151,21 @@ def test_resstack_groupnorm_glu_on_load():
     _log(f"resstack glu-on-load: max abs diff {float((a - b).abs().max()):.3e}")
     assert torch.equal(a, b)
     # the encoder's form: the normalised rows are also written out once (the skip connection), each by the tile that owns them
-    for dils, Tn in (((1, 7), T), ((1,), 701), ((1, 7), 48128)):
-        rawn = _rand(B, Tn, 2 * C, seed=17).cuda()
-        stn = torch.zeros(B, 1, 4, device="cuda")
+    # (the pair (1, 9) cannot carry its 54 shared rows: one tile per run, two full tiles and one row, side rows bit-equal)
+    for dils, Tn, Bn in (((1, 7), T, B), ((1,), 701, B), ((1, 7), 48128, B), ((1, 9), 405, 3)):
+        rawn = _rand(Bn, Tn, 2 * C, seed=17).cuda()
+        stn = torch.zeros(Bn, 1, 4, device="cuda")
         stn[:, 0, 0] = rawn[:, :, :C].sum((1, 2)); stn[:, 0, 1] = (rawn[:, :, :C] ** 2).sum((1, 2))
         stn[:, 0, 2] = rawn[:, :, C:].sum((1, 2)); stn[:, 0, 3] = (rawn[:, :, C:] ** 2).sum((1, 2))
         xn, mrn = ops.gn_glu(rawn, stn, gg, gb), ops.gn_finalize(stn, Tn, C)
         ly = _dev_layers(ops, _layers(dils, 7, seed=71))
-        side = torch.full((B, Tn, C), float("nan"), device="cuda")
-        c = ops.resstack(None, ly, taps=7, glu=(rawn, mrn, gg, gb), glu_out=side)
+        side = torch.full((Bn, Tn, C), float("nan"), device="cuda")
+        c, names = _profiled(lambda: ops.resstack(None, ly, taps=7, glu=(rawn, mrn, gg, gb), glu_out=side))
         assert torch.equal(c, ops.resstack(xn, ly, taps=7))
         d = float((side - xn).abs().max())
         _log(f"resstack glu side output dils={dils} T={Tn}: max abs diff to asw_gn_glu {d:.3e}, bit-equal {torch.equal(side, xn)}")
         assert torch.isfinite(side).all() and d <= 1e-6
+        assert dils != (1, 9) or (torch.equal(side, xn) and _one_tile_per_run(names)), names
 
 
 def test_resstack_full_size_properties():

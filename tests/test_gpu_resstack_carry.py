@@ -6,33 +6,16 @@ the bars of tests/test_gpu_resstack.py (relative L2 <= 2e-5 against torch fp32, 
 kernels, <= 2e-3 in the single-pass mode) and of tests/test_gpu_srcstack.py (<= 3e-6 against the staged pair).
 Lengths: 470 = head tile + one steady tile, 471 one row more, 982 = 214 + 3 x 256, 1000; 726 with two runs (each a head
 and a steady tile); 3010 with 1, 2, 5 runs and the library's own choice.  Needs an MI355X."""
-import ctypes
-import json
 import re
 
 import pytest
 import torch
 
-from tests.test_gpu_resstack import C, _dev_layers, _hip_layers, _layers, _rand, _rel, _torch_stack
+from tests.test_gpu_resstack import C, _dev_layers, _hip_layers, _layers, _profiled, _rand, _rel, _torch_stack
 
 pytestmark = pytest.mark.gpu
 K, B = 7, 3
 CASES = [(470, 0), (471, 0), (982, 0), (1000, 0), (726, 2), (3010, 1), (3010, 2), (3010, 5), (3010, 0)]
-
-
-def _profiled(fn):
-    """launch names while fn() runs, with their shapes and the tiling form (profile mode 3)"""
-    from acousticswarms_speech_amd import native
-    L = native.lib()
-    L.asw_profile_enable(3)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-        buf = ctypes.create_string_buffer(1 << 16)
-        native.check(L.asw_profile_report(buf, len(buf)))
-    finally:
-        L.asw_profile_enable(0)
-    return out, list(json.loads(buf.value.decode()))
 
 
 _REF = {}

@@ -40,17 +40,14 @@ def _rel(a, b):
 _WEIGHTS = {}
 
 
-def _weights():
+def _weights(dils=DILS):
     """preproc (bias x10: a boundary mistake is large) and the two residual layers, torch layout, made once"""
     if not _WEIGHTS:
         _WEIGHTS["pre_w"] = _rand(C, M, seed=401, scale=1.0 / math.sqrt(M))
         _WEIGHTS["pre_b"] = _rand(C, seed=402, scale=0.1) * 10
-        layers = []
-        for i, d in enumerate(DILS):
-            layers.append((_rand(C, C, K, seed=410 + 10 * i, scale=1.0 / math.sqrt(C * K)), _rand(C, seed=411 + 10 * i, scale=0.1),
-                           1 + _rand(C, seed=412 + 10 * i, scale=0.1), _rand(C, seed=413 + 10 * i, scale=0.1), d))
-        _WEIGHTS["layers"] = layers
-    return _WEIGHTS["pre_w"], _WEIGHTS["pre_b"], _WEIGHTS["layers"]
+        _WEIGHTS["layers"] = [(_rand(C, C, K, seed=410 + 10 * i, scale=1.0 / math.sqrt(C * K)), _rand(C, seed=411 + 10 * i, scale=0.1),
+                               1 + _rand(C, seed=412 + 10 * i, scale=0.1), _rand(C, seed=413 + 10 * i, scale=0.1)) for i in range(2)]
+    return _WEIGHTS["pre_w"], _WEIGHTS["pre_b"], [ly + (d,) for ly, d in zip(_WEIGHTS["layers"], dils)]
 
 
 OFFSETS = np.array([[0, 0, 0, 0, 0, 0], [3, -5, 8, -13, 21, -34], [-40, 30, -20, 10, -5, 2]], dtype=np.int32)
@@ -122,6 +119,26 @@ def test_source_fed_pair_vs_separate_preproc_and_float64(Tp, pad, circular):
     perm = [2, 0, 1]
     _, _, refn_p, got_p = _run_both(ops, mix_d, torch.from_numpy(OFFSETS[perm].copy()).cuda(), Tp, circular, pre_w, pre_b, layers)
     assert torch.equal(got_p, got[perm]) and torch.equal(refn_p, refn[perm])
+
+
+def test_source_fed_pair_of_one_tile_per_run():
+    """the pair (1, 9): its 2 x 27 shared layer-0 rows exceed the 48 the carrying registers hold, so every tile of 202
+    rows is a run of its own (image 278 rows); Tp = 405 is two full tiles and one row.  Against the separate preproc
+    pass + staged pair."""
+    from acousticswarms_speech_amd import ops
+    from tests.test_gpu_resstack import _one_tile_per_run, _profiled
+    pre_w, pre_b, layers = _weights((1, 9))
+    Tp = 405
+    mix_d, off_d = _rand(M, Tp, seed=7 + Tp, scale=0.3).cuda(), torch.from_numpy(OFFSETS).cuda()
+    (mean, std, _, got), names = _profiled(lambda: _run_both(ops, mix_d, off_d, Tp, True, pre_w, pre_b, layers))
+    assert any(n.startswith("resstack64<2,4x2,src>") for n in names) and _one_tile_per_run(names), names
+    x0, _ = ops.shift_norm_preproc(mix_d, off_d, mean, std, pre_w.cuda(), pre_b.cuda(), Tp, True)
+    want = ops.resstack(x0, [(ops.pack_conv_weight(w).cuda(), b.cuda(), g.cuda(), be.cuda(), d) for w, b, g, be, d in layers], taps=K)
+    assert torch.isfinite(got).all()
+    for name, (r0, r1) in {"all": (0, Tp), "head": (0, 8), "tail": (Tp - 8, Tp), "tile boundary": (198, 206)}.items():
+        ra = _rel(got[:, r0:r1].cpu(), want[:, r0:r1].cpu())
+        _log(f"src pair (1, 9) Tp={Tp} rows {name}: rel vs preproc + pair {ra:.3e}")
+        assert ra <= 3e-6, (name, ra)
 
 
 def test_source_fed_form_refuses_other_shapes():
