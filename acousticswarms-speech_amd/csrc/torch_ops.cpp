@@ -1036,6 +1036,60 @@ Tensor train_losses(const Tensor& est, const Tensor& gt) {
   return out;
 }
 
+// ---- corpus voices (voiceprep.py) ---------------------------------------------------------------------------------------
+// -> [n, T_out] float32 or (out_f64) float64: the rows of the packed x float32 [x_len], resampled by up/down through the
+// filter table h float64 (voiceprep.resample_filter) and windowed (voiceprep.resample_poly_f64, window_f64).  The four row
+// tables are host integers, validated by the library before its launch.
+Tensor voice_resample(const Tensor& x, at::IntArrayRef row_offset, at::IntArrayRef row_len, int64_t up, int64_t down, const Tensor& h,
+                      at::IntArrayRef win_begin, at::IntArrayRef win_len, int64_t T_out, bool out_f64) {
+  need(x, "x", at::kFloat, 1);
+  need(h, "h", at::kDouble, 1);
+  same_device(x, h, "x and h");
+  const int n = checked_int(static_cast<int64_t>(row_len.size()), "n");
+  TORCH_CHECK(n <= 65535, "voice_resample takes at most 65535 rows, got ", n);
+  TORCH_CHECK(static_cast<int64_t>(row_offset.size()) == n && static_cast<int64_t>(win_begin.size()) == n &&
+                  static_cast<int64_t>(win_len.size()) == n,
+              "voice_resample: row_len holds ", n, " rows, the other tables do not");
+  TORCH_CHECK(T_out >= 1 && T_out <= (1 << 30), "voice_resample: T_out = ", T_out, " outside 1..2^30");
+  const Counts len = checked_counts(row_len, "row_len", 0, INT32_MAX), wl = checked_counts(win_len, "win_len", 0, T_out);
+  const std::vector<int64_t> off(row_offset.begin(), row_offset.end()), wb(win_begin.begin(), win_begin.end());
+  Tensor out = at::empty({n, T_out}, x.options().dtype(out_f64 ? at::kDouble : at::kFloat));
+  const size_t ws_bytes = asw_voice_resample_workspace_bytes(n);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_voice_resample_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, x.options().dtype(at::kDouble));
+  Launch l(x);
+  check_status(asw_voice_resample(x.data_ptr<float>(), x.size(0), off.data(), len.v.data(), n, checked_int(up, "up"),
+                                  checked_int(down, "down"), h.data_ptr<double>(), checked_int(h.size(0), "h_len"), wb.data(),
+                                  wl.v.data(), static_cast<int>(T_out), out.data_ptr(), out_f64 ? 1 : 0, ws.data_ptr(), ws_bytes,
+                                  l.stream),
+               "asw_voice_resample");
+  return out;
+}
+
+// -> (bounds [n, 2] int32, stats [n, 2] float64): begin and end of the non-silent span of every row of the packed x, the
+// peak frame mean square and the variance of the span (voiceprep.trim_f64).  The threshold is formed here in double as the
+// statement forms it: 10 ** (-top_db / 10).
+std::tuple<Tensor, Tensor> voice_trim(const Tensor& x, at::IntArrayRef row_offset, at::IntArrayRef row_len, double top_db) {
+  need(x, "x", at::kFloat, 1);
+  const int n = checked_int(static_cast<int64_t>(row_len.size()), "n");
+  TORCH_CHECK(n <= 65535, "voice_trim takes at most 65535 rows, got ", n);
+  TORCH_CHECK(static_cast<int64_t>(row_offset.size()) == n, "voice_trim: row_len holds ", n, " rows, row_offset ", row_offset.size());
+  TORCH_CHECK(top_db == top_db, "voice_trim: top_db is not a number");
+  const Counts len = checked_counts(row_len, "row_len", 0, INT32_MAX);
+  const std::vector<int64_t> off(row_offset.begin(), row_offset.end());
+  const int max_len = n ? *std::max_element(len.v.begin(), len.v.end()) : 0;
+  Tensor bounds = at::empty({n, 2}, x.options().dtype(at::kInt));
+  Tensor stats = at::empty({n, 2}, x.options().dtype(at::kDouble));
+  const size_t ws_bytes = asw_voice_trim_workspace_bytes(n, max_len);
+  TORCH_CHECK(ws_bytes > 0, "libasw_hip: asw_voice_trim_workspace_bytes failed: ", asw_last_error());
+  Tensor ws = at::empty({static_cast<int64_t>((ws_bytes + 7) / 8)}, x.options().dtype(at::kDouble));
+  Launch l(x);
+  check_status(asw_voice_trim(x.data_ptr<float>(), x.size(0), off.data(), len.v.data(), n, max_len, std::pow(10.0, -top_db / 10.0),
+                              bounds.data_ptr<int32_t>(), stats.data_ptr<double>(), ws.data_ptr(), ws_bytes, l.stream),
+               "asw_voice_trim");
+  return {bounds, stats};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(asw, m) {
@@ -1094,6 +1148,9 @@ TORCH_LIBRARY(asw, m) {
   m.def("train_batch(Tensor mix, int[] item_mix, int[] shifts, int S_max, int[] counts, float[] pink_level, float[] white_level, "
         "int[] white_key, Tensor? pink=None, bool out_f64=False) -> Tensor");
   m.def("train_losses(Tensor est, Tensor gt) -> Tensor");
+  m.def("voice_resample(Tensor x, int[] row_offset, int[] row_len, int up, int down, Tensor h, int[] win_begin, int[] win_len, "
+        "int T_out, bool out_f64=False) -> Tensor");
+  m.def("voice_trim(Tensor x, int[] row_offset, int[] row_len, float top_db=18.0) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(asw, CUDA, m) {
@@ -1135,6 +1192,8 @@ TORCH_LIBRARY_IMPL(asw, CUDA, m) {
   m.impl("room_convolve", &room_convolve);
   m.impl("train_batch", &train_batch);
   m.impl("train_losses", &train_losses);
+  m.impl("voice_resample", &voice_resample);
+  m.impl("voice_trim", &voice_trim);
 }
 
 // room_rir takes its geometry as host tensors (the library validates it on the host) and answers on the current device

@@ -19,13 +19,15 @@ SOURCES = ["asw_common.cpp", "convgemm.hip", "resconv.hip", "pipegemm.hip", "res
            "misc_kernels.hip", "attention.hip", "srp_kernels.hip",
            "pruner_kernels.hip", "geometry_kernels.hip", "cluster_kernels.hip",
            "search_host.cpp", "sep_kernels.hip", "spot_model.hip", "sep_model.hip", "bss_kernels.hip", "eval_kernels.hip",
-           "longform_kernels.hip", "stft_kernels.hip", "room_kernels.hip", "augment_kernels.hip"]
+           "longform_kernels.hip", "stft_kernels.hip", "room_kernels.hip", "augment_kernels.hip", "voice_kernels.hip"]
 # geometry_kernels.hip reproduces numpy's float64 roundings: no fused multiply-add may replace a multiply and an add
 # (cluster_kernels.hip reproduces a float64 statement too; its one fused multiply-add is written out; eval_kernels.hip
 # rounds a * ref before it subtracts, as hostdsp.si_sdr does; room_kernels.hip must floor every image delay as
-# roomsim.image_delays_f64 does: a delay that floors the other way moves a whole tap window)
+# roomsim.image_delays_f64 does: a delay that floors the other way moves a whole tap window; voice_kernels.hip rounds
+# every product and sum of voiceprep's statements on its own)
 EXTRA_FLAGS = {"geometry_kernels.hip": ["-ffp-contract=off"], "cluster_kernels.hip": ["-ffp-contract=off"],
-               "eval_kernels.hip": ["-ffp-contract=off"], "room_kernels.hip": ["-ffp-contract=off"]}
+               "eval_kernels.hip": ["-ffp-contract=off"], "room_kernels.hip": ["-ffp-contract=off"],
+               "voice_kernels.hip": ["-ffp-contract=off"]}
 OPS_PATH = os.path.join(_HERE, "libasw_torch_ops.so")      # TORCH_LIBRARY(asw, ...) adapters over the C ABI
 OPS_SOURCE = "torch_ops.cpp"
 
@@ -330,6 +332,12 @@ SIGNATURES = {
     "asw_train_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "asw_train_losses": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "asw_voice_resample_workspace_bytes": (c_size_t, [c_int]),
+    "asw_voice_resample": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "asw_voice_trim_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "asw_voice_trim": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
 }
 
 _lib = None

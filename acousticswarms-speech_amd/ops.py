@@ -679,6 +679,71 @@ def train_losses(est, gt, out=None):
     return res
 
 
+def _host_i64_array(values):
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(list(values), dtype=np.int64).reshape(-1))
+
+
+_voice_filters = {}
+
+
+def voice_filter(up, down, device):
+    """The resampler's filter table (``voiceprep.resample_filter``) on ``device``, built once per ratio and device."""
+    from . import voiceprep
+    key = voiceprep.reduced(up, down) + (str(device),)
+    if key not in _voice_filters:
+        _voice_filters[key] = torch.from_numpy(voiceprep.resample_filter(up, down)).to(device)
+    return _voice_filters[key]
+
+
+def voice_resample(x, row_offset, row_len, up, down, win_begin, win_len, T_out, h=None, dtype=torch.float32, out=None):
+    """The rows ``x[row_offset[r] : row_offset[r] + row_len[r]]`` of the packed float32 ``x``, resampled by ``up / down``
+    (``voiceprep.resample_poly_f64``) -> [n,T_out]: row r holds the ``win_len[r]`` resampled samples from ``win_begin[r]``
+    on and zeros past them or past the row's end.  The tables are host integers; ``h``: the filter table on the device
+    (``voice_filter`` by default).  ``dtype``: torch.float32 (the float64 sum rounded once) or torch.float64.  ``out``:
+    write into this tensor (tests)."""
+    n = len(row_len)
+    assert len(row_offset) == len(win_begin) == len(win_len) == n
+    assert x.dim() == 1 and dtype in (torch.float32, torch.float64)
+    if h is None:
+        h = voice_filter(up, down, x.device)
+    assert h.is_cuda and h.dtype == torch.float64 and h.is_contiguous() and h.dim() == 1 and h.device == x.device
+    res = torch.empty((n, int(T_out)), dtype=dtype, device=x.device) if out is None else out
+    assert res.shape == (n, int(T_out)) and res.dtype == dtype and res.is_cuda and res.is_contiguous()
+    nbytes = lib().asw_voice_resample_workspace_bytes(n)
+    if nbytes == 0:
+        check(-1)
+    off, wb = _host_i64_array(row_offset), _host_i64_array(win_begin)
+    with torch.cuda.device(x.device):
+        ws = _ws_f64(nbytes, x.device)
+        check(lib().asw_voice_resample(ptr(_f32(x)), x.shape[0], off.ctypes.data, _host_i32(row_len), n, int(up), int(down), ptr(h),
+                                       h.shape[0], wb.ctypes.data, _host_i32(win_len), int(T_out), ptr(res),
+                                       int(dtype == torch.float64), ptr(ws), nbytes, current_stream()))
+    return res
+
+
+def voice_trim(x, row_offset, row_len, top_db=18.0, out=None):
+    """``voiceprep.trim_f64`` of every row of the packed float32 ``x`` -> (bounds [n,2] int32 = begin and end of the
+    non-silent span, stats [n,2] float64 = the peak frame mean square and the variance of the span).  The tables are
+    host integers.  ``out``: the pair of tensors to write into (tests)."""
+    n = len(row_len)
+    assert len(row_offset) == n and x.dim() == 1
+    bounds, stats = (torch.empty((n, 2), dtype=torch.int32, device=x.device),
+                     torch.empty((n, 2), dtype=torch.float64, device=x.device)) if out is None else out
+    for t, dt in ((bounds, torch.int32), (stats, torch.float64)):
+        assert t.shape == (n, 2) and t.dtype == dt and t.is_cuda and t.is_contiguous()
+    max_len = max([int(v) for v in row_len], default=0)
+    nbytes = lib().asw_voice_trim_workspace_bytes(n, max_len)
+    if nbytes == 0:
+        check(-1)
+    off = _host_i64_array(row_offset)
+    with torch.cuda.device(x.device):
+        ws = _ws_f64(nbytes, x.device)
+        check(lib().asw_voice_trim(ptr(_f32(x)), x.shape[0], off.ctypes.data, _host_i32(row_len), n, max_len,
+                                   10.0 ** (-float(top_db) / 10.0), ptr(bounds), ptr(stats), ptr(ws), nbytes, current_stream()))
+    return bounds, stats
+
+
 def f16x3_overflow_count(reset=True) -> int:
     """Threads of f16x3 launches that produced an activation beyond the fp16 range since the last
     reset (asw_f16x3_overflow_count); 0 means no later GEMM clipped its input."""

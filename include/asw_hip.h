@@ -1173,6 +1173,48 @@ int asw_train_batch(const float* mix, int K, int M, int T, int items, int S_max,
                     void* stream);
 int asw_train_losses(const float* est, const float* gt, int N, int T, double* out, void* stream);
 
+/* Corpus voices on the device (voiceprep.py): the polyphase resampler and the silence trim that
+ * the dataset generator applies to voice files, as voiceprep.resample_poly_f64 and voiceprep.trim_f64 state them and
+ * equal to those statements bit for bit.  Both calls take a ragged batch: x float32 [x_len] (device) holds the rows packed
+ * in any order, row r = x[row_offset[r] .. + row_len[r]); a padded [n][T_max] matrix is the table row_offset[r] = r T_max.
+ * row_offset, row_len, win_begin and win_len are HOST arrays, validated and read before the call returns.  No atomics,
+ * one writer per address, every output element written: two calls give identical bytes.
+ *
+ * asw_voice_resample: one call serves one ratio up/down (reduced by their gcd here).  h float64 [h_len] (device) is the
+ *   filter table voiceprep.resample_filter(up, down): 2 half + 1 taps, half = 10 max(up, down) of the reduced ratio,
+ *   scaled by up; one tap 1.0 for the ratio 1/1, which makes the call a windowed copy.  With n_out = ceil(row_len up /
+ *   down) and m = n down + half, y[n] = sum_j h[m % up + j up] x[m / up - j] over ascending j while the tap index stays
+ *   <= 2 half, terms outside the row left out, every product and sum rounded on its own.  out [n][T_out], float32 or
+ *   (out_f64 != 0) float64, device: out[r][t] = y_r[win_begin[r] + t] for t < win_len[r] while that index is below
+ *   n_out, else 0; the float32 value is the float64 value rounded once.  The same entry therefore serves the whole rows
+ *   (win_begin 0, win_len n_out) and the cropped, zero-padded T samples a scene keeps.
+ *   Limit: max(up, down) <= ASW_VOICE_MAX_RATIO after reduction -- the table (102,408 bytes then) is staged in the LDS of
+ *   one workgroup; it covers 8 / 11.025 / 16 / 22.05 / 32 / 44.1 kHz to and from 16 / 48 kHz.
+ *   workspace: asw_voice_resample_workspace_bytes(n) bytes, 8-byte aligned.
+ *   Refused before any launch: n outside 0..65535, up or down < 1, a ratio beyond the limit, h_len that is not the
+ *   ratio's, T_out outside 1..2^30, a row that leaves x, win_begin outside 0..2^40, win_len outside 0..T_out, a null
+ *   pointer, a short workspace.  n = 0 succeeds and launches nothing.
+ *
+ * asw_voice_trim: librosa.effects.trim over centred, zero-padded frames of 2048 at hop 512, nfr = 1 + row_len / 512
+ *   frames, without logarithms.  A 512-sample block sum is 64 partial sums of 8 consecutive squares, left to right, and
+ *   a six-step butterfly; a frame is its four blocks left to right, / 2048.  Frame f is non-silent iff
+ *   max(1e-10, ms[f]) > thr max(1e-10, max_f ms[f]); thr = 10^(-top_db / 10) is the caller's double.  bounds int32
+ *   [n][2] = (512 first, min(row_len, 512 (last + 1))) over the non-silent frames ((0, 0) when there is none);
+ *   stats float64 [n][2] = (max_f ms[f], the two-pass population variance of the kept span in the order of
+ *   voiceprep.span_var_f64; 0 for an empty span).  row_len[r] <= max_len.
+ *   workspace: asw_voice_trim_workspace_bytes(n, max_len) bytes, 8-byte aligned (the row table and the block sums).
+ *   Refused before any launch: n outside 0..65535, max_len < 0, a row longer than max_len or one that leaves x, a
+ *   threshold that is not a number, a null pointer, a short workspace.  With NaN or Inf samples the result is
+ *   unspecified but every access stays in bounds. */
+#define ASW_VOICE_MAX_RATIO 640
+size_t asw_voice_resample_workspace_bytes(int n);
+int asw_voice_resample(const float* x, int64_t x_len, const int64_t* row_offset_host, const int32_t* row_len_host, int n, int up,
+                       int down, const double* h, int h_len, const int64_t* win_begin_host, const int32_t* win_len_host, int T_out,
+                       void* out, int out_f64, void* workspace, size_t workspace_bytes, void* stream);
+size_t asw_voice_trim_workspace_bytes(int n, int max_len);
+int asw_voice_trim(const float* x, int64_t x_len, const int64_t* row_offset_host, const int32_t* row_len_host, int n, int max_len,
+                   double thr, int32_t* bounds, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
