@@ -365,6 +365,7 @@ int inter_attention_launch(const char* who, const float* qkv, const int32_t* bou
   static const Kern kern[3] = {inter_attention_groups_kernel<4>, inter_attention_groups_kernel<2>, inter_attention_groups_kernel<1>};
   static SmemAttr attr[3];                                     // per device and instantiation
   if (int rc = attr[v].ensure(reinterpret_cast<const void*>(kern[v]), smem)) return rc;
+  asw::ProfScope prof(st, who, 4.0 * G * L * nhead * (double)s_max * s_max * (d / nhead));   // s_max: an upper bound when ragged
   hipLaunchKernelGGL(kern[v], dim3(cdiv((long)G * L * nhead, waves)), dim3(64 * waves), smem, st, qkv, tab, G, S_uniform, s_max,
                      L, d, nhead, ctx);
   ASW_LAUNCH_CHECK();

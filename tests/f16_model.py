@@ -8,7 +8,8 @@ between the arithmetic and the truth (2^-11 per operand in the one-term mode), s
 about a thousand times tighter in "f16" and tens of times tighter in "f16x3" than one held to float64 of the inputs.
 
 Two layers:
-  splits and products   rtz16 / rn16 / split_act (csrc/mfma_util.h: split4, split4_rn), split_np / split_w
+  splits and products   rtz16 / rn16 / split_act (csrc/mfma_util.h: split4, split4_rn), split_attn (csrc/attention.hip:
+                        split4h; its users are in tests/attention_cases.py), split_np / split_w
                         (csrc/asw_common.cpp: asw_split_weights_f16), accumulate (the three terms of mma3)
   fused operations      conv_layer (im2col, + bias, ReLU / Swish, (x + x2), * mul, residual, LayerNorm), gn_glu,
                         stats4, stack (the hand-over between fused layers), up_tail (UpFeed)
@@ -55,6 +56,16 @@ def split_act(x, nterm):
     with np.errstate(over="ignore", invalid="ignore"):
         lo = rtz16(x - hi.astype(np.float32))
     return hi, lo
+
+
+def split_attn(x):
+    """The split of attention_mfma16_kernel (csrc/attention.hip, split4h): hi truncated, lo = the remainder ROUNDED TO
+    NEAREST.  -> float64(hi) + float64(lo), the value the f16 MFMAs multiply"""
+    x = _f32(x)
+    hi = rtz16(x)
+    with np.errstate(over="ignore", invalid="ignore"):
+        lo = rn16(x - hi.astype(np.float32))
+    return hi.astype(np.float64) + lo.astype(np.float64)
 
 
 def split_np(w):

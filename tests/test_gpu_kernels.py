@@ -167,7 +167,7 @@ def test_linear_residual_layernorm(ops, d, f, L, B):
                                          (150, 256, 8, 2), (5, 256, 8, 2), (150, 96, 2, 1), (150, 512, 8, 1)])
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
 def test_attention(ops, L, d, nhead, B, precision):
-    """f32: exact fp32 MFMA; f16x3: both products on the f16 MFMA with split operands (head_dim 128, L <= 352; other
+    """f32: exact fp32 MFMA; f16x3: both products on the f16 MFMA with split operands (head_dim 128, L <= 320; other
     shapes run the f32 kernels), the softmax in fp32 either way: same bar.  The last four shapes are the VALU kernel at
     head_dim 32 (two key tiles; inside one query tile), 48 and 64; (19, 128, 8, 3) is head_dim 16."""
     qkv = _rand(B, L, 3 * d, seed=28)
